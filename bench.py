@@ -24,6 +24,17 @@ order: rank 0 alone drives all N GPUs through one multi-device handle (RCCL nccl
 copies) — still a multi-GPU measurement, labelled in `config.parallelism` — and only with more ranks than GPUs (the one-GPU
 test box) the host shared-memory transport, which is labelled as not a valid multi-GPU measurement.
 
+A plain run does what the headline needs and nothing else: set-up, the untimed pre-conditioning, W warm-up steps, the K
+timed steps, the dump of --dump-outputs, the line.  `--full` adds every secondary measurement below that takes work of its
+own (the cold window, the copy bandwidth, the kernel identity and the PMC counters quoted for it, fp64, developed_window,
+end_to_end, parity, cpu_baseline); `--no-extras` / `--no-cpu-baseline` switch parts of `--full` off again.
+
+--dump-outputs DIR: after the timed steps, the state the last of them left — what sphmi_download hands a caller — as
+DIR/<field>.npy: Position and Density in float64 (the engine keeps their double-float state), Velocity, Acceleration and
+Pressure in float32 (their fp32 values exactly), ID in float64; rows sorted by ID, so that two builds compare row for row.
+Beyond 64 MB (64·10⁶ bytes) in all, a fixed seeded sample of the ID-sorted rows is written (the same IDs on every run of
+the same arguments).
+
 Objects on the JSON line beyond the contract's keys:
   roofline     — dominant kernel (k_neighbor_force): ALGORITHMIC bytes per launch ÷ its average launch duration (HIP events
                  on the engine's stream) against the 8 TB/s HBM peak: `achieved`, `peak`, `frac` are that HBM figure.
@@ -33,16 +44,17 @@ Objects on the JSON line beyond the contract's keys:
                  micro-benchmark's figures), with vector-ALU issue ≈10 % behind (`valu`) — priced from the committed
                  counters of the shipped kernel.  Counters are only quoted when the ISA of the loaded library's two bench
                  kernels hashes to what the counter record was taken on (tools/isa_report.py): otherwise `traffic` and
-                 `valu` are null and `counters_refused` says why.
-  cpu_baseline — the CPU oracle (OpenMP restatement of the reference algorithm, fp64, "port") timed on this box's host cores
-                 on a bounded sample of the same workload.
-  value_cold   — the same W + K window on a handle that starts on an idle device (no pre-conditioning); `value` is measured
-                 after `config.preconditioning` (the clock governor: profiles/r02_cold_start_timeline.md).
+                 `valu` are null and `counters_refused` says why.  `peak_measured`, `traffic`, `valu` and `kernel_identity`:
+                 --full only.
+  cpu_baseline — (--full) the CPU oracle (OpenMP restatement of the reference algorithm, fp64, "port") timed on this box's
+                 host cores on a bounded sample of the same workload.
+  value_cold   — (--full) the same W + K window on a handle that starts on an idle device (no pre-conditioning); `value` is
+                 measured after `config.preconditioning` (the clock governor: profiles/r02_cold_start_timeline.md).
   value_excl_rebuild — the window with the cell-list rebuilds' device time taken out (every sphmi_advance opens with one:
                  the reference re-arms Δx at src/SPHCellList.jl:739).
-  fp64, developed_window, parity — secondary measurements (the reference's own arithmetic; 200 steps at t ≈ 0.4 s; a short
-                 fp32-vs-oracle check).  `--no-extras` skips them and value_cold.
-  value_end_to_end / end_to_end — the reference's RunSimulation call pattern at the headline size: one sphmi_advance per 0.01 s of
+  fp64, developed_window, parity — (--full) secondary measurements (the reference's own arithmetic; 200 steps at t ≈ 0.4 s;
+                 a short fp32-vs-oracle check).  `--no-extras` skips them and value_cold.
+  value_end_to_end / end_to_end — (--full) the reference's RunSimulation call pattern at the headline size: one sphmi_advance per 0.01 s of
                  simulated time, every call followed by the asynchronous download of all carried fields, t = 0 → 0.05 s on a cold
                  handle; updates/s over the whole run (host work between the calls included).
 """
@@ -317,6 +329,54 @@ def extra_parity(device, dp=0.0085, steps=10):
     return out
 
 
+DUMP_DTYPES = {"ID": "float64", "Position": "float64", "Density": "float64", "Velocity": "float32", "Acceleration": "float32", "Pressure": "float32"}
+DUMP_LIMIT_BYTES = 64 * 10**6
+NPY_HEADER_BYTES = 4096                 # allowance for the headers of the six .npy files
+
+
+def dump_outputs(out_dir, state, limit=DUMP_LIMIT_BYTES, seed=0):
+    """--dump-outputs: the fields of DUMP_DTYPES of a download() dict (or of several, concatenated: one per slab) as
+    out_dir/<field>.npy, rows sorted by ID; over `limit` bytes in all, a seeded sample of the sorted rows.  Returns {field: shape}."""
+    import numpy as np
+    parts = state if isinstance(state, list) else [state]
+    cols = {k: np.concatenate([p[k] for p in parts]) for k in DUMP_DTYPES}
+    rows = np.argsort(cols["ID"], kind="stable")
+    row_bytes = sum(np.dtype(t).itemsize * int(np.prod(cols[k].shape[1:])) for k, t in DUMP_DTYPES.items())
+    if len(rows) * row_bytes > limit - NPY_HEADER_BYTES:
+        keep = np.random.default_rng(seed).choice(len(rows), (limit - NPY_HEADER_BYTES) // row_bytes, replace=False)
+        rows = rows[np.sort(keep)]
+    os.makedirs(out_dir, exist_ok=True)
+    out = {}
+    for k, t in DUMP_DTYPES.items():
+        a = np.ascontiguousarray(cols[k][rows], dtype=t)
+        np.save(os.path.join(out_dir, f"{k}.npy"), a)
+        out[k] = list(a.shape)
+    return out
+
+
+def gather_dump_state(eng, active, rank, rdv, out_dir):
+    """The state the timed steps left, on rank 0: its own download and, in rank mode, every other rank's slab (handed over
+    as out_dir/.rank<r>.npz).  None on the other ranks."""
+    import numpy as np
+    mine = eng.download(tuple(DUMP_DTYPES)) if active else None
+    if rdv is None:
+        return mine
+    os.makedirs(out_dir, exist_ok=True)
+    if rank != 0 and mine is not None:
+        np.savez(os.path.join(out_dir, f".rank{rank}.npz"), **mine)
+    rdv.barrier()
+    if rank != 0:
+        return None
+    parts = [mine] if mine is not None else []
+    for r in range(1, rdv.world):
+        path = os.path.join(out_dir, f".rank{r}.npz")
+        if os.path.exists(path):
+            with np.load(path) as z:
+                parts.append({k: z[k] for k in z.files})
+            os.remove(path)
+    return parts
+
+
 def parallelism_text(world, info, n_dev, how):
     if world == 1:
         return "single GPU"
@@ -355,8 +415,13 @@ def main():
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--dp", type=float, default=None, help="override lattice spacing")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the secondary objects (cold window, fp64, developed flow, parity)")
+    ap.add_argument("--full", action="store_true",
+                    help="also every secondary measurement (cold window, copy bandwidth, kernel identity + counters, fp64, developed flow, "
+                         "end to end, parity, CPU baseline); a plain run measures the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the state the last timed step left as DIR/<field>.npy (ID-sorted rows, at most 64 MB)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="(--full) skip the secondary objects (cold window, fp64, developed flow, parity)")
     ap.add_argument("--precondition-ms", type=float, default=60.0,
                     help="untimed device pre-conditioning on a scratch handle before the warm-up steps (0 = off: value = value_cold)")
     ap.add_argument("--single-process", action="store_true",
@@ -364,6 +429,9 @@ def main():
     ap.add_argument("--force-distributed", action="store_true",
                     help="use the slab driver even for one rank (measures its host overhead)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    extras = args.full and not args.no_extras
 
     launch = os.environ.get("SPHMI_BENCH_LAUNCH", "")
     spawn_failure = None
@@ -404,16 +472,16 @@ def main():
     from sphexample_amd.engine import dam_break_3d_count, make_engine, make_generated_dam_break_engine
     dp = args.dp or DP1 / (world ** (1.0 / 3.0))
     setup = setup_dam_break_3d(dp)
-    identity = loaded_kernel_identity() if rank == 0 else None
+    identity = loaded_kernel_identity() if rank == 0 and args.full else None
 
-    # ---- the scratch handle: the cold window (value_cold), then the pre-conditioning load -------------------------------
+    # ---- the scratch handle: the cold window (value_cold, --full), then the pre-conditioning load -----------------------
     cold = None
     scratch = None
     pre_steps = 0
     plain = world == 1 and not args.force_distributed
-    if plain and (args.precondition_ms > 0 or not args.no_extras):
+    if plain and (args.precondition_ms > 0 or extras):
         scratch = make_generated_dam_break_engine(DP1, setup_dam_break_3d(DP1), device_float_bytes=4, device=device)
-        if not args.no_extras and not args.dp:
+        if extras and not args.dp:
             el, _, kms, _, _, _ = timed_window(scratch, args.warmup, args.steps)
             cold = {"value": sum(dam_break_3d_count(DP1)) * args.steps / el, "ms_per_step": el / args.steps * 1e3, "kernel_avg_launch_ms": kms}
 
@@ -489,7 +557,7 @@ def main():
         if active:
             info = eng.multi_info()
 
-    copy_gbs = measured_copy_bandwidth(torch.device("cuda", device)) if rank == 0 else 0.0
+    copy_gbs = measured_copy_bandwidth(torch.device("cuda", device)) if rank == 0 and args.full else 0.0
     if scratch is not None and args.precondition_ms > 0:
         pre_steps = precondition(scratch, args.precondition_ms)
     run_watchdog = None
@@ -512,13 +580,18 @@ def main():
         reduce_max(0.0)
     if run_watchdog is not None:
         run_watchdog.cancel()
+    dumped = None
+    if args.dump_outputs:
+        state = gather_dump_state(eng, active, rank, rdv, args.dump_outputs)
+        if rank == 0:
+            dumped = dump_outputs(args.dump_outputs, state)
 
     if rank == 0:
         value = n_total * args.steps / elapsed
         n_local = n_total / world
         alg_bytes_launch = BYTES_PER_UPDATE_3D_FP32 / 2.0 * n_local
         achieved = alg_bytes_launch / (kern_ms * 1e-3) / 1e9 if kern_ms > 0 else 0.0
-        traffic, valu, refused = counters_for(identity, n_local, kern_ms)
+        traffic, valu, refused = counters_for(identity, n_local, kern_ms) if args.full else (None, None, None)
         out = {
             "metric": "particle-updates/sec (3D dam-break)", "value": value,
             # the same W + K window on a handle that starts on an idle device (no pre-conditioning) — next to `value`, so that nobody reads one without the other
@@ -540,27 +613,32 @@ def main():
                                                               "÷ 8 TB/s); the kernel is bound by the rate at which the texture path takes per-lane gathers — `valu.gather` — "
                                                               "with vector-ALU issue ≈10 % behind (`valu`; until the middle of round 5 it was the other way round)",
                          "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
-                         "peak_measured": copy_gbs, "frac_of_measured": achieved / copy_gbs if copy_gbs > 0 else None,
-                         "peak_measured_source": "1 GiB device-to-device copy (read + write bytes) on this GPU, measured in this run before the warm-up steps",
-                         "traffic": traffic,
-                         "traffic_source": COUNTER_RECORD + " (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes; bytes leaving the L2s, Infinity-Cache hits included)",
                          "kernel": "k_neighbor_force", "avg_launch_ms": kern_ms,
                          # two launches per step (predictor, corrector); the average is taken over HIP-event pairs on every 8th
                          # step (an event pair costs a stream bubble), each weighted 8: `launch_time_samples` is that weighted count
                          # `launches_expected`: predictor + corrector of every step of the window (edge-list launches of slab handles and steps the
                          # device-side control cancelled are not counted); `launch_time_samples`: the weighted count avg_launch_ms was averaged over
                          "launches_expected": 2 * args.steps, "launch_time_samples": kern_launches,
-                         "algorithmic_bytes_per_launch": alg_bytes_launch, "valu": valu, "kernel_identity": identity},
+                         "algorithmic_bytes_per_launch": alg_bytes_launch},
             "value_excl_rebuild": n_total * args.steps / max(elapsed - rebuild_s, 1e-9),
             "rebuild_ms_in_window": rebuild_s * 1e3,
         }
+        if args.full:
+            out["roofline"].update({
+                "peak_measured": copy_gbs, "frac_of_measured": achieved / copy_gbs if copy_gbs > 0 else None,
+                "peak_measured_source": "1 GiB device-to-device copy (read + write bytes) on this GPU, measured in this run before the warm-up steps",
+                "traffic": traffic,
+                "traffic_source": COUNTER_RECORD + " (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes; bytes leaving the L2s, Infinity-Cache hits included)",
+                "valu": valu, "kernel_identity": identity})
         if refused:
             out["roofline"]["counters_refused"] = refused
+        if dumped is not None:
+            out["outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
         if cold:
             out["cold_window"] = cold
         if spawn_failure is not None:
             out["fallback_from_failed_ranks_exit_code"] = spawn_failure        # (the line below was measured by ONE process: its ranks could not be started)
-        if plain and not args.no_extras and not args.dp:
+        if plain and extras and not args.dp:
             for name, fn in (("fp64", lambda: extra_fp64(device, args.warmup, args.steps)),
                              ("developed_window", lambda: extra_developed(device)), ("end_to_end", lambda: extra_end_to_end(device)),
                              ("parity", lambda: extra_parity(device))):
@@ -570,7 +648,7 @@ def main():
                     out[name] = {"error": f"{type(exc).__name__}: {exc}"}
             if isinstance(out.get("end_to_end"), dict) and "value" in out["end_to_end"]:
                 out["value_end_to_end"] = out["end_to_end"]["value"]      # next to value and value_cold: what RunSimulation's call pattern sees
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline()
         print(json.dumps(out), flush=True)
     del scratch

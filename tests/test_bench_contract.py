@@ -1,5 +1,6 @@
-"""bench.py keeps the driver's contract: one JSON line on stdout with the agreed keys, the roofline and (at N = 1) the CPU
-baseline objects; without a GPU it refuses to run (no CPU path); under torchrun with more ranks than GPUs the ranks share
+"""bench.py keeps the driver's contract: one JSON line on stdout with the agreed keys and the roofline object, under --full
+also the CPU baseline (at N = 1) and the other secondary objects, in a plain run none of them; --dump-outputs writes the state
+the timed steps left; without a GPU it refuses to run (no CPU path); under torchrun with more ranks than GPUs the ranks share
 the device through the library's shared-memory transport and the line says so."""
 import json
 import os
@@ -30,7 +31,7 @@ def test_bench_refuses_to_run_without_a_gpu():
 @pytest.mark.gpu
 def test_bench_line_single_gpu():
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "2", "--dp", "0.02",
-                        "--precondition-ms", "5"], capture_output=True, text=True, timeout=600)
+                        "--precondition-ms", "5", "--full"], capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     j = _line(r.stdout)
     assert KEYS <= set(j) and "cpu_baseline" in j
@@ -45,6 +46,61 @@ def test_bench_line_single_gpu():
     assert j["config"]["launch"] == "one process"
     cb = j["cpu_baseline"]
     assert cb["kind"] == "port" and cb["cores"] >= 1 and cb["value"] > 0 and cb["unit"] == j["unit"]
+
+
+@pytest.mark.gpu
+def test_bench_plain_line_measures_the_headline_only_and_dumps_its_outputs(tmp_path):
+    """Without --full: the contract's keys, K timed steps, none of the secondary measurements; --dump-outputs writes the state the
+    last timed step left, ID-sorted, in float32 / float64."""
+    import numpy as np
+    out = tmp_path / "outputs"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--dp", "0.02",
+                        "--precondition-ms", "5", "--dump-outputs", str(out)], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    j = _line(r.stdout)
+    assert KEYS <= set(j) and (j["n_gpus"], j["steps"], j["warmup"], j["dtype"], j["higher_is_better"]) == (1, 3, 1, "f32", True)
+    assert j["value"] > 0 and j["ms_per_step"] > 0 and j["value"] == pytest.approx(j["config"]["particles"] * 1e3 / j["ms_per_step"])
+    assert not {"cpu_baseline", "fp64", "developed_window", "end_to_end", "parity", "cold_window"} & set(j) and j["value_cold"] is None
+    assert not {"peak_measured", "traffic", "valu", "kernel_identity"} & set(j["roofline"]) and j["roofline"]["avg_launch_ms"] > 0
+    n = j["config"]["particles"]
+    arrays = {k: np.load(out / f"{k}.npy") for k in ("ID", "Position", "Velocity", "Acceleration", "Density", "Pressure")}
+    assert {k: list(v.shape) for k, v in arrays.items()} == j["outputs"]["arrays"]
+    assert arrays["ID"].dtype == np.float64 and arrays["Position"].dtype == np.float64 and arrays["Velocity"].dtype == np.float32
+    assert arrays["Position"].shape == (n, 3) and arrays["Density"].shape == (n,)
+    np.testing.assert_array_equal(arrays["ID"], np.sort(arrays["ID"]))
+    assert len(np.unique(arrays["ID"])) == n and all(np.isfinite(a).all() for a in arrays.values())
+    assert arrays["Density"].min() > 0 and np.abs(arrays["Velocity"]).max() > 0          # the state after steps, not the lattice
+
+
+def test_dump_outputs_sorts_by_id_and_keeps_within_the_limit(tmp_path):
+    """The --dump-outputs writer (CPU): slabs merged, rows sorted by ID, dtypes fixed; over the byte limit, the same seeded sample of rows
+    on every call."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    rng = np.random.default_rng(3)
+    n = 1000
+    ids = rng.permutation(n).astype(np.int64) + 1
+    state = {"ID": ids, "Position": rng.random((n, 3)), "Velocity": rng.random((n, 3)), "Acceleration": rng.random((n, 3)),
+             "Density": 1000 + rng.random(n), "Pressure": rng.random(n)}
+    half = [{k: v[:400] for k, v in state.items()}, {k: v[400:] for k, v in state.items()}]
+    shapes = bench.dump_outputs(str(tmp_path / "all"), half)
+    assert shapes["ID"] == [n] and shapes["Position"] == [n, 3]
+    got = {k: np.load(tmp_path / "all" / f"{k}.npy") for k in bench.DUMP_DTYPES}
+    assert all(str(got[k].dtype) == t for k, t in bench.DUMP_DTYPES.items())
+    order = np.argsort(ids)
+    np.testing.assert_array_equal(got["ID"], np.arange(1, n + 1))
+    np.testing.assert_array_equal(got["Position"], state["Position"][order])
+    np.testing.assert_array_equal(got["Velocity"], state["Velocity"][order].astype(np.float32))
+    row = 8 + 24 + 12 + 12 + 8 + 4
+    limit = 300 * row + bench.NPY_HEADER_BYTES
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), state, limit=limit)
+    a, b = ({k: np.load(tmp_path / d / f"{k}.npy") for k in bench.DUMP_DTYPES} for d in ("a", "b"))
+    assert sum(os.path.getsize(tmp_path / "a" / f"{k}.npy") for k in a) <= limit and len(a["ID"]) == 300
+    assert all(np.array_equal(a[k], b[k]) for k in a)
+    np.testing.assert_array_equal(a["ID"], np.sort(a["ID"]))
+    np.testing.assert_array_equal(a["Density"], state["Density"][order][a["ID"].astype(np.int64) - 1])
 
 
 @pytest.mark.gpu
@@ -79,9 +135,11 @@ def test_bench_line_of_rank_processes_over_the_rccl_branch(world):
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("transport", [None, "rccl"])
-def test_bench_line_two_ranks_on_one_gpu(transport):
+def test_bench_line_two_ranks_on_one_gpu(transport, tmp_path):
     """transport = "rccl": RCCL is ASKED for and refuses (two ranks on one device) — every rank learns it, the run falls back to
-    the shared-memory transport and still produces its line (what a node whose RCCL cannot be set up would get)."""
+    the shared-memory transport and still produces its line (what a node whose RCCL cannot be set up would get).  The dump of
+    --dump-outputs holds both slabs: every particle once."""
+    import numpy as np
     import torch
     if torch.cuda.device_count() > 1:
         pytest.skip("more than one GPU: the ranks would not share a device")
@@ -90,11 +148,13 @@ def test_bench_line_two_ranks_on_one_gpu(transport):
         env["SPHMI_TRANSPORT"] = transport
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                         "--master-port", "29547" if transport is None else "29549", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "2", "--dp", "0.02",
-                        "--precondition-ms", "0"], capture_output=True, text=True, timeout=600, env=env)
+                        "--precondition-ms", "0", "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=600, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     j = _line(r.stdout)
     assert KEYS <= set(j) and "cpu_baseline" not in j
     assert j["n_gpus"] == 2 and "SHARED-MEMORY" in j["config"]["parallelism"]
+    ids = np.load(tmp_path / "ID.npy")
+    assert len(ids) == j["config"]["particles"] and np.array_equal(ids, np.unique(ids)) and not list(tmp_path.glob(".rank*"))
     assert ("RCCL set-up failed" in r.stderr) == (transport == "rccl")
     if transport == "rccl":                                 # the text names the slab and the call, not a bare "invalid usage"
         assert "slab" in r.stderr and "ncclCommInitRank" in r.stderr

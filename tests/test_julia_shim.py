@@ -7,12 +7,13 @@ The image has no Julia, so the shim has never executed; it is edited by hand whe
       type tuple lists, and the tuple equals the header's prototype in length and in class (pointer / 32-bit integer / 64-bit integer
       / double) argument for argument, return type included;
   (c) `ABI_VERSION` equals `SPHMI_ABI_VERSION`;
-  (d) when /root/reference is present (this container, not the GPU box): every `SimKernel.x`, `SimConstants.x`, `SimMetaData.x`,
-      `P.x` and MotionDetails field the shim touches is a field of the reference struct it binds
-      (src/SPHKernels.jl:30-40, src/SimulationConstantsConfiguration.jl:36-52, src/SimulationMetaDataConfiguration.jl:28-67,
-      src/PreProcess.jl:114, src/SimulationGeometry.jl:17-22), and the `SimulationLoop` method's argument list equals
-      src/SPHCellList.jl:727-733 name for name.
+  (d) every `SimKernel.x`, `SimConstants.x`, `SimMetaData.x`, `P.x` and MotionDetails field the shim touches is a field of the
+      reference struct it binds (src/SPHKernels.jl:30-40, src/SimulationConstantsConfiguration.jl:36-52,
+      src/SimulationMetaDataConfiguration.jl:28-67, src/PreProcess.jl:114, src/SimulationGeometry.jl:17-22), and the
+      `SimulationLoop` method's argument list equals src/SPHCellList.jl:727-733 name for name.  The reference's names are read
+      from tests/golden/reference_names.json, which reference_names() below extracts from an SPHExample checkout.
 A renamed header field, a dropped ccall argument or a reordered struct member fails here instead of on a user's machine."""
+import json
 import os
 import re
 
@@ -21,7 +22,7 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SHIM = os.path.join(ROOT, "julia", "SPHExampleMI355X.jl")
 HEADER = os.path.join(ROOT, "include", "sphmi.h")
-REF = "/root/reference"
+NAMES = os.path.join(ROOT, "tests", "golden", "reference_names.json")
 
 
 def _strip_c_comments(text):
@@ -172,49 +173,67 @@ def test_every_ccall_matches_its_prototype():
             assert jl_class(jt) == c_class(cd), f"{sym}: argument {k + 1} is {jt} in the shim and `{cd}` in the header"
 
 
-def _ref_struct_fields(path, struct_name):
-    text = open(os.path.join(REF, path), encoding="utf-8").read()
+# struct → file of the reference, for the structs whose field names the shim may touch
+REF_STRUCTS = {"SPHKernelInstance": "src/SPHKernels.jl", "CubicSpline": "src/SPHKernels.jl",
+               "SimulationConstants": "src/SimulationConstantsConfiguration.jl", "SimulationMetaData": "src/SimulationMetaDataConfiguration.jl",
+               "MotionDetails": "src/SimulationGeometry.jl"}
+
+
+def _ref_struct_fields(text, struct_name):
     m = re.search(r"struct\s+%s\b.*?\n(.*?)\nend" % struct_name, text, flags=re.S)
-    assert m, (path, struct_name)
-    return set(re.findall(r"^\s*([^\W\d][\w⁻¹²₀ᵩ]*)\s*::", m.group(1), flags=re.M))
+    assert m, struct_name
+    return sorted(set(re.findall(r"^\s*([^\W\d][\w⁻¹²₀ᵩ]*)\s*::", m.group(1), flags=re.M)))
 
 
-@pytest.mark.skipif(not os.path.isdir(os.path.join(REF, "src")), reason="the reference checkout is not on this machine")
+def _arg_names(text, start):
+    i = text.index("(", start) + 1
+    depth, j = 1, i
+    while depth:
+        depth += {"(": 1, ")": -1}.get(text[j], 0)
+        j += 1
+    return [re.match(r"\s*([^\s:]+)", a).group(1) for a in _split_top(text[i:j - 1])]
+
+
+def reference_names(ref_root):
+    """The names the shim is checked against, read from an SPHExample checkout at `ref_root` — what
+    tests/golden/reference_names.json holds (json.dump(reference_names(root), f, indent=1, ensure_ascii=False))."""
+    read = lambda path: open(os.path.join(ref_root, path), encoding="utf-8").read()  # noqa: E731
+    structs = {name: _ref_struct_fields(read(path), name) for name, path in REF_STRUCTS.items()}
+    sa = re.search(r"SimParticles\s*=\s*StructArray\(\((.*?)\)\)", read("src/PreProcess.jl"), flags=re.S)
+    cells = read("src/SPHCellList.jl")
+    return {"structs": structs, "SimParticles": sorted(set(re.findall(r"(\w+)\s*=", sa.group(1)))),
+            "SimulationLoop": _arg_names(cells, cells.index("function SimulationLoop("))}
+
+
+def stored_reference_names():
+    with open(NAMES, encoding="utf-8") as f:
+        return json.load(f)
+
+
 def test_the_shim_binds_fields_the_reference_has():
     text = shim_text()
     ident = r"([^\W\d][\w⁻¹²₀ᵩ⁺]*)"
     used = lambda var: set(re.findall(r"\b%s\.%s" % (var, ident), text))  # noqa: E731
-    kern = _ref_struct_fields("src/SPHKernels.jl", "SPHKernelInstance")
+    ref = stored_reference_names()
+    kern = set(ref["structs"]["SPHKernelInstance"])
     assert used("SimKernel") and used("SimKernel") <= kern, used("SimKernel") - kern
-    cons = _ref_struct_fields("src/SimulationConstantsConfiguration.jl", "SimulationConstants")
+    cons = set(ref["structs"]["SimulationConstants"])
     assert len(used("SimConstants")) >= 11 and used("SimConstants") <= cons, used("SimConstants") - cons
-    meta = _ref_struct_fields("src/SimulationMetaDataConfiguration.jl", "SimulationMetaData")
+    meta = set(ref["structs"]["SimulationMetaData"])
     assert used("SimMetaData") and used("SimMetaData") <= meta, used("SimMetaData") - meta
-    motion = _ref_struct_fields("src/SimulationGeometry.jl", "MotionDetails")
+    motion = set(ref["structs"]["MotionDetails"])
     assert used("m") == {"Direction", "Velocity", "StartTime", "Duration"} and used("m") <= motion, used("m") - motion
-    pre = open(os.path.join(REF, "src/PreProcess.jl"), encoding="utf-8").read()
-    sa = re.search(r"SimParticles\s*=\s*StructArray\(\((.*?)\)\)", pre, flags=re.S)
-    columns = set(re.findall(r"(\w+)\s*=", sa.group(1)))
+    columns = set(ref["SimParticles"])
     assert len(columns) == 17
     assert used("P") and used("P") <= columns, used("P") - columns
     # the CubicSpline tensile parameter the shim forwards (src/SPHKernels.jl:15-19)
-    assert "eps" in _ref_struct_fields("src/SPHKernels.jl", "CubicSpline")
+    assert "eps" in ref["structs"]["CubicSpline"]
 
 
-@pytest.mark.skipif(not os.path.isdir(os.path.join(REF, "src")), reason="the reference checkout is not on this machine")
 def test_simulationloop_signature_is_the_references():
-    def arg_names(text, start):
-        i = text.index("(", start) + 1
-        depth, j = 1, i
-        while depth:
-            depth += {"(": 1, ")": -1}.get(text[j], 0)
-            j += 1
-        return [re.match(r"\s*([^\s:]+)", a).group(1) for a in _split_top(text[i:j - 1])]
-    ref = open(os.path.join(REF, "src/SPHCellList.jl"), encoding="utf-8").read()
-    r0 = ref.index("function SimulationLoop(")
+    a = stored_reference_names()["SimulationLoop"]
     shim = open(SHIM, encoding="utf-8").read()
-    s0 = shim.index("function SimulationLoop(")
-    a, b = arg_names(ref, r0), arg_names(shim, s0)
+    b = _arg_names(shim, shim.index("function SimulationLoop("))
     assert len(a) == 19 and a == b, list(zip(a, b))
     # and it extends the reference's function, not a namesake
     assert re.search(r"import\s+SPHExample\.SPHCellList:\s*SimulationLoop", shim)
