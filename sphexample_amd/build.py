@@ -28,7 +28,7 @@ def is_stale() -> bool:
 
 
 def build(force: bool = False, verbose: bool = False, extra_flags=(), out: str = None) -> str:
-    """extra_flags / $SPHMI_CXXFLAGS carry experiment switches such as -DSPHMI_KSLOTS=16."""
+    """extra_flags / $SPHMI_CXXFLAGS carry experiment switches such as -DSPHMI_DIAG=1."""
     out = out or LIB
     extra_flags = tuple(extra_flags) + tuple(os.environ.get("SPHMI_CXXFLAGS", "").split())
     if not force and not is_stale() and out == LIB and not extra_flags:

@@ -269,7 +269,7 @@ struct Engine final : EngineBase {
     // slots only — where the launch fits the chip at once every tile starts at t = 0 and the classes are fine already.  $SPHMI_TAIL_SORT = per mille (0: off)
     int tail_sort = 200;
     int tail_sort_permille(int ntile) const { return ntile < classes_fine_below ? 0 : tail_sort; }
-    int tile_classes(int ntile) const { return ntile < classes_fine_below ? SPHMI_TILE_CLASSES_ONE_ROUND : SPHMI_TILE_CLASSES; }
+    int tile_classes(int ntile) const { return ntile < classes_fine_below ? kTileClassesOneRound : kTileClasses; }
     // waves per tile by tile count (measured with the paired two-wave launches and sixteen classes, updates/s WPT 2 / WPT 1:
     // 2 481 tiles 8.03 / 7.16e8, 3 454: 8.47 / 8.22, 5 050: 9.19 / 9.02, 6 985: 9.62 / 9.80, 9 428: 9.76e8 / 1.022e9,
     // 11 689: 0.986 / 1.054e9, 16 527: 0.978 / 1.08e9)

@@ -58,78 +58,25 @@ template <class V> struct Half {
 };
 
 constexpr int kWave = 64;
-// Build switches that remain.  Everything else that rounds 2 and 3 measured and left off (role bits in the queue entries, half
-// prefetch, two neighbours in flight, phase 1 pipelined, s_setprio, the predictor's masks handed to the corrector, the sign bits
-// on the matrix pipe; round 5: packed fp32 arithmetic, lane pairs that gather one record per instruction) lives as patches under
-// profiles/ (r03_raw/mask_mfma_experiment.patch, r04_retired_switches.patch, r05_retired_switches.patch,
-// r05_pair_gather_experiment.patch, r05_deep_pair_experiment.patch) with its figures in profiles/r03_pair_loop_experiments.md and profiles/HISTORY.md §4.9 — not in this file.
+// Build switches:
+//   SPHMI_LDS_STAGE=1   the ablation build of BASELINE config 3 (below)
+//   SPHMI_DIAG=1/2/4    diagnostic builds with WRONG results, the floors BASELINE and VERDICT quote: gathers without the pair arithmetic /
+//                       the arithmetic without the gathers / neither (profiles/HISTORY.md §4.6; tools/fp64_bounds.sh)
+//   SPHMI_STATS, SPHMI_TRACE, SPHMI_TRACE_WAVES   the probe and trace builds of tools/: pair-loop counters (ForceParams::stats),
+//                       per-tile timestamps (ForceParams::trace) and, with SPHMI_TRACE_WAVES, one record per wave
+// The A/B switches of rounds 4-6 (SPHMI_HALF_TILE, _HALF4, _HALF_INTERLEAVE, _BALANCE, _F16_SCAN, _PAIR_FETCH64, _SMALL_TRIMS, _PREFETCH_RANGES,
+// _LOOP_UNROLL, _FAST_PAIR, _F64_TRIMS, _TRANS_SPLIT, _TRACE_SYNC, _QCAP_HALF2, _QCAP_HALF4, _TILE_CLASSES, _TILE_CLASSES_ONE_ROUND, the
+// SPHMI_DIAG = 5 / 8 / 16 diagnostics and SPHMI_RING_RECORDS / _SHARED / _STAGE / _SOA) were folded into what ships: `git log -S SPHMI_RING_SOA`
+// finds the commit that removed them; their figures stay in profiles/, as do the patches of the experiments retired before them.
 #ifndef SPHMI_LDS_STAGE
 #define SPHMI_LDS_STAGE 0       // ABLATION BUILD (BASELINE config 3: "LDS cell-tile staging on"): the candidate records of a chunk are staged in LDS
                                 // and the pair loop reads them from there, chunk by chunk, instead of gathering from L1 through per-lane mask queues
                                 // (build/variants/libsphmi_ldsstage.so: __graft_entry__.build(); parity: tests/test_lds_stage_variant_gpu.py)
 #endif
-#ifndef SPHMI_HALF_TILE
-#define SPHMI_HALF_TILE 1       // two-wave tiles: 1 = each wave serves 32 targets, two lanes per target (k_neighbor_force, kHalf); 0 = both waves serve
-                                // the tile's 64 targets and split its chunks (rounds 1-4) — A/B builds only
-#endif
-#ifndef SPHMI_HALF4
-#define SPHMI_HALF4 1           // four-wave tiles: 1 = two half tiles of two waves each (the waves of a half deal its chunks alternately), 0 = four waves
-                                // that serve the tile's 64 targets and split its chunks (rounds 2-4) — A/B builds only
-#endif
-#ifndef SPHMI_BALANCE
-#define SPHMI_BALANCE 1         // interleaved half tiles: per chunk the lane of a target that has had FEWER pairs so far takes the larger of the two interleaved shares
-                                // (whole 32-bit words change hands; see the push of phase 1).  0 = every lane keeps the share the matrix layout hands it (A/B builds)
-#endif
-#ifndef SPHMI_PAIR_FETCH64
-#define SPHMI_PAIR_FETCH64 1    // fp64 half tiles of one wave per half, compiled-in models: adjacent lanes fetch the two 16-byte halves of ONE packet per instruction
-                                // (run_pairs_piped, kPairFetch64).  0 = four gathers of a lane's own record (A/B builds; what every other kernel does)
-#endif
-#ifndef SPHMI_F16_SCAN
-#define SPHMI_F16_SCAN 1        // half tiles: the distance matrix of phase 1 from ONE v_mfma_f32_32x32x16_f16 per 32x32 block instead of three
-                                // v_mfma_f32_32x32x2_f32 (see scan_chunk16).  0 = the f32-input form (A/B builds; what full tiles keep)
-#endif
-#ifndef SPHMI_HALF_INTERLEAVE
-#define SPHMI_HALF_INTERLEAVE 1 // half tiles: the two lanes of a target take alternate groups of FOUR candidates (1) or the lower / upper 32 of a chunk (0: A/B builds).
-                                // (Round 5 built alternate SINGLE candidates — no index arithmetic per pair — and packed fp32 arithmetic for the pair; both measured
-                                // slower and live in profiles/r05_retired_switches.patch, profiles/HISTORY.md §4.9.)
-#endif
-#ifndef SPHMI_SMALL_TRIMS
-#define SPHMI_SMALL_TRIMS 1     // launches of four and eight waves per tile (a few hundred waves, 10 µs): the epilogue's loads requested at the wave's start, no
-                                // pre-test in front of the reduction atomics (round 5); 0: A/B builds
-#endif
-#ifndef SPHMI_PREFETCH_RANGES
-#define SPHMI_PREFETCH_RANGES 1 // launches of four and eight waves per tile: the cell ranges of all rows requested at once, parked in a private LDS column (round 6; 0: one exposed look-up per row)
-#endif
-#ifndef SPHMI_LOOP_UNROLL
-#define SPHMI_LOOP_UNROLL 2     // fp32 pair loop (one pair per iteration): iterations per loop test (1: rounds 1-4)
-#endif
-#ifndef SPHMI_FAST_PAIR
-#define SPHMI_FAST_PAIR 1       // fp32 kernels of the compiled-in models: pair_fast (one reciprocal per pair, transcendentals back to back, lane constants out of
-                                // the loop — round 5); 0 = pair_core for every kernel (rounds 1-4), A/B builds
-#endif
 #ifndef SPHMI_DIAG
-#define SPHMI_DIAG 0            // 1 / 2 / 4 / 5 / 8: diagnostic builds with WRONG results — gathers without arithmetic / arithmetic without gathers /
-                                // neither / adjacent lanes sharing a gathered record (profiles/HISTORY.md §4.6) / adjacent lanes walking the union of their masks (§4.9)
-                                // 16 (round 6): the PRICE of an LDS record ring under the per-lane queues — the pair loop of the fp32 half-tile kernels of one wave per half
-                                // reads both packets of a neighbour with two ds_read_b128 from a ring in LDS, at the address its record index maps to, instead of gathering
-                                // them through the texture path.  SPHMI_RING_RECORDS (a power of two) records of 32 bytes per WAVE, or per four-wave BLOCK with
-                                // SPHMI_RING_SHARED=1 — the LDS allocation, and with it the occupancy, of the real design; SPHMI_RING_STAGE=1 adds what filling the ring costs
-                                // (the second packet of every scanned chunk loaded with the first, two ds_write_b128 per lane and chunk; shared ring: by one wave in four).
-                                // Nothing guarantees that the slot still holds the record: wrong results.  profiles/r06_lds_ring_price.md
+#define SPHMI_DIAG 0
 #endif
-#ifndef SPHMI_RING_RECORDS
-#define SPHMI_RING_RECORDS 128
-#endif
-#ifndef SPHMI_RING_SHARED
-#define SPHMI_RING_SHARED 0
-#endif
-#ifndef SPHMI_RING_STAGE
-#define SPHMI_RING_STAGE 0
-#endif
-#ifndef SPHMI_RING_SOA
-#define SPHMI_RING_SOA 0        // the ring as two arrays of packets (16-byte stride: sixteen bank positions for the sixteen lanes of a ds_read_b128 group) instead of
-                                // records (32-byte stride: eight)
-#endif
+static_assert(SPHMI_DIAG == 0 || SPHMI_DIAG == 1 || SPHMI_DIAG == 2 || SPHMI_DIAG == 4, "SPHMI_DIAG: 0, or the diagnostic build 1, 2 or 4");
 
 // Queue depth of the per-lane queues of non-empty 32-candidate accept masks.  A simulation of the queues on real tiles (profiles/HISTORY.md §4.4)
 // and the loop counters of the kernel agree: with 8 entries drained by 4 (round 1) the lanes of a wave are busy in 70–72 % of the
@@ -139,25 +86,24 @@ constexpr int kWave = 64;
 // 14 → 1.037e9, 16 → 0.983e9 / 1.019e9: 12 entries = 6 KB per wave = six four-tile blocks (24 waves) per compute unit.
 // The fp64 kernels hold ≤ 16 waves per unit by their registers: 16 entries.
 // Eight waves per tile (the smallest cases; four waves per half tile) scan every fourth chunk of their half: eight entries.
-#ifndef SPHMI_QCAP_HALF2
-#define SPHMI_QCAP_HALF2 6      // fp32 half tiles of ONE wave per half, compiled-in models (the launches of 3 000 tiles and more: the bench)
-#endif
-#ifndef SPHMI_QCAP_HALF4
-#define SPHMI_QCAP_HALF4 6       // … and of TWO waves per half (330 … 3 000 tiles: 70 k / 102 k / 159 k particles −3.3 / −1.9 / −1.3 % per step against twelve; profiles/r05_raw/qcap4_ab.txt)
-#endif
 template <class T, int WPT = 1, int MODEL = 0> constexpr int queue_entries() {
     // (fp64 half tiles: 10 / 12 / 16 / 20 entries all within 0.5 % of each other at 1.06 M / 159 k / 70 k particles: sixteen stay)
     // (half tiles of two / four waves per half: 8 / 10 / 12 / 16 and 6 / 8 / 10 / 12 entries within 1 % of each other from 273 to 2 482 tiles)
-    // (round 5, after the two lanes of a target had learnt to share evenly (SPHMI_BALANCE): fp32 half tiles of one wave per half with a compiled-in model run
-    // 4 / 5 / 6 / 10 entries at 0.4161 / 0.4081 / 0.4093 / 0.4160 ms per launch at C3, five interleaved repetitions — more, shorter bursts of the pair loop,
-    // whose lanes drift less apart: 8.15 instead of 7.03 M gathers per launch at 30 instead of 36 CU-cycles each, the L1 hits 81-83 % instead of 77;
-    // it is the corrector's queue that matters (predictor 6 + corrector 10: no gain).  The run-time models lose 5-12 % with six and keep ten,
-    // every other class is within noise of its value: profiles/r05_raw/qcap_*.txt)
-    return WPT >= 8 ? 8 : (sizeof(T) == 8 ? 16 : (WPT == 2 && SPHMI_HALF_TILE != 0 && SPHMI_LDS_STAGE == 0 ? (MODEL >= 0 ? SPHMI_QCAP_HALF2 : 10) : (WPT == 4 && MODEL >= 0 && SPHMI_HALF4 != 0 && SPHMI_HALF_TILE != 0 && SPHMI_LDS_STAGE == 0 ? SPHMI_QCAP_HALF4 : 12)));
+    if (WPT >= 8) return 8;
+    if (sizeof(T) == 8) return 16;
+    // fp32 half tiles of one wave per half with a compiled-in model (the launches of 3 000 tiles and more: the bench): six.  Round 5, after the two
+    // lanes of a target had learnt to share evenly: 4 / 5 / 6 / 10 entries at 0.4161 / 0.4081 / 0.4093 / 0.4160 ms per launch at C3, five interleaved
+    // repetitions — more, shorter bursts of the pair loop, whose lanes drift less apart: 8.15 instead of 7.03 M gathers per launch at 30 instead of
+    // 36 CU-cycles each, the L1 hits 81-83 % instead of 77; it is the corrector's queue that matters (predictor 6 + corrector 10: no gain).  The
+    // run-time models lose 5-12 % with six and keep ten, every other class is within noise of its value: profiles/r05_raw/qcap_*.txt
+    if (WPT == 2 && SPHMI_LDS_STAGE == 0) return MODEL >= 0 ? 6 : 10;
+    // … and of TWO waves per half (330 … 3 000 tiles: 70 k / 102 k / 159 k particles −3.3 / −1.9 / −1.3 % per step against twelve; profiles/r05_raw/qcap4_ab.txt)
+    if (WPT == 4 && MODEL >= 0 && SPHMI_LDS_STAGE == 0) return 6;
+    return 12;
 }
 // a full queue is consumed down to QUEUE − 1 − slack entries before scanning goes on: one, and two for the six-entry queues (0.4228 → 0.4192 ms per launch at C3,
 // six interleaved repetitions; applied to every class it moves the 82 instantiations by −0.8 % in the geometric mean and single ones by ±1.4 %: profiles/r05_raw/slack_*.txt)
-template <class T, int WPT = 1, int MODEL = 0> constexpr int queue_slack() { return queue_entries<T, WPT, MODEL>() == SPHMI_QCAP_HALF2 && SPHMI_QCAP_HALF2 < 8 ? 2 : 1; }
+template <class T, int WPT = 1, int MODEL = 0> constexpr int queue_slack() { return queue_entries<T, WPT, MODEL>() == 6 ? 2 : 1; }
 
 enum { PASS_FORCES_ONLY = 0, PASS_PREDICTOR = 1, PASS_CORRECTOR = 2 };
 // model tags (values of include/sphmi.h)
@@ -314,18 +260,9 @@ __device__ __forceinline__ float  fast_sqrt(float x)  { return __builtin_amdgcn_
 // another one (tools/ubench/issue_patterns.hip, loop_replay.hip); the s_nop is also the wait state a VALU instruction needs before it reads a
 // transcendental's result (the compiler cannot see into an asm).
 __device__ __forceinline__ void sqrt_and_rcp(const float a, const float b, float& sqrt_a, float& rcp_b) {
-#if defined(SPHMI_TRANS_SPLIT)
-    asm("v_sqrt_f32 %0, %2\n\ts_nop 0\n\tv_rcp_f32 %1, %3\n\ts_nop 0" : "=&v"(sqrt_a), "=v"(rcp_b) : "v"(a), "v"(b));
-#else
     asm("v_sqrt_f32 %0, %2\n\tv_rcp_f32 %1, %3\n\ts_nop 0" : "=&v"(sqrt_a), "=v"(rcp_b) : "v"(a), "v"(b));
-#endif
 }
-#ifndef SPHMI_F64_TRIMS
-#define SPHMI_F64_TRIMS 1       // fp64 pair loop (round 5): square root without the compiler's range scaling, the clamp of u as an output modifier, the neighbour's
-                                // EOS with a multiply for its division — 0: rounds 1-4, A/B builds
-#endif
 __device__ __forceinline__ double fast_sqrt(double x) {
-#if SPHMI_F64_TRIMS
     // sqrt of an r² of the pair loop (0 for the self pair, else 1e-8 … 1e-2 of a length² in metres: no subnormals, no infinities) — the compiler's sqrt() is
     // v_rsq_f64 + the same two refinements INSIDE a range scaling of two v_ldexp_f64, a v_cmp_class and four selects (17 instructions; this: 9).
     const double xs = x > 1e-300 ? x : 1e-300;
@@ -335,9 +272,6 @@ __device__ __forceinline__ double fast_sqrt(double x) {
     g = __builtin_fma(g, r, g); h = __builtin_fma(h, r, h);
     const double d = __builtin_fma(-g, g, xs);
     return __builtin_fma(d, h, g);
-#else
-    return sqrt(x);
-#endif
 }
 
 __device__ __forceinline__ float  absT(float x)  { return __builtin_fabsf(x); }
@@ -372,12 +306,7 @@ __device__ __forceinline__ float fma1_clamp01_ready(float a, float b) {
     float r; asm("v_fma_f32 %0, %1, %2, 1.0 clamp" : "=v"(r) : "v"(a), "s"(b)); return r;
 }
 __device__ __forceinline__ double fma1_clamp01(double a, double b) {
-#if SPHMI_F64_TRIMS
     double r; asm("v_fma_f64 %0, %1, %2, 1.0 clamp" : "=v"(r) : "v"(a), "v"(b)); return r;      // (two compares and three selects as ONE output modifier)
-#else
-    const double t = __builtin_fma(a, b, 1.0);
-    return t < 0.0 ? 0.0 : (t > 1.0 ? 1.0 : t);
-#endif
 }
 // 1 for a positive (Fluid) signed density, 0 for a negative one — the MotionLimiter of the neighbour as a factor
 __device__ __forceinline__ float step01(float s, float big) {
@@ -533,18 +462,8 @@ k_neighbor_force(const ForceParams<T> P) {
     // SPHMI_LDS_STAGE: the two packets of the 64 candidates of the chunk being worked on, per wave (2 / 4 KB in fp32 / fp64)
     __shared__ V4 s_stage_all[SPHMI_LDS_STAGE ? WPT * TPB * 2 * kWave : 1];
 
-    // SPHMI_DIAG == 16: the record ring whose price is being taken (fp32 half tiles of one wave per half, compiled-in models: the bench's kernels)
-    constexpr bool kRing = SPHMI_DIAG == 16 && sizeof(T) == 4 && WPT == 2 && MODEL >= 0 && SPHMI_HALF_TILE != 0 && SPHMI_LDS_STAGE == 0;
-    constexpr int kRingRec = SPHMI_RING_RECORDS;
-    static_assert((kRingRec & (kRingRec - 1)) == 0 && kRingRec >= 64, "ring: a power of two of at least one chunk");
-    __shared__ V4 s_ring_all[kRing ? 2 * kRingRec * (SPHMI_RING_SHARED ? 1 : WPT * TPB) : 1];
-
     const int lane = threadIdx.x & (kWave - 1);
     const int wvb = threadIdx.x >> 6;                      // wave of the block
-    [[maybe_unused]] char* const s_ringb = reinterpret_cast<char*>(s_ring_all + (kRing && !SPHMI_RING_SHARED ? wvb * 2 * kRingRec : 0));
-    // byte offsets of the two packets of the record whose offset in the record array is jr (= 32 × index)
-    [[maybe_unused]] auto ring_off0 = [](const unsigned jr) -> unsigned { return SPHMI_RING_SOA ? ((jr >> 1) & (unsigned)(kRingRec * 16 - 1)) : (jr & (unsigned)(kRingRec * 32 - 1)); };
-    [[maybe_unused]] constexpr unsigned kRingOff1 = SPHMI_RING_SOA ? (unsigned)kRingRec * 16u : 16u;
     // wave of the tile, tile of the block.  Two tiles of two waves (the launches that fit the chip at once): a workgroup of
     // FOUR waves puts one wave on each SIMD of its compute unit, so every SIMD of a unit holds the same number of waves —
     // workgroups of two left the SIMDs with 4 … 9 waves and 35 % more work on the fullest than on average, and the launch
@@ -559,7 +478,7 @@ k_neighbor_force(const ForceParams<T> P) {
     // Tile schedule (sphmi_rebuild.h): the dispatcher places block b on XCD b % 8; every XCD works through
     // one contiguous, cost-balanced run of tiles, expensive tiles first.  Measured on the 1 M-particle dam
     // break: equal-count contiguous runs 1.02 ms, 64-tile round-robin chunks 1.10 ms, identity 1.13 ms.
-    constexpr bool kHalf = (WPT == 2 || ((WPT == 4 || WPT == 8) && SPHMI_HALF4 != 0)) && SPHMI_HALF_TILE != 0 && SPHMI_LDS_STAGE == 0;
+    constexpr bool kHalf = (WPT == 2 || WPT == 4 || WPT == 8) && SPHMI_LDS_STAGE == 0;
     constexpr int kPar = kHalf ? WPT / 2 : 1;               // waves per half tile
     // waves of one workgroup may leave early for DIFFERENT reasons while others go on to a workgroup barrier (see below)
     constexpr bool kMixedExit = (kHalf && kPar > 1) || (!kHalf && WPT > 1 && TPB > 1);
@@ -583,14 +502,14 @@ k_neighbor_force(const ForceParams<T> P) {
         b = dead ? 0 : P.order[P.part[x] + r];
     }
     // kHalf (tiles of two waves): wave w serves targets 32w … 32w+31 of the tile, TWO LANES PER TARGET — lane l and lane l + 32 hold the
-    // same target and take the lower / upper 32 candidates of every chunk (what the matrix layout hands each lane half anyway: one
-    // target block per chunk instead of two, no exchange of mask halves), and add their sums once after the loop.  The two waves of a
+    // same target and take alternate groups of four candidates of every chunk (what the matrix layout hands each lane half anyway: one
+    // target block per chunk instead of two, no exchange of mask halves; rec_of below), and add their sums once after the loop.  The two waves of a
     // tile share nothing — no partial sums in LDS, no barrier — and a target's pairs are dealt half-chunk by half-chunk instead of chunk
     // by chunk: 159 k particles ran 93.8 pair-loop iterations per wave for 67.6 pairs per lane (72 % of the lane slots; one wave per
     // tile: 90 %).
     // Four-wave tiles (launches of 512 … 850 tiles) are two half tiles of TWO waves: the waves of a half deal its chunks alternately and the
     // second hands its sums to the first through LDS — the lanes of a target still share every chunk they scan.
-    const int hl = kHalf ? (lane >> 5) : 0;                 // which 32 candidates of a chunk this lane takes
+    const int hl = kHalf ? (lane >> 5) : 0;                 // which 32 candidates of a chunk this lane takes (rec_of)
     const int half = kHalf ? (wv & 1) : 0;                  // which half of the tile this wave serves
     [[maybe_unused]] const int par = kHalf ? (wv >> 1) : 0; // … and which of the half's waves it is
     const int t0 = kHalf ? b * kWave + 32 * half : b * kWave;
@@ -611,14 +530,6 @@ k_neighbor_force(const ForceParams<T> P) {
     const V4 q0 = P.src0[ac];
     const V4 q1 = P.src1[ac];
     const T xa = q0.x, ya = q0.y, za = q0.z;
-    if constexpr (kRing) {
-        // finite values in every slot (the lane's own record): what the loop reads is wrong, but it is not a NaN from a previous kernel's LDS
-        for (int k = lane; k < kRingRec; k += kWave) {
-            *reinterpret_cast<V4*>(s_ringb + ring_off0((unsigned)k << 5)) = q0;
-            *reinterpret_cast<V4*>(s_ringb + ring_off0((unsigned)k << 5) + kRingOff1) = q1;
-        }
-        // (a shared ring: every wave fills ALL of it — waves of a block may have left already, so no barrier; whoever writes, the values are finite)
-    }
     T rho_a, rhon_a, P_a, s_a;
     if constexpr (PASS == PASS_CORRECTOR) {
         rho_a = q0.w;                                   // ρ⁺
@@ -636,7 +547,7 @@ k_neighbor_force(const ForceParams<T> P) {
     // registers that those kernels have to spare, the large launches do not)
     // (compiled-in models only: the run-time-model corrector of eight waves per tile sits at 127 registers, and twelve more cost it its second workgroup per
     // compute unit — +5 … +14 % per step on the 17 k-particle Laminar / SPS / shifting handles, caught by tools/variants_vs_previous.sh)
-    constexpr bool kEarlyEpilogueLoads = PASS == PASS_CORRECTOR && WPT >= 4 && MODEL >= 0 && SPHMI_SMALL_TRIMS != 0;
+    constexpr bool kEarlyEpilogueLoads = PASS == PASS_CORRECTOR && WPT >= 4 && MODEL >= 0;
     [[maybe_unused]] V4 pre_s0, pre_s1, pre_lo;
     if constexpr (kEarlyEpilogueLoads) {
         pre_s0 = P.a0[ac]; pre_s1 = P.a1[ac];
@@ -697,15 +608,16 @@ k_neighbor_force(const ForceParams<T> P) {
     // ---- pair physics for one accepted neighbour j ------------------------------------------
     T sum_c = 0, sum_d = 0;                             // Σ (1/ρ_b)·(∇W·vᵢⱼ) (continuity without ρₐm₀), Σ density diffusion
     constexpr int kRecShift = sizeof(T) == 4 ? 5 : 6;      // log2 of the record size
-    // bit p of a queue entry → the candidate's distance from the entry's base.  Half tiles with interleaved shares: the matrix layout
-    // hands lane half h the rows 8g + 4h + k (g = 0 … 7, k = 0 … 3) of a chunk loaded in natural order, so bit p = 4g + k is candidate
-    // 8g + k = p + (p & ~3) behind the base cb + 4h — the two lanes of a target take alternate groups of four candidates and their
-    // pair counts differ by a handful instead of by half a cell (one v_and + one v_add per pair)
-    constexpr bool kInterleave = kHalf && SPHMI_HALF_INTERLEAVE != 0;
+    // bit p of a queue entry → the candidate's distance from the entry's base.  Half tiles: the matrix layout hands lane half h the
+    // rows 8g + 4h + k (g = 0 … 7, k = 0 … 3) of a chunk loaded in natural order, so bit p = 4g + k is candidate 8g + k = p + (p & ~3)
+    // behind the base cb + 4h — the two lanes of a target take alternate groups of four candidates and their pair counts differ by a
+    // handful instead of by half a cell, as with the lower / upper 32 of a chunk (one v_and + one v_add per pair).  (Round 5 built
+    // alternate SINGLE candidates — no index arithmetic per pair — and packed fp32 arithmetic for the pair; both measured slower:
+    // profiles/r05_retired_switches.patch, profiles/HISTORY.md §4.9.)
     // record offset of the candidate at the lowest set bit of m, for an entry whose bit 0 sits at record offset `base`
     auto rec_of = [](const unsigned m, const unsigned base) -> unsigned {
         const unsigned p = (unsigned)__builtin_ctz(m);
-        if constexpr (kInterleave) return ((p + (p & 0x1Cu)) << kRecShift) + base;
+        if constexpr (kHalf) return ((p + (p & 0x1Cu)) << kRecShift) + base;
         else return (p << kRecShift) + base;
     };
     // (record offsets of the target's cell [cs_ar, ce_ar) and of the record BEHIND the target, a_r1: what the orientation rule and the kernel output compare with)
@@ -783,8 +695,7 @@ k_neighbor_force(const ForceParams<T> P) {
             // (fp64: ρ/ρ₀ as in src/SimulationEquations.jl:10 costs an IEEE division — a dozen instructions — per PAIR.  Division by a CONSTANT: the
             // quotient through the reciprocal, corrected with the exact residual — two FMAs, and the correctly rounded ρ/ρ₀ again but for rare double
             // roundings; a bare multiply is off by an ulp often enough to move MovingSquare2d's r = H ties, 4.6e-13 → 3e-8 against the oracle after 100 steps)
-            if constexpr (sizeof(T) == 8 && SPHMI_F64_TRIMS == 0) rr = rho_b / P.rho0;
-            else if constexpr (sizeof(T) == 8) { const T q0 = rho_b * P.inv_rho0; rr = __builtin_fma(__builtin_fma(-q0, P.rho0, rho_b), P.inv_rho0, q0); }
+            if constexpr (sizeof(T) == 8) { const T q0 = rho_b * P.inv_rho0; rr = __builtin_fma(__builtin_fma(-q0, P.rho0, rho_b), P.inv_rho0, q0); }
             else rr = rho_b * P.inv_rho0;
             const T rr2 = rr * rr, rr4 = rr2 * rr2, rr7 = (rr4 * rr2) * rr;
             Psum = P.Cbe * rr7 + PaC;
@@ -857,8 +768,8 @@ k_neighbor_force(const ForceParams<T> P) {
     //  * Pressure! of a neighbour's ρ⁺ (corrector) as ρ⁷·(Cb/γ/ρ₀⁷) − Cb/γ: no scaling multiply;
     //  (packed fp32 for the head of the pair and the accumulators — 47 instead of 56 vector instructions — was built and measured 1.3 % slower: on gfx950 v_fma_f32 runs at
     //  the double rate and v_pk_* at the full rate; profiles/r05_retired_switches.patch, profiles/HISTORY.md §4.9)
-    constexpr bool kFast = kFoldKv2 && MODEL >= 0 && ((MODEL >> 4) & 15) == kDdtLinear && SPHMI_FAST_PAIR != 0;
-    constexpr bool kFastDiag = SPHMI_DIAG == 0 || SPHMI_DIAG == 2 || SPHMI_DIAG == 5 || SPHMI_DIAG == 8 || SPHMI_DIAG == 16;      // (the diagnostic builds that keep the arithmetic)
+    constexpr bool kFast = kFoldKv2 && MODEL >= 0 && ((MODEL >> 4) & 15) == kDdtLinear;
+    constexpr bool kFastDiag = SPHMI_DIAG == 0 || SPHMI_DIAG == 2;      // (the diagnostic builds that keep the arithmetic)
     [[maybe_unused]] auto pair_fast = [&](const V4& n0, const V4& n1, const bool a_is_i) {
         if constexpr (kFast) {
             float dz = 0.0f, r2, vdx;
@@ -1012,10 +923,10 @@ k_neighbor_force(const ForceParams<T> P) {
     constexpr bool kPipe = (sizeof(T) == 4 || WPT == 2) && !kTwoPairs && SPHMI_LDS_STAGE == 0;
     [[maybe_unused]] bool pv = false;
     [[maybe_unused]] unsigned pjr = 0;
-    // (round 5: the loop test — a compare, a ballot and a branch — once per TWO iterations, SPHMI_LOOP_UNROLL: a burst may run one iteration longer than it
+    // (fp32, round 5: the loop test — a compare, a ballot and a branch — once per TWO iterations: a burst may run one iteration longer than it
     // had to, which only moves a pair from the next burst into this one; the copy that rotated `cm` goes with it)
     // (the run-time-model kernels lose 5-12 % with it at 1 098 tiles: registers — compiled-in models only)
-    constexpr bool kPairFetch64 = SPHMI_PAIR_FETCH64 != 0 && sizeof(T) == 8 && kHalf && MODEL >= 0 && SPHMI_DIAG == 0;
+    constexpr bool kPairFetch64 = sizeof(T) == 8 && kHalf && MODEL >= 0 && SPHMI_DIAG == 0;
     [[maybe_unused]] const unsigned pf_c = (lane & 1) ? 16u : 0u, pf_self = a_r1 - (1u << kRecShift);
     auto run_pairs_piped = [&](const int keep, const bool drain) __attribute__((always_inline)) {
         unsigned qf = qn != 0 ? 1u : 0u;
@@ -1041,18 +952,9 @@ k_neighbor_force(const ForceParams<T> P) {
                 A = __builtin_amdgcn_raw_buffer_load_b128(rs0, (int)jE, 0, 0); B = __builtin_amdgcn_raw_buffer_load_b128(rs0, (int)(jE + 32u), 0, 0);
                 Cq = __builtin_amdgcn_raw_buffer_load_b128(rs0, (int)jO, 0, 0); Dq = __builtin_amdgcn_raw_buffer_load_b128(rs0, (int)(jO + 32u), 0, 0);
             } else
-#if SPHMI_DIAG == 5
-            // DIAGNOSTIC BUILD (wrong results): every odd lane gathers the record its even neighbour gathers — what the texture path
-            // charges when the two lanes of a pair address the same 32 bytes (the lane-pair design of profiles/HISTORY.md §4.6)
-            if (v) { const unsigned js = (unsigned)__builtin_amdgcn_mov_dpp((int)jr, 0xA0, 0xF, 0xF, true);      // quad_perm [0, 0, 2, 2]
-                     n0 = gather_packet(rs0, js, 0, T()); n1 = gather_packet(rs0, js, 1, T()); }
-#elif SPHMI_DIAG == 2 || SPHMI_DIAG == 4
+#if SPHMI_DIAG == 2 || SPHMI_DIAG == 4
             // DIAGNOSTIC BUILD (wrong results): the arithmetic without the gathers — the floor set by the vector ALU
             if (v) { n0 = q0; n1 = q1; n0.x += __uint_as_float(jr) * T(1e-30); n0.y += T(0.003); n0.w = q0.w + T(1); }
-#elif SPHMI_DIAG == 16
-            // DIAGNOSTIC BUILD (wrong results): both packets from the LDS ring, at the slot the record index maps to
-            if constexpr (kRing) { if (v) { const unsigned ro = ring_off0(jr); n0 = *reinterpret_cast<const V4*>(s_ringb + ro); n1 = *reinterpret_cast<const V4*>(s_ringb + ro + kRingOff1); } }
-            else { if (v) { n0 = gather_packet(rs0, jr, 0, T()); n1 = gather_packet(rs0, jr, 1, T()); } }
 #else
             { if (v) { n0 = gather_packet(rs0, jr, 0, T()); n1 = gather_packet(rs0, jr, 1, T()); } }
 #endif
@@ -1099,7 +1001,7 @@ k_neighbor_force(const ForceParams<T> P) {
         };
         if (__builtin_amdgcn_ballot_w64(drain ? (pv | ((qf | cm) != 0u)) : (qn > keep)) != 0) do {
             iteration();
-            if constexpr (SPHMI_LOOP_UNROLL == 2 && sizeof(T) == 4) iteration();
+            if constexpr (sizeof(T) == 4) iteration();
         } while (__builtin_amdgcn_ballot_w64(drain ? (pv | ((qf | cm) != 0u)) : (qn > keep)) != 0);
     };
     // the two-pair loop with the addresses of the NEXT one or two neighbours worked out while the four gathers fly (compiled-in
@@ -1153,7 +1055,7 @@ k_neighbor_force(const ForceParams<T> P) {
     // column for 16 candidate rows per 32×32 block; their sign bits are shifted into a word with
     // v_alignbit (one op per result), and one v_permlane32_swap hands each target lane both halves.
     // The candidates are loaded lane-permuted so that bit b of the mask is candidate cb + b.
-    const int bperm = kInterleave ? lane : (((lane >> 2) & 1) << 5) | ((lane >> 5) << 4) | (((lane >> 3) & 3) << 2) | (lane & 3);
+    const int bperm = kHalf ? lane : (((lane >> 2) & 1) << 5) | ((lane >> 5) << 4) | (((lane >> 3) & 3) << 2) | (lane & 3);
     float B0[2], B1[2], B2[2], A2;
     if constexpr (kHalf) {
         // lanes l and l + 32 hold the same target: the operand layout without an exchange, one target block
@@ -1178,10 +1080,9 @@ k_neighbor_force(const ForceParams<T> P) {
     // per value, both roundings towards zero), the fp32 accumulation and half-precision subnormals flushed by the matrix pipe (lo
     // parts below 6e-5 times a partner of at most 384).  An ordinary tile reaches 4-5 H: eps ~ 1e-3, 0.15 % more candidates for the
     // pair loop; a tile of spray that spans 100 H gets eps ~ 0.26.  The mask is a superset either way; the pair loop applies the exact cut.
-    constexpr bool kF16 = kHalf && SPHMI_F16_SCAN != 0;
     [[maybe_unused]] u32x4s Bh = {0u, 0u, 0u, 0u};
     [[maybe_unused]] float hinv = 0.0f;
-    if constexpr (kF16) {
+    if constexpr (kHalf) {
         const float Hinv = __builtin_amdgcn_rsqf((float)P.H2);
         const float Rs = fast_sqrt(wave_max(owned ? tt : 0.0f)) * Hinv + 3.0f;            // wave-uniform
         hinv = Hinv * fminf(16.0f, 192.0f * fast_rcp(Rs));
@@ -1208,7 +1109,7 @@ k_neighbor_force(const ForceParams<T> P) {
         unsigned W = 0u;
 #pragma unroll
         for (int C = 1; C >= 0; --C) {
-            if (kInterleave && C == 1 && HI - cb <= 32) continue;       // (as in scan_chunk)
+            if (C == 1 && HI - cb <= 32) continue;       // (as in scan_chunk)
             u32x4s aw; aw[0] = C ? Z[0] : X[0]; aw[1] = C ? Z[1] : X[1]; aw[2] = C ? Z[2] : X[2]; aw[3] = C ? Z[3] : X[3];
             f32x16 d = {0};
             d = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, aw), __builtin_bit_cast(f16x8, Bh), d, 0, 0, 0);
@@ -1237,9 +1138,9 @@ k_neighbor_force(const ForceParams<T> P) {
         unsigned W[2] = {0u, 0u};
 #pragma unroll
         for (int C = 1; C >= 0; --C) {
-            // (interleaved half tiles: the last chunk of a row is half empty on average — when its candidates 32 … 63 do not exist their
+            // (half tiles: the last chunk of a row is half empty on average — when its candidates 32 … 63 do not exist their
             // block is not computed; its sixteen bits of every lane stay zero)
-            if (kInterleave && C == 1 && HI - cb <= 32) continue;      // (C3: 890 -> 873 µs per step)
+            if (kHalf && C == 1 && HI - cb <= 32) continue;      // (C3: 890 -> 873 µs per step)
 #pragma unroll
             for (int Tb = 0; Tb < (kHalf ? 1 : 2); ++Tb) {
                 f32x16 d = {0};
@@ -1252,7 +1153,7 @@ k_neighbor_force(const ForceParams<T> P) {
                 __builtin_amdgcn_sched_barrier(0);      // one 32×32 block in flight: 16 accumulator registers
             }
         }
-        // (kHalf: W[0] IS this lane's share — its target against candidates cb + 32·hl … + 31)
+        // (kHalf: W[0] IS this lane's share — its target against its 32 candidates of the chunk)
         if constexpr (kHalf) return (unsigned long long)W[0];
         swap_halves(W[0], W[1]);
         return ((unsigned long long)W[1] << 32) | W[0];
@@ -1269,10 +1170,9 @@ k_neighbor_force(const ForceParams<T> P) {
     // Round 6: half tiles of several waves per half (every launch of four and eight waves per tile since round 4) lost that sharing with the full tiles it was
     // written for, and each wave was back to one exposed round trip per cell row — nine in 3-D — in launches whose whole life is 10–40 µs.  They now request the
     // ranges of ALL rows at once and park them in a private LDS column ([wave][row][lane]: no barrier, no other wave reads it): one round trip instead of NSEG.
-    // (-DSPHMI_PREFETCH_RANGES=0: A/B builds)
     // (compiled-in models only: the run-time-model kernels of four waves per tile sit at 127 registers and pay 12–31 % for the eighteen more — 158 791 particles
     // Laminar 193 → 233 µs per step, 70 262 with PlanarShifting 94 → 123: profiles/r06_raw/prefetch_ranges_sizes_ab.txt)
-    constexpr bool kPrefetchRanges = SPHMI_PREFETCH_RANGES != 0 && WPT >= 4 && kHalf && MODEL >= 0;
+    constexpr bool kPrefetchRanges = WPT >= 4 && kHalf && MODEL >= 0;
     __shared__ int2 s_rng_own[kPrefetchRanges ? WPT * TPB * NSEG * kWave : 1];
     [[maybe_unused]] int2* const s_rng_w = s_rng_own + (kPrefetchRanges ? wvb * NSEG * kWave + lane : 0);
     if constexpr (kShareRanges) {
@@ -1286,7 +1186,7 @@ k_neighbor_force(const ForceParams<T> P) {
         }
         __syncthreads();
     }
-    [[maybe_unused]] int bal = 0;                       // SPHMI_BALANCE: pairs queued by the lower lane of this target so far − pairs queued by the upper one
+    [[maybe_unused]] int bal = 0;                       // half tiles: pairs queued by the lower lane of this target so far − pairs queued by the upper one
     auto push_entry = [&](const unsigned bits, const int c0) {
         if (bits != 0) {
             *reinterpret_cast<uint2*>(s_qb + waddr) = make_uint2(bits, (unsigned)c0 << kRecShift); waddr = q_next(waddr); qn += 1;
@@ -1319,11 +1219,11 @@ k_neighbor_force(const ForceParams<T> P) {
         // keys are sorted, cstart is monotone: the union over the tile is [lo(first), hi(last))
         const int LO = rl_i(lo_l, 0);
         const int HI = rl_i(hi_l, last_lane);
-        // kInterleave: this lane's candidates of the chunk at cb are cb + 4·hl + 8g + k (g = 0 … 7, k = 0 … 3); how many of them sit below a
+        // kHalf: this lane's candidates of the chunk at cb are cb + 4·hl + 8g + k (g = 0 … 7, k = 0 … 3); how many of them sit below a
         // bound X relative to cb + 4·hl: below(X) = 4·(X >> 3) + min(X & 7, 4) (floor shift: exact for negative X too), and a chunk further on
         // it is 32 less — so the range of MY cells' bits is worked out once per row and moved by 32 per chunk
         [[maybe_unused]] int row_b0 = 0, row_b1 = 0;
-        if constexpr (kInterleave) {
+        if constexpr (kHalf) {
             auto below = [](const int X) -> int { return 4 * (X >> 3) + min(X & 7, 4); };
             row_b0 = below(lo_l - LO - 4 * hl); row_b1 = below(hi_l - LO - 4 * hl);
         }
@@ -1347,35 +1247,14 @@ k_neighbor_force(const ForceParams<T> P) {
             unsigned long long m;
             {
                 const V4 cpk = chunk_packet(cb, HI);
-                if constexpr (kRing && SPHMI_RING_STAGE != 0) {
-                    // what filling the ring costs: the chunk's second packets loaded with the first, both parked at the records' slots
-                    // (a ring shared by the four waves of a block: each of them stages a quarter of the chunks)
-                    if (SPHMI_RING_SHARED == 0 || ((cb >> 6) & 3) == wvb) {
-                        const unsigned cr = (unsigned)(cb + bperm) << kRecShift;
-                        const V4 cpk1 = gather_packet(rs0, cr, 1, T());
-                        // (a lane beyond the array loads zeros — ρ = 0 would put an infinity into sums that the closing multiply by zero turns into NaN: its own record instead)
-                        const bool in = cb + bperm < P.N;
-                        V4 w0 = cpk, w1 = cpk1;
-                        if (!in) { w0 = q0; w1 = q1; }
-                        *reinterpret_cast<V4*>(s_ringb + ring_off0(cr)) = w0;
-                        *reinterpret_cast<V4*>(s_ringb + ring_off0(cr) + kRingOff1) = w1;
-                    }
-                }
-                if constexpr (kF16) m = scan_chunk16(cb, HI, cpk);
+                if constexpr (kHalf) m = scan_chunk16(cb, HI, cpk);
                 else m = scan_chunk(cb, HI, cpk);
                 // keep only the candidates of MY three cells of this row (the reference's stale cell list,
                 // quirk Q1): bits [lo_l − cb, hi_l − cb) of the tile-wide mask
-                if constexpr (kInterleave) {
+                if constexpr (kHalf) {
                     // the bits of MY cells: [below(lo) − 32j, below(hi) − 32j) within 0 … 32 for the j-th chunk of the row (row_b0 / row_b1 above)
                     const int t = (cb - LO) >> 1;
                     const int b0 = min(max(row_b0 - t, 0), 32), b1 = min(max(row_b1 - t, 0), 32);
-                    const int w = b1 - b0;
-                    const unsigned rm = ((~0u) >> ((32 - w) & 31)) << (b0 & 31);
-                    m = (w > 0) ? (unsigned long long)((unsigned)m & rm) : 0ull;
-                } else if constexpr (kHalf) {
-                    // (this lane's 32 candidates start at cb + 32·hl)
-                    const int cbh = cb + 32 * hl;
-                    const int b0 = max(lo_l - cbh, 0), b1 = min(hi_l - cbh, 32);
                     const int w = b1 - b0;
                     const unsigned rm = ((~0u) >> ((32 - w) & 31)) << (b0 & 31);
                     m = (w > 0) ? (unsigned long long)((unsigned)m & rm) : 0ull;
@@ -1419,11 +1298,7 @@ k_neighbor_force(const ForceParams<T> P) {
                 continue;
             }
 #endif
-#if SPHMI_DIAG == 8
-            // DIAGNOSTIC BUILD (wrong results): adjacent lanes — adjacent targets — walk the UNION of their accept masks in step and gather the same record
-            m = (unsigned long long)((unsigned)m | (unsigned)__builtin_amdgcn_mov_dpp((int)(unsigned)m, 0xB1, 0xF, 0xF, true));
-#endif
-            if constexpr (kInterleave && SPHMI_BALANCE != 0) {
+            if constexpr (kHalf) {
                 // Who takes which share.  The two lanes of a target get the candidates 8g + k and 8g + 4 + k of a chunk — a random half each, and a wave runs as many
                 // pair iterations as its fullest LANE needs: 79.8 per half tile at rest with 85 % of the lane slots busy, where two equal halves would need 72.5
                 // (tools/half_tile_balance_sim.py).  Every idle slot is texture-path time (profiles/HISTORY.md §4.9), so per chunk the lane that is BEHIND takes the larger of the two
@@ -1437,10 +1312,7 @@ k_neighbor_force(const ForceParams<T> P) {
                 bal += d;
                 const bool take_upper = lower_takes_upper != (hl != 0);
                 push_entry(take_upper ? wu : wl, cb + (take_upper ? 4 : 0));
-            } else
-            if constexpr (kInterleave) push_entry((unsigned)m, cb + 4 * hl);
-            else if constexpr (kHalf) push_entry((unsigned)m, cb + 32 * hl);
-            else { push_entry((unsigned)m, cb); push_entry((unsigned)(m >> 32), cb + 32); }
+            } else { push_entry((unsigned)m, cb); push_entry((unsigned)(m >> 32), cb + 32); }
         }
     }
     run_pairs(0, true);
@@ -1541,9 +1413,6 @@ k_neighbor_force(const ForceParams<T> P) {
         }
         __syncthreads();
         if (wv > 0) return;
-#ifdef SPHMI_TRACE_SYNC
-        if (lane == 0 && P.trace) P.trace[4 * b + 1] = __builtin_amdgcn_s_memrealtime();     // experiment: when the slowest wave of the tile arrived
-#endif
         // the workgroup holds its WPT wave slots until the slowest wave is done
 #pragma unroll
         for (int k = 1; k < WPT; ++k) tile_work = max(tile_work, s_work[k]);
@@ -1646,7 +1515,7 @@ k_neighbor_force(const ForceParams<T> P) {
         // every lane holds the three maxima: lanes 0, 1, 2 serve one slot each — ONE pre-test load and ONE atomic instruction
         // per wave instead of three dependent round trips to the coherence point (a device-scope load is served beyond the
         // XCD's L2; the epilogue of a lone wave: 5.3 → 4.1 µs, tools/trace_small.py)
-        if (lane < 3) atomic_max_bits(&P.red[lane], lane == 0 ? disp2 : (lane == 1 ? vis : a2), /*pretest=*/WPT < 8 || SPHMI_SMALL_TRIMS == 0);
+        if (lane < 3) atomic_max_bits(&P.red[lane], lane == 0 ? disp2 : (lane == 1 ? vis : a2), /*pretest=*/WPT < 8);
     }
 #if defined(SPHMI_STATS) || defined(SPHMI_TRACE)
     if (lane == 0 && wv == 0 && P.trace) {

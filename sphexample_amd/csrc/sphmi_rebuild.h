@@ -318,12 +318,7 @@ __global__ void __launch_bounds__(256) k_tile_cost(const int* key, const int* cs
 // Sixteen for the launches that fit the chip at once (two waves per tile, below 10 k tiles): there every tile starts at
 // t = 0, the dispatcher deals the blocks round the compute units in launch order, and the finer the deal follows the
 // cost the more even the units' sums — 158 791 particles 7.23e8 → 7.53e8 updates/s, 517 818 particles 9.40 → 9.57e8.
-#ifndef SPHMI_TILE_CLASSES
-#define SPHMI_TILE_CLASSES 4
-#endif
-#ifndef SPHMI_TILE_CLASSES_ONE_ROUND
-#define SPHMI_TILE_CLASSES_ONE_ROUND 16
-#endif
+constexpr int kTileClasses = 4, kTileClassesOneRound = 16;
 // one workgroup per XCD run: find the run, then a STABLE partition of its tiles into cost classes, most
 // expensive class first.  Inside a class the tiles keep their sorted order, so the ~1000 tiles an XCD has
 // in flight at any time are still neighbours in space and share their source rows in its L2 (a full sort
