@@ -419,7 +419,7 @@ struct Engine final : EngineBase {
         {   // experiment build: loop statistics of the neighbour kernel, summed over every launch
             unsigned long long st[16];
             if (hipMemcpy(st, red_d, sizeof st, hipMemcpyDeviceToHost) == hipSuccess)
-                fprintf(stderr, "[sphmi stats] wave-iterations %llu  lane-iterations %llu  refills %llu  empty refills %llu  chunks %llu  waves %llu\n",
+                fprintf(stderr, "[sphmi stats] wave-iterations %llu  lane-iterations %llu  window pairs %llu  gather-free iterations %llu  chunks %llu  waves %llu\n",
                         st[8], st[9], st[10], st[11], st[12], st[13]);
         }
 #endif

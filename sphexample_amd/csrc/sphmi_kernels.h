@@ -480,8 +480,16 @@ k_neighbor_force(const ForceParams<T> P) {
     // break: equal-count contiguous runs 1.02 ms, 64-tile round-robin chunks 1.10 ms, identity 1.13 ms.
     constexpr bool kHalf = (WPT == 2 || WPT == 4 || WPT == 8) && SPHMI_LDS_STAGE == 0;
     constexpr int kPar = kHalf ? WPT / 2 : 1;               // waves per half tile
+    // The own-row window: the records of 256 consecutive indices around the workgroup's targets, staged in LDS once at its
+    // start; the pair loop reads a neighbour inside it with two ds_read_b128 instead of two gathers through the texture path.  The cell
+    // row of a target's own cell (dy = dz = 0) is one index range of about ±1.5 cells around the target itself (x is the fastest sort axis),
+    // so the window serves most of that row's pairs.  The launches of 3 000 tiles and more only: fp32 half tiles of one wave per half, two
+    // tiles per workgroup, the compiled-in default model (the bench's kernels).
+    constexpr bool kWindow = sizeof(T) == 4 && D == 3 && PASS != PASS_FORCES_ONLY && MODEL == kModelDefault && WPT == 2 && TPB == 2 &&
+                             SPHMI_LDS_STAGE == 0;
+    constexpr int kWinRecords = 256;                        // 8 KB: 12 KB of queues + 8 KB per workgroup, below the occupancy the registers allow
     // waves of one workgroup may leave early for DIFFERENT reasons while others go on to a workgroup barrier (see below)
-    constexpr bool kMixedExit = (kHalf && kPar > 1) || (!kHalf && WPT > 1 && TPB > 1);
+    constexpr bool kMixedExit = (kHalf && kPar > 1) || (!kHalf && WPT > 1 && TPB > 1) || kWindow;
     bool dead = false;
     int b;
     {
@@ -500,6 +508,31 @@ k_neighbor_force(const ForceParams<T> P) {
             dead = true;
         }
         b = dead ? 0 : P.order[P.part[x] + r];
+    }
+    // Own-row window.  The two tiles of a workgroup are consecutive entries of the XCD's run, and mostly neighbouring tiles: then the window
+    // [64·min − 64, 64·min + 192) holds 64 records on either side of their 128 targets.  Otherwise it is [64·b − 96, 64·b + 160) around the
+    // first tile, and the second reads every neighbour through the texture path.  The window is clipped to [0, N): moved to start at
+    // max(0, min(w0, N − 256)), so that it never reaches below record 0 or beyond record N − 1 (a handle of fewer than 256 particles: [0, 256),
+    // whose records beyond N − 1 nobody asks for).  Each wave stages 64 records, one per lane (two coalesced 16-byte loads; indices beyond N − 1
+    // read zeros through the descriptor); the workgroup barrier in front of phase 1 publishes them.  The window holds the record set the pass
+    // reads (predictor: A, corrector: H), which no wave of the launch writes.
+    // `win_r`: record offset of the window's first record; `win_len`: its length in bytes, 0 for a tile without a window.  A neighbour j is in
+    // the window iff (j·32 − win_r) mod 2³² < win_len: record offsets j·32 < N·32 ≤ 2³² (the descriptor's byte range) and win_r ≤ N·32 − 8 192,
+    // so a j below the window maps to at least 2³² − win_r ≥ 8 192 — no neighbour index wraps into it, whatever N.
+    __shared__ V4 s_win[kWindow ? 2 * kWinRecords : 1];
+    [[maybe_unused]] unsigned win_r = 0u, win_len = 0u;
+    [[maybe_unused]] V4 win0, win1;
+    if constexpr (kWindow) {
+        const int x = blockIdx.x & 7, r0 = (int)(blockIdx.x >> 3) * TPB, n = P.part[8 + x];
+        if (r0 >= n) return;                                      // (no tile of this block exists: the whole workgroup leaves)
+        const int b0 = P.order[P.part[x] + r0], b1 = r0 + 1 < n ? P.order[P.part[x] + r0 + 1] : -2;
+        const bool adjacent = b1 == b0 + 1 || b1 == b0 - 1;
+        const int w0 = max(0, min(adjacent ? kWave * min(b0, b1) - kWave : kWave * b0 - 96, P.N - kWinRecords));
+        win_r = (unsigned)w0 << 5;
+        win_len = (adjacent || tib == 0) ? (unsigned)(kWinRecords * 32) : 0u;
+        const unsigned g = (unsigned)(w0 + kWave * wvb + lane) << 5;
+        const __amdgpu_buffer_rsrc_t rsw = __builtin_amdgcn_make_buffer_rsrc((void*)P.src0.p, 0, (int)((unsigned)P.N * 2u * (unsigned)sizeof(V4)), 0x00020000);
+        win0 = gather_packet(rsw, g, 0, T()); win1 = gather_packet(rsw, g, 1, T());
     }
     // kHalf (tiles of two waves): wave w serves targets 32w … 32w+31 of the tile, TWO LANES PER TARGET — lane l and lane l + 32 hold the
     // same target and take alternate groups of four candidates of every chunk (what the matrix layout hands each lane half anyway: one
@@ -956,7 +989,23 @@ k_neighbor_force(const ForceParams<T> P) {
             // DIAGNOSTIC BUILD (wrong results): the arithmetic without the gathers — the floor set by the vector ALU
             if (v) { n0 = q0; n1 = q1; n0.x += __uint_as_float(jr) * T(1e-30); n0.y += T(0.003); n0.w = q0.w + T(1); }
 #else
-            { if (v) { n0 = gather_packet(rs0, jr, 0, T()); n1 = gather_packet(rs0, jr, 1, T()); } }
+            if constexpr (kWindow) {
+                // a neighbour inside the own-row window: two ds_read_b128 at its offset in the window (the window's LDS address folds
+                // into their immediate offsets); the others gather.  Each branch is skipped when no lane takes it, so an iteration
+                // whose lanes all read the window costs the texture path nothing.
+                const unsigned wo = jr - win_r;
+                const bool in_win = wo < win_len;
+#ifdef SPHMI_STATS
+                st_ref += __builtin_popcountll(__builtin_amdgcn_ballot_w64(v && in_win));
+                st_emp += (__builtin_amdgcn_ballot_w64(v && !in_win) == 0 && __builtin_amdgcn_ballot_w64(v) != 0) ? 1 : 0;
+#endif
+                if (v) {
+                    if (in_win) {
+                        const char* const w = reinterpret_cast<const char*>(s_win) + wo;
+                        n0 = *reinterpret_cast<const V4*>(w); n1 = *reinterpret_cast<const V4*>(w + 16);
+                    } else { n0 = gather_packet(rs0, jr, 0, T()); n1 = gather_packet(rs0, jr, 1, T()); }
+                }
+            } else { if (v) { n0 = gather_packet(rs0, jr, 0, T()); n1 = gather_packet(rs0, jr, 1, T()); } }
 #endif
             // 2. while they fly: the next pair of this lane — refill when the mask is used up, lowest set bit, record offset
             unsigned m = cm;
@@ -1205,8 +1254,17 @@ k_neighbor_force(const ForceParams<T> P) {
             for (int seg = 0; seg < NSEG; ++seg) s_rng_w[seg * kWave] = rg[seg];
         }
     }
+    if constexpr (kWindow) {
+        // (every wave of the workgroup, dead ones included, stages its 64 records and reaches this barrier)
+        V4* const w = s_win + 2 * (kWave * wvb + lane);
+        w[0] = win0; w[1] = win1;
+        __syncthreads();
+    }
 #pragma unroll 1
-    for (int seg = 0; seg < nseg; ++seg) {
+    for (int s = 0; s < nseg; ++s) {
+        // (kWindow: the own row first, so that the entries the window serves sit at the head of every lane's queue and are consumed
+        // together, in iterations where no lane gathers)
+        const int seg = kWindow ? (s + NSEG / 2) % NSEG : s;
         // the three x-adjacent cells of a row are one contiguous index range (x is the fastest sort axis)
         int lo_l, hi_l;
         if constexpr (kShareRanges) { const int2 rg = s_rng[seg * kWave + lane]; lo_l = rg.x; hi_l = rg.y; }
