@@ -39,6 +39,8 @@ extern "C" {
 
 #define SPHMI_ABI_VERSION 5
 #define SPHMI_MAX_DEVICES 16
+#define SPHMI_MAX_COLUMNS 16
+#define SPHMI_MAX_COLUMN_ROW_BYTES 64
 
 /* status codes */
 enum {
@@ -208,6 +210,29 @@ int sphmi_download_kernel_output(sphmi_handle* h, void* kernel, void* kernel_gra
  * column that travels with the particles); multi-device handles derive it from the ID column.  Not for rank-mode handles.
  */
 int sphmi_download_permutation(sphmi_handle* h, int64_t* prev_row);
+
+/*
+ * The caller's passive columns on the device: the fields of the StructArray the engine does not carry (ChunkID, GravityFactor,
+ * MotionLimiter, BoundaryBool, GhostNormals, Kernel / KernelGradient without StoreKernelOutput) and any user column, attached
+ * once and delivered with every output in the current cell-sorted order — the permutation never visits the host.
+ *   attach: after sphmi_upload / sphmi_generate_dam_break_3d, at any later time too.  columns[c] holds n_particles x row_bytes[c]
+ *     opaque bytes; row r belongs to the particle that is row r of what sphmi_download would deliver NOW.  The data are copied: the
+ *     caller may free them on return.  1 <= row_bytes[c] <= SPHMI_MAX_COLUMN_ROW_BYTES (any value), n_columns <= SPHMI_MAX_COLUMNS.
+ *     A second call replaces the set, n_columns = 0 detaches; sphmi_upload and the generator detach (a new particle set).
+ *   download: columns_out[c] receives column c in the current order; a NULL entry skips that column.  begin / end, page-locked
+ *     (sphmi_host_register) against bounce-buffer targets: exactly as sphmi_download_begin.  sphmi_download_columns_begin may be
+ *     called on its own or directly after sphmi_download_begin; it then neither completes nor waits for the pending field
+ *     download: both snapshots are taken in stream order with no step between them — row i of every column is the particle of
+ *     row i of every field — and ONE sphmi_download_end completes both.  sphmi_download_columns = begin + sphmi_download_end.
+ *   sphmi_download_permutation is independent: called any number of times or never, it does not change what the columns
+ *     deliver, and a column download does not move its epoch.
+ *   SPHMI_ERR_STATE: before the upload; download with nothing attached; rank-mode handles (a process holds one slab of the rows).
+ *   SPHMI_ERR_ARGUMENT: null table, n_columns or a row_bytes out of range, a null column in attach.
+ * Multi-device handles of one process keep the attached columns on the host (they merge every download there anyway).
+ */
+int sphmi_attach_columns(sphmi_handle* h, int32_t n_columns, const void* const* columns, const int32_t* row_bytes);
+int sphmi_download_columns_begin(sphmi_handle* h, void* const* columns_out);
+int sphmi_download_columns(sphmi_handle* h, void* const* columns_out);
 
 /*
  * MotionDetails of the Geometry with this GroupMarker (src/SimulationGeometry.jl:17-22): particles of Type Moving

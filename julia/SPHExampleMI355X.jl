@@ -11,12 +11,13 @@
 # Zero / ZeroGravityLinear / Linear / Complex density diffusion and leaves user-defined SPHViscosity / SPHDensityDiffusion
 # subtypes (example/Dambreak2dMDBC.jl:46-66) on the CPU path — no method is overwritten.
 #
-# What one call costs on the host (round 3): the device → host copies of the fields the engine carries
-# (sphmi_download_begin … _end, straight into the columns of the StructArray, which are page-locked once), ONE gather per
-# passive column with the permutation the engine hands over (sphmi_download_permutation: the reference's sort! permutes all
-# 17 columns, src/SPHCellList.jl:142; the engine carries ten) — no sortperm, no per-particle loop: Type, GravityFactor,
-# MotionLimiter and BoundaryBool are per-particle constants and follow the same gather, Cells are written in place
-# (a CartesianIndex{D} is D Int64s).  The gathers run while the copies are in flight.
+# What one call costs on the host: the device → host copies of the fields the engine carries (sphmi_download_begin … _end,
+# straight into the columns of the StructArray, which are page-locked once) and of the passive columns — the reference's sort!
+# permutes all 17 columns, src/SPHCellList.jl:142; the engine carries ten and keeps the others (Type, GravityFactor,
+# MotionLimiter, BoundaryBool, GhostNormals, ChunkID, Kernel / KernelGradient without StoreKernelOutput) on the device as opaque
+# attached columns (sphmi_attach_columns once, sphmi_download_columns_begin per output): no sortperm, no gather, no per-particle
+# loop on the host.  Cells are written in place (a CartesianIndex{D} is D Int64s).  SPHMI_COLUMNS=0 keeps the earlier path: the
+# sort as a permutation (sphmi_download_permutation) and ONE host gather per passive column while the copies are in flight.
 #
 # Environment: SPHMI_LIB (path of libsphmi.so), SPHMI_DEVICE_FLOAT_BYTES (0, default = the library chooses — fp32 kernels when every
 # term of the path is continuous: the kernel vanishes at its cut-off, SimKernel.k >= 2, and BMode is NoMDBC (Dambreak3d.jl); fp64
@@ -64,6 +65,8 @@ mutable struct Session
     calls::Vector{Int64}
     perm::Vector{Int}                    # the same, 1-based
     ucells::Vector{Int64}
+    columns::Vector{Any}                 # the passive columns attached to the engine (empty under SPHMI_COLUMNS=0)
+    colptrs::Vector{Ptr{Cvoid}}          # their addresses: the table sphmi_download_columns_begin receives
 end
 const SESSIONS = IdDict{Any,Session}()            # SimParticles (identity) → session
 atexit(() -> foreach(s -> ccall((:sphmi_destroy, LIB), Cint, (Ptr{Cvoid},), s.h), values(SESSIONS)))
@@ -110,7 +113,21 @@ function open_session(SimDensityDiffusion, SimViscosity, SimKernel, SimMetaData:
         pin(h, a)
     end
     B <: SimpleMDBC && pin(h, P.GhostPoints)
-    return Session(h, Vector{Int64}(undef, N), zeros(8), zeros(Int64, 8), Vector{Int}(undef, N), Vector{Int64}(undef, SimMetaData.ExportGridCells ? N * D : 0))
+    # the columns the engine does not carry ride on the device as opaque rows (the arrays of the StructArray keep their addresses)
+    columns = Any[]
+    if get(ENV, "SPHMI_COLUMNS", "1") != "0"
+        append!(columns, (P.GravityFactor, P.MotionLimiter, P.BoundaryBool, P.GhostNormals, P.ChunkID, P.Type))
+        K <: StoreKernelOutput || append!(columns, (P.Kernel, P.KernelGradient))
+    end
+    colptrs = Ptr{Cvoid}[Ptr{Cvoid}(pointer(a)) for a in columns]
+    if !isempty(columns)
+        widths = Int32[Int32(sizeof(eltype(a))) for a in columns]
+        GC.@preserve columns colptrs widths check(h, ccall((:sphmi_attach_columns, LIB), Cint, (Ptr{Cvoid}, Int32, Ptr{Ptr{Cvoid}}, Ptr{Int32}),
+                                                          h, Int32(length(columns)), pointer(colptrs), pointer(widths)))
+        foreach(a -> pin(h, a), columns)
+    end
+    return Session(h, Vector{Int64}(undef, N), zeros(8), zeros(Int64, 8), Vector{Int}(undef, N), Vector{Int64}(undef, SimMetaData.ExportGridCells ? N * D : 0),
+                   columns, colptrs)
     catch
         ccall((:sphmi_destroy, LIB), Cint, (Ptr{Cvoid},), h)
         rethrow()
@@ -158,16 +175,20 @@ function SimulationLoop(SimDensityDiffusion::BuiltinDDT, SimViscosity::BuiltinVi
             h, pointer(P.Position), pointer(P.Velocity), pointer(P.Acceleration), pointer(P.Density), pointer(P.Pressure),
             pointer(P.ID), C_NULL, pointer(P.GroupMarker), B <: SimpleMDBC ? pointer(P.GhostPoints) : C_NULL,
             Ptr{Int64}(pointer(P.Cells))))
-        # while they are in flight: the sort as a permutation, and one gather per passive column
-        check(h, ccall((:sphmi_download_permutation, LIB), Cint, (Ptr{Cvoid}, Ptr{Int64}), h, pointer(s.prev_row)))
-        s.perm .= s.prev_row .+ 1
-        for col in (P.Type, P.GravityFactor, P.MotionLimiter, P.BoundaryBool, P.GhostNormals, P.ChunkID)
-            permute_column!(col, s.perm)
+        if !isempty(s.columns)
+            # the passive columns: a second snapshot of the same rows (no step in between), copied like the fields
+            check(h, ccall((:sphmi_download_columns_begin, LIB), Cint, (Ptr{Cvoid}, Ptr{Ptr{Cvoid}}), h, pointer(s.colptrs)))
+        else
+            # SPHMI_COLUMNS=0 — while the copies are in flight: the sort as a permutation, and one gather per passive column
+            check(h, ccall((:sphmi_download_permutation, LIB), Cint, (Ptr{Cvoid}, Ptr{Int64}), h, pointer(s.prev_row)))
+            s.perm .= s.prev_row .+ 1
+            for col in (P.Type, P.GravityFactor, P.MotionLimiter, P.BoundaryBool, P.GhostNormals, P.ChunkID)
+                permute_column!(col, s.perm)
+            end
+            K <: StoreKernelOutput || (permute_column!(P.Kernel, s.perm); permute_column!(P.KernelGradient, s.perm))
         end
         if K <: StoreKernelOutput
             check(h, ccall((:sphmi_download_kernel_output, LIB), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}), h, pointer(P.Kernel), pointer(P.KernelGradient)))
-        else
-            permute_column!(P.Kernel, s.perm); permute_column!(P.KernelGradient, s.perm)
         end
         if SimMetaData.ExportGridCells     # UniqueCells[2:IndexCounter] for save_grid (:890-893); slot 1 is the reference's dummy entry (:145-147)
             nref = Ref{Int64}(0)

@@ -15,6 +15,8 @@ from .config import (NoMDBC, SimpleMDBC, SimulationConstants, SimulationMetaData
 
 ABI_VERSION = 5
 MAX_DEVICES = 16
+MAX_COLUMNS = 16
+MAX_COLUMN_ROW_BYTES = 64
 
 OK, ERR_ARGUMENT, ERR_DEVICE, ERR_NUMERIC, ERR_DOMAIN, ERR_STATE = range(6)
 
@@ -157,6 +159,7 @@ class Backend:
                 None if GroupMarker is None else np.ascontiguousarray(GroupMarker, dtype=np.uint64),
                 self._f(GhostPoints, (N, D))]
         self._check(self._fn("upload")(self._h, *[_ptr(a) for a in keep]))
+        self._column_widths = None         # (sphmi_upload detaches the columns)
 
     def upload_particles(self, p):
         self.upload(p.Position, p.Velocity, p.Acceleration, p.Density, p.Type, p.ID, p.GroupMarker,
@@ -253,9 +256,12 @@ class Backend:
             return
         self._fn("host_register").argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
         self._pinned = getattr(self, "_pinned", [])
-        for k in ("Position", "Velocity", "Acceleration", "Density", "Pressure", "ID", "Type", "GroupMarker", "GhostPoints", "Cells"):
-            a = getattr(p, k, None)
-            if isinstance(a, np.ndarray) and a.flags.c_contiguous and a.nbytes:
+        if isinstance(p, np.ndarray) or isinstance(p, (list, tuple)):        # arbitrary arrays: the targets of download_columns
+            arrays = [p] if isinstance(p, np.ndarray) else list(p)
+        else:
+            arrays = [getattr(p, k, None) for k in ("Position", "Velocity", "Acceleration", "Density", "Pressure", "ID", "Type", "GroupMarker", "GhostPoints", "Cells")]
+        for a in arrays:
+            if isinstance(a, np.ndarray) and a.flags.c_contiguous and a.nbytes and not any(a is b for b in self._pinned):
                 self._check(self._fn("host_register")(self._h, _ptr(a), a.nbytes))
                 self._pinned.append(a)
 
@@ -285,6 +291,48 @@ class Backend:
         out = np.empty(self.N, dtype=np.int64)
         self._check(self._fn("download_permutation")(self._h, _ptr(out)))
         return out
+
+    # -- the caller's passive columns on the device (sphmi_attach_columns / sphmi_download_columns*) --------------------
+    def has_columns(self) -> bool:
+        return all(self._has(n) for n in ("attach_columns", "download_columns", "download_columns_begin"))
+
+    def _column_table(self, arrays, what):
+        arrays = list(arrays)
+        for a in arrays:
+            if a is None:
+                continue
+            if not (isinstance(a, np.ndarray) and a.flags.c_contiguous and len(a) == self.N and a.nbytes % self.N == 0):
+                raise ValueError(f"{what}: every column is a C-contiguous array of {self.N} rows")
+        return arrays, (C.c_void_p * max(len(arrays), 1))(*[None if a is None else a.ctypes.data for a in arrays])
+
+    def attach_columns(self, arrays) -> None:
+        """Hand the engine columns it does not carry: C-contiguous arrays of N rows in the order download() delivers NOW
+        (`row_bytes = a.nbytes // N`, opaque).  The data are copied; every download_columns delivers them in the then
+        current cell-sorted order.  An empty sequence detaches."""
+        arrays, table = self._column_table(arrays, "attach_columns")
+        if any(a is None for a in arrays):
+            raise ValueError("attach_columns: a column is None")
+        widths = (C.c_int32 * max(len(arrays), 1))(*[a.nbytes // self.N for a in arrays])
+        self._fn("attach_columns").argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
+        self._check(self._fn("attach_columns")(self._h, len(arrays), table, widths))
+        self._column_widths = [a.nbytes // self.N for a in arrays]
+
+    def _download_columns(self, name, outs) -> None:
+        outs, table = self._column_table(outs, name)
+        widths = getattr(self, "_column_widths", None)
+        if widths is not None and (len(outs) != len(widths) or any(a is not None and a.nbytes // self.N != w for a, w in zip(outs, widths))):
+            raise ValueError(f"{name}: the arrays do not match the attached columns")
+        self._fn(name).argtypes = [C.c_void_p, C.c_void_p]
+        self._check(self._fn(name)(self._h, table))
+
+    def download_columns(self, outs) -> None:
+        """Write the attached columns IN PLACE into `outs` (one array per attached column, None skips one)."""
+        self._download_columns("download_columns", outs)
+
+    def download_columns_begin(self, outs) -> None:
+        """Asynchronous download_columns — on its own or directly after download_into_begin: `outs` must not be touched
+        until download_end(), which completes both."""
+        self._download_columns("download_columns_begin", outs)
 
     def forces_once(self, apply_mdbc: bool = False):
         drho = np.empty(self.N, dtype=self._ft)

@@ -17,6 +17,7 @@
 #include "../../include/sphmi_internal.h"
 #include "sphmi_kernels.h"
 #include "sphmi_rebuild.h"
+#include "sphmi_columns.h"
 
 namespace sphmi {
 
@@ -110,6 +111,17 @@ struct sphmi_dd_control {
     int32_t reserved;
 };
 
+// sphmi_attach_columns: the argument errors every kind of handle reports alike
+inline void check_column_table(int32_t n_columns, const void* const* columns, const int32_t* row_bytes) {
+    if (n_columns < 0 || n_columns > kMaxColumns) throw EngineError(SPHMI_ERR_ARGUMENT, "sphmi_attach_columns: n_columns out of range [0, 16]");
+    if (n_columns == 0) return;
+    if (!columns || !row_bytes) throw EngineError(SPHMI_ERR_ARGUMENT, "sphmi_attach_columns: null table");
+    for (int c = 0; c < n_columns; ++c) {
+        if (row_bytes[c] < 1 || row_bytes[c] > kMaxColumnRowBytes) throw EngineError(SPHMI_ERR_ARGUMENT, "sphmi_attach_columns: row_bytes out of range [1, 64]");
+        if (!columns[c]) throw EngineError(SPHMI_ERR_ARGUMENT, "sphmi_attach_columns: null column");
+    }
+}
+
 struct EngineBase {
     sphmi_config cfg{};
     std::string err;
@@ -129,6 +141,8 @@ struct EngineBase {
     virtual void forces_once(int apply_mdbc, void* drhodt, void* acc) = 0;
     virtual void download_kernel_output(void* kernel, void* kernel_gradient) = 0;
     virtual void download_permutation(int64_t* prev_row) = 0;
+    virtual void attach_columns(int32_t n_columns, const void* const* columns, const int32_t* row_bytes) = 0;
+    virtual void download_columns_begin(void* const* columns_out) = 0;
     virtual void unique_cells(int64_t* out, int64_t cap, int64_t* n) = 0;
     virtual void timers(int32_t cap, const char** names, double* secs, int64_t* calls, int32_t* n) = 0;
     virtual void force_stats(int reset, double* avg_ms, int64_t* launches) = 0;
@@ -399,6 +413,7 @@ struct Engine final : EngineBase {
         if (copy_stream) { (void)hipStreamSynchronize(copy_stream); (void)hipStreamDestroy(copy_stream); (void)hipEventDestroy(ev_packed); }
         for (auto& e : host_pinned) (void)hipHostUnregister(e.first);
         (void)hipFree(out_arena);
+        (void)hipFree(col_arena); (void)hipFree(col_store); (void)hipFree(col_base[0]); (void)hipFree(col_base[1]);
         (void)hipFree(slot); (void)hipFree(tmp_idx); (void)hipFree(perm);
         for (int k = 0; k < 2; ++k) { (void)hipFree(tile_cost[k]); (void)hipFree(tile_order[k]); }
         (void)hipFree(kout_d); (void)hipFree(tile_work_d); (void)hipFree(tile_work1_d); (void)hipFree(xcd_clock_d); (void)hipHostFree(xcd_clock_h);
@@ -1208,6 +1223,7 @@ struct Engine final : EngineBase {
         else pack_host<float>(position, velocity, acceleration, density, ty, ghost_points, h0, h1, ha, hg, hc);
         for (int i = 0; i < N; ++i)
             if (!(std::fabs((double)h0[i].w) > 0.0)) throw EngineError(SPHMI_ERR_ARGUMENT, "sphmi_upload: density must be positive");
+        detach_columns();                          // a new particle set: the attached columns described the old one
         iA = 0; iH = 1; iB = 2; cur = 0;
         ghost_given = ghost_points != nullptr;
         {
@@ -1266,6 +1282,7 @@ struct Engine final : EngineBase {
         HC(hipMalloc(&flag, (size_t)M * 4)); HC(hipMalloc(&pos, (size_t)M * 4)); HC(hipMalloc(&tsum, (size_t)(ntiles + 2) * 4)); HC(hipMalloc(&tot_d, 16));
         auto release = [&]() { (void)hipFree(flag); (void)hipFree(pos); (void)hipFree(tsum); (void)hipFree(tot_d); };
         try {
+            detach_columns();
             iA = 0; iH = 1; iB = 2; cur = 0; ghost_given = false; mdbc_n_list = 0; mdbc_list_valid = false;
             int base = 0;
             const unsigned nbM = (unsigned)((M + 255) / 256);
@@ -1335,13 +1352,16 @@ struct Engine final : EngineBase {
         if (c != D && c != 3) throw EngineError(SPHMI_ERR_ARGUMENT, "sphmi_set_output_components: dims or 3");
         out_comp = c;
     }
+    void ensure_copy_stream() {
+        if (!copy_stream) { HC(hipStreamCreateWithFlags(&copy_stream, hipStreamNonBlocking)); HC(hipEventCreateWithFlags(&ev_packed, hipEventDisableTiming)); }
+    }
     // begin: snapshot every requested field into the arena IN STREAM ORDER (so later steps cannot disturb it), then
     // hand the device→host copies to a second stream; end: wait for them.  Between the two the caller may advance.
     template <class H>
     void download_begin_as(void* position, void* velocity, void* acceleration, void* density, void* pressure,
                            int64_t* ids, uint8_t* ty, uint64_t* groups, void* ghost_points, int64_t* cells) {
-        if (!copy_stream) { HC(hipStreamCreateWithFlags(&copy_stream, hipStreamNonBlocking)); HC(hipEventCreateWithFlags(&ev_packed, hipEventDisableTiming)); }
-        if (download_pending) download_end();
+        ensure_copy_stream();
+        if (download_pending || columns_pending) download_end();
         const size_t n = (size_t)N, nd = n * (size_t)out_comp, ncell_d = n * (size_t)D;
         const size_t need = (4 * nd + 2 * n) * sizeof(H) + ncell_d * 8 + n * 25 + 256 * 13;
         if (need > out_arena_bytes) {
@@ -1402,12 +1422,14 @@ struct Engine final : EngineBase {
         else download_begin_as<float>(position, velocity, acceleration, density, pressure, ids, ty, groups, ghost_points, cells);
     }
     void download_end() override {
-        if (!download_pending) return;
+        if (!download_pending && !columns_pending) return;
         HC(hipSetDevice(cfg.device));
         HC(hipStreamSynchronize(copy_stream));
-        download_pending = false;
+        download_pending = columns_pending = false;
         for (const Deferred& d : out_deferred) bounce.d2h(d.dst, d.src, d.bytes, copy_stream);
         out_deferred.clear();
+        for (const Deferred& d : col_deferred) bounce.d2h(d.dst, d.src, d.bytes, copy_stream);
+        col_deferred.clear();
     }
     void download(void* position, void* velocity, void* acceleration, void* density, void* pressure,
                   int64_t* ids, uint8_t* ty, uint64_t* groups, void* ghost_points, int64_t* cells) override {
@@ -1434,10 +1456,110 @@ struct Engine final : EngineBase {
         HC(hipSetDevice(cfg.device));
         std::vector<int> tmp((size_t)N);
         bounce.d2h(tmp.data(), prow[cur], (size_t)N * 4, stream);
+        if (col_store) {                               // attached columns: their records are found through the epoch that ends here
+            hipLaunchKernelGGL(k_columns_base_compose, dim3((N + 255) / 256), dim3(256), 0, stream, (const int*)col_base[col_cur], (const int*)prow[cur], col_base[col_cur ^ 1], N);
+            col_cur ^= 1;
+        }
         hipLaunchKernelGGL(k_iota, dim3((N + 255) / 256), dim3(256), 0, stream, prow[cur], N);
         HC(hipGetLastError());
         HC(hipStreamSynchronize(stream));
         for (int i = 0; i < N; ++i) prev_row[i] = tmp[(size_t)i];
+    }
+
+    // ---- the caller's passive columns (sphmi_columns.h): packed records in attach order, never moved ---------------------
+    uint4* col_store = nullptr;                    // N records of col_table.stride bytes
+    int* col_base[2] = {};                         // row at the last permutation epoch → record; [col_cur] is live
+    int col_cur = 0;
+    ColumnTable col_table{};                       // offsets / widths in the caller's column order (out[] is filled per download)
+    char* col_arena = nullptr; size_t col_arena_bytes = 0;      // snapshot of a column download: a pending field download keeps out_arena
+    bool columns_pending = false;
+    std::vector<Deferred> col_deferred;
+    void detach_columns() {
+        if (columns_pending) download_end();
+        if (col_store) HC(hipStreamSynchronize(stream));
+        (void)hipFree(col_store); (void)hipFree(col_base[0]); (void)hipFree(col_base[1]);
+        col_store = nullptr; col_base[0] = col_base[1] = nullptr; col_cur = 0; col_table = ColumnTable{};
+    }
+    void attach_columns(int32_t n_columns, const void* const* columns, const int32_t* row_bytes) override {
+        if (!uploaded) throw EngineError(SPHMI_ERR_STATE, "sphmi_attach_columns before sphmi_upload");
+        check_column_table(n_columns, columns, row_bytes);
+        HC(hipSetDevice(cfg.device));
+        detach_columns();
+        if (n_columns == 0) return;
+        // record layout: widths divisible by 16 first, then by 8, 4, 2, then the odd ones — no padding between columns
+        ColumnTable t{};
+        t.n_columns = n_columns;
+        int at = 0;
+        for (int align = 16; align >= 1; align >>= 1)
+            for (int c = 0; c < n_columns; ++c) {
+                const int w = row_bytes[c];
+                if (w % align == 0 && (align == 16 || w % (2 * align) != 0)) { t.offset[c] = at; t.width[c] = w; at += w; }
+            }
+        t.stride = (at + 15) & ~15;
+        t.rows_per_block = gather_rows_per_block(t.stride);
+        const size_t n = (size_t)N, S = (size_t)t.stride;
+        std::vector<char> packed(n * S, 0);
+        for (int c = 0; c < n_columns; ++c) {
+            const size_t w = (size_t)t.width[c];
+            const char* src = (const char*)columns[c];
+            char* dst = packed.data() + t.offset[c];
+            for (size_t i = 0; i < n; ++i) memcpy(dst + i * S, src + i * w, w);
+        }
+        try {
+            HC(hipMalloc(&col_store, n * S)); HC(hipMalloc(&col_base[0], n * 4)); HC(hipMalloc(&col_base[1], n * 4));
+            bounce.h2d(col_store, packed.data(), n * S, stream);
+            // row i of the attached arrays is row i of the present order: its row at the last epoch is prow[i]
+            hipLaunchKernelGGL(k_columns_base_init, dim3((N + 255) / 256), dim3(256), 0, stream, (const int*)prow[cur], col_base[0], N);
+            HC(hipGetLastError());
+            HC(hipStreamSynchronize(stream));
+        } catch (...) {
+            (void)hipFree(col_store); (void)hipFree(col_base[0]); (void)hipFree(col_base[1]);
+            col_store = nullptr; col_base[0] = col_base[1] = nullptr;
+            throw;
+        }
+        col_table = t;
+    }
+    // Like download_begin_as: the gather runs on the engine's stream (a snapshot in stream order — directly after
+    // sphmi_download_begin it sees the same rows), the device → host copies on the copy stream; a field download in flight is
+    // neither waited for nor disturbed (own arena, own list of deferred copies), one download_end completes both.
+    void download_columns_begin(void* const* columns_out) override {
+        if (!uploaded) throw EngineError(SPHMI_ERR_STATE, "sphmi_download_columns before sphmi_upload");
+        if (!col_store) throw EngineError(SPHMI_ERR_STATE, "sphmi_download_columns: no columns attached (sphmi_attach_columns)");
+        if (!columns_out) throw EngineError(SPHMI_ERR_ARGUMENT, "sphmi_download_columns: null table");
+        HC(hipSetDevice(cfg.device));
+        ensure_copy_stream();
+        if (columns_pending) download_end();
+        const size_t n = (size_t)N;
+        ColumnTable t = col_table;
+        size_t need = 0;
+        for (int c = 0; c < t.n_columns; ++c) need += (n * (size_t)t.width[c] + 255) & ~size_t(255);
+        if (need > col_arena_bytes) {
+            (void)hipFree(col_arena);
+            col_arena = nullptr; col_arena_bytes = 0;
+            HC(hipMalloc(&col_arena, need));
+            col_arena_bytes = need;
+        }
+        char* cursor = col_arena;
+        bool any = false;
+        for (int c = 0; c < t.n_columns; ++c) {
+            t.out[c] = columns_out[c] ? cursor : nullptr;
+            if (columns_out[c]) { cursor += (n * (size_t)t.width[c] + 255) & ~size_t(255); any = true; }
+        }
+        if (!any) return;
+        const int blocks = (N + t.rows_per_block - 1) / t.rows_per_block;
+        hipLaunchKernelGGL(k_gather_columns, dim3(blocks), dim3(kGatherThreads), gather_lds_bytes(t), stream, (const uint4*)col_store,
+                           (const int*)col_base[col_cur], (const int*)prow[cur], N, t);
+        HC(hipGetLastError());
+        HC(hipEventRecord(ev_packed, stream));
+        HC(hipStreamWaitEvent(copy_stream, ev_packed, 0));
+        col_deferred.clear();
+        for (int c = 0; c < t.n_columns; ++c) {
+            if (!columns_out[c]) continue;
+            const size_t bytes = n * (size_t)t.width[c];
+            if (is_registered(columns_out[c], bytes)) HC(hipMemcpyAsync(columns_out[c], t.out[c], bytes, hipMemcpyDeviceToHost, copy_stream));
+            else col_deferred.push_back({columns_out[c], t.out[c], bytes});
+        }
+        columns_pending = true;
     }
     // Pressure! + [mDBC] + ONE forces-only neighbour pass on the current cell list; {a, dρ/dt} of every particle held are left
     // in the scratch record array rec[iB] (N contiguous packets), SimParticles.Acceleration survives.  all_lists: a slab
@@ -1970,6 +2092,14 @@ int sphmi_download_kernel_output(sphmi_handle* h, void* kernel, void* kernel_gra
     SPHMI_GUARD(h, h->e->download_kernel_output(kernel, kernel_gradient));
 }
 int sphmi_download_permutation(sphmi_handle* h, int64_t* prev_row) { SPHMI_GUARD(h, h->e->download_permutation(prev_row)); }
+static_assert(SPHMI_MAX_COLUMNS == sphmi::kMaxColumns && SPHMI_MAX_COLUMN_ROW_BYTES == sphmi::kMaxColumnRowBytes, "sphmi_columns.h and sphmi.h disagree");
+int sphmi_attach_columns(sphmi_handle* h, int32_t n_columns, const void* const* columns, const int32_t* row_bytes) {
+    SPHMI_GUARD(h, h->e->attach_columns(n_columns, columns, row_bytes));
+}
+int sphmi_download_columns_begin(sphmi_handle* h, void* const* columns_out) { SPHMI_GUARD(h, h->e->download_columns_begin(columns_out)); }
+int sphmi_download_columns(sphmi_handle* h, void* const* columns_out) {
+    SPHMI_GUARD(h, (h->e->download_columns_begin(columns_out), h->e->download_end()));
+}
 int sphmi_set_motion(sphmi_handle* h, uint64_t group_marker, double velocity, double start_time, double duration,
                      const double* direction) {
     SPHMI_GUARD(h, h->e->set_motion(group_marker, velocity, start_time, duration, direction));

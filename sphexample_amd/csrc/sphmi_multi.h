@@ -906,6 +906,7 @@ struct MultiEngine final : EngineBase {
         if (cfg.mdbc != SPHMI_MDBC_NONE && !ghost_points) throw EngineError(SPHMI_ERR_ARGUMENT, "sphmi_upload: mDBC handle without ghost points");
         const int64_t N = cfg.n_particles;
         n_total = N;
+        col_data.clear(); col_width.clear(); col_base.clear();     // a new particle set: the attached columns described the old one
         SlabSetup S;
         plan_slabs(cfg, position, ghost_points, N, world, cfg.slab_axis - 1, given_plan.world() == world ? &given_plan : nullptr, 1.6, S);
         axis = S.axis; halo_width = S.halo_width; plan = S.plan;
@@ -1630,10 +1631,25 @@ struct MultiEngine final : EngineBase {
         if (!uploaded) throw EngineError(SPHMI_ERR_STATE, "sphmi_download_permutation before sphmi_upload");
         if (!prev_row) throw EngineError(SPHMI_ERR_ARGUMENT, "sphmi_download_permutation: null array");
         if (rank_mode) throw EngineError(SPHMI_ERR_STATE, "sphmi_download_permutation: one-process handles only (a rank-mode process holds one slab of the rows)");
-        if (cfg.n_particles > (int64_t)INT32_MAX) throw EngineError(SPHMI_ERR_ARGUMENT, "sphmi_download_permutation: more than 2^31 - 1 rows");
+        SlabRows sr;
+        fetch_rows("sphmi_download_permutation", sr, prev_row);
+        if (!col_data.empty()) {                     // attached columns: their rows are found through the epoch that ends here
+            std::vector<int64_t> nb(col_base.size());
+            for (size_t o = 0; o < nb.size(); ++o) nb[o] = col_base[(size_t)prev_row[o]];
+            col_base.swap(nb);
+        }
+        renumber_rows(sr);
+    }
+    // "fetch rows": the row column of every slab, merged by order tag like a download → prev_row (row at the last epoch of every
+    // present row); sr.rows[q][i] becomes the present row of slab q's particle i.  Changes nothing on the devices.
+    struct SlabRows { std::vector<std::vector<int>> rows; std::vector<size_t> ns; };
+    void fetch_rows(const char* who, SlabRows& sr, int64_t* prev_row) {
+        if (cfg.n_particles > (int64_t)INT32_MAX) throw EngineError(SPHMI_ERR_ARGUMENT, std::string(who) + ": more than 2^31 - 1 rows");
         const size_t N = (size_t)cfg.n_particles, L = R.size();
-        std::vector<std::vector<int>> rows(L); std::vector<std::vector<uint8_t>> ty(L); std::vector<std::vector<unsigned long long>> tag(L);
-        std::vector<const uint8_t*> tys(L); std::vector<const unsigned long long*> tags(L); std::vector<size_t> ns(L);
+        std::vector<std::vector<int>>& rows = sr.rows; std::vector<size_t>& ns = sr.ns;
+        rows.assign(L, {}); ns.assign(L, 0);
+        std::vector<std::vector<uint8_t>> ty(L); std::vector<std::vector<unsigned long long>> tag(L);
+        std::vector<const uint8_t*> tys(L); std::vector<const unsigned long long*> tags(L);
         for (size_t q = 0; q < L; ++q) {
             Rank& r = R[q]; HC(hipSetDevice(r.device));
             Engine<T>& e = *r.e;
@@ -1650,15 +1666,55 @@ struct MultiEngine final : EngineBase {
         std::vector<uint8_t> seen(N, 0);
         const size_t got = merged_rows(tys, tags, ns, [&](size_t o, size_t q, size_t i) {
             const int64_t v = rows[q][i];
-            if (v < 0 || (size_t)v >= N || seen[(size_t)v]) throw EngineError(SPHMI_ERR_STATE, "sphmi_download_permutation: the row column of the slabs is not a permutation");
+            if (v < 0 || (size_t)v >= N || seen[(size_t)v]) throw EngineError(SPHMI_ERR_STATE, std::string(who) + ": the row column of the slabs is not a permutation");
             seen[(size_t)v] = 1;
             prev_row[o] = v;
             rows[q][i] = (int)o;                                        // the row NOW: what the next call hands out
         });
-        if (got != N) throw EngineError(SPHMI_ERR_STATE, "sphmi_download_permutation: the handle does not hold the uploaded particle set");
-        for (size_t q = 0; q < L; ++q) {
+        if (got != N) throw EngineError(SPHMI_ERR_STATE, std::string(who) + ": the handle does not hold the uploaded particle set");
+    }
+    // "renumber": a new epoch starts — the slabs' row columns take the present rows
+    void renumber_rows(const SlabRows& sr) {
+        for (size_t q = 0; q < R.size(); ++q) {
             Rank& r = R[q]; HC(hipSetDevice(r.device));
-            if (ns[q]) r.e->bounce.h2d(r.e->prow[r.e->cur], rows[q].data(), ns[q] * 4, r.main);      // (ghost copies keep a stale row: they die at the next rebuild)
+            if (sr.ns[q]) r.e->bounce.h2d(r.e->prow[r.e->cur], sr.rows[q].data(), sr.ns[q] * 4, r.main);      // (ghost copies keep a stale row: they die at the next rebuild)
+        }
+    }
+    // The caller's passive columns (sphmi_attach_columns): this handle merges every download on the host, so it keeps the columns
+    // there — as attached, never moved — and composes the row column the slabs carry: col_base maps a row of the last permutation
+    // epoch to its attached row (download_permutation composes it), a download fetches the rows WITHOUT renumbering them — the
+    // caller's epoch stays where it is — and gathers.  The gather is done when download_columns_begin returns; a field download in
+    // flight is not disturbed (the fetch reads the slabs' live columns, not their staging).
+    std::vector<std::vector<char>> col_data; std::vector<int> col_width; std::vector<int64_t> col_base;
+    void attach_columns(int32_t n_columns, const void* const* columns, const int32_t* row_bytes) override {
+        if (rank_mode) throw EngineError(SPHMI_ERR_STATE, "sphmi_attach_columns: one-process handles only (a rank-mode process holds one slab of the rows)");
+        if (!uploaded) throw EngineError(SPHMI_ERR_STATE, "sphmi_attach_columns before sphmi_upload");
+        check_column_table(n_columns, columns, row_bytes);
+        col_data.clear(); col_width.clear(); col_base.clear();
+        if (n_columns == 0) return;
+        const size_t N = (size_t)cfg.n_particles;
+        SlabRows sr; std::vector<int64_t> prev(N);
+        fetch_rows("sphmi_attach_columns", sr, prev.data());
+        col_base.resize(N);
+        for (size_t o = 0; o < N; ++o) col_base[(size_t)prev[o]] = (int64_t)o;          // row o of the attached arrays is row o of the present order
+        for (int c = 0; c < n_columns; ++c) {
+            col_width.push_back(row_bytes[c]);
+            col_data.emplace_back((const char*)columns[c], (const char*)columns[c] + N * (size_t)row_bytes[c]);
+        }
+    }
+    void download_columns_begin(void* const* columns_out) override {
+        if (rank_mode) throw EngineError(SPHMI_ERR_STATE, "sphmi_download_columns: one-process handles only (a rank-mode process holds one slab of the rows)");
+        if (!uploaded) throw EngineError(SPHMI_ERR_STATE, "sphmi_download_columns before sphmi_upload");
+        if (col_data.empty()) throw EngineError(SPHMI_ERR_STATE, "sphmi_download_columns: no columns attached (sphmi_attach_columns)");
+        if (!columns_out) throw EngineError(SPHMI_ERR_ARGUMENT, "sphmi_download_columns: null table");
+        const size_t N = (size_t)cfg.n_particles;
+        SlabRows sr; std::vector<int64_t> prev(N);
+        fetch_rows("sphmi_download_columns", sr, prev.data());
+        for (size_t c = 0; c < col_data.size(); ++c) {
+            if (!columns_out[c]) continue;
+            const size_t w = (size_t)col_width[c];
+            const char* src = col_data[c].data(); char* dst = (char*)columns_out[c];
+            for (size_t o = 0; o < N; ++o) memcpy(dst + o * w, src + (size_t)col_base[(size_t)prev[o]] * w, w);
         }
     }
     void unique_cells(int64_t* out, int64_t cap, int64_t* n_out) override {

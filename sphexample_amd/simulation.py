@@ -9,6 +9,7 @@ Restates the bookkeeping of /root/reference/src/SPHCellList.jl:808-930 that surr
 from __future__ import annotations
 
 import copy
+import os
 from typing import Callable, List, Optional
 
 import numpy as np
@@ -21,7 +22,8 @@ from .preprocess import LoadMDBCNormals, SimParticles
 
 # Fields of the StructArray the engine does not carry (src/PreProcess.jl:114): the reference's sort! (src/SPHCellList.jl:142)
 # permutes them with everything else, so after a download they follow through the engine's own permutation
-# (sphmi_download_permutation) — one gather per field, no sort on the host.
+# (sphmi_download_permutation) — one gather per field, no sort on the host.  Backends with sphmi_attach_columns keep them on
+# the device instead and deliver them with every output (SPHMI_COLUMNS=0: the host gathers, for A/B runs).
 PASSIVE_FIELDS = ("ChunkID", "GravityFactor", "MotionLimiter", "BoundaryBool", "GhostNormals")
 
 
@@ -53,18 +55,30 @@ def RunSimulation(*, SimGeometry=None, SimMetaData: SimulationMetaData, SimConst
     eng = (backend_factory or Engine)(cfg)
     eng.upload_particles(SimParticles)
     eng.set_motions(SimGeometry)                      # MotionDefinition, src/SPHCellList.jl:846-850
+    kout = SimMetaData.KMode.__name__ == "StoreKernelOutput"
+    # the fields the engine does not carry: on the device with the particles when the backend can hold them
+    columns = None
+    if getattr(eng, "has_columns", lambda: False)() and os.environ.get("SPHMI_COLUMNS", "1") != "0":
+        columns = [getattr(SimParticles, k) for k in PASSIVE_FIELDS + (() if kout else ("Kernel", "KernelGradient"))]
+        if all(isinstance(a, np.ndarray) and a.flags.c_contiguous and len(a) == len(SimParticles) for a in columns):
+            eng.attach_columns(columns)
+        else:
+            columns = None                             # a field in another layout: the host gathers take any
     if on_output:
         eng.pin(SimParticles)                          # the same arrays receive every output
+        if columns:
+            eng.pin(columns)
     eng.set_clock(SimMetaData.Iteration, SimMetaData.TotalTime)
     time_steps: List[float] = []
     SimMetaData.OutputIterationCounter = 1                                       # :849
     if on_output:
         on_output(SimMetaData, SimParticles)                                     # :850
-    kout = SimMetaData.KMode.__name__ == "StoreKernelOutput"
 
-    def finish_output():
+    def finish_output(begin_only: bool = False):
         """The fields the engine does not carry follow the sort; a StoreKernelOutput handle hands over Kernel / KernelGradient."""
-        if eng._has("download_permutation"):
+        if columns:
+            (eng.download_columns_begin if begin_only else eng.download_columns)(columns)
+        elif eng._has("download_permutation"):
             permute_passive_fields(SimParticles, eng.download_permutation(), kernel_output=kout)
         if kout:
             SimParticles.Kernel[...], SimParticles.KernelGradient[...] = eng.kernel_output()
@@ -86,7 +100,7 @@ def RunSimulation(*, SimGeometry=None, SimMetaData: SimulationMetaData, SimConst
                 eng.download_end()
                 on_output(pending, SimParticles)
             eng.download_into_begin(SimParticles)
-            finish_output()                    # (host-side gathers on fields that are not in flight: they overlap the copies)
+            finish_output(begin_only=True)     # (attached columns: a second snapshot in flight; otherwise host-side gathers that overlap the copies)
             pending = copy.copy(SimMetaData)
             if done:
                 eng.download_end()
