@@ -91,11 +91,12 @@ template <class T, int WPT = 1, int MODEL = 0> constexpr int queue_entries() {
     // (half tiles of two / four waves per half: 8 / 10 / 12 / 16 and 6 / 8 / 10 / 12 entries within 1 % of each other from 273 to 2 482 tiles)
     if (WPT >= 8) return 8;
     if (sizeof(T) == 8) return 16;
-    // fp32 half tiles of one wave per half with a compiled-in model (the launches of 3 000 tiles and more: the bench): six.  Round 5, after the two
-    // lanes of a target had learnt to share evenly: 4 / 5 / 6 / 10 entries at 0.4161 / 0.4081 / 0.4093 / 0.4160 ms per launch at C3, five interleaved
+    // fp32 half tiles of one wave per half with a compiled-in model (the launches of 3 000 tiles and more): six.  Round 5, measured on the bench's
+    // kernels while the texture path bound them: 4 / 5 / 6 / 10 entries at 0.4161 / 0.4081 / 0.4093 / 0.4160 ms per launch at C3, five interleaved
     // repetitions — more, shorter bursts of the pair loop, whose lanes drift less apart: 8.15 instead of 7.03 M gathers per launch at 30 instead of
-    // 36 CU-cycles each, the L1 hits 81-83 % instead of 77; it is the corrector's queue that matters (predictor 6 + corrector 10: no gain).  The
+    // 36 CU-cycles each, the L1 hits 81-83 % instead of 77; it was the corrector's queue that mattered (predictor 6 + corrector 10: no gain).  The
     // run-time models lose 5-12 % with six and keep ten, every other class is within noise of its value: profiles/r05_raw/qcap_*.txt
+    // (The bench's kernels themselves — the window kernels, which the vector ALU binds since round 7 — no longer take this value: NeighborLds below.)
     if (WPT == 2 && SPHMI_LDS_STAGE == 0) return MODEL >= 0 ? 6 : 10;
     // … and of TWO waves per half (330 … 3 000 tiles: 70 k / 102 k / 159 k particles −3.3 / −1.9 / −1.3 % per step against twelve; profiles/r05_raw/qcap4_ab.txt)
     if (WPT == 4 && MODEL >= 0 && SPHMI_LDS_STAGE == 0) return 6;
@@ -110,6 +111,45 @@ enum { PASS_FORCES_ONLY = 0, PASS_PREDICTOR = 1, PASS_CORRECTOR = 2 };
 enum { kViscZero = 0, kViscArtificial = 1, kViscLaminar = 2, kViscLaminarSPS = 3 };
 enum { kDdtNone = 0, kDdtZeroGravityLinear = 1, kDdtLinear = 2, kDdtComplex = 3 };
 constexpr int kModelDefault = kViscArtificial | (kDdtLinear << 4), kModelGeneric = -1;
+
+// The LDS of one instantiation of k_neighbor_force, stated once: the per-lane queues, and the own-row window of the kernels that have one.
+//   kWindow    the window kernels: fp32, 3-D, a fused pass, the compiled-in default model, half tiles of one wave per half, two
+//              tiles per workgroup — the launches of 3 000 tiles and more, the bench's two kernels
+//   kEntries / kSlack   depth of a lane's queue, and how far below full a burst of the pair loop drains it.  The window kernels choose them
+//              here, per pass; every other class takes queue_entries() / queue_slack() above.
+//   kWorkgroupsPerCU    the four-wave workgroups a compute unit is MEANT to hold (window kernels: six = six waves per SIMD, what their
+//              69 / 80 registers allow); the static_assert next to the __shared__ arrays holds queues + window to it
+// The window kernels' queues: NINE entries drained by one, both passes (profiles/r08_queue_depth.md).  In order:
+//   Round 5 gave them six entries drained by two.  The launch then waited for the texture path, and shorter bursts of the pair loop kept the
+//   lanes of a wave closer together and the gathers cheaper: 4 / 5 / 6 / 10 entries at 0.4161 / 0.4081 / 0.4093 / 0.4160 ms per launch, ten
+//   entries issuing 7.03 M gathers at 36 CU-cycles against 8.15 M at 30 (L1 hits 77 against 81–83 %): profiles/r05_raw/qcap_*.txt, slack_*.txt.
+//   The own-row window (round 7) moved 37.5 % of the pairs to LDS reads; since then the vector ALU is the busier unit, and an iteration of the
+//   pair loop costs its ≈ 70 / 78 vector instructions whether its 64 lanes hold a pair or not.  With six entries one lane slot in four was idle
+//   (103 iterations per wave for 77.3 pairs per lane); the lane with the most neighbours bounds a half tile at 80 iterations, and
+//   tools/half_tile_balance_sim.py prices the depths in between: 6 / 2 → 98.5 iterations per half tile, 7 / 1 → 91.3, 8 / 1 → 87.8,
+//   9 / 2 → 85.4, 9 / 1 → 83.2, 10 / 1 → 80.8, 11 and more → 80.7.
+//   LDS decides what can be had: the device hands it out in blocks of 1 280 B, so nine entries + window (26 624 B → 26 880 B) are the most
+//   that six workgroups fit into 160 KB; ten and eleven entries keep five, twelve (33 280 B allocated) four.
+//   Measured, three interleaved repetitions, ms per launch / updates/s at 1.06 M particles: 6 / 2 → 0.3769 / 1.404e9; 7 / 1 → 0.3634 / 1.451e9;
+//   8 / 1 and 8 / 2 → 0.3707 / 0.3738 (with eight entries the corrector comes out at 81 registers: five waves per SIMD); 9 / 3 → 0.3622; 9 / 2 → 0.3585 / 1.473e9;
+//   **9 / 1 → 0.3567 / 1.475e9 (−5.4 % / +5.1 %)**; 10 / 1 and 11 / 1 at five workgroups → 0.3691 / 0.3705; 12 / 1 at four → 0.4023.  Per pass:
+//   predictor 6 / 2 + corrector 9 / 1 → 0.3672, predictor 9 / 1 + corrector 6 / 2 → 0.3704 — each pass gains about half; mixing the slacks 1
+//   and 2 at nine entries is within noise of either.  A sixth wave per SIMD is worth more than the last two iterations per half tile.
+constexpr int kLdsPerCU = 160 * 1024, kLdsBlock = 1280;    // gfx950: LDS per compute unit, and the block (320 dwords) a workgroup's LDS is rounded up to
+template <class T, int D, int PASS, int MODEL, int WPT, int TPB> struct NeighborLds {
+    static constexpr bool kWindow = sizeof(T) == 4 && D == 3 && PASS != PASS_FORCES_ONLY && MODEL == kModelDefault && WPT == 2 && TPB == 2 &&
+                                    SPHMI_LDS_STAGE == 0;
+    // The two-way choices below are deliberate: PREDICTOR : CORRECTOR.  The passes were measured apart (each gains about half, the corrector
+    // more) and the same geometry won both, so the arms are equal today; they stay apart because the passes differ in register head-room
+    // (69 / 80) and a future change may again want them different.
+    static constexpr int kEntries = !kWindow ? queue_entries<T, WPT, MODEL>() : PASS == PASS_PREDICTOR ? 9 : 9;
+    static constexpr int kSlack = !kWindow ? queue_slack<T, WPT, MODEL>() : PASS == PASS_PREDICTOR ? 1 : 1;
+    static constexpr int kWinRecords = 256;                 // two 16-byte packets each: 8 KB
+    static constexpr int kQueueBytes = SPHMI_LDS_STAGE ? 8 : WPT * TPB * kEntries * kWave * 8;
+    static constexpr int kWindowBytes = kWindow ? kWinRecords * 32 : 0;
+    static constexpr int kAllocatedBytes = (kQueueBytes + kWindowBytes + kLdsBlock - 1) / kLdsBlock * kLdsBlock;      // what the device sets aside per workgroup
+    static constexpr int kWorkgroupsPerCU = 6;
+};
 // bit 8 of a compiled-in model tag: the kernel is cut off BEFORE it vanishes (H = k·h with k < 2 — example/DucklingMDBC.jl: 1.5), so the
 // r² ≤ H² test of src/SPHCellList.jl:275 is applied per pair.  Round 4: DucklingMDBC ran the run-time variant for this flag alone.
 constexpr int kModelCutBit = 256, kModelDefaultCut = kModelDefault | kModelCutBit;
@@ -454,11 +494,12 @@ k_neighbor_force(const ForceParams<T> P) {
     const bool shift = MODEL >= 0 ? false : (P.shift != 0 && PASS == PASS_CORRECTOR);
     using V4 = typename Vec4<T>::type;
     constexpr int NSEG = (D == 3) ? 9 : 3;
-    constexpr int QCAP = queue_entries<T, WPT, MODEL>();         // per-lane queue of non-empty accept masks
-    constexpr int kQueueSlack = queue_slack<T, WPT, MODEL>();
+    using Lds = NeighborLds<T, D, PASS, MODEL, WPT, TPB>;
+    constexpr int QCAP = Lds::kEntries;                          // per-lane queue of non-empty accept masks
+    constexpr int kQueueSlack = Lds::kSlack;
     static_assert(QCAP >= 4 && kQueueSlack >= 1 && kQueueSlack <= QCAP - 1, "queue geometry");
     // entry = { 32-bit accept mask, record size × candidate index of its bit 0 }: 8 bytes, one ds_read_b64 per refill
-    __shared__ uint2 s_q_all[SPHMI_LDS_STAGE ? 1 : WPT * TPB * QCAP * kWave];    // [wave][entry][lane]
+    __shared__ uint2 s_q_all[Lds::kQueueBytes / 8];              // [wave][entry][lane]
     // SPHMI_LDS_STAGE: the two packets of the 64 candidates of the chunk being worked on, per wave (2 / 4 KB in fp32 / fp64)
     __shared__ V4 s_stage_all[SPHMI_LDS_STAGE ? WPT * TPB * 2 * kWave : 1];
 
@@ -485,9 +526,8 @@ k_neighbor_force(const ForceParams<T> P) {
     // row of a target's own cell (dy = dz = 0) is one index range of about ±1.5 cells around the target itself (x is the fastest sort axis),
     // so the window serves most of that row's pairs.  The launches of 3 000 tiles and more only: fp32 half tiles of one wave per half, two
     // tiles per workgroup, the compiled-in default model (the bench's kernels).
-    constexpr bool kWindow = sizeof(T) == 4 && D == 3 && PASS != PASS_FORCES_ONLY && MODEL == kModelDefault && WPT == 2 && TPB == 2 &&
-                             SPHMI_LDS_STAGE == 0;
-    constexpr int kWinRecords = 256;                        // 8 KB: 12 KB of queues + 8 KB per workgroup, below the occupancy the registers allow
+    constexpr bool kWindow = Lds::kWindow;
+    constexpr int kWinRecords = Lds::kWinRecords;
     // waves of one workgroup may leave early for DIFFERENT reasons while others go on to a workgroup barrier (see below)
     constexpr bool kMixedExit = (kHalf && kPar > 1) || (!kHalf && WPT > 1 && TPB > 1) || kWindow;
     bool dead = false;
@@ -520,6 +560,12 @@ k_neighbor_force(const ForceParams<T> P) {
     // the window iff (j·32 − win_r) mod 2³² < win_len: record offsets j·32 < N·32 ≤ 2³² (the descriptor's byte range) and win_r ≤ N·32 − 8 192,
     // so a j below the window maps to at least 2³² − win_r ≥ 8 192 — no neighbour index wraps into it, whatever N.
     __shared__ V4 s_win[kWindow ? 2 * kWinRecords : 1];
+    // Queues + window are all the LDS a window kernel holds.  Growing either array past this line costs every compute unit a resident
+    // workgroup — a wave per SIMD: decide that on a measurement and lower kWorkgroupsPerCU with it.  The device hands LDS out in blocks of
+    // 1 280 B, so it is the ROUNDED size that is held to the budget (26 624 B declared → 26 880 B × 6 = 161 280 B; ten entries, 29 440 B, keep
+    // five).  tests/test_lds_budget.py holds the size in the built code object to the same arithmetic.
+    static_assert(!kWindow || Lds::kAllocatedBytes * Lds::kWorkgroupsPerCU <= kLdsPerCU,
+                  "window kernel: queues + own-row window no longer fit the intended number of workgroups into a compute unit's 160 KB of LDS");
     [[maybe_unused]] unsigned win_r = 0u, win_len = 0u;
     [[maybe_unused]] V4 win0, win1;
     if constexpr (kWindow) {

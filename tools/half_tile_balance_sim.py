@@ -5,9 +5,12 @@ accept masks chunk by chunk in scan order and counts the pairs each of the 64 la
   interleave  the shipped split: the lane of half h takes candidates 8g + 4h + k of every 32-candidate block (what the matrix layout hands it)
   halves      the lower / upper half of the SET bits of every chunk (contiguous runs: lines stay with one lane), odd counts alternating
   ideal       half of the target's total
-and replays the queue policy (scan until a queue holds QCAP - 1 entries, pair loop until no lane holds more than QCAP - 2, drain at the end).
-Output: pair-loop iterations per half tile and the fraction of lane slots that do a pair.
-usage: python tools/half_tile_balance_sim.py [half tiles] [dp] [jitter]"""
+and replays the queue policy of the window kernels (the bench's): cell rows in the shipped order, the target's own row first; scan until a
+queue holds QCAP - 1 entries, pair loop until no lane holds more than QCAP - 1 - slack, its exit tested every second iteration as the fp32
+loop does; drain at the end.
+Output: pair-loop iterations per half tile and the fraction of lane slots that do a pair for every split at the given queue geometry
+(default: what ships), then the depth x slack table of the shipped split ("swap") that profiles/r08_queue_depth.md quotes.
+usage: python tools/half_tile_balance_sim.py [half tiles] [dp] [jitter] [entries] [slack]"""
 import os, sys
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -15,6 +18,9 @@ from sphexample_amd.cases import dam_break_3d, setup_dam_break_3d
 nsample = int(sys.argv[1]) if len(sys.argv) > 1 else 150
 dp = float(sys.argv[2]) if len(sys.argv) > 2 else 0.0085
 jit = float(sys.argv[3]) if len(sys.argv) > 3 else 0.0
+entries = int(sys.argv[4]) if len(sys.argv) > 4 else 6
+slack = int(sys.argv[5]) if len(sys.argv) > 5 else 2
+NSEG = 9
 p, s = dam_break_3d(dp), setup_dam_break_3d(dp)
 H = s.SimKernel.H
 rng = np.random.default_rng(0)
@@ -32,7 +38,8 @@ nxp = npd[0]; nxyp = npd[0] * npd[1]
 def chunk_masks(ht):
     """per chunk in scan order: bool [32 targets, 64 candidates]"""
     a = np.arange(ht * 32, min(ht * 32 + 32, N)); out = []
-    for seg in range(9):
+    for s_ in range(NSEG):
+        seg = (s_ + NSEG // 2) % NSEG                      # the shipped order: the own row (dy = dz = 0) first
         off = ((seg % 3) - 1) * nxp + ((seg // 3) - 1) * nxyp
         lo_l = cstart[key[a] + off - 1]; hi_l = cstart[key[a] + off + 2]
         LO = lo_l[0]; HI = hi_l[-1]
@@ -105,7 +112,8 @@ def lane_entries(masks, mode):
     return ent
 
 
-def simulate(ent, QCAP=10):
+def simulate(ent, QCAP=entries, slack=slack, per_test=2):
+    """per_test: iterations between two tests of the burst's exit condition (the fp32 pair loop: two)"""
     q = [[] for _ in range(64)]; cur = np.zeros(64); iters = 0; slots = 0.0
 
     def burst(keep, drain):
@@ -113,22 +121,33 @@ def simulate(ent, QCAP=10):
         while True:
             ql = np.array([len(v) for v in q])
             if not ((ql > keep).any() if not drain else ((cur > 0) | (ql > 0)).any()): break
-            for l in range(64):
-                if cur[l] <= 0 and q[l]: cur[l] = q[l].pop(0)
-            act = cur > 0
-            slots += np.minimum(cur[act], 1.0).sum(); cur[act] -= 1; cur = np.maximum(cur, 0); iters += 1
+            for _ in range(per_test):
+                for l in range(64):
+                    if cur[l] <= 0 and q[l]: cur[l] = q[l].pop(0)
+                act = cur > 0
+                slots += np.minimum(cur[act], 1.0).sum(); cur[act] -= 1; cur = np.maximum(cur, 0); iters += 1
     for e in ent:
-        if max(len(v) for v in q) > QCAP - 2: burst(QCAP - 2, False)
+        if max(len(v) for v in q) > QCAP - 2: burst(QCAP - 1 - slack, False)
         for l in range(64):
             if e[l] > 0: q[l].append(float(e[l]))
     burst(0, True)
     return iters, slots
 
 
+all_masks = [chunk_masks(ht) for ht in halves]
 for mode in ("interleave", "halves", "swap", "greedy32", "adaptive"):
     it = 0; sl = 0.0; lb = 0
-    for ht in halves:
-        ent = lane_entries(chunk_masks(ht), mode)
+    for masks in all_masks:
+        ent = lane_entries(masks, mode)
         a, b = simulate(ent); it += a; sl += b
         lb += np.ceil(np.sum(ent, axis=0).max())
     print(f"{mode:10s}: {it / nsample:6.1f} iterations per half tile, lane slots busy {sl / (64 * it):.3f}   (max-lane bound: {lb / nsample:6.1f} iterations)")
+
+print(f"\nswap, {entries} entries / slack {slack} above; depth x slack (dp = {dp}, {nsample} half tiles):")
+print("| entries / slack | iterations per half tile | lane slots busy |\n|---|---|---|")
+swap_ent = [lane_entries(masks, "swap") for masks in all_masks]
+for e_, s_ in ((6, 2), (6, 1), (7, 2), (7, 1), (8, 3), (8, 2), (8, 1), (9, 3), (9, 2), (9, 1), (10, 2), (10, 1), (11, 2), (11, 1), (12, 1)):
+    it = 0; sl = 0.0
+    for ent in swap_ent:
+        a, b = simulate(ent, e_, s_); it += a; sl += b
+    print(f"| {e_} / {s_} | {it / nsample:.1f} | {sl / (64 * it):.3f} |", flush=True)

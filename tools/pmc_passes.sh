@@ -16,6 +16,9 @@ while read -r line; do
   i=$((i+1))
   [ $i -gt ${PMC_MAX:-99} ] && break
   timeout 300 rocprofv3 --pmc $line -d $R/gpurun_out/$out/p$i -o p -- ${PMC_CMD:-python $R/bench.py --steps 6 --warmup 2 --no-cpu-baseline --no-extras --precondition-ms 0 "$@"} > $R/gpurun_out/$out/p$i.log 2>&1
+  rc=$?
+  # (a pass that fails or runs into its time limit ends the script: nothing more is started on a device that has just faulted)
+  [ $rc -eq 0 ] || { echo "### pass $i FAILED (exit $rc): $line"; exit 1; }
   db=$(find $R/gpurun_out/$out/p$i -name '*.db' | head -1)
   echo "### pass $i: $line"
   case "$line" in
