@@ -41,6 +41,7 @@ extern "C" {
 #define SPHMI_MAX_DEVICES 16
 #define SPHMI_MAX_COLUMNS 16
 #define SPHMI_MAX_COLUMN_ROW_BYTES 64
+#define SPHMI_MAX_FORCE_GROUPS 16
 
 /* status codes */
 enum {
@@ -233,6 +234,33 @@ int sphmi_download_permutation(sphmi_handle* h, int64_t* prev_row);
 int sphmi_attach_columns(sphmi_handle* h, int32_t n_columns, const void* const* columns, const int32_t* row_bytes);
 int sphmi_download_columns_begin(sphmi_handle* h, void* const* columns_out);
 int sphmi_download_columns(sphmi_handle* h, void* const* columns_out);
+
+/*
+ * The force on particle groups at STEP resolution, recorded on the device: the drag on a moving body, the impact load on a wall — an
+ * integrated load whose peaks last a few steps where an output interval has hundreds.  For every executed step and every selected
+ * GroupMarker g
+ *     F_g = m0 * sum of Acceleration[i] over the rows i of the handle with GroupMarker[i] == g
+ * with Acceleration what sphmi_download would deliver directly after that step (the corrector's value, gravity included; the reference
+ * writes it for boundary particles too).  The sum is formed in fp64 on fp32 and fp64 handles alike, in an order that depends on the
+ * particle order alone: repeated runs give the same bits.  Off by default; a handle that never enables it launches what it always did.
+ *   enable: after sphmi_upload / sphmi_generate_dam_break_3d, at any later time too.  1 <= n_groups <= SPHMI_MAX_FORCE_GROUPS distinct
+ *     markers; a marker no particle carries is legal and yields zeros.  The handle keeps the newest capacity_steps (>= 1) samples that
+ *     have not been read.  A second call replaces the selection and drops the series; n_groups = 0 disables.  sphmi_upload and the
+ *     generator disable (a new particle set), as they detach the columns.  No step waits for the host: the records of a batch of
+ *     queued steps come back with the control block the host fetches anyway.  sphmi_forces_once records nothing.
+ *   read: delivers and clears the oldest `capacity` samples recorded since the last read, oldest first: iteration_out / time_out / dt_out
+ *     [capacity] receive SimMetaData.Iteration, TotalTime (at the END of the step) and the step's dt exactly as sphmi_progress reports them
+ *     after that step, force_out [capacity x n_groups x 3] the forces (2-D handles: a zero third component); any of the four may be NULL.
+ *     *n_out: samples delivered; *n_dropped (may be NULL): samples lost since the last read because more than capacity_steps had
+ *     accumulated (the oldest go).  capacity = 0 asks: *n_out = samples waiting, nothing is delivered or cleared.
+ *   SPHMI_ERR_STATE: before the upload; read while disabled; rank-mode handles (a process holds one slab of the rows).
+ *   SPHMI_ERR_ARGUMENT: null table, n_groups out of range, duplicate markers, capacity_steps < 1, null n_out.
+ * Multi-device handles of one process: every slab sums the rows it owns (ghost copies do not count) and the handle adds the slabs'
+ * records in slab order.
+ */
+int sphmi_group_forces_enable(sphmi_handle* h, int32_t n_groups, const uint64_t* markers, int64_t capacity_steps);
+int sphmi_group_forces_read(sphmi_handle* h, int64_t capacity, int64_t* iteration_out, double* time_out, double* dt_out,
+                            double* force_out, int64_t* n_out, int64_t* n_dropped);
 
 /*
  * MotionDetails of the Geometry with this GroupMarker (src/SimulationGeometry.jl:17-22): particles of Type Moving

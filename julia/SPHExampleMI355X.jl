@@ -23,7 +23,9 @@
 # term of the path is continuous: the kernel vanishes at its cut-off, SimKernel.k >= 2, and BMode is NoMDBC (Dambreak3d.jl); fp64
 # kernels for DucklingMDBC.jl / MovingSquare2d.jl (k < 2) and every SimpleMDBC run (sphmi_auto_device_float_bytes, include/sphmi.h);
 # 4 = fp32; 8 = fp64),
-# SPHMI_DEVICES ("0" default; "0,1,2,3,4,5,6,7" = one slab per GPU, halos over RCCL — same calls, see sphmi.h).
+# SPHMI_DEVICES ("0" default; "0,1,2,3,4,5,6,7" = one slab per GPU, halos over RCCL — same calls, see sphmi.h),
+# SPHMI_GROUP_FORCES (unset by default; "1,3" = record the force on the Geometries with these GroupMarkers at every step on the
+# device — sphmi_group_forces_enable — and collect the series of a run in SPHExampleMI355X.GROUP_FORCES[SimParticles]).
 #
 # EXPERIMENTAL: the build image has no Julia, so this file has never been executed.  struct layout and ABI version
 # are asserted against the library at first use (sphmi_create refuses a mismatching struct_size / abi_version).
@@ -69,6 +71,29 @@ mutable struct Session
     colptrs::Vector{Ptr{Cvoid}}          # their addresses: the table sphmi_download_columns_begin receives
 end
 const SESSIONS = IdDict{Any,Session}()            # SimParticles (identity) → session
+# SPHMI_GROUP_FORCES: the step-resolution series of a run, appended to after every output interval and kept after the run ends —
+# iteration, time (at the end of the step), dt, and force[:, g, s] = m₀·Σ Acceleration over the rows of marker g at sample s
+mutable struct GroupForceSeries
+    markers::Vector{UInt64}
+    iteration::Vector{Int64}; time::Vector{Float64}; dt::Vector{Float64}
+    force::Array{Float64,3}              # 3 × groups × samples
+    dropped::Int64
+end
+const GROUP_FORCES = IdDict{Any,GroupForceSeries}()
+group_force_markers() = UInt64[parse(UInt64, strip(m)) for m in split(get(ENV, "SPHMI_GROUP_FORCES", ""), ",") if !isempty(strip(m))]
+
+# the samples recorded since the last call (sphmi_group_forces_read: first how many wait, then the samples themselves)
+function read_group_forces!(h, gf::GroupForceSeries)
+    n = Ref{Int64}(0); dropped = Ref{Int64}(0)
+    check(h, ccall((:sphmi_group_forces_read, LIB), Cint, (Ptr{Cvoid}, Int64, Ptr{Int64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ref{Int64}, Ref{Int64}),
+                   h, 0, C_NULL, C_NULL, C_NULL, C_NULL, n, dropped))
+    k = Int(n[]); k == 0 && return nothing
+    it = Vector{Int64}(undef, k); t = Vector{Float64}(undef, k); dt = Vector{Float64}(undef, k); f = Array{Float64,3}(undef, 3, length(gf.markers), k)
+    GC.@preserve it t dt f check(h, ccall((:sphmi_group_forces_read, LIB), Cint, (Ptr{Cvoid}, Int64, Ptr{Int64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ref{Int64}, Ref{Int64}),
+                                          h, k, pointer(it), pointer(t), pointer(dt), pointer(f), n, dropped))
+    append!(gf.iteration, it); append!(gf.time, t); append!(gf.dt, dt); gf.force = cat(gf.force, f; dims = 3); gf.dropped += dropped[]
+    return nothing
+end
 atexit(() -> foreach(s -> ccall((:sphmi_destroy, LIB), Cint, (Ptr{Cvoid},), s.h), values(SESSIONS)))
 
 function check(h, rc)
@@ -126,6 +151,12 @@ function open_session(SimDensityDiffusion, SimViscosity, SimKernel, SimMetaData:
                                                           h, Int32(length(columns)), pointer(colptrs), pointer(widths)))
         foreach(a -> pin(h, a), columns)
     end
+    markers = group_force_markers()                # opt-in: nothing is recorded, and nothing more launched, without SPHMI_GROUP_FORCES
+    if !isempty(markers)
+        GC.@preserve markers check(h, ccall((:sphmi_group_forces_enable, LIB), Cint, (Ptr{Cvoid}, Int32, Ptr{UInt64}, Int64),
+                                            h, Int32(length(markers)), pointer(markers), 1 << 20))
+        GROUP_FORCES[P] = GroupForceSeries(markers, Int64[], Float64[], Float64[], Array{Float64,3}(undef, 3, length(markers), 0), 0)
+    end
     return Session(h, Vector{Int64}(undef, N), zeros(8), zeros(Int64, 8), Vector{Int}(undef, N), Vector{Int64}(undef, SimMetaData.ExportGridCells ? N * D : 0),
                    columns, colptrs)
     catch
@@ -167,6 +198,7 @@ function SimulationLoop(SimDensityDiffusion::BuiltinDDT, SimViscosity::BuiltinVi
     SimMetaData.Iteration, SimMetaData.CurrentTimeStep, SimMetaData.TotalTime = prog.iteration, T(prog.last_dt), T(prog.total_time)
     SimMetaData.IndexCounter = prog.index_counter
     forward_timers!(SimMetaData.HourGlass, s)
+    haskey(GROUP_FORCES, P) && read_group_forces!(h, GROUP_FORCES[P])
     GC.@preserve P s begin
         # the carried fields: snapshot on the device, copies on a second stream, straight into the StructArray's columns
         # (Cells: a Vector{CartesianIndex{D}} is N·D Int64; Type is a per-particle constant and follows the gather below)

@@ -17,6 +17,7 @@ ABI_VERSION = 5
 MAX_DEVICES = 16
 MAX_COLUMNS = 16
 MAX_COLUMN_ROW_BYTES = 64
+MAX_FORCE_GROUPS = 16
 
 OK, ERR_ARGUMENT, ERR_DEVICE, ERR_NUMERIC, ERR_DOMAIN, ERR_STATE = range(6)
 
@@ -160,6 +161,7 @@ class Backend:
                 self._f(GhostPoints, (N, D))]
         self._check(self._fn("upload")(self._h, *[_ptr(a) for a in keep]))
         self._column_widths = None         # (sphmi_upload detaches the columns)
+        self._force_groups = 0             # (… and disables the group forces)
 
     def upload_particles(self, p):
         self.upload(p.Position, p.Velocity, p.Acceleration, p.Density, p.Type, p.ID, p.GroupMarker,
@@ -333,6 +335,33 @@ class Backend:
         """Asynchronous download_columns — on its own or directly after download_into_begin: `outs` must not be touched
         until download_end(), which completes both."""
         self._download_columns("download_columns_begin", outs)
+
+    # -- the per-step force on particle groups (sphmi_group_forces_enable / sphmi_group_forces_read) ---------------------
+    def has_group_forces(self) -> bool:
+        return self._has("group_forces_enable") and self._has("group_forces_read")
+
+    def group_forces_enable(self, markers, capacity: int = 4096) -> None:
+        """Record F_g = m0 * sum(Acceleration[GroupMarker == g]) of every executed step on the device, for the listed
+        GroupMarkers (at most 16, distinct); the newest `capacity` unread samples are kept.  An empty list disables."""
+        m = np.ascontiguousarray(list(markers), dtype=np.uint64)
+        self._fn("group_forces_enable").argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64]
+        self._check(self._fn("group_forces_enable")(self._h, len(m), _ptr(m) if len(m) else None, int(capacity)))
+        self._force_groups = len(m)
+
+    def group_forces_read(self):
+        """(iteration[n], time[n], dt[n], F[n, groups, 3]) of the steps executed since the last read, oldest first, and clears
+        them; `group_forces_dropped` holds how many older samples the capacity pushed out."""
+        f = self._fn("group_forces_read")
+        f.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+        n, dropped = C.c_int64(), C.c_int64()
+        self._check(f(self._h, 0, None, None, None, None, C.byref(n), C.byref(dropped)))        # capacity 0: how many are waiting
+        g = int(getattr(self, "_force_groups", 0))
+        k = max(n.value, 1)
+        it, t, dt = np.zeros(k, dtype=np.int64), np.zeros(k), np.zeros(k)
+        F = np.zeros((k, g, 3))
+        self._check(f(self._h, k, _ptr(it), _ptr(t), _ptr(dt), _ptr(F), C.byref(n), C.byref(dropped)))
+        self.group_forces_dropped = dropped.value
+        return it[:n.value], t[:n.value], dt[:n.value], F[:n.value]
 
     def forces_once(self, apply_mdbc: bool = False):
         drho = np.empty(self.N, dtype=self._ft)

@@ -8,6 +8,7 @@
 #include <cmath>
 #include <cstdio>
 #include <cstring>
+#include <deque>
 #include <limits>
 #include <stdexcept>
 #include <string>
@@ -18,6 +19,7 @@
 #include "sphmi_kernels.h"
 #include "sphmi_rebuild.h"
 #include "sphmi_columns.h"
+#include "sphmi_group_forces.h"
 
 namespace sphmi {
 
@@ -122,6 +124,54 @@ inline void check_column_table(int32_t n_columns, const void* const* columns, co
     }
 }
 
+// sphmi_group_forces_enable: the argument errors every kind of handle reports alike
+inline void check_group_table(int32_t n_groups, const uint64_t* markers, int64_t capacity_steps) {
+    if (n_groups < 0 || n_groups > kMaxForceGroups) throw EngineError(SPHMI_ERR_ARGUMENT, "sphmi_group_forces_enable: n_groups out of range [0, 16]");
+    if (n_groups == 0) return;
+    if (!markers) throw EngineError(SPHMI_ERR_ARGUMENT, "sphmi_group_forces_enable: null table");
+    if (capacity_steps < 1) throw EngineError(SPHMI_ERR_ARGUMENT, "sphmi_group_forces_enable: capacity_steps must be positive");
+    for (int a = 0; a < n_groups; ++a)
+        for (int b = 0; b < a; ++b)
+            if (markers[a] == markers[b]) throw EngineError(SPHMI_ERR_ARGUMENT, "sphmi_group_forces_enable: duplicate marker");
+}
+
+// The host side of the series: what the batches delivered since the last sphmi_group_forces_read, the newest `capacity` of it.
+struct GroupForceSeries {
+    struct Sample { int64_t iteration; double time, dt; double f[3 * kMaxForceGroups]; };
+    int n_groups = 0;
+    int64_t capacity = 0, dropped = 0;
+    std::deque<Sample> q;
+    void reset(int n, int64_t cap) { n_groups = n; capacity = cap; dropped = 0; q.clear(); }
+    void push(const Sample& s) {
+        if ((int64_t)q.size() >= capacity) { q.pop_front(); dropped += 1; }
+        q.push_back(s);
+    }
+    // one record of a device-side log (sphmi_group_forces.h)
+    static Sample decode(const double* rec, int n) {
+        Sample s{};
+        memcpy(&s.iteration, rec, 8); s.time = rec[1]; s.dt = rec[2];
+        for (int k = 0; k < 3 * n; ++k) s.f[k] = rec[kGfHeader + k];
+        return s;
+    }
+    void read(int64_t cap, int64_t* iteration, double* time, double* dt, double* force, int64_t* n_out, int64_t* n_dropped) {
+        if (!n_out) throw EngineError(SPHMI_ERR_ARGUMENT, "sphmi_group_forces_read: null n_out");
+        if (cap < 0) throw EngineError(SPHMI_ERR_ARGUMENT, "sphmi_group_forces_read: negative capacity");
+        if (cap == 0) { *n_out = (int64_t)q.size(); if (n_dropped) *n_dropped = dropped; return; }      // a question: nothing is delivered, nothing cleared
+        const int64_t n = std::min<int64_t>(cap, (int64_t)q.size());
+        for (int64_t k = 0; k < n; ++k) {
+            const Sample& s = q.front();
+            if (iteration) iteration[k] = s.iteration;
+            if (time) time[k] = s.time;
+            if (dt) dt[k] = s.dt;
+            if (force) memcpy(force + (size_t)k * 3 * n_groups, s.f, (size_t)3 * n_groups * 8);
+            q.pop_front();
+        }
+        *n_out = n;
+        if (n_dropped) *n_dropped = dropped;
+        dropped = 0;
+    }
+};
+
 struct EngineBase {
     sphmi_config cfg{};
     std::string err;
@@ -143,6 +193,8 @@ struct EngineBase {
     virtual void download_permutation(int64_t* prev_row) = 0;
     virtual void attach_columns(int32_t n_columns, const void* const* columns, const int32_t* row_bytes) = 0;
     virtual void download_columns_begin(void* const* columns_out) = 0;
+    virtual void group_forces_enable(int32_t n_groups, const uint64_t* markers, int64_t capacity_steps) = 0;
+    virtual void group_forces_read(int64_t capacity, int64_t* iteration, double* time, double* dt, double* force, int64_t* n_out, int64_t* n_dropped) = 0;
     virtual void unique_cells(int64_t* out, int64_t cap, int64_t* n) = 0;
     virtual void timers(int32_t cap, const char** names, double* secs, int64_t* calls, int32_t* n) = 0;
     virtual void force_stats(int reset, double* avg_ms, int64_t* launches) = 0;
@@ -414,6 +466,7 @@ struct Engine final : EngineBase {
         for (auto& e : host_pinned) (void)hipHostUnregister(e.first);
         (void)hipFree(out_arena);
         (void)hipFree(col_arena); (void)hipFree(col_store); (void)hipFree(col_base[0]); (void)hipFree(col_base[1]);
+        gf_release();
         (void)hipFree(slot); (void)hipFree(tmp_idx); (void)hipFree(perm);
         for (int k = 0; k < 2; ++k) { (void)hipFree(tile_cost[k]); (void)hipFree(tile_order[k]); }
         (void)hipFree(kout_d); (void)hipFree(tile_work_d); (void)hipFree(tile_work1_d); (void)hipFree(xcd_clock_d); (void)hipHostFree(xcd_clock_h);
@@ -852,6 +905,7 @@ struct Engine final : EngineBase {
         }
         have_grid = true;
         n_rebuilds += 1;
+        if (gf_on) gf_build_lists();
         sched_state = 1; sched1_state = dd_slab ? 1 : 0; resched0_pending = false; resched1_pending = false; work_valid = false;
         end_phase(ev);
     }
@@ -910,6 +964,7 @@ struct Engine final : EngineBase {
         nonempty_pending = true;               // (misc_d[0] and the run table travel with the copy of the control block at the next batch boundary)
         hipLaunchKernelGGL(k_tile_schedule_small, dim3(8), dim3(1024), 0, stream, small_sched(nullptr, 0, ctrl_cur()));
         HC(hipGetLastError());
+        if (gf_on) gf_build_lists();
         part_copy_queued = true;
         part_max[0] = part_bound(); part_max[1] = 0;
         list_tiles[0] = (N + kWave - 1) / kWave; list_tiles[1] = 0;
@@ -1082,6 +1137,7 @@ struct Engine final : EngineBase {
         Ev e2 = begin_phase(PH_PASS2);
         launch_force<PASS_CORRECTOR>(P2);                                      // :789-798
         end_phase(e2);
+        if (gf_on) gf_sample(ctrl_cur(), gf_iteration0, gf_steps_base);        // Σ Acceleration of the selected groups → the batch's log
         std::swap(iA, iB);
     }
 
@@ -1090,6 +1146,7 @@ struct Engine final : EngineBase {
         HC(hipSetDevice(cfg.device));
         delta_x = 1.0 + cfg.h;                                                // :739
         int64_t steps = 0;
+        gf_iteration0 = iteration;
         StepCtrl c{};
         c.delta_x = delta_x; c.total_time = total_time; c.t_step_start = total_time; c.t_target = t_target;
         c.max_steps = max_steps; c.last_dt = last_dt;
@@ -1115,11 +1172,13 @@ struct Engine final : EngineBase {
                 if (dx0 >= cfg.h) batch = 1;
                 else if (dx_rate > 0.0) batch = (int)std::max(1.0, std::min((double)kBatch, std::ceil((cfg.h - dx0) / dx_rate) + (fresh ? 2.0 : 1.0)));
                 if (max_steps >= 0) batch = (int)std::min<int64_t>(batch, std::max<int64_t>(max_steps - steps, 1));
+                gf_steps_base = steps;
                 for (int k = 0; k < batch; ++k) { batch_step = k; enqueue_step(); iteration += 1; }      // iteration: provisional (event sampling)
                 batch_step = -1;
                 // the block the last queued step wrote, both sets of slots (below: the bad-ρ flag), the counters and the run table of a
                 // device-side rebuild: one copy
                 HC(hipMemcpyAsync(ctl_m, ctl_d, kCtlBytes, hipMemcpyDeviceToHost, stream));
+                if (gf_on) gf_fetch(batch);                                       // … and the group-force records of the batch with it
                 // (the XCD finishing times of a sampled launch: the host-side rebuild reads them at its own synchronisation; handles that
                 // rebuild on the device have none — the shares of the next measured-work schedule would never move: 3 % on the 159 k-particle
                 // LaminarSPS case)
@@ -1132,6 +1191,7 @@ struct Engine final : EngineBase {
                 c = *ctrl_h;
                 steps = c.steps_done;
                 const int64_t executed = steps - before;
+                if (gf_on) for (int64_t k = 0; k < executed; ++k) gf_series.push(GroupForceSeries::decode(gf_record(k), gf_table.n));
                 // (control inside the predictor: the slots flipped at queue time, once per queued step; what counts is where
                 // the last EXECUTED corrector left its maxima — cancelled steps consume nothing and zero nothing)
                 if (batch_fused) rpar = rpar0 ^ (int)(executed & 1);
@@ -1224,6 +1284,7 @@ struct Engine final : EngineBase {
         for (int i = 0; i < N; ++i)
             if (!(std::fabs((double)h0[i].w) > 0.0)) throw EngineError(SPHMI_ERR_ARGUMENT, "sphmi_upload: density must be positive");
         detach_columns();                          // a new particle set: the attached columns described the old one
+        gf_disable();                              // … and so did the selected groups' row lists
         iA = 0; iH = 1; iB = 2; cur = 0;
         ghost_given = ghost_points != nullptr;
         {
@@ -1283,6 +1344,7 @@ struct Engine final : EngineBase {
         auto release = [&]() { (void)hipFree(flag); (void)hipFree(pos); (void)hipFree(tsum); (void)hipFree(tot_d); };
         try {
             detach_columns();
+            gf_disable();
             iA = 0; iH = 1; iB = 2; cur = 0; ghost_given = false; mdbc_n_list = 0; mdbc_list_valid = false;
             int base = 0;
             const unsigned nbM = (unsigned)((M + 255) / 256);
@@ -1561,6 +1623,87 @@ struct Engine final : EngineBase {
         }
         columns_pending = true;
     }
+    // ---- per-step force on particle groups (sphmi_group_forces.h) -------------------------------------------------------
+    // Off: none of the members below is touched by a step.  On: three launches behind every rebuild that permutes (the row
+    // lists), one or two behind every corrector (the sums → the batch's log), one more copy per batch boundary.
+    bool gf_on = false;
+    GroupTable gf_table{};
+    int *gf_list = nullptr, *gf_counts = nullptr, *gf_offsets = nullptr;
+    GroupListMeta* gf_meta = nullptr;
+    double *gf_partial = nullptr, *gf_log_d = nullptr, *gf_log_m = nullptr;
+    int64_t gf_iteration0 = 0, gf_steps_base = 0;
+    GroupForceSeries gf_series;
+    int gf_record_doubles() const { return kGfHeader + 3 * gf_table.n; }
+    int gf_nblk_cap() const { return (cap + 255) / 256; }
+    int gf_list_cap() const { return cap + kMaxForceGroups * kGfChunk; }
+    int gf_chunk_cap() const { return cap / kGfChunk + kMaxForceGroups + 1; }
+    const double* gf_record(int64_t k) const { return gf_log_m + (size_t)k * (size_t)gf_record_doubles(); }
+    void gf_release() {
+        (void)hipFree(gf_list); (void)hipFree(gf_counts); (void)hipFree(gf_offsets); (void)hipFree(gf_meta);
+        (void)hipFree(gf_partial); (void)hipFree(gf_log_d); (void)hipHostFree(gf_log_m);
+        gf_list = gf_counts = gf_offsets = nullptr; gf_meta = nullptr; gf_partial = gf_log_d = gf_log_m = nullptr;
+    }
+    void gf_disable() {
+        if (!gf_on) return;
+        gf_on = false; gf_table = GroupTable{}; gf_series.reset(0, 0);
+        HC(hipStreamSynchronize(stream));
+        gf_release();
+    }
+    // the device side: what a slab engine of a multi-device handle needs too (the series lives in the handle)
+    void gf_enable_device(int32_t n_groups, const uint64_t* markers) {
+        HC(hipSetDevice(cfg.device));
+        gf_disable();
+        if (n_groups == 0) return;
+        try {
+            HC(hipMalloc(&gf_list, (size_t)gf_list_cap() * 4));
+            HC(hipMalloc(&gf_counts, (size_t)kMaxForceGroups * gf_nblk_cap() * 4)); HC(hipMalloc(&gf_offsets, (size_t)kMaxForceGroups * gf_nblk_cap() * 4));
+            HC(hipMalloc(&gf_meta, sizeof(GroupListMeta))); HC(hipMemset(gf_meta, 0, sizeof(GroupListMeta)));
+            HC(hipMalloc(&gf_partial, (size_t)gf_chunk_cap() * 3 * 8));
+            HC(hipMalloc(&gf_log_d, (size_t)kBatch * kGfRecordMax * 8)); HC(hipHostMalloc(&gf_log_m, (size_t)kBatch * kGfRecordMax * 8));
+        } catch (...) { gf_release(); throw; }
+        gf_table.n = n_groups;
+        for (int g = 0; g < n_groups; ++g) gf_table.marker[g] = markers[g];
+        gf_on = true;
+        gf_build_lists();                          // the rows as they lie now; every rebuild that permutes builds them again
+        HC(hipStreamSynchronize(stream));
+    }
+    void gf_build_lists() {
+        const int nblk = (N + 255) / 256;
+        hipLaunchKernelGGL(k_gf_count, dim3(nblk), dim3(256), 0, stream, (const unsigned long long*)grp[cur], (const uint8_t*)type[cur], N, gf_table, nblk, gf_counts);
+        hipLaunchKernelGGL(k_gf_offsets, dim3(1), dim3(1024), 0, stream, (const int*)gf_counts, nblk, gf_table.n, gf_offsets, gf_meta);
+        hipLaunchKernelGGL(k_gf_fill, dim3(nblk), dim3(256), 0, stream, (const unsigned long long*)grp[cur], (const uint8_t*)type[cur], N, gf_table, nblk,
+                           (const int*)gf_offsets, gf_list, gf_list_cap());
+        HC(hipGetLastError());
+    }
+    // behind the corrector of a queued step; `ctrl`: the control block that corrector read
+    void gf_sample(const StepCtrl* ctrl, int64_t iteration0, int64_t steps_base) {
+        GroupSampleArgs A{};
+        A.ctrl = ctrl; A.list = gf_list; A.meta = gf_meta; A.partial = gf_partial; A.log = gf_log_d;
+        A.iteration0 = iteration0; A.steps_base = steps_base; A.m0 = cfg.m0;
+        A.n_groups = gf_table.n; A.N = N; A.D = D; A.record = gf_record_doubles(); A.slots = kBatch;
+        if (N <= kGfSmallRows) hipLaunchKernelGGL(k_gf_small<T>, dim3(1), dim3(kGfChunk), 0, stream, (const V4*)acc[cur], A);
+        else {
+            const int max_chunks = std::min(N / kGfChunk + gf_table.n + 1, gf_chunk_cap());
+            hipLaunchKernelGGL(k_gf_partial<T>, dim3(std::min(max_chunks, 1024)), dim3(kGfChunk), 0, stream, (const V4*)acc[cur], A, max_chunks);
+            hipLaunchKernelGGL(k_gf_final, dim3(1), dim3(64), 0, stream, A);
+        }
+        HC(hipGetLastError());
+    }
+    void gf_fetch(int batch) {
+        HC(hipMemcpyAsync(gf_log_m, gf_log_d, (size_t)std::min(batch, kBatch) * (size_t)gf_record_doubles() * 8, hipMemcpyDeviceToHost, stream));
+    }
+    void group_forces_enable(int32_t n_groups, const uint64_t* markers, int64_t capacity_steps) override {
+        if (!uploaded) throw EngineError(SPHMI_ERR_STATE, "sphmi_group_forces_enable before sphmi_upload");
+        check_group_table(n_groups, markers, capacity_steps);
+        gf_enable_device(n_groups, markers);
+        gf_series.reset(n_groups, capacity_steps);
+    }
+    void group_forces_read(int64_t capacity, int64_t* iteration_out, double* time, double* dt, double* force, int64_t* n_out, int64_t* n_dropped) override {
+        if (!uploaded) throw EngineError(SPHMI_ERR_STATE, "sphmi_group_forces_read before sphmi_upload");
+        if (!gf_on) throw EngineError(SPHMI_ERR_STATE, "sphmi_group_forces_read: sampling is not enabled (sphmi_group_forces_enable)");
+        gf_series.read(capacity, iteration_out, time, dt, force, n_out, n_dropped);
+    }
+
     // Pressure! + [mDBC] + ONE forces-only neighbour pass on the current cell list; {a, dρ/dt} of every particle held are left
     // in the scratch record array rec[iB] (N contiguous packets), SimParticles.Acceleration survives.  all_lists: a slab
     // engine runs its interior and its slab-edge tiles (the ghost layers must be current: the caller has just rebuilt).
@@ -2099,6 +2242,14 @@ int sphmi_attach_columns(sphmi_handle* h, int32_t n_columns, const void* const* 
 int sphmi_download_columns_begin(sphmi_handle* h, void* const* columns_out) { SPHMI_GUARD(h, h->e->download_columns_begin(columns_out)); }
 int sphmi_download_columns(sphmi_handle* h, void* const* columns_out) {
     SPHMI_GUARD(h, (h->e->download_columns_begin(columns_out), h->e->download_end()));
+}
+static_assert(SPHMI_MAX_FORCE_GROUPS == sphmi::kMaxForceGroups, "sphmi_group_forces.h and sphmi.h disagree");
+int sphmi_group_forces_enable(sphmi_handle* h, int32_t n_groups, const uint64_t* markers, int64_t capacity_steps) {
+    SPHMI_GUARD(h, h->e->group_forces_enable(n_groups, markers, capacity_steps));
+}
+int sphmi_group_forces_read(sphmi_handle* h, int64_t capacity, int64_t* iteration_out, double* time_out, double* dt_out, double* force_out,
+                            int64_t* n_out, int64_t* n_dropped) {
+    SPHMI_GUARD(h, h->e->group_forces_read(capacity, iteration_out, time_out, dt_out, force_out, n_out, n_dropped));
 }
 int sphmi_set_motion(sphmi_handle* h, uint64_t group_marker, double velocity, double start_time, double duration,
                      const double* direction) {

@@ -907,6 +907,7 @@ struct MultiEngine final : EngineBase {
         const int64_t N = cfg.n_particles;
         n_total = N;
         col_data.clear(); col_width.clear(); col_base.clear();     // a new particle set: the attached columns described the old one
+        gf_on = false; gf_series.reset(0, 0);                      // … and the selected groups (the slab engines are made anew below)
         SlabSetup S;
         plan_slabs(cfg, position, ghost_points, N, world, cfg.slab_axis - 1, given_plan.world() == world ? &given_plan : nullptr, 1.6, S);
         axis = S.axis; halo_width = S.halo_width; plan = S.plan;
@@ -1408,8 +1409,13 @@ struct MultiEngine final : EngineBase {
                 const double dx0 = dxl; const int64_t steps0 = steps;
                 for (int k = 0; k < batch; ++k) {
                     reductions_and_control();
-                    if (have_halo) { pass(1); pass(2); }                 // before the first rebuild there is no ghost layer to exchange
+                    if (have_halo) {                                     // before the first rebuild there is no ghost layer to exchange
+                        pass(1); pass(2);
+                        // every slab sums its OWNED rows behind its corrector (the edge tiles have joined `main`)
+                        if (gf_on) for (auto& r : R) { HC(hipSetDevice(r.device)); r.e->gf_sample(r.e->ctrl_d, iteration, steps0); }
+                    }
                 }
+                if (gf_on) for (auto& r : R) { HC(hipSetDevice(r.device)); r.e->gf_fetch(batch); }
                 for (auto& r : R) {
                     HC(hipSetDevice(r.device)); sphmi_dd_control s{}; r.e->dd_ctrl_sync(&s);
                     if (&r == &R[0]) st = s;
@@ -1424,6 +1430,7 @@ struct MultiEngine final : EngineBase {
                     }
                 }
                 steps = st.steps_done;
+                if (gf_on) gf_collect(steps - steps0);
                 total_time = st.total_time; last_dt = st.last_dt; dxl = st.delta_x;
                 const int64_t grown = (steps - steps0) + (st.need_rebuild ? 1 : 0) - (fresh && steps > steps0 ? 1 : 0);
                 if (steps > steps0) fresh = false;
@@ -1700,6 +1707,38 @@ struct MultiEngine final : EngineBase {
         for (int c = 0; c < n_columns; ++c) {
             col_width.push_back(row_bytes[c]);
             col_data.emplace_back((const char*)columns[c], (const char*)columns[c] + N * (size_t)row_bytes[c]);
+        }
+    }
+    // The per-step force on particle groups (sphmi_group_forces.h): every slab engine records the sums over the rows it owns —
+    // ghost copies do not count — and the handle adds the slabs' records of a step in slab order, in fp64.
+    bool gf_on = false; GroupForceSeries gf_series;
+    void group_forces_enable(int32_t n_groups, const uint64_t* markers, int64_t capacity_steps) override {
+        if (rank_mode) throw EngineError(SPHMI_ERR_STATE, "sphmi_group_forces_enable: one-process handles only (a rank-mode process holds one slab of the rows)");
+        if (!uploaded) throw EngineError(SPHMI_ERR_STATE, "sphmi_group_forces_enable before sphmi_upload");
+        check_group_table(n_groups, markers, capacity_steps);
+        gf_on = false; gf_series.reset(0, 0);
+        for (auto& r : R) r.e->gf_enable_device(n_groups, markers);
+        if (n_groups == 0) return;
+        gf_series.reset(n_groups, capacity_steps);
+        gf_on = true;
+    }
+    void group_forces_read(int64_t capacity, int64_t* iteration_out, double* time, double* dt, double* force, int64_t* n_out, int64_t* n_dropped) override {
+        if (rank_mode) throw EngineError(SPHMI_ERR_STATE, "sphmi_group_forces_read: one-process handles only (a rank-mode process holds one slab of the rows)");
+        if (!uploaded) throw EngineError(SPHMI_ERR_STATE, "sphmi_group_forces_read before sphmi_upload");
+        if (!gf_on) throw EngineError(SPHMI_ERR_STATE, "sphmi_group_forces_read: sampling is not enabled (sphmi_group_forces_enable)");
+        gf_series.read(capacity, iteration_out, time, dt, force, n_out, n_dropped);
+    }
+    // after the synchronisation of a batch: the records of its `executed` steps, slab by slab
+    void gf_collect(int64_t executed) {
+        const int n = gf_series.n_groups;
+        for (int64_t k = 0; k < executed; ++k) {
+            GroupForceSeries::Sample s = GroupForceSeries::decode(R[0].e->gf_record(k), n);
+            for (size_t q = 1; q < R.size(); ++q) {
+                const GroupForceSeries::Sample o = GroupForceSeries::decode(R[q].e->gf_record(k), n);
+                if (o.iteration != s.iteration) throw EngineError(SPHMI_ERR_STATE, "group forces: the slabs' records of a step do not belong together");
+                for (int c = 0; c < 3 * n; ++c) s.f[c] += o.f[c];
+            }
+            gf_series.push(s);
         }
     }
     void download_columns_begin(void* const* columns_out) override {

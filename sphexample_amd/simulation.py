@@ -42,10 +42,15 @@ def RunSimulation(*, SimGeometry=None, SimMetaData: SimulationMetaData, SimConst
                   ParticleNormalsPath: Optional[str] = None,
                   on_output: Optional[Callable[[SimulationMetaData, SimParticles], None]] = None,
                   device_float_bytes: int = 0, device: int = 0, backend_factory=None,
-                  async_output: bool = False) -> List[float]:
+                  async_output: bool = False, group_forces=None) -> List[float]:
     """Same keyword signature as the reference (src/SPHCellList.jl:808-817); returns the list of
     time steps the reference collects in ``TimeSteps`` (:823,:884).  ``SimParticles`` is updated in
-    place at every output time, in the engine's cell-sorted order, as the reference's is."""
+    place at every output time, in the engine's cell-sorted order, as the reference's is.
+
+    ``group_forces=[markers]``: the force on those particle groups is recorded on the device at every step
+    (``Backend.group_forces_enable``) and ``on_output`` is called with a third argument, the samples of the interval that ends
+    at this output, ``(iteration[n], time[n], dt[n], F[n, len(markers), 3])`` (empty arrays at the first call).  ``None``
+    (default): nothing is recorded and the callback keeps its two arguments."""
     if SimMetaData.BMode.__name__ == "SimpleMDBC":
         LoadMDBCNormals(SimParticles, ParticleNormalsPath)                       # :827
     host_bytes = SimParticles.Position.dtype.itemsize
@@ -71,8 +76,16 @@ def RunSimulation(*, SimGeometry=None, SimMetaData: SimulationMetaData, SimConst
     eng.set_clock(SimMetaData.Iteration, SimMetaData.TotalTime)
     time_steps: List[float] = []
     SimMetaData.OutputIterationCounter = 1                                       # :849
+    if group_forces is not None:
+        markers = [int(m) for m in group_forces]
+        eng.group_forces_enable(markers, capacity=1 << 20)
+        none_yet = (np.zeros(0, dtype=np.int64), np.zeros(0), np.zeros(0), np.zeros((0, len(markers), 3)))
+        emit = lambda meta, samples: on_output(meta, SimParticles, samples)      # noqa: E731
+    else:
+        none_yet = None
+        emit = lambda meta, samples: on_output(meta, SimParticles)               # noqa: E731
     if on_output:
-        on_output(SimMetaData, SimParticles)                                     # :850
+        emit(SimMetaData, none_yet)                                              # :850
 
     def finish_output(begin_only: bool = False):
         """The fields the engine does not carry follow the sort; a StoreKernelOutput handle hands over Kernel / KernelGradient."""
@@ -93,24 +106,25 @@ def RunSimulation(*, SimGeometry=None, SimMetaData: SimulationMetaData, SimConst
         time_steps.append(prog.last_dt)                                          # :884
         SimMetaData.OutputIterationCounter += 1                                  # :888
         done = SimMetaData.TotalTime > SimMetaData.SimulationTime               # :909
+        samples = eng.group_forces_read() if group_forces is not None else None  # the steps of this interval
         if on_output and async_output:
             # The copies of snapshot k run while interval k+1 is computed: the callback for k is made after the
             # NEXT advance, with the metadata captured at the snapshot.
             if pending is not None:
                 eng.download_end()
-                on_output(pending, SimParticles)
+                emit(*pending)
             eng.download_into_begin(SimParticles)
             finish_output(begin_only=True)     # (attached columns: a second snapshot in flight; otherwise host-side gathers that overlap the copies)
-            pending = copy.copy(SimMetaData)
+            pending = (copy.copy(SimMetaData), samples)
             if done:
                 eng.download_end()
-                on_output(pending, SimParticles)
+                emit(*pending)
                 break
             continue
         if on_output:
             eng.download_into(SimParticles)
             finish_output()
-            on_output(SimMetaData, SimParticles)                                 # :891-894
+            emit(SimMetaData, samples)                                           # :891-894
         if done:
             if not on_output:
                 eng.download_into(SimParticles)
