@@ -42,6 +42,7 @@ extern "C" {
 #define SPHMI_MAX_COLUMNS 16
 #define SPHMI_MAX_COLUMN_ROW_BYTES 64
 #define SPHMI_MAX_FORCE_GROUPS 16
+#define SPHMI_MAX_PROBES 1024
 
 /* status codes */
 enum {
@@ -261,6 +262,37 @@ int sphmi_download_columns(sphmi_handle* h, void* const* columns_out);
 int sphmi_group_forces_enable(sphmi_handle* h, int32_t n_groups, const uint64_t* markers, int64_t capacity_steps);
 int sphmi_group_forces_read(sphmi_handle* h, int64_t capacity, int64_t* iteration_out, double* time_out, double* dt_out,
                             double* force_out, int64_t* n_out, int64_t* n_dropped);
+
+/*
+ * Pressure, density and velocity at fixed PROBE points at STEP resolution, recorded on the device: the pressure sensors on an obstacle,
+ * the columns of points of a water-height gauge.  For every executed step and every probe p at x_p (`dims` doubles), over the rows j of
+ * the handle with Type == Fluid and |x_p - x_j|^2 <= H^2 on the state sphmi_download would deliver directly after that step:
+ *     w_j = (m0 / rho_j) * W(|x_p - x_j|)     W: the handle's kernel (Wendland C2 or CubicSpline, its alphaD and h)
+ *     n = number of such rows    S = sum w_j    SP = sum w_j P_j    Srho = sum w_j rho_j    Sv = sum w_j v_j
+ * A probe is not a particle: there is no self term and r = 0 is legal.  The sums cover EVERY Fluid row within H of the probe on the
+ * current positions, however long ago the cell list was rebuilt (the pair loop's stale lists, quirk Q1, are not reproduced here).  They
+ * are formed in fp64 on fp32 and fp64 handles alike, in an order that depends on the particle order alone: repeated runs give the same
+ * bits.  Off by default; a handle that never enables it launches what it always did.
+ *   enable: after sphmi_upload / sphmi_generate_dam_break_3d, at any later time too.  1 <= n_probes <= SPHMI_MAX_PROBES finite points,
+ *     positions[n_probes x dims]; a probe in empty space or outside the particles' bounding grid is legal and yields zeros.  The handle
+ *     keeps the newest capacity_steps (>= 1) samples that have not been read.  A second call replaces the set and drops the series;
+ *     n_probes = 0 disables.  sphmi_upload and the generator disable.  No step waits for the host: the records of a batch of queued
+ *     steps come back with the control block the host fetches anyway.  sphmi_forces_once records nothing.
+ *   read: delivers and clears the oldest `capacity` samples recorded since the last read, oldest first: iteration_out / time_out / dt_out
+ *     [capacity] as sphmi_group_forces_read; weight_out [capacity x n_probes] S, count_out [capacity x n_probes] n, pressure_out /
+ *     density_out [capacity x n_probes] SP / S and Srho / S, velocity_out [capacity x n_probes x 3] Sv / S (2-D handles: a zero third
+ *     component) - normalised on the host from the raw sums, 0 where n == 0.  S is the Shepard sum: ~1 inside the fluid, ~1/2 at a
+ *     free surface, 0 in empty space (a water level is the height at which S crosses a threshold along a column of probes).  Any output
+ *     pointer may be NULL.  *n_out, *n_dropped, capacity = 0: as sphmi_group_forces_read.
+ *   SPHMI_ERR_STATE: before the upload; read while disabled; rank-mode handles (a process holds one slab of the rows); handles with H < h.
+ *   SPHMI_ERR_ARGUMENT: null table, n_probes out of range, a non-finite coordinate, capacity_steps < 1, null n_out.
+ * Multi-device handles of one process: every slab sums the rows it owns for every probe (ghost copies do not count), the handle adds the
+ * slabs' raw sums in slab order and then normalises.  Probes and group forces may be enabled together.
+ */
+int sphmi_probes_enable(sphmi_handle* h, int32_t n_probes, const double* positions /* n_probes x dims */, int64_t capacity_steps);
+int sphmi_probes_read(sphmi_handle* h, int64_t capacity, int64_t* iteration_out, double* time_out, double* dt_out,
+                      double* weight_out, int64_t* count_out, double* pressure_out, double* density_out, double* velocity_out,
+                      int64_t* n_out, int64_t* n_dropped);
 
 /*
  * MotionDetails of the Geometry with this GroupMarker (src/SimulationGeometry.jl:17-22): particles of Type Moving

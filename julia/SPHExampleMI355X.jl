@@ -26,6 +26,8 @@
 # SPHMI_DEVICES ("0" default; "0,1,2,3,4,5,6,7" = one slab per GPU, halos over RCCL — same calls, see sphmi.h),
 # SPHMI_GROUP_FORCES (unset by default; "1,3" = record the force on the Geometries with these GroupMarkers at every step on the
 # device — sphmi_group_forces_enable — and collect the series of a run in SPHExampleMI355X.GROUP_FORCES[SimParticles]).
+# SPHMI_PROBES (unset by default; "x,y,z;x,y,z" = sample pressure, density and velocity at these fixed points at every step on the
+# device — sphmi_probes_enable, `dims` coordinates per point — and collect the series in SPHExampleMI355X.PROBES[SimParticles]).
 #
 # EXPERIMENTAL: the build image has no Julia, so this file has never been executed.  struct layout and ABI version
 # are asserted against the library at first use (sphmi_create refuses a mismatching struct_size / abi_version).
@@ -94,6 +96,37 @@ function read_group_forces!(h, gf::GroupForceSeries)
     append!(gf.iteration, it); append!(gf.time, t); append!(gf.dt, dt); gf.force = cat(gf.force, f; dims = 3); gf.dropped += dropped[]
     return nothing
 end
+# SPHMI_PROBES: the step-resolution series of a run at the probe points, bound like GROUP_FORCES — weight[p, s] = Σ wⱼ (the Shepard sum:
+# ≈1 in the fluid, ≈½ at a free surface, 0 in empty space), count[p, s] the rows within H, pressure / density[p, s] and velocity[:, p, s]
+# the w-weighted means at probe p and sample s (0 where count is 0)
+mutable struct ProbeSeries
+    positions::Matrix{Float64}           # dims × probes
+    iteration::Vector{Int64}; time::Vector{Float64}; dt::Vector{Float64}
+    weight::Matrix{Float64}; count::Matrix{Int64}; pressure::Matrix{Float64}; density::Matrix{Float64}      # probes × samples
+    velocity::Array{Float64,3}           # 3 × probes × samples
+    dropped::Int64
+end
+const PROBES = IdDict{Any,ProbeSeries}()
+function probe_positions(D)
+    pts = [parse.(Float64, strip.(split(p, ","))) for p in split(get(ENV, "SPHMI_PROBES", ""), ";") if !isempty(strip(p))]
+    all(p -> length(p) == D, pts) || error("SPHMI_PROBES: every point needs $D coordinates (\"x,y;x,y\" / \"x,y,z;x,y,z\")")
+    return isempty(pts) ? zeros(Float64, D, 0) : reduce(hcat, pts)
+end
+function read_probes!(h, pr::ProbeSeries)
+    n = Ref{Int64}(0); dropped = Ref{Int64}(0)
+    check(h, ccall((:sphmi_probes_read, LIB), Cint, (Ptr{Cvoid}, Int64, Ptr{Int64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ref{Int64}, Ref{Int64}), h, 0, C_NULL, C_NULL, C_NULL, C_NULL, C_NULL, C_NULL, C_NULL, C_NULL, n, dropped))
+    k = Int(n[]); k == 0 && return nothing
+    m = size(pr.positions, 2)
+    it = Vector{Int64}(undef, k); t = Vector{Float64}(undef, k); dt = Vector{Float64}(undef, k)
+    w = Matrix{Float64}(undef, m, k); c = Matrix{Int64}(undef, m, k); pp = Matrix{Float64}(undef, m, k); rho = Matrix{Float64}(undef, m, k)
+    v = Array{Float64,3}(undef, 3, m, k)
+    GC.@preserve it t dt w c pp rho v check(h, ccall((:sphmi_probes_read, LIB), Cint, (Ptr{Cvoid}, Int64, Ptr{Int64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ref{Int64}, Ref{Int64}),
+                                                     h, k, pointer(it), pointer(t), pointer(dt), pointer(w), pointer(c), pointer(pp), pointer(rho), pointer(v), n, dropped))
+    append!(pr.iteration, it); append!(pr.time, t); append!(pr.dt, dt)
+    pr.weight = hcat(pr.weight, w); pr.count = hcat(pr.count, c); pr.pressure = hcat(pr.pressure, pp); pr.density = hcat(pr.density, rho)
+    pr.velocity = cat(pr.velocity, v; dims = 3); pr.dropped += dropped[]
+    return nothing
+end
 atexit(() -> foreach(s -> ccall((:sphmi_destroy, LIB), Cint, (Ptr{Cvoid},), s.h), values(SESSIONS)))
 
 function check(h, rc)
@@ -157,6 +190,13 @@ function open_session(SimDensityDiffusion, SimViscosity, SimKernel, SimMetaData:
                                             h, Int32(length(markers)), pointer(markers), 1 << 20))
         GROUP_FORCES[P] = GroupForceSeries(markers, Int64[], Float64[], Float64[], Array{Float64,3}(undef, 3, length(markers), 0), 0)
     end
+    points = probe_positions(D)                    # opt-in as well: SPHMI_PROBES
+    if !isempty(points)
+        m = size(points, 2)
+        GC.@preserve points check(h, ccall((:sphmi_probes_enable, LIB), Cint, (Ptr{Cvoid}, Int32, Ptr{Float64}, Int64), h, Int32(m), pointer(points), 1 << 16))
+        PROBES[P] = ProbeSeries(points, Int64[], Float64[], Float64[], zeros(Float64, m, 0), zeros(Int64, m, 0), zeros(Float64, m, 0), zeros(Float64, m, 0),
+                                Array{Float64,3}(undef, 3, m, 0), 0)
+    end
     return Session(h, Vector{Int64}(undef, N), zeros(8), zeros(Int64, 8), Vector{Int}(undef, N), Vector{Int64}(undef, SimMetaData.ExportGridCells ? N * D : 0),
                    columns, colptrs)
     catch
@@ -199,6 +239,7 @@ function SimulationLoop(SimDensityDiffusion::BuiltinDDT, SimViscosity::BuiltinVi
     SimMetaData.IndexCounter = prog.index_counter
     forward_timers!(SimMetaData.HourGlass, s)
     haskey(GROUP_FORCES, P) && read_group_forces!(h, GROUP_FORCES[P])
+    haskey(PROBES, P) && read_probes!(h, PROBES[P])
     GC.@preserve P s begin
         # the carried fields: snapshot on the device, copies on a second stream, straight into the StructArray's columns
         # (Cells: a Vector{CartesianIndex{D}} is N·D Int64; Type is a per-particle constant and follows the gather below)

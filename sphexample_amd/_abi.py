@@ -18,6 +18,7 @@ MAX_DEVICES = 16
 MAX_COLUMNS = 16
 MAX_COLUMN_ROW_BYTES = 64
 MAX_FORCE_GROUPS = 16
+MAX_PROBES = 1024
 
 OK, ERR_ARGUMENT, ERR_DEVICE, ERR_NUMERIC, ERR_DOMAIN, ERR_STATE = range(6)
 
@@ -162,6 +163,7 @@ class Backend:
         self._check(self._fn("upload")(self._h, *[_ptr(a) for a in keep]))
         self._column_widths = None         # (sphmi_upload detaches the columns)
         self._force_groups = 0             # (… and disables the group forces)
+        self._probes = 0                   # (… and the probes)
 
     def upload_particles(self, p):
         self.upload(p.Position, p.Velocity, p.Acceleration, p.Density, p.Type, p.ID, p.GroupMarker,
@@ -362,6 +364,36 @@ class Backend:
         self._check(f(self._h, k, _ptr(it), _ptr(t), _ptr(dt), _ptr(F), C.byref(n), C.byref(dropped)))
         self.group_forces_dropped = dropped.value
         return it[:n.value], t[:n.value], dt[:n.value], F[:n.value]
+
+    # -- kernel sums at fixed probe points (sphmi_probes_enable / sphmi_probes_read) ---------------------------------------
+    def has_probes(self) -> bool:
+        return self._has("probes_enable") and self._has("probes_read")
+
+    def probes_enable(self, positions, capacity: int = 4096) -> None:
+        """Sample S = sum w_j, and the w-weighted means of Pressure, Density and Velocity over the Fluid rows within H, at the
+        fixed points `positions` [n, dims] (at most 1024) after every executed step, on the device; the newest `capacity`
+        unread samples are kept.  An empty array disables."""
+        x = np.ascontiguousarray(positions, dtype=np.float64).reshape(-1, self.D)
+        self._fn("probes_enable").argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64]
+        self._check(self._fn("probes_enable")(self._h, len(x), _ptr(x) if len(x) else None, int(capacity)))
+        self._probes = len(x)
+
+    def probes_read(self) -> dict:
+        """The steps executed since the last read, oldest first, and clears them: a dict of iteration[n], time[n], dt[n],
+        weight[n, probes] (S), count[n, probes], pressure[n, probes], density[n, probes], velocity[n, probes, 3];
+        `probes_dropped` holds how many older samples the capacity pushed out."""
+        f = self._fn("probes_read")
+        f.argtypes = [C.c_void_p, C.c_int64] + [C.c_void_p] * 8 + [C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+        n, dropped = C.c_int64(), C.c_int64()
+        self._check(f(self._h, 0, *[None] * 8, C.byref(n), C.byref(dropped)))                   # capacity 0: how many are waiting
+        m = int(getattr(self, "_probes", 0))
+        k = max(n.value, 1)
+        out = {"iteration": np.zeros(k, dtype=np.int64), "time": np.zeros(k), "dt": np.zeros(k), "weight": np.zeros((k, m)),
+               "count": np.zeros((k, m), dtype=np.int64), "pressure": np.zeros((k, m)), "density": np.zeros((k, m)),
+               "velocity": np.zeros((k, m, 3))}
+        self._check(f(self._h, k, *[_ptr(a) for a in out.values()], C.byref(n), C.byref(dropped)))
+        self.probes_dropped = dropped.value
+        return {key: a[:n.value] for key, a in out.items()}
 
     def forces_once(self, apply_mdbc: bool = False):
         drho = np.empty(self.N, dtype=self._ft)

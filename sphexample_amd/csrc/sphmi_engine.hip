@@ -20,6 +20,7 @@
 #include "sphmi_rebuild.h"
 #include "sphmi_columns.h"
 #include "sphmi_group_forces.h"
+#include "sphmi_probes.h"
 
 namespace sphmi {
 
@@ -172,6 +173,63 @@ struct GroupForceSeries {
     }
 };
 
+// sphmi_probes_enable: the argument errors every kind of handle reports alike
+inline void check_probe_table(int32_t n_probes, const double* positions, int dims, int64_t capacity_steps) {
+    if (n_probes < 0 || n_probes > kMaxProbes) throw EngineError(SPHMI_ERR_ARGUMENT, "sphmi_probes_enable: n_probes out of range [0, 1024]");
+    if (n_probes == 0) return;
+    if (!positions) throw EngineError(SPHMI_ERR_ARGUMENT, "sphmi_probes_enable: null table");
+    if (capacity_steps < 1) throw EngineError(SPHMI_ERR_ARGUMENT, "sphmi_probes_enable: capacity_steps must be positive");
+    for (int64_t k = 0; k < (int64_t)n_probes * dims; ++k)
+        if (!std::isfinite(positions[k])) throw EngineError(SPHMI_ERR_ARGUMENT, "sphmi_probes_enable: non-finite coordinate");
+}
+
+// The host side of the probe series: the RAW sums of the records (sphmi_probes.h) the batches delivered since the last
+// sphmi_probes_read, the newest `capacity` of them; the read normalises.
+struct ProbeSeries {
+    struct Sample { int64_t iteration; double time, dt; std::vector<double> v; };      // v: kPrValues per probe
+    int n_probes = 0;
+    int64_t capacity = 0, dropped = 0;
+    std::deque<Sample> q;
+    void reset(int n, int64_t cap) { n_probes = n; capacity = cap; dropped = 0; q.clear(); }
+    void push(Sample&& s) {
+        if ((int64_t)q.size() >= capacity) { q.pop_front(); dropped += 1; }
+        q.push_back(std::move(s));
+    }
+    static Sample decode(const double* rec, int n) {
+        Sample s{};
+        memcpy(&s.iteration, rec, 8); s.time = rec[1]; s.dt = rec[2];
+        s.v.assign(rec + kPrHeader, rec + kPrHeader + (size_t)kPrValues * n);
+        return s;
+    }
+    void read(int64_t cap, int64_t* iteration, double* time, double* dt, double* weight, int64_t* count, double* pressure, double* density,
+              double* velocity, int64_t* n_out, int64_t* n_dropped) {
+        if (!n_out) throw EngineError(SPHMI_ERR_ARGUMENT, "sphmi_probes_read: null n_out");
+        if (cap < 0) throw EngineError(SPHMI_ERR_ARGUMENT, "sphmi_probes_read: negative capacity");
+        if (cap == 0) { *n_out = (int64_t)q.size(); if (n_dropped) *n_dropped = dropped; return; }      // a question: nothing is delivered, nothing cleared
+        const int64_t n = std::min<int64_t>(cap, (int64_t)q.size());
+        for (int64_t k = 0; k < n; ++k) {
+            const Sample& s = q.front();
+            if (iteration) iteration[k] = s.iteration;
+            if (time) time[k] = s.time;
+            if (dt) dt[k] = s.dt;
+            for (int p = 0; p < n_probes; ++p) {
+                const double* v = s.v.data() + (size_t)kPrValues * p;
+                const size_t at = (size_t)k * n_probes + p;
+                const bool some = v[6] > 0.0 && v[0] > 0.0;              // n == 0: every value is 0
+                if (weight) weight[at] = v[0];
+                if (count) count[at] = (int64_t)v[6];
+                if (pressure) pressure[at] = some ? v[1] / v[0] : 0.0;
+                if (density) density[at] = some ? v[2] / v[0] : 0.0;
+                if (velocity) for (int d = 0; d < 3; ++d) velocity[3 * at + d] = some ? v[3 + d] / v[0] : 0.0;
+            }
+            q.pop_front();
+        }
+        *n_out = n;
+        if (n_dropped) *n_dropped = dropped;
+        dropped = 0;
+    }
+};
+
 struct EngineBase {
     sphmi_config cfg{};
     std::string err;
@@ -195,6 +253,9 @@ struct EngineBase {
     virtual void download_columns_begin(void* const* columns_out) = 0;
     virtual void group_forces_enable(int32_t n_groups, const uint64_t* markers, int64_t capacity_steps) = 0;
     virtual void group_forces_read(int64_t capacity, int64_t* iteration, double* time, double* dt, double* force, int64_t* n_out, int64_t* n_dropped) = 0;
+    virtual void probes_enable(int32_t n_probes, const double* positions, int64_t capacity_steps) = 0;
+    virtual void probes_read(int64_t capacity, int64_t* iteration, double* time, double* dt, double* weight, int64_t* count, double* pressure,
+                             double* density, double* velocity, int64_t* n_out, int64_t* n_dropped) = 0;
     virtual void unique_cells(int64_t* out, int64_t cap, int64_t* n) = 0;
     virtual void timers(int32_t cap, const char** names, double* secs, int64_t* calls, int32_t* n) = 0;
     virtual void force_stats(int reset, double* avg_ms, int64_t* launches) = 0;
@@ -466,7 +527,7 @@ struct Engine final : EngineBase {
         for (auto& e : host_pinned) (void)hipHostUnregister(e.first);
         (void)hipFree(out_arena);
         (void)hipFree(col_arena); (void)hipFree(col_store); (void)hipFree(col_base[0]); (void)hipFree(col_base[1]);
-        gf_release();
+        gf_release(); pr_release();
         (void)hipFree(slot); (void)hipFree(tmp_idx); (void)hipFree(perm);
         for (int k = 0; k < 2; ++k) { (void)hipFree(tile_cost[k]); (void)hipFree(tile_order[k]); }
         (void)hipFree(kout_d); (void)hipFree(tile_work_d); (void)hipFree(tile_work1_d); (void)hipFree(xcd_clock_d); (void)hipHostFree(xcd_clock_h);
@@ -1138,6 +1199,7 @@ struct Engine final : EngineBase {
         launch_force<PASS_CORRECTOR>(P2);                                      // :789-798
         end_phase(e2);
         if (gf_on) gf_sample(ctrl_cur(), gf_iteration0, gf_steps_base);        // Σ Acceleration of the selected groups → the batch's log
+        if (pr_on) pr_sample(ctrl_cur(), gf_iteration0, gf_steps_base, iB);    // the kernel sums at the probes, on the corrector's output set → the batch's log
         std::swap(iA, iB);
     }
 
@@ -1179,6 +1241,7 @@ struct Engine final : EngineBase {
                 // device-side rebuild: one copy
                 HC(hipMemcpyAsync(ctl_m, ctl_d, kCtlBytes, hipMemcpyDeviceToHost, stream));
                 if (gf_on) gf_fetch(batch);                                       // … and the group-force records of the batch with it
+                if (pr_on) pr_fetch(batch);                                       // … and the probe records
                 // (the XCD finishing times of a sampled launch: the host-side rebuild reads them at its own synchronisation; handles that
                 // rebuild on the device have none — the shares of the next measured-work schedule would never move: 3 % on the 159 k-particle
                 // LaminarSPS case)
@@ -1192,6 +1255,7 @@ struct Engine final : EngineBase {
                 steps = c.steps_done;
                 const int64_t executed = steps - before;
                 if (gf_on) for (int64_t k = 0; k < executed; ++k) gf_series.push(GroupForceSeries::decode(gf_record(k), gf_table.n));
+                if (pr_on) for (int64_t k = 0; k < executed; ++k) pr_series.push(ProbeSeries::decode(pr_record(k), pr_n));
                 // (control inside the predictor: the slots flipped at queue time, once per queued step; what counts is where
                 // the last EXECUTED corrector left its maxima — cancelled steps consume nothing and zero nothing)
                 if (batch_fused) rpar = rpar0 ^ (int)(executed & 1);
@@ -1285,6 +1349,7 @@ struct Engine final : EngineBase {
             if (!(std::fabs((double)h0[i].w) > 0.0)) throw EngineError(SPHMI_ERR_ARGUMENT, "sphmi_upload: density must be positive");
         detach_columns();                          // a new particle set: the attached columns described the old one
         gf_disable();                              // … and so did the selected groups' row lists
+        pr_disable();                              // … and the probes go with them
         iA = 0; iH = 1; iB = 2; cur = 0;
         ghost_given = ghost_points != nullptr;
         {
@@ -1345,6 +1410,7 @@ struct Engine final : EngineBase {
         try {
             detach_columns();
             gf_disable();
+            pr_disable();
             iA = 0; iH = 1; iB = 2; cur = 0; ghost_given = false; mdbc_n_list = 0; mdbc_list_valid = false;
             int base = 0;
             const unsigned nbM = (unsigned)((M + 255) / 256);
@@ -1702,6 +1768,70 @@ struct Engine final : EngineBase {
         if (!uploaded) throw EngineError(SPHMI_ERR_STATE, "sphmi_group_forces_read before sphmi_upload");
         if (!gf_on) throw EngineError(SPHMI_ERR_STATE, "sphmi_group_forces_read: sampling is not enabled (sphmi_group_forces_enable)");
         gf_series.read(capacity, iteration_out, time, dt, force, n_out, n_dropped);
+    }
+
+    // ---- kernel sums at fixed probe points (sphmi_probes.h) -----------------------------------------------------------------
+    // The records of a batch go where the group forces' go: a log of kBatch slots on the device, fetched with the control block
+    // (gf_iteration0 / gf_steps_base: the clock of the batch is the same for both).
+    bool pr_on = false; int pr_n = 0;
+    double *pr_pos_d = nullptr, *pr_log_d = nullptr, *pr_log_m = nullptr;
+    ProbeSeries pr_series;
+    int pr_record_doubles() const { return kPrHeader + kPrValues * pr_n; }
+    const double* pr_record(int64_t k) const { return pr_log_m + (size_t)k * (size_t)pr_record_doubles(); }
+    void pr_release() {
+        (void)hipFree(pr_pos_d); (void)hipFree(pr_log_d); (void)hipHostFree(pr_log_m);
+        pr_pos_d = pr_log_d = pr_log_m = nullptr;
+    }
+    void pr_disable() {
+        if (!pr_on) return;
+        pr_on = false; pr_n = 0; pr_series.reset(0, 0);
+        HC(hipSetDevice(cfg.device)); HC(hipStreamSynchronize(stream));
+        pr_release();
+    }
+    // the device side of sphmi_probes_enable (a multi-device handle calls it on every slab engine and keeps the series itself)
+    void pr_enable_device(int32_t n_probes, const double* positions) {
+        HC(hipSetDevice(cfg.device));
+        pr_disable();
+        if (n_probes == 0) return;
+        if (!(cfg.h <= cfg.H)) throw EngineError(SPHMI_ERR_STATE, "sphmi_probes_enable: handles with H < h are not served (the candidate cells of a probe are laid out for H + h <= 2H)");
+        std::vector<double> xyz((size_t)3 * n_probes, 0.0);
+        for (int p = 0; p < n_probes; ++p) for (int d = 0; d < D; ++d) xyz[3 * (size_t)p + d] = positions[(size_t)p * D + d];
+        const size_t rec_bytes = (size_t)(kPrHeader + kPrValues * n_probes) * 8;
+        try {
+            HC(hipMalloc(&pr_pos_d, xyz.size() * 8));
+            HC(hipMalloc(&pr_log_d, (size_t)kBatch * rec_bytes)); HC(hipHostMalloc(&pr_log_m, (size_t)kBatch * rec_bytes));
+            bounce.h2d(pr_pos_d, xyz.data(), xyz.size() * 8, stream);
+        } catch (...) { pr_release(); throw; }
+        pr_n = n_probes;
+        pr_on = true;
+    }
+    // queued behind the corrector of a step; `set`: the state set that corrector wrote
+    void pr_sample(const StepCtrl* ctrl, int64_t iteration0, int64_t steps_base, int set) {
+        ProbeSampleArgs<T> A{};
+        A.ctrl = ctrl; A.pk0 = pk0[set]; A.pk1 = pk1[set]; A.half0 = pk0[iH]; A.comp = comp[cur];
+        A.type = dd_slab ? type[cur] : nullptr; A.cstart = cstart; A.pos = pr_pos_d; A.log = pr_log_d; A.g = grid;
+        A.iteration0 = iteration0; A.steps_base = steps_base;
+        A.H_inv = cfg.H_inv; A.H2 = cfg.H2; A.h_inv = cfg.h_inv; A.reach = cfg.H + cfg.h;
+        A.alphaD = cfg.alphaD; A.m0 = cfg.m0;
+        A.rho0 = (T)cfg.rho0; A.inv_rho0 = (T)(1.0 / cfg.rho0); A.Cbe = (T)((cfg.c0 * cfg.c0 * cfg.rho0) / 7.0);
+        A.n_probes = pr_n; A.N = N; A.D = D; A.kernel = cfg.kernel; A.record = pr_record_doubles(); A.slots = kBatch;
+        hipLaunchKernelGGL(k_probe_sample<T>, dim3((pr_n + 3) / 4), dim3(256), 0, stream, A);
+        HC(hipGetLastError());
+    }
+    void pr_fetch(int batch) {
+        HC(hipMemcpyAsync(pr_log_m, pr_log_d, (size_t)std::min(batch, kBatch) * (size_t)pr_record_doubles() * 8, hipMemcpyDeviceToHost, stream));
+    }
+    void probes_enable(int32_t n_probes, const double* positions, int64_t capacity_steps) override {
+        if (!uploaded) throw EngineError(SPHMI_ERR_STATE, "sphmi_probes_enable before sphmi_upload");
+        check_probe_table(n_probes, positions, D, capacity_steps);
+        pr_enable_device(n_probes, positions);
+        pr_series.reset(n_probes, capacity_steps);
+    }
+    void probes_read(int64_t capacity, int64_t* iteration_out, double* time, double* dt, double* weight, int64_t* count, double* pressure,
+                     double* density, double* velocity, int64_t* n_out, int64_t* n_dropped) override {
+        if (!uploaded) throw EngineError(SPHMI_ERR_STATE, "sphmi_probes_read before sphmi_upload");
+        if (!pr_on) throw EngineError(SPHMI_ERR_STATE, "sphmi_probes_read: sampling is not enabled (sphmi_probes_enable)");
+        pr_series.read(capacity, iteration_out, time, dt, weight, count, pressure, density, velocity, n_out, n_dropped);
     }
 
     // Pressure! + [mDBC] + ONE forces-only neighbour pass on the current cell list; {a, dρ/dt} of every particle held are left
@@ -2246,6 +2376,14 @@ int sphmi_download_columns(sphmi_handle* h, void* const* columns_out) {
 static_assert(SPHMI_MAX_FORCE_GROUPS == sphmi::kMaxForceGroups, "sphmi_group_forces.h and sphmi.h disagree");
 int sphmi_group_forces_enable(sphmi_handle* h, int32_t n_groups, const uint64_t* markers, int64_t capacity_steps) {
     SPHMI_GUARD(h, h->e->group_forces_enable(n_groups, markers, capacity_steps));
+}
+static_assert(SPHMI_MAX_PROBES == sphmi::kMaxProbes, "sphmi_probes.h and sphmi.h disagree");
+int sphmi_probes_enable(sphmi_handle* h, int32_t n_probes, const double* positions, int64_t capacity_steps) {
+    SPHMI_GUARD(h, h->e->probes_enable(n_probes, positions, capacity_steps));
+}
+int sphmi_probes_read(sphmi_handle* h, int64_t capacity, int64_t* iteration_out, double* time_out, double* dt_out, double* weight_out,
+                      int64_t* count_out, double* pressure_out, double* density_out, double* velocity_out, int64_t* n_out, int64_t* n_dropped) {
+    SPHMI_GUARD(h, h->e->probes_read(capacity, iteration_out, time_out, dt_out, weight_out, count_out, pressure_out, density_out, velocity_out, n_out, n_dropped));
 }
 int sphmi_group_forces_read(sphmi_handle* h, int64_t capacity, int64_t* iteration_out, double* time_out, double* dt_out, double* force_out,
                             int64_t* n_out, int64_t* n_dropped) {

@@ -908,6 +908,7 @@ struct MultiEngine final : EngineBase {
         n_total = N;
         col_data.clear(); col_width.clear(); col_base.clear();     // a new particle set: the attached columns described the old one
         gf_on = false; gf_series.reset(0, 0);                      // … and the selected groups (the slab engines are made anew below)
+        pr_on = false; pr_series.reset(0, 0);                      // … and the probes
         SlabSetup S;
         plan_slabs(cfg, position, ghost_points, N, world, cfg.slab_axis - 1, given_plan.world() == world ? &given_plan : nullptr, 1.6, S);
         axis = S.axis; halo_width = S.halo_width; plan = S.plan;
@@ -1413,9 +1414,12 @@ struct MultiEngine final : EngineBase {
                         pass(1); pass(2);
                         // every slab sums its OWNED rows behind its corrector (the edge tiles have joined `main`)
                         if (gf_on) for (auto& r : R) { HC(hipSetDevice(r.device)); r.e->gf_sample(r.e->ctrl_d, iteration, steps0); }
+                        // … and the kernel sums at the probes (the corrector's output set is iA here: dd_pass has rotated the sets)
+                        if (pr_on) for (auto& r : R) { HC(hipSetDevice(r.device)); r.e->pr_sample(r.e->ctrl_d, iteration, steps0, r.e->iA); }
                     }
                 }
                 if (gf_on) for (auto& r : R) { HC(hipSetDevice(r.device)); r.e->gf_fetch(batch); }
+                if (pr_on) for (auto& r : R) { HC(hipSetDevice(r.device)); r.e->pr_fetch(batch); }
                 for (auto& r : R) {
                     HC(hipSetDevice(r.device)); sphmi_dd_control s{}; r.e->dd_ctrl_sync(&s);
                     if (&r == &R[0]) st = s;
@@ -1431,6 +1435,7 @@ struct MultiEngine final : EngineBase {
                 }
                 steps = st.steps_done;
                 if (gf_on) gf_collect(steps - steps0);
+                if (pr_on) pr_collect(steps - steps0);
                 total_time = st.total_time; last_dt = st.last_dt; dxl = st.delta_x;
                 const int64_t grown = (steps - steps0) + (st.need_rebuild ? 1 : 0) - (fresh && steps > steps0 ? 1 : 0);
                 if (steps > steps0) fresh = false;
@@ -1739,6 +1744,39 @@ struct MultiEngine final : EngineBase {
                 for (int c = 0; c < 3 * n; ++c) s.f[c] += o.f[c];
             }
             gf_series.push(s);
+        }
+    }
+    // Kernel sums at fixed probe points (sphmi_probes.h): every slab engine sums the rows it owns for every probe — a row sits in
+    // exactly one slab, ghost copies do not count — and the handle adds the slabs' RAW sums of a step in slab order; the read normalises.
+    bool pr_on = false; ProbeSeries pr_series;
+    void probes_enable(int32_t n_probes, const double* positions, int64_t capacity_steps) override {
+        if (rank_mode) throw EngineError(SPHMI_ERR_STATE, "sphmi_probes_enable: one-process handles only (a rank-mode process holds one slab of the rows)");
+        if (!uploaded) throw EngineError(SPHMI_ERR_STATE, "sphmi_probes_enable before sphmi_upload");
+        check_probe_table(n_probes, positions, cfg.dims, capacity_steps);
+        pr_on = false; pr_series.reset(0, 0);
+        for (auto& r : R) r.e->pr_enable_device(n_probes, positions);
+        if (n_probes == 0) return;
+        pr_series.reset(n_probes, capacity_steps);
+        pr_on = true;
+    }
+    void probes_read(int64_t capacity, int64_t* iteration_out, double* time, double* dt, double* weight, int64_t* count, double* pressure,
+                     double* density, double* velocity, int64_t* n_out, int64_t* n_dropped) override {
+        if (rank_mode) throw EngineError(SPHMI_ERR_STATE, "sphmi_probes_read: one-process handles only (a rank-mode process holds one slab of the rows)");
+        if (!uploaded) throw EngineError(SPHMI_ERR_STATE, "sphmi_probes_read before sphmi_upload");
+        if (!pr_on) throw EngineError(SPHMI_ERR_STATE, "sphmi_probes_read: sampling is not enabled (sphmi_probes_enable)");
+        pr_series.read(capacity, iteration_out, time, dt, weight, count, pressure, density, velocity, n_out, n_dropped);
+    }
+    // after the synchronisation of a batch: the records of its `executed` steps, slab by slab
+    void pr_collect(int64_t executed) {
+        const int n = pr_series.n_probes;
+        for (int64_t k = 0; k < executed; ++k) {
+            ProbeSeries::Sample s = ProbeSeries::decode(R[0].e->pr_record(k), n);
+            for (size_t q = 1; q < R.size(); ++q) {
+                const ProbeSeries::Sample o = ProbeSeries::decode(R[q].e->pr_record(k), n);
+                if (o.iteration != s.iteration) throw EngineError(SPHMI_ERR_STATE, "probes: the slabs' records of a step do not belong together");
+                for (size_t c = 0; c < s.v.size(); ++c) s.v[c] += o.v[c];
+            }
+            pr_series.push(std::move(s));
         }
     }
     void download_columns_begin(void* const* columns_out) override {

@@ -42,7 +42,7 @@ def RunSimulation(*, SimGeometry=None, SimMetaData: SimulationMetaData, SimConst
                   ParticleNormalsPath: Optional[str] = None,
                   on_output: Optional[Callable[[SimulationMetaData, SimParticles], None]] = None,
                   device_float_bytes: int = 0, device: int = 0, backend_factory=None,
-                  async_output: bool = False, group_forces=None) -> List[float]:
+                  async_output: bool = False, group_forces=None, probes=None) -> List[float]:
     """Same keyword signature as the reference (src/SPHCellList.jl:808-817); returns the list of
     time steps the reference collects in ``TimeSteps`` (:823,:884).  ``SimParticles`` is updated in
     place at every output time, in the engine's cell-sorted order, as the reference's is.
@@ -50,7 +50,12 @@ def RunSimulation(*, SimGeometry=None, SimMetaData: SimulationMetaData, SimConst
     ``group_forces=[markers]``: the force on those particle groups is recorded on the device at every step
     (``Backend.group_forces_enable``) and ``on_output`` is called with a third argument, the samples of the interval that ends
     at this output, ``(iteration[n], time[n], dt[n], F[n, len(markers), 3])`` (empty arrays at the first call).  ``None``
-    (default): nothing is recorded and the callback keeps its two arguments."""
+    (default): nothing is recorded and the callback keeps its two arguments.
+
+    ``probes=positions`` ([n, dims]): pressure, density and velocity are sampled at those fixed points on the device at every
+    step (``Backend.probes_enable``; ``sphexample_amd.probes`` builds gauge columns and reads water levels off them) and
+    ``on_output`` receives the samples of the interval as one more argument, the dict of ``Backend.probes_read`` — behind the
+    group forces when both are asked for."""
     if SimMetaData.BMode.__name__ == "SimpleMDBC":
         LoadMDBCNormals(SimParticles, ParticleNormalsPath)                       # :827
     host_bytes = SimParticles.Position.dtype.itemsize
@@ -76,14 +81,20 @@ def RunSimulation(*, SimGeometry=None, SimMetaData: SimulationMetaData, SimConst
     eng.set_clock(SimMetaData.Iteration, SimMetaData.TotalTime)
     time_steps: List[float] = []
     SimMetaData.OutputIterationCounter = 1                                       # :849
+    extras = []          # per output: what the callback receives behind the particles — a list of (first value, reader)
     if group_forces is not None:
         markers = [int(m) for m in group_forces]
         eng.group_forces_enable(markers, capacity=1 << 20)
-        none_yet = (np.zeros(0, dtype=np.int64), np.zeros(0), np.zeros(0), np.zeros((0, len(markers), 3)))
-        emit = lambda meta, samples: on_output(meta, SimParticles, samples)      # noqa: E731
-    else:
-        none_yet = None
-        emit = lambda meta, samples: on_output(meta, SimParticles)               # noqa: E731
+        extras.append(((np.zeros(0, dtype=np.int64), np.zeros(0), np.zeros(0), np.zeros((0, len(markers), 3))), eng.group_forces_read))
+    if probes is not None:
+        points = np.ascontiguousarray(probes, dtype=np.float64).reshape(-1, SimMetaData.Dimensions)
+        eng.probes_enable(points, capacity=1 << 16)
+        m = len(points)
+        extras.append(({"iteration": np.zeros(0, dtype=np.int64), "time": np.zeros(0), "dt": np.zeros(0), "weight": np.zeros((0, m)),
+                        "count": np.zeros((0, m), dtype=np.int64), "pressure": np.zeros((0, m)), "density": np.zeros((0, m)),
+                        "velocity": np.zeros((0, m, 3))}, eng.probes_read))
+    none_yet = tuple(first for first, _ in extras)
+    emit = lambda meta, samples: on_output(meta, SimParticles, *samples)         # noqa: E731
     if on_output:
         emit(SimMetaData, none_yet)                                              # :850
 
@@ -106,7 +117,7 @@ def RunSimulation(*, SimGeometry=None, SimMetaData: SimulationMetaData, SimConst
         time_steps.append(prog.last_dt)                                          # :884
         SimMetaData.OutputIterationCounter += 1                                  # :888
         done = SimMetaData.TotalTime > SimMetaData.SimulationTime               # :909
-        samples = eng.group_forces_read() if group_forces is not None else None  # the steps of this interval
+        samples = tuple(read() for _, read in extras)                            # the steps of this interval
         if on_output and async_output:
             # The copies of snapshot k run while interval k+1 is computed: the callback for k is made after the
             # NEXT advance, with the metadata captured at the snapshot.
