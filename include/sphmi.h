@@ -384,6 +384,31 @@ int sphmi_multi_info_get(sphmi_handle* h, sphmi_multi_info* out);
 /* (Test hooks of the slab driver — the shared-memory transport's self-test, initial cuts, host-only planning, the work
  * measure of the re-cut — are declared in include/sphmi_internal.h; they are not part of the drop-in boundary.) */
 
+/*
+ * Pressure, density, velocity and fill on a regular lattice, on demand: the sums of sphmi_probes_enable at every node of a lattice,
+ * evaluated NOW - a free-surface height map, a slice through an obstacle, a volume of image data - by a kernel that shares the
+ * staged particle rows among up to 256 neighbouring nodes (csrc/sphmi_field_grid.h).
+ *   Synchronous, called between sphmi_advance calls like sphmi_download; it changes no state a later step, download, column download,
+ *   probe series or group-force series reads, and leaves a download begun with sphmi_download_begin alone.
+ *   Node (i, j, k) lies at origin[d] + (double)i_d * spacing[d] (one multiply, one add, not fused: a host forms the same doubles); its
+ *   index is i + nx * (j + ny * k), x fastest - the order of VTK image data.  `dims` entries of origin, spacing and counts are read.
+ *   Per node: n Fluid rows the handle owns within H (inclusive, on the current positions, however stale the cell list), S = sum w_j,
+ *   SP, Srho, Sv with w_j = (m0 / rho_j) W(|x_n - x_j|), on the state sphmi_download would deliver now (Pressure = Pressure!(rho_n+) of
+ *   the half-step set), all in fp64, no self term, r = 0 legal; summed in row order, without atomics: repeated calls give the same bits.
+ *   weight_out [nodes] S, count_out [nodes] n, pressure_out / density_out [nodes] SP / S and Srho / S, velocity_out [nodes x 3] Sv / S
+ *   (2-D handles: a zero third component) - normalised on the host, 0 where n == 0; nodes in empty space or outside the cell grid
+ *   read zeros.  Any output pointer may be NULL (all NULL: the sums are formed in the device arena and nothing is delivered).
+ *   SPHMI_ERR_STATE: before the upload; before the handle has executed its first step since the upload or generator (no cell list, no
+ *     half-step set); rank-mode handles; handles with H < h.
+ *   SPHMI_ERR_ARGUMENT: null origin, spacing or counts; a non-finite origin; a spacing that is not finite and positive; a count < 1;
+ *     more than SPHMI_MAX_GRID_NODES nodes.   SPHMI_ERR_DEVICE: the device cannot hold the result arena (7 doubles per node).
+ * Multi-device handles of one process: every slab samples the whole lattice over the rows it owns (ghost copies do not count), the
+ * handle adds the slabs' raw sums in slab order and then normalises.
+ */
+#define SPHMI_MAX_GRID_NODES (1 << 24)
+int sphmi_sample_grid(sphmi_handle* h, const double* origin, const double* spacing, const int64_t* counts,
+                      double* weight_out, int64_t* count_out, double* pressure_out, double* density_out, double* velocity_out);
+
 #ifdef __cplusplus
 }
 #endif

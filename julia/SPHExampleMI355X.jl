@@ -127,6 +127,18 @@ function read_probes!(h, pr::ProbeSeries)
     pr.velocity = cat(pr.velocity, v; dims = 3); pr.dropped += dropped[]
     return nothing
 end
+# The probes' sums at every node of a regular lattice, evaluated on the state the session holds NOW (sphmi_sample_grid): node (i, j[, k])
+# lies at origin .+ (i, j[, k]) .* spacing, zero-based.  Returns arrays indexed [i, j[, k]] (x fastest: Julia's column-major order IS the
+# node order), velocity as 3 × nx × ny[ × nz].  Call it from an output callback, i.e. between two SimulationLoop calls, after the first step.
+function sample_grid(P, origin::Vector{Float64}, spacing::Vector{Float64}, counts::Vector{Int64})
+    h = SESSIONS[P].h
+    dims = Tuple(Int.(counts))
+    w = Array{Float64}(undef, dims); c = Array{Int64}(undef, dims); pp = Array{Float64}(undef, dims); rho = Array{Float64}(undef, dims)
+    v = Array{Float64}(undef, (3, dims...))
+    GC.@preserve origin spacing counts w c pp rho v check(h, ccall((:sphmi_sample_grid, LIB), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Int64}, Ptr{Float64}, Ptr{Int64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+                                                                       h, pointer(origin), pointer(spacing), pointer(counts), pointer(w), pointer(c), pointer(pp), pointer(rho), pointer(v)))
+    return (weight = w, count = c, pressure = pp, density = rho, velocity = v)
+end
 atexit(() -> foreach(s -> ccall((:sphmi_destroy, LIB), Cint, (Ptr{Cvoid},), s.h), values(SESSIONS)))
 
 function check(h, rc)

@@ -21,6 +21,7 @@
 #include "sphmi_columns.h"
 #include "sphmi_group_forces.h"
 #include "sphmi_probes.h"
+#include "sphmi_field_grid.h"
 
 namespace sphmi {
 
@@ -230,6 +231,48 @@ struct ProbeSeries {
     }
 };
 
+// sphmi_sample_grid: the argument errors every kind of handle reports alike; returns the number of nodes
+inline int64_t check_grid_lattice(const double* origin, const double* spacing, const int64_t* counts, int dims) {
+    if (!origin || !spacing || !counts) throw EngineError(SPHMI_ERR_ARGUMENT, "sphmi_sample_grid: null origin, spacing or counts");
+    int64_t nodes = 1;
+    for (int d = 0; d < dims; ++d) {
+        if (!std::isfinite(origin[d])) throw EngineError(SPHMI_ERR_ARGUMENT, "sphmi_sample_grid: non-finite origin");
+        if (!std::isfinite(spacing[d]) || !(spacing[d] > 0.0)) throw EngineError(SPHMI_ERR_ARGUMENT, "sphmi_sample_grid: every spacing must be finite and positive");
+        if (counts[d] < 1) throw EngineError(SPHMI_ERR_ARGUMENT, "sphmi_sample_grid: every count must be at least 1");
+        if (counts[d] > kMaxGridNodes || nodes * counts[d] > kMaxGridNodes) throw EngineError(SPHMI_ERR_ARGUMENT, "sphmi_sample_grid: more than SPHMI_MAX_GRID_NODES nodes");
+        nodes *= counts[d];
+    }
+    return nodes;
+}
+
+// The host side of sphmi_sample_grid: the raw sums { S, SP, Sρ, Sv[3], n } of the lattice (sphmi_field_grid.h), the ones the
+// requested outputs need.  S lands in weight_out itself when that is asked for; the means are formed here, 0 where n == 0.
+struct GridSums {
+    int64_t nodes = 0;
+    double* S = nullptr;                       // weight_out, or s[0]
+    std::vector<double> s[kFgValues];
+    bool want[kFgValues] = {};
+    double* dst(int f) { return f == 0 ? S : s[f].data(); }
+    GridSums(int64_t n, double* weight, const int64_t* count, const double* pressure, const double* density, const double* velocity) : nodes(n) {
+        const bool means = pressure || density || velocity;
+        want[0] = weight || means; want[1] = pressure != nullptr; want[2] = density != nullptr;
+        want[3] = want[4] = want[5] = velocity != nullptr; want[6] = count || means;
+        for (int f = 0; f < kFgValues; ++f) if (want[f] && !(f == 0 && weight)) s[f].assign((size_t)n, 0.0);
+        S = weight ? weight : s[0].data();
+    }
+    void deliver(int64_t* count, double* pressure, double* density, double* velocity) const {
+        const double *SP = s[1].data(), *Sr = s[2].data(), *Sx = s[3].data(), *Sy = s[4].data(), *Sz = s[5].data(), *n = s[6].data();
+        for (int64_t k = 0; k < nodes; ++k) {
+            if (count) count[k] = (int64_t)n[k];
+            if (!pressure && !density && !velocity) continue;
+            const bool some = n[k] > 0.0 && S[k] > 0.0;
+            if (pressure) pressure[k] = some ? SP[k] / S[k] : 0.0;
+            if (density) density[k] = some ? Sr[k] / S[k] : 0.0;
+            if (velocity) { velocity[3 * k] = some ? Sx[k] / S[k] : 0.0; velocity[3 * k + 1] = some ? Sy[k] / S[k] : 0.0; velocity[3 * k + 2] = some ? Sz[k] / S[k] : 0.0; }
+        }
+    }
+};
+
 struct EngineBase {
     sphmi_config cfg{};
     std::string err;
@@ -256,6 +299,8 @@ struct EngineBase {
     virtual void probes_enable(int32_t n_probes, const double* positions, int64_t capacity_steps) = 0;
     virtual void probes_read(int64_t capacity, int64_t* iteration, double* time, double* dt, double* weight, int64_t* count, double* pressure,
                              double* density, double* velocity, int64_t* n_out, int64_t* n_dropped) = 0;
+    virtual void sample_grid(const double* origin, const double* spacing, const int64_t* counts, double* weight, int64_t* count, double* pressure,
+                             double* density, double* velocity) = 0;
     virtual void unique_cells(int64_t* out, int64_t cap, int64_t* n) = 0;
     virtual void timers(int32_t cap, const char** names, double* secs, int64_t* calls, int32_t* n) = 0;
     virtual void force_stats(int reset, double* avg_ms, int64_t* launches) = 0;
@@ -527,7 +572,7 @@ struct Engine final : EngineBase {
         for (auto& e : host_pinned) (void)hipHostUnregister(e.first);
         (void)hipFree(out_arena);
         (void)hipFree(col_arena); (void)hipFree(col_store); (void)hipFree(col_base[0]); (void)hipFree(col_base[1]);
-        gf_release(); pr_release();
+        gf_release(); pr_release(); (void)hipFree(fg_arena);
         (void)hipFree(slot); (void)hipFree(tmp_idx); (void)hipFree(perm);
         for (int k = 0; k < 2; ++k) { (void)hipFree(tile_cost[k]); (void)hipFree(tile_order[k]); }
         (void)hipFree(kout_d); (void)hipFree(tile_work_d); (void)hipFree(tile_work1_d); (void)hipFree(xcd_clock_d); (void)hipHostFree(xcd_clock_h);
@@ -1834,6 +1879,62 @@ struct Engine final : EngineBase {
         pr_series.read(capacity, iteration_out, time, dt, weight, count, pressure, density, velocity, n_out, n_dropped);
     }
 
+    // ---- kernel sums on a regular lattice, on demand (sphmi_field_grid.h) ------------------------------------------------------
+    // Reads what sphmi_download reads — the current set, the half-step set, the low words — plus `cstart` and the grid of the last
+    // rebuild; writes its own arena and nothing else.  A download in flight keeps out_arena and the copy stream to itself.
+    double* fg_arena = nullptr; size_t fg_arena_doubles = 0;
+    bool fg_ready() const { return stepped && have_grid && cstart != nullptr && N > 0; }
+    // queue the kernel for the whole lattice on the engine's stream (a multi-device handle calls it on every slab engine)
+    void fg_launch(const double* origin, const double* spacing, const int64_t* counts, int64_t nodes) {
+        HC(hipSetDevice(cfg.device));
+        const size_t need = (size_t)kFgValues * (size_t)nodes;
+        if (need > fg_arena_doubles) {
+            (void)hipFree(fg_arena);
+            fg_arena = nullptr; fg_arena_doubles = 0;
+            if (hipMalloc(&fg_arena, need * 8) != hipSuccess) {
+                (void)hipGetLastError();
+                char buf[160];
+                snprintf(buf, sizeof(buf), "sphmi_sample_grid: no device memory for the result arena of %lld nodes (%.2f GB)", (long long)nodes, (double)need * 8.0 / 1e9);
+                throw EngineError(SPHMI_ERR_DEVICE, buf);
+            }
+            fg_arena_doubles = need;
+        }
+        FieldGridArgs<T> A{};
+        A.pk0 = pk0[iA]; A.pk1 = pk1[iA]; A.half0 = pk0[iH]; A.comp = comp[cur];
+        A.type = dd_slab ? type[cur] : nullptr; A.cstart = cstart; A.out = fg_arena; A.g = grid;
+        int64_t c3[3] = {1, 1, 1};
+        for (int d = 0; d < 3; ++d) { A.origin[d] = d < D ? origin[d] : 0.0; A.spacing[d] = d < D ? spacing[d] : 1.0; if (d < D) c3[d] = counts[d]; }
+        fg_plan_brick(D, A.spacing, c3, A.brick);
+        long long nb = 1;
+        for (int d = 0; d < 3; ++d) { A.counts[d] = (int)c3[d]; A.nbricks[d] = (int)((c3[d] + A.brick[d] - 1) / A.brick[d]); nb *= A.nbricks[d]; }
+        A.nodes = nodes;
+        A.H_inv = cfg.H_inv; A.H2 = cfg.H2; A.h_inv = cfg.h_inv; A.reach = cfg.H + cfg.h;
+        A.alphaD = cfg.alphaD; A.m0 = cfg.m0;
+        A.rho0 = (T)cfg.rho0; A.inv_rho0 = (T)(1.0 / cfg.rho0); A.Cbe = (T)((cfg.c0 * cfg.c0 * cfg.rho0) / 7.0);
+        A.N = N; A.kernel = cfg.kernel;
+        if (D == 3) hipLaunchKernelGGL((k_field_grid<T, 3>), dim3((unsigned)nb), dim3(kFgThreads), 0, stream, A);
+        else        hipLaunchKernelGGL((k_field_grid<T, 2>), dim3((unsigned)nb), dim3(kFgThreads), 0, stream, A);
+        HC(hipGetLastError());
+    }
+    // one raw sum of the lattice → host, behind the kernel: directly into memory the caller page-locked, else through the bounce buffer
+    void fg_fetch(int f, double* dst, int64_t nodes) {
+        const size_t bytes = (size_t)nodes * 8;
+        if (is_registered(dst, bytes)) { HC(hipMemcpyAsync(dst, fg_arena + (size_t)f * (size_t)nodes, bytes, hipMemcpyDeviceToHost, stream)); HC(hipStreamSynchronize(stream)); }
+        else bounce.d2h(dst, fg_arena + (size_t)f * (size_t)nodes, bytes, stream);
+    }
+    void sample_grid(const double* origin, const double* spacing, const int64_t* counts, double* weight, int64_t* count, double* pressure,
+                     double* density, double* velocity) override {
+        if (!uploaded) throw EngineError(SPHMI_ERR_STATE, "sphmi_sample_grid before sphmi_upload");
+        if (!(cfg.h <= cfg.H)) throw EngineError(SPHMI_ERR_STATE, "sphmi_sample_grid: handles with H < h are not served (the candidate cells are laid out for H + h <= 2H)");
+        if (!fg_ready()) throw EngineError(SPHMI_ERR_STATE, "sphmi_sample_grid: the handle has not executed a step since the upload (no cell list, no half-step set)");
+        const int64_t nodes = check_grid_lattice(origin, spacing, counts, D);
+        fg_launch(origin, spacing, counts, nodes);
+        GridSums G(nodes, weight, count, pressure, density, velocity);
+        for (int f = 0; f < kFgValues; ++f) if (G.want[f]) fg_fetch(f, G.dst(f), nodes);
+        HC(hipStreamSynchronize(stream));
+        G.deliver(count, pressure, density, velocity);
+    }
+
     // Pressure! + [mDBC] + ONE forces-only neighbour pass on the current cell list; {a, dρ/dt} of every particle held are left
     // in the scratch record array rec[iB] (N contiguous packets), SimParticles.Acceleration survives.  all_lists: a slab
     // engine runs its interior and its slab-edge tiles (the ghost layers must be current: the caller has just rebuilt).
@@ -2384,6 +2485,11 @@ int sphmi_probes_enable(sphmi_handle* h, int32_t n_probes, const double* positio
 int sphmi_probes_read(sphmi_handle* h, int64_t capacity, int64_t* iteration_out, double* time_out, double* dt_out, double* weight_out,
                       int64_t* count_out, double* pressure_out, double* density_out, double* velocity_out, int64_t* n_out, int64_t* n_dropped) {
     SPHMI_GUARD(h, h->e->probes_read(capacity, iteration_out, time_out, dt_out, weight_out, count_out, pressure_out, density_out, velocity_out, n_out, n_dropped));
+}
+static_assert(SPHMI_MAX_GRID_NODES == sphmi::kMaxGridNodes, "sphmi_field_grid.h and sphmi.h disagree");
+int sphmi_sample_grid(sphmi_handle* h, const double* origin, const double* spacing, const int64_t* counts, double* weight_out, int64_t* count_out,
+                      double* pressure_out, double* density_out, double* velocity_out) {
+    SPHMI_GUARD(h, h->e->sample_grid(origin, spacing, counts, weight_out, count_out, pressure_out, density_out, velocity_out));
 }
 int sphmi_group_forces_read(sphmi_handle* h, int64_t capacity, int64_t* iteration_out, double* time_out, double* dt_out, double* force_out,
                             int64_t* n_out, int64_t* n_dropped) {

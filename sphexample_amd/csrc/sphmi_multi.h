@@ -1767,6 +1767,37 @@ struct MultiEngine final : EngineBase {
         pr_series.read(capacity, iteration_out, time, dt, weight, count, pressure, density, velocity, n_out, n_dropped);
     }
     // after the synchronisation of a batch: the records of its `executed` steps, slab by slab
+    // Kernel sums on a lattice (sphmi_field_grid.h): every slab samples the WHOLE lattice over the rows it owns — the type byte keeps
+    // ghost copies out — the handle adds the raw sums in slab order, then normalises, as for the probes.
+    void sample_grid(const double* origin, const double* spacing, const int64_t* counts, double* weight, int64_t* count, double* pressure,
+                     double* density, double* velocity) override {
+        if (rank_mode) throw EngineError(SPHMI_ERR_STATE, "sphmi_sample_grid: one-process handles only (a rank-mode process holds one slab of the rows)");
+        if (!uploaded) throw EngineError(SPHMI_ERR_STATE, "sphmi_sample_grid before sphmi_upload");
+        bool any = false;
+        for (auto& r : R) any = any || r.e->fg_ready();
+        if (!(cfg.h <= cfg.H)) throw EngineError(SPHMI_ERR_STATE, "sphmi_sample_grid: handles with H < h are not served (the candidate cells are laid out for H + h <= 2H)");
+        if (!any) throw EngineError(SPHMI_ERR_STATE, "sphmi_sample_grid: the handle has not executed a step since the upload (no cell list, no half-step set)");
+        const int64_t nodes = check_grid_lattice(origin, spacing, counts, D);
+        for (auto& r : R) if (r.e->fg_ready()) r.e->fg_launch(origin, spacing, counts, nodes);        // all slabs at once, each on its device
+        GridSums G(nodes, weight, count, pressure, density, velocity);
+        std::vector<double> part;
+        bool first = true;
+        for (auto& r : R) {
+            if (!r.e->fg_ready()) continue;                // (a slab that holds no rows has no cell list: it adds nothing)
+            HC(hipSetDevice(r.device));
+            for (int f = 0; f < kFgValues; ++f) {
+                if (!G.want[f]) continue;
+                double* dst = G.dst(f);
+                if (first) { r.e->fg_fetch(f, dst, nodes); continue; }
+                part.resize((size_t)nodes);
+                r.e->fg_fetch(f, part.data(), nodes);
+                for (int64_t k = 0; k < nodes; ++k) dst[k] += part[(size_t)k];
+            }
+            HC(hipStreamSynchronize(r.e->stream));
+            first = false;
+        }
+        G.deliver(count, pressure, density, velocity);
+    }
     void pr_collect(int64_t executed) {
         const int n = pr_series.n_probes;
         for (int64_t k = 0; k < executed; ++k) {

@@ -42,7 +42,7 @@ def RunSimulation(*, SimGeometry=None, SimMetaData: SimulationMetaData, SimConst
                   ParticleNormalsPath: Optional[str] = None,
                   on_output: Optional[Callable[[SimulationMetaData, SimParticles], None]] = None,
                   device_float_bytes: int = 0, device: int = 0, backend_factory=None,
-                  async_output: bool = False, group_forces=None, probes=None) -> List[float]:
+                  async_output: bool = False, group_forces=None, probes=None, field_grid=None) -> List[float]:
     """Same keyword signature as the reference (src/SPHCellList.jl:808-817); returns the list of
     time steps the reference collects in ``TimeSteps`` (:823,:884).  ``SimParticles`` is updated in
     place at every output time, in the engine's cell-sorted order, as the reference's is.
@@ -55,7 +55,12 @@ def RunSimulation(*, SimGeometry=None, SimMetaData: SimulationMetaData, SimConst
     ``probes=positions`` ([n, dims]): pressure, density and velocity are sampled at those fixed points on the device at every
     step (``Backend.probes_enable``; ``sphexample_amd.probes`` builds gauge columns and reads water levels off them) and
     ``on_output`` receives the samples of the interval as one more argument, the dict of ``Backend.probes_read`` — behind the
-    group forces when both are asked for."""
+    group forces when both are asked for.
+
+    ``field_grid=(origin, spacing, counts)``: at every output the same sums are sampled on that regular lattice
+    (``Backend.sample_grid``; ``sphexample_amd.fields`` forms the node coordinates and reads a surface height off the
+    result) and ``on_output`` receives the dict of fields as one more argument, behind group forces and probes when those
+    are on — ``None`` at the first call, which precedes the first step.  ``None`` (default): nothing is sampled."""
     if SimMetaData.BMode.__name__ == "SimpleMDBC":
         LoadMDBCNormals(SimParticles, ParticleNormalsPath)                       # :827
     host_bytes = SimParticles.Position.dtype.itemsize
@@ -93,6 +98,9 @@ def RunSimulation(*, SimGeometry=None, SimMetaData: SimulationMetaData, SimConst
         extras.append(({"iteration": np.zeros(0, dtype=np.int64), "time": np.zeros(0), "dt": np.zeros(0), "weight": np.zeros((0, m)),
                         "count": np.zeros((0, m), dtype=np.int64), "pressure": np.zeros((0, m)), "density": np.zeros((0, m)),
                         "velocity": np.zeros((0, m, 3))}, eng.probes_read))
+    if field_grid is not None:
+        lattice = tuple(field_grid)
+        extras.append((None, lambda: eng.sample_grid(*lattice)))                 # (the state of this output: sampled before the next advance)
     none_yet = tuple(first for first, _ in extras)
     emit = lambda meta, samples: on_output(meta, SimParticles, *samples)         # noqa: E731
     if on_output:
