@@ -409,6 +409,40 @@ int sphmi_multi_info_get(sphmi_handle* h, sphmi_multi_info* out);
 int sphmi_sample_grid(sphmi_handle* h, const double* origin, const double* spacing, const int64_t* counts,
                       double* weight_out, int64_t* count_out, double* pressure_out, double* density_out, double* velocity_out);
 
+/*
+ * Differential fields AT THE PARTICLES, on demand: vorticity, velocity divergence, the free-surface indicator div r, the free-surface
+ * normal, the Shepard sum and the neighbour count of every row - what a post-processor colours a breaking wave by or extracts a free
+ * surface from - by a kernel that shares the staged rows among 256 consecutive target rows (csrc/sphmi_particle_fields.h).
+ *   Synchronous, called between sphmi_advance calls like sphmi_sample_grid; it changes no state a later step, download, column download,
+ *   probe series, group-force series or sphmi_sample_grid reads, and leaves a download begun with sphmi_download_begin alone.
+ *   n = sphmi_owned_count rows; row i of every output is row i of what sphmi_download delivers now.  Outputs are doubles whatever
+ *   host_float_bytes is.  Any output pointer may be NULL (all NULL: the sums are formed in the device arena and nothing is delivered).
+ *   For every row i, of any Type, over every row j != i of any Type with r^2 = |x_i - x_j|^2 <= H^2 (inclusive, on the current positions,
+ *   however stale the cell list; r^2 = ((dx^2 + dy^2) + dz^2), not fused), with V_j = m0 / rho_j, W the handle's kernel and
+ *   grad_i W_ij = W'(r) (x_i - x_j) / r, on the Position, Velocity and Density sphmi_download would deliver now (no pressure is involved):
+ *     count_out      n_i       the number of such j
+ *     shepard_out    S_i       V_i W(0) + sum V_j W_ij            (the self term is in: i is a particle; about 1 inside the fluid)
+ *     normal_out     N_i       sum V_j grad_i W_ij                (about 0 inside; the gradient of the colour function: at a free surface
+ *                                                                 it points INTO the fluid, the outward normal is -N / |N|)
+ *     div_r_out      (div r)_i sum V_j (x_j - x_i) . grad_i W_ij  (about dims inside; lower at a free surface)
+ *     div_v_out      (div v)_i sum V_j (v_j - v_i) . grad_i W_ij
+ *     vorticity_out  w_i       sum V_j grad_i W_ij x (v_j - v_i)  (a rigid rotation v = Omega x x gives 2 Omega)
+ *   2-D handles deliver only the z component of the vorticity: its x and y, and the third component of N, are exact zeros.  A coincident
+ *   row (r = 0) counts in n and S and adds nothing to the four gradient sums.  All in fp64, summed in row order without atomics:
+ *   repeated calls give the same bits.
+ *   SPHMI_ERR_STATE: before the upload; before the handle has executed its first step since the upload or generator (no cell list);
+ *     handles with H < h; rank-mode handles; multi-device handles - after the corrector a slab's ghost copies hold the half-step state,
+ *     so a slab cannot see its neighbours' current rows without a halo exchange of its own, which is not built.
+ *   SPHMI_ERR_DEVICE: the device cannot hold the result arena (10 doubles per row).
+ */
+int sphmi_particle_fields(sphmi_handle* h,
+        int64_t* count_out,      /* [n]      n_i       */
+        double*  shepard_out,    /* [n]      S_i       */
+        double*  normal_out,     /* [n x 3]  N_i       */
+        double*  div_r_out,      /* [n]      div r     */
+        double*  div_v_out,      /* [n]      div v     */
+        double*  vorticity_out); /* [n x 3]  w_i       */
+
 #ifdef __cplusplus
 }
 #endif

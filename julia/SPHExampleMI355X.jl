@@ -139,6 +139,18 @@ function sample_grid(P, origin::Vector{Float64}, spacing::Vector{Float64}, count
                                                                        h, pointer(origin), pointer(spacing), pointer(counts), pointer(w), pointer(c), pointer(pp), pointer(rho), pointer(v)))
     return (weight = w, count = c, pressure = pp, density = rho, velocity = v)
 end
+# Differential fields at the particles, evaluated on the state the session holds NOW (sphmi_particle_fields): row i is row i of the next
+# download.  count[i] rows within H, shepard[i], div_r[i] (≈ D inside, lower at a free surface), div_v[i], normal[:, i] and vorticity[:, i]
+# (3 × n; 2-D: only vorticity[3, :] and normal[1:2, :] are non-zero).  Single-device sessions; call it from an output callback, after the first step.
+function particle_fields(P)
+    h = SESSIONS[P].h
+    n = length(P)
+    c = Vector{Int64}(undef, n); s = Vector{Float64}(undef, n); nrm = Matrix{Float64}(undef, 3, n)
+    dr = Vector{Float64}(undef, n); dv = Vector{Float64}(undef, n); w = Matrix{Float64}(undef, 3, n)
+    GC.@preserve c s nrm dr dv w check(h, ccall((:sphmi_particle_fields, LIB), Cint, (Ptr{Cvoid}, Ptr{Int64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+                                                h, pointer(c), pointer(s), pointer(nrm), pointer(dr), pointer(dv), pointer(w)))
+    return (count = c, shepard = s, normal = nrm, div_r = dr, div_v = dv, vorticity = w)
+end
 atexit(() -> foreach(s -> ccall((:sphmi_destroy, LIB), Cint, (Ptr{Cvoid},), s.h), values(SESSIONS)))
 
 function check(h, rc)

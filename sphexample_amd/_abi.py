@@ -429,6 +429,30 @@ class Backend:
         self._check(f(self._h, _ptr(o), _ptr(s), _ptr(c), *[_ptr(out[k]) for k in self.GRID_FIELDS]))
         return {k: v for k, v in out.items() if v is not None}
 
+    # -- differential fields at the particles, on demand (sphmi_particle_fields) ------------------------------------------------
+    PARTICLE_FIELDS = ("count", "shepard", "normal", "div_r", "div_v", "vorticity")
+
+    def has_particle_fields(self) -> bool:
+        return self._has("particle_fields")
+
+    def particle_fields(self, fields=PARTICLE_FIELDS) -> dict:
+        """Vorticity, velocity divergence, the free-surface indicator div r, the free-surface normal, the Shepard sum and the
+        neighbour count of every row, evaluated now over all rows within H on the current positions: a dict of `count` [n]
+        (int64), `shepard`, `div_r`, `div_v` [n] and `normal`, `vorticity` [n, 3] (2-D: only the z component of the vorticity
+        and the x, y of the normal are non-zero), row i being row i of what `download` delivers now.  Only the fields named are
+        computed into host arrays.  Single-device handles; call it between `advance` calls, after the first executed step."""
+        fields = tuple(fields)
+        unknown = [k for k in fields if k not in self.PARTICLE_FIELDS]
+        if unknown:
+            raise ValueError(f"particle_fields: unknown fields {unknown}")
+        f = self._fn("particle_fields")
+        f.argtypes = [C.c_void_p] * 7
+        n = self.N
+        out = {k: (np.zeros((n, 3) if k in ("normal", "vorticity") else n, dtype=np.int64 if k == "count" else np.float64) if k in fields else None)
+               for k in self.PARTICLE_FIELDS}
+        self._check(f(self._h, *[_ptr(out[k]) for k in self.PARTICLE_FIELDS]))
+        return {k: v for k, v in out.items() if v is not None}
+
     def forces_once(self, apply_mdbc: bool = False):
         drho = np.empty(self.N, dtype=self._ft)
         acc = np.empty((self.N, self.D), dtype=self._ft)

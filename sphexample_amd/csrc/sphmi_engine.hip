@@ -22,6 +22,7 @@
 #include "sphmi_group_forces.h"
 #include "sphmi_probes.h"
 #include "sphmi_field_grid.h"
+#include "sphmi_particle_fields.h"
 
 namespace sphmi {
 
@@ -301,6 +302,7 @@ struct EngineBase {
                              double* density, double* velocity, int64_t* n_out, int64_t* n_dropped) = 0;
     virtual void sample_grid(const double* origin, const double* spacing, const int64_t* counts, double* weight, int64_t* count, double* pressure,
                              double* density, double* velocity) = 0;
+    virtual void particle_fields(int64_t* count, double* shepard, double* normal, double* div_r, double* div_v, double* vorticity) = 0;
     virtual void unique_cells(int64_t* out, int64_t cap, int64_t* n) = 0;
     virtual void timers(int32_t cap, const char** names, double* secs, int64_t* calls, int32_t* n) = 0;
     virtual void force_stats(int reset, double* avg_ms, int64_t* launches) = 0;
@@ -572,7 +574,7 @@ struct Engine final : EngineBase {
         for (auto& e : host_pinned) (void)hipHostUnregister(e.first);
         (void)hipFree(out_arena);
         (void)hipFree(col_arena); (void)hipFree(col_store); (void)hipFree(col_base[0]); (void)hipFree(col_base[1]);
-        gf_release(); pr_release(); (void)hipFree(fg_arena);
+        gf_release(); pr_release(); (void)hipFree(fg_arena); (void)hipFree(pf_arena);
         (void)hipFree(slot); (void)hipFree(tmp_idx); (void)hipFree(perm);
         for (int k = 0; k < 2; ++k) { (void)hipFree(tile_cost[k]); (void)hipFree(tile_order[k]); }
         (void)hipFree(kout_d); (void)hipFree(tile_work_d); (void)hipFree(tile_work1_d); (void)hipFree(xcd_clock_d); (void)hipHostFree(xcd_clock_h);
@@ -1935,6 +1937,47 @@ struct Engine final : EngineBase {
         G.deliver(count, pressure, density, velocity);
     }
 
+    // ---- differential fields at the particles, on demand (sphmi_particle_fields.h) -------------------------------------------------
+    // Reads the current set, the low words, `cstart` and the grid of the last rebuild; writes its own arena and nothing else.
+    double* pf_arena = nullptr; size_t pf_arena_doubles = 0;
+    void particle_fields(int64_t* count, double* shepard, double* normal, double* div_r, double* div_v, double* vorticity) override {
+        if (!uploaded) throw EngineError(SPHMI_ERR_STATE, "sphmi_particle_fields before sphmi_upload");
+        if (!(cfg.h <= cfg.H)) throw EngineError(SPHMI_ERR_STATE, "sphmi_particle_fields: handles with H < h are not served (the candidate cells are laid out for H + h <= 2H)");
+        if (!fg_ready()) throw EngineError(SPHMI_ERR_STATE, "sphmi_particle_fields: the handle has not executed a step since the upload (no cell list)");
+        HC(hipSetDevice(cfg.device));
+        const size_t n = (size_t)N, need = (size_t)kPfValues * n;
+        if (need > pf_arena_doubles) {
+            (void)hipFree(pf_arena);
+            pf_arena = nullptr; pf_arena_doubles = 0;
+            if (hipMalloc(&pf_arena, need * 8) != hipSuccess) {
+                (void)hipGetLastError();
+                char buf[160];
+                snprintf(buf, sizeof(buf), "sphmi_particle_fields: no device memory for the result arena of %d rows (%.2f GB)", N, (double)need * 8.0 / 1e9);
+                throw EngineError(SPHMI_ERR_DEVICE, buf);
+            }
+            pf_arena_doubles = need;
+        }
+        ParticleFieldArgs<T> A{};
+        A.pk0 = pk0[iA]; A.pk1 = pk1[iA]; A.comp = comp[cur]; A.cstart = cstart; A.g = grid;
+        A.count = (long long*)pf_arena; A.shepard = pf_arena + n; A.normal = pf_arena + 2 * n; A.div_r = pf_arena + 5 * n;
+        A.div_v = pf_arena + 6 * n; A.vorticity = pf_arena + 7 * n;
+        A.H_inv = cfg.H_inv; A.H2 = cfg.H2; A.h_inv = cfg.h_inv; A.reach = cfg.H + cfg.h;
+        A.alphaD = cfg.alphaD; A.m0 = cfg.m0; A.N = N; A.kernel = cfg.kernel;
+        const unsigned nb = (unsigned)((N + kPfThreads - 1) / kPfThreads);
+        if (D == 3) hipLaunchKernelGGL((k_particle_fields<T, 3>), dim3(nb), dim3(kPfThreads), 0, stream, A);
+        else        hipLaunchKernelGGL((k_particle_fields<T, 2>), dim3(nb), dim3(kPfThreads), 0, stream, A);
+        HC(hipGetLastError());
+        // behind the kernel: directly into memory the caller page-locked, else through the bounce buffer
+        auto fetch = [&](void* dst, const double* src, size_t doubles) {
+            if (!dst) return;
+            if (is_registered(dst, doubles * 8)) HC(hipMemcpyAsync(dst, src, doubles * 8, hipMemcpyDeviceToHost, stream));
+            else bounce.d2h(dst, src, doubles * 8, stream);
+        };
+        fetch(count, pf_arena, n); fetch(shepard, A.shepard, n); fetch(normal, A.normal, 3 * n); fetch(div_r, A.div_r, n);
+        fetch(div_v, A.div_v, n); fetch(vorticity, A.vorticity, 3 * n);
+        HC(hipStreamSynchronize(stream));
+    }
+
     // Pressure! + [mDBC] + ONE forces-only neighbour pass on the current cell list; {a, dρ/dt} of every particle held are left
     // in the scratch record array rec[iB] (N contiguous packets), SimParticles.Acceleration survives.  all_lists: a slab
     // engine runs its interior and its slab-edge tiles (the ghost layers must be current: the caller has just rebuilt).
@@ -2490,6 +2533,10 @@ static_assert(SPHMI_MAX_GRID_NODES == sphmi::kMaxGridNodes, "sphmi_field_grid.h 
 int sphmi_sample_grid(sphmi_handle* h, const double* origin, const double* spacing, const int64_t* counts, double* weight_out, int64_t* count_out,
                       double* pressure_out, double* density_out, double* velocity_out) {
     SPHMI_GUARD(h, h->e->sample_grid(origin, spacing, counts, weight_out, count_out, pressure_out, density_out, velocity_out));
+}
+int sphmi_particle_fields(sphmi_handle* h, int64_t* count_out, double* shepard_out, double* normal_out, double* div_r_out, double* div_v_out,
+                          double* vorticity_out) {
+    SPHMI_GUARD(h, h->e->particle_fields(count_out, shepard_out, normal_out, div_r_out, div_v_out, vorticity_out));
 }
 int sphmi_group_forces_read(sphmi_handle* h, int64_t capacity, int64_t* iteration_out, double* time_out, double* dt_out, double* force_out,
                             int64_t* n_out, int64_t* n_dropped) {

@@ -1798,6 +1798,12 @@ struct MultiEngine final : EngineBase {
         }
         G.deliver(count, pressure, density, velocity);
     }
+    // Differential fields at the particles (sphmi_particle_fields.h): single-device handles only.  After the corrector a slab's ghost
+    // copies hold the half-step state, so a slab cannot see its neighbours' current rows without a halo exchange of its own.
+    void particle_fields(int64_t*, double*, double*, double*, double*, double*) override {
+        if (rank_mode) throw EngineError(SPHMI_ERR_STATE, "sphmi_particle_fields: single-device handles only (a rank-mode process holds one slab of the rows)");
+        throw EngineError(SPHMI_ERR_STATE, "sphmi_particle_fields: single-device handles only (a slab's ghost copies hold the half-step state; the halo exchange this needs is not built)");
+    }
     void pr_collect(int64_t executed) {
         const int n = pr_series.n_probes;
         for (int64_t k = 0; k < executed; ++k) {

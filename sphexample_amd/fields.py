@@ -1,4 +1,5 @@
-"""Fields on a regular lattice, on top of ``Backend.sample_grid`` (host only).
+"""Fields on a regular lattice, on top of ``Backend.sample_grid``, and a free-surface mask on top of
+``Backend.particle_fields`` (host only).
 
 The device delivers, per lattice node, the probes' sums (``sphexample_amd.probes``): the Shepard sum ``S`` — about 1 inside the
 fluid, about 1/2 at a free surface, 0 in empty space — and the S-weighted means of pressure, density and velocity.  Arrays
@@ -55,4 +56,20 @@ def surface_height(weight, origin, spacing, threshold: float = 0.5) -> np.ndarra
     return np.asarray(water_level(z, cols, threshold)).reshape(S.shape[1:])
 
 
-__all__ = ["grid_axes", "grid_nodes", "surface_height"]
+# the usual cuts on div r for a free-surface particle (about dims inside the fluid, lower where the support is cut off)
+FREE_SURFACE_DIV_R = {2: 1.5, 3: 2.4}
+
+
+def free_surface_mask(div_r, dims: int, threshold: float = None) -> np.ndarray:
+    """True where a particle lies at a free surface: ``div_r < threshold``, with `div_r` the field of that name of
+    ``Backend.particle_fields`` — about `dims` inside the fluid, lower where a part of the kernel support is empty.  The
+    default threshold is 1.5 in 2-D and 2.4 in 3-D: the values in common use in the SPH literature, conventions taken over
+    as they are, not measured on this engine's cases.  Boundary rows at the edge of the particle set are flagged like any
+    other row; select by Type where only the fluid is wanted."""
+    if dims not in FREE_SURFACE_DIV_R:
+        raise ValueError("free_surface_mask: dims is 2 or 3")
+    t = FREE_SURFACE_DIV_R[dims] if threshold is None else float(threshold)
+    return np.asarray(div_r, dtype=np.float64) < t
+
+
+__all__ = ["grid_axes", "grid_nodes", "surface_height", "free_surface_mask", "FREE_SURFACE_DIV_R"]

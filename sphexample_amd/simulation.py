@@ -42,7 +42,8 @@ def RunSimulation(*, SimGeometry=None, SimMetaData: SimulationMetaData, SimConst
                   ParticleNormalsPath: Optional[str] = None,
                   on_output: Optional[Callable[[SimulationMetaData, SimParticles], None]] = None,
                   device_float_bytes: int = 0, device: int = 0, backend_factory=None,
-                  async_output: bool = False, group_forces=None, probes=None, field_grid=None) -> List[float]:
+                  async_output: bool = False, group_forces=None, probes=None, field_grid=None,
+                  particle_fields=None) -> List[float]:
     """Same keyword signature as the reference (src/SPHCellList.jl:808-817); returns the list of
     time steps the reference collects in ``TimeSteps`` (:823,:884).  ``SimParticles`` is updated in
     place at every output time, in the engine's cell-sorted order, as the reference's is.
@@ -60,7 +61,14 @@ def RunSimulation(*, SimGeometry=None, SimMetaData: SimulationMetaData, SimConst
     ``field_grid=(origin, spacing, counts)``: at every output the same sums are sampled on that regular lattice
     (``Backend.sample_grid``; ``sphexample_amd.fields`` forms the node coordinates and reads a surface height off the
     result) and ``on_output`` receives the dict of fields as one more argument, behind group forces and probes when those
-    are on — ``None`` at the first call, which precedes the first step.  ``None`` (default): nothing is sampled."""
+    are on — ``None`` at the first call, which precedes the first step.  ``None`` (default): nothing is sampled.
+
+    ``particle_fields=(names…)``: at every output the differential fields of ``Backend.particle_fields`` — ``"count"``,
+    ``"shepard"``, ``"normal"``, ``"div_r"``, ``"div_v"``, ``"vorticity"`` — are evaluated at the particles and ``on_output``
+    receives the dict as one more argument, behind group forces, probes and the field grid when those are on (``None`` at the
+    first call).  It is taken at the same point as the snapshot: row i is particle i of that output
+    (``sphexample_amd.fields.free_surface_mask`` reads a free surface off ``div_r``).  ``None`` (default): nothing is evaluated
+    and the callback keeps its arguments."""
     if SimMetaData.BMode.__name__ == "SimpleMDBC":
         LoadMDBCNormals(SimParticles, ParticleNormalsPath)                       # :827
     host_bytes = SimParticles.Position.dtype.itemsize
@@ -101,6 +109,9 @@ def RunSimulation(*, SimGeometry=None, SimMetaData: SimulationMetaData, SimConst
     if field_grid is not None:
         lattice = tuple(field_grid)
         extras.append((None, lambda: eng.sample_grid(*lattice)))                 # (the state of this output: sampled before the next advance)
+    if particle_fields is not None:
+        names = tuple(particle_fields)
+        extras.append((None, lambda: eng.particle_fields(names)))                # (the rows of this output: no step lies between it and the download)
     none_yet = tuple(first for first, _ in extras)
     emit = lambda meta, samples: on_output(meta, SimParticles, *samples)         # noqa: E731
     if on_output:
