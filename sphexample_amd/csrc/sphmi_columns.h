@@ -20,10 +20,10 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "sphmi_series.h"      // kMaxColumns, kMaxColumnRowBytes
+
 namespace sphmi {
 
-constexpr int kMaxColumns = 16;          // SPHMI_MAX_COLUMNS
-constexpr int kMaxColumnRowBytes = 64;   // SPHMI_MAX_COLUMN_ROW_BYTES
 constexpr int kGatherThreads = 256;
 constexpr int kGatherLdsBytes = 32768;   // records + source rows of one block
 

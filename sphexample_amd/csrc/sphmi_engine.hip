@@ -8,14 +8,13 @@
 #include <cmath>
 #include <cstdio>
 #include <cstring>
-#include <deque>
 #include <limits>
-#include <stdexcept>
 #include <string>
 #include <vector>
 
 #include "../../include/sphmi.h"
 #include "../../include/sphmi_internal.h"
+#include "sphmi_series.h"
 #include "sphmi_kernels.h"
 #include "sphmi_rebuild.h"
 #include "sphmi_columns.h"
@@ -25,11 +24,6 @@
 #include "sphmi_particle_fields.h"
 
 namespace sphmi {
-
-struct EngineError : std::runtime_error {
-    int status;
-    EngineError(int s, const std::string& m) : std::runtime_error(m), status(s) {}
-};
 
 #define HC(expr)                                                                                   \
     do {                                                                                           \
@@ -116,170 +110,49 @@ struct sphmi_dd_control {
     int32_t reserved;
 };
 
-// sphmi_attach_columns: the argument errors every kind of handle reports alike
-inline void check_column_table(int32_t n_columns, const void* const* columns, const int32_t* row_bytes) {
-    if (n_columns < 0 || n_columns > kMaxColumns) throw EngineError(SPHMI_ERR_ARGUMENT, "sphmi_attach_columns: n_columns out of range [0, 16]");
-    if (n_columns == 0) return;
-    if (!columns || !row_bytes) throw EngineError(SPHMI_ERR_ARGUMENT, "sphmi_attach_columns: null table");
-    for (int c = 0; c < n_columns; ++c) {
-        if (row_bytes[c] < 1 || row_bytes[c] > kMaxColumnRowBytes) throw EngineError(SPHMI_ERR_ARGUMENT, "sphmi_attach_columns: row_bytes out of range [1, 64]");
-        if (!columns[c]) throw EngineError(SPHMI_ERR_ARGUMENT, "sphmi_attach_columns: null column");
-    }
-}
-
-// sphmi_group_forces_enable: the argument errors every kind of handle reports alike
-inline void check_group_table(int32_t n_groups, const uint64_t* markers, int64_t capacity_steps) {
-    if (n_groups < 0 || n_groups > kMaxForceGroups) throw EngineError(SPHMI_ERR_ARGUMENT, "sphmi_group_forces_enable: n_groups out of range [0, 16]");
-    if (n_groups == 0) return;
-    if (!markers) throw EngineError(SPHMI_ERR_ARGUMENT, "sphmi_group_forces_enable: null table");
-    if (capacity_steps < 1) throw EngineError(SPHMI_ERR_ARGUMENT, "sphmi_group_forces_enable: capacity_steps must be positive");
-    for (int a = 0; a < n_groups; ++a)
-        for (int b = 0; b < a; ++b)
-            if (markers[a] == markers[b]) throw EngineError(SPHMI_ERR_ARGUMENT, "sphmi_group_forces_enable: duplicate marker");
-}
-
-// The host side of the series: what the batches delivered since the last sphmi_group_forces_read, the newest `capacity` of it.
-struct GroupForceSeries {
-    struct Sample { int64_t iteration; double time, dt; double f[3 * kMaxForceGroups]; };
-    int n_groups = 0;
-    int64_t capacity = 0, dropped = 0;
-    std::deque<Sample> q;
-    void reset(int n, int64_t cap) { n_groups = n; capacity = cap; dropped = 0; q.clear(); }
-    void push(const Sample& s) {
-        if ((int64_t)q.size() >= capacity) { q.pop_front(); dropped += 1; }
-        q.push_back(s);
-    }
-    // one record of a device-side log (sphmi_group_forces.h)
-    static Sample decode(const double* rec, int n) {
-        Sample s{};
-        memcpy(&s.iteration, rec, 8); s.time = rec[1]; s.dt = rec[2];
-        for (int k = 0; k < 3 * n; ++k) s.f[k] = rec[kGfHeader + k];
-        return s;
-    }
-    void read(int64_t cap, int64_t* iteration, double* time, double* dt, double* force, int64_t* n_out, int64_t* n_dropped) {
-        if (!n_out) throw EngineError(SPHMI_ERR_ARGUMENT, "sphmi_group_forces_read: null n_out");
-        if (cap < 0) throw EngineError(SPHMI_ERR_ARGUMENT, "sphmi_group_forces_read: negative capacity");
-        if (cap == 0) { *n_out = (int64_t)q.size(); if (n_dropped) *n_dropped = dropped; return; }      // a question: nothing is delivered, nothing cleared
-        const int64_t n = std::min<int64_t>(cap, (int64_t)q.size());
-        for (int64_t k = 0; k < n; ++k) {
-            const Sample& s = q.front();
-            if (iteration) iteration[k] = s.iteration;
-            if (time) time[k] = s.time;
-            if (dt) dt[k] = s.dt;
-            if (force) memcpy(force + (size_t)k * 3 * n_groups, s.f, (size_t)3 * n_groups * 8);
-            q.pop_front();
-        }
-        *n_out = n;
-        if (n_dropped) *n_dropped = dropped;
-        dropped = 0;
-    }
-};
-
-// sphmi_probes_enable: the argument errors every kind of handle reports alike
-inline void check_probe_table(int32_t n_probes, const double* positions, int dims, int64_t capacity_steps) {
-    if (n_probes < 0 || n_probes > kMaxProbes) throw EngineError(SPHMI_ERR_ARGUMENT, "sphmi_probes_enable: n_probes out of range [0, 1024]");
-    if (n_probes == 0) return;
-    if (!positions) throw EngineError(SPHMI_ERR_ARGUMENT, "sphmi_probes_enable: null table");
-    if (capacity_steps < 1) throw EngineError(SPHMI_ERR_ARGUMENT, "sphmi_probes_enable: capacity_steps must be positive");
-    for (int64_t k = 0; k < (int64_t)n_probes * dims; ++k)
-        if (!std::isfinite(positions[k])) throw EngineError(SPHMI_ERR_ARGUMENT, "sphmi_probes_enable: non-finite coordinate");
-}
-
-// The host side of the probe series: the RAW sums of the records (sphmi_probes.h) the batches delivered since the last
-// sphmi_probes_read, the newest `capacity` of them; the read normalises.
-struct ProbeSeries {
-    struct Sample { int64_t iteration; double time, dt; std::vector<double> v; };      // v: kPrValues per probe
-    int n_probes = 0;
-    int64_t capacity = 0, dropped = 0;
-    std::deque<Sample> q;
-    void reset(int n, int64_t cap) { n_probes = n; capacity = cap; dropped = 0; q.clear(); }
-    void push(Sample&& s) {
-        if ((int64_t)q.size() >= capacity) { q.pop_front(); dropped += 1; }
-        q.push_back(std::move(s));
-    }
-    static Sample decode(const double* rec, int n) {
-        Sample s{};
-        memcpy(&s.iteration, rec, 8); s.time = rec[1]; s.dt = rec[2];
-        s.v.assign(rec + kPrHeader, rec + kPrHeader + (size_t)kPrValues * n);
-        return s;
-    }
-    void read(int64_t cap, int64_t* iteration, double* time, double* dt, double* weight, int64_t* count, double* pressure, double* density,
-              double* velocity, int64_t* n_out, int64_t* n_dropped) {
-        if (!n_out) throw EngineError(SPHMI_ERR_ARGUMENT, "sphmi_probes_read: null n_out");
-        if (cap < 0) throw EngineError(SPHMI_ERR_ARGUMENT, "sphmi_probes_read: negative capacity");
-        if (cap == 0) { *n_out = (int64_t)q.size(); if (n_dropped) *n_dropped = dropped; return; }      // a question: nothing is delivered, nothing cleared
-        const int64_t n = std::min<int64_t>(cap, (int64_t)q.size());
-        for (int64_t k = 0; k < n; ++k) {
-            const Sample& s = q.front();
-            if (iteration) iteration[k] = s.iteration;
-            if (time) time[k] = s.time;
-            if (dt) dt[k] = s.dt;
-            for (int p = 0; p < n_probes; ++p) {
-                const double* v = s.v.data() + (size_t)kPrValues * p;
-                const size_t at = (size_t)k * n_probes + p;
-                const bool some = v[6] > 0.0 && v[0] > 0.0;              // n == 0: every value is 0
-                if (weight) weight[at] = v[0];
-                if (count) count[at] = (int64_t)v[6];
-                if (pressure) pressure[at] = some ? v[1] / v[0] : 0.0;
-                if (density) density[at] = some ? v[2] / v[0] : 0.0;
-                if (velocity) for (int d = 0; d < 3; ++d) velocity[3 * at + d] = some ? v[3 + d] / v[0] : 0.0;
-            }
-            q.pop_front();
-        }
-        *n_out = n;
-        if (n_dropped) *n_dropped = dropped;
-        dropped = 0;
-    }
-};
-
-// sphmi_sample_grid: the argument errors every kind of handle reports alike; returns the number of nodes
-inline int64_t check_grid_lattice(const double* origin, const double* spacing, const int64_t* counts, int dims) {
-    if (!origin || !spacing || !counts) throw EngineError(SPHMI_ERR_ARGUMENT, "sphmi_sample_grid: null origin, spacing or counts");
-    int64_t nodes = 1;
-    for (int d = 0; d < dims; ++d) {
-        if (!std::isfinite(origin[d])) throw EngineError(SPHMI_ERR_ARGUMENT, "sphmi_sample_grid: non-finite origin");
-        if (!std::isfinite(spacing[d]) || !(spacing[d] > 0.0)) throw EngineError(SPHMI_ERR_ARGUMENT, "sphmi_sample_grid: every spacing must be finite and positive");
-        if (counts[d] < 1) throw EngineError(SPHMI_ERR_ARGUMENT, "sphmi_sample_grid: every count must be at least 1");
-        if (counts[d] > kMaxGridNodes || nodes * counts[d] > kMaxGridNodes) throw EngineError(SPHMI_ERR_ARGUMENT, "sphmi_sample_grid: more than SPHMI_MAX_GRID_NODES nodes");
-        nodes *= counts[d];
-    }
-    return nodes;
-}
-
-// The host side of sphmi_sample_grid: the raw sums { S, SP, Sρ, Sv[3], n } of the lattice (sphmi_field_grid.h), the ones the
-// requested outputs need.  S lands in weight_out itself when that is asked for; the means are formed here, 0 where n == 0.
-struct GridSums {
-    int64_t nodes = 0;
-    double* S = nullptr;                       // weight_out, or s[0]
-    std::vector<double> s[kFgValues];
-    bool want[kFgValues] = {};
-    double* dst(int f) { return f == 0 ? S : s[f].data(); }
-    GridSums(int64_t n, double* weight, const int64_t* count, const double* pressure, const double* density, const double* velocity) : nodes(n) {
-        const bool means = pressure || density || velocity;
-        want[0] = weight || means; want[1] = pressure != nullptr; want[2] = density != nullptr;
-        want[3] = want[4] = want[5] = velocity != nullptr; want[6] = count || means;
-        for (int f = 0; f < kFgValues; ++f) if (want[f] && !(f == 0 && weight)) s[f].assign((size_t)n, 0.0);
-        S = weight ? weight : s[0].data();
-    }
-    void deliver(int64_t* count, double* pressure, double* density, double* velocity) const {
-        const double *SP = s[1].data(), *Sr = s[2].data(), *Sx = s[3].data(), *Sy = s[4].data(), *Sz = s[5].data(), *n = s[6].data();
-        for (int64_t k = 0; k < nodes; ++k) {
-            if (count) count[k] = (int64_t)n[k];
-            if (!pressure && !density && !velocity) continue;
-            const bool some = n[k] > 0.0 && S[k] > 0.0;
-            if (pressure) pressure[k] = some ? SP[k] / S[k] : 0.0;
-            if (density) density[k] = some ? Sr[k] / S[k] : 0.0;
-            if (velocity) { velocity[3 * k] = some ? Sx[k] / S[k] : 0.0; velocity[3 * k + 1] = some ? Sy[k] / S[k] : 0.0; velocity[3 * k + 2] = some ? Sz[k] / S[k] : 0.0; }
-        }
-    }
-};
-
 struct EngineBase {
     sphmi_config cfg{};
     std::string err;
     int64_t iteration = 0, n_rebuilds = 0, index_counter = 0;
     double total_time = 0, last_dt = 0, delta_x = 0;
     bool uploaded = false;
+    void require_uploaded(const char* fn) const {
+        if (!uploaded) throw EngineError(SPHMI_ERR_STATE, std::string(fn) + " before sphmi_upload");
+    }
+    // entry points that need every row in this process: a multi-device handle refuses them in rank mode
+    virtual void require_one_process(const char* fn) const { require_uploaded(fn); }
+    // The observers' series (sphmi_series.h).  A multi-device handle keeps them itself; those of its slab engines stay empty.
+    bool gf_on = false, pr_on = false;
+    StepSeries gf_series, pr_series;           // payload: 3 forces per group / the RAW sums, kPrValues per probe (the read normalises)
+    // the device side of an enable: the handle's own sampling, or that of every slab engine of a multi-device handle
+    virtual void gf_enable_device(int32_t n_groups, const uint64_t* markers) = 0;
+    virtual void pr_enable_device(int32_t n_probes, const double* positions) = 0;
+    void group_forces_enable(int32_t n_groups, const uint64_t* markers, int64_t capacity_steps) {
+        require_one_process("sphmi_group_forces_enable");
+        check_group_table(n_groups, markers, capacity_steps);
+        gf_enable_device(n_groups, markers);
+        gf_series.reset(3 * n_groups, capacity_steps);
+    }
+    void probes_enable(int32_t n_probes, const double* positions, int64_t capacity_steps) {
+        require_one_process("sphmi_probes_enable");
+        check_probe_table(n_probes, positions, cfg.dims, capacity_steps);
+        pr_enable_device(n_probes, positions);
+        pr_series.reset(kPrValues * n_probes, capacity_steps);
+    }
+    void group_forces_read(int64_t capacity, int64_t* iteration_out, double* time, double* dt, double* force, int64_t* n_out, int64_t* n_dropped) {
+        require_one_process("sphmi_group_forces_read");
+        if (!gf_on) throw EngineError(SPHMI_ERR_STATE, "sphmi_group_forces_read: sampling is not enabled (sphmi_group_forces_enable)");
+        gf_series.read("sphmi_group_forces_read", capacity, iteration_out, time, dt, n_out, n_dropped,
+                       [&](int64_t k, const double* v) { deliver_forces(gf_series.values / 3, k, v, force); });
+    }
+    void probes_read(int64_t capacity, int64_t* iteration_out, double* time, double* dt, double* weight, int64_t* count, double* pressure,
+                     double* density, double* velocity, int64_t* n_out, int64_t* n_dropped) {
+        require_one_process("sphmi_probes_read");
+        if (!pr_on) throw EngineError(SPHMI_ERR_STATE, "sphmi_probes_read: sampling is not enabled (sphmi_probes_enable)");
+        pr_series.read("sphmi_probes_read", capacity, iteration_out, time, dt, n_out, n_dropped, [&](int64_t k, const double* v) {
+            deliver_probe_means(pr_series.values / kPrValues, k, v, weight, count, pressure, density, velocity);
+        });
+    }
     virtual ~EngineBase() {}
     virtual void upload(const void*, const void*, const void*, const void*, const uint8_t*, const int64_t*,
                         const uint64_t*, const void*) = 0;
@@ -295,11 +168,6 @@ struct EngineBase {
     virtual void download_permutation(int64_t* prev_row) = 0;
     virtual void attach_columns(int32_t n_columns, const void* const* columns, const int32_t* row_bytes) = 0;
     virtual void download_columns_begin(void* const* columns_out) = 0;
-    virtual void group_forces_enable(int32_t n_groups, const uint64_t* markers, int64_t capacity_steps) = 0;
-    virtual void group_forces_read(int64_t capacity, int64_t* iteration, double* time, double* dt, double* force, int64_t* n_out, int64_t* n_dropped) = 0;
-    virtual void probes_enable(int32_t n_probes, const double* positions, int64_t capacity_steps) = 0;
-    virtual void probes_read(int64_t capacity, int64_t* iteration, double* time, double* dt, double* weight, int64_t* count, double* pressure,
-                             double* density, double* velocity, int64_t* n_out, int64_t* n_dropped) = 0;
     virtual void sample_grid(const double* origin, const double* spacing, const int64_t* counts, double* weight, int64_t* count, double* pressure,
                              double* density, double* velocity) = 0;
     virtual void particle_fields(int64_t* count, double* shepard, double* normal, double* div_r, double* div_v, double* vorticity) = 0;
@@ -574,7 +442,7 @@ struct Engine final : EngineBase {
         for (auto& e : host_pinned) (void)hipHostUnregister(e.first);
         (void)hipFree(out_arena);
         (void)hipFree(col_arena); (void)hipFree(col_store); (void)hipFree(col_base[0]); (void)hipFree(col_base[1]);
-        gf_release(); pr_release(); (void)hipFree(fg_arena); (void)hipFree(pf_arena);
+        gf_release(); pr_release(); (void)hipFree(fg_arena.p); (void)hipFree(pf_arena.p);
         (void)hipFree(slot); (void)hipFree(tmp_idx); (void)hipFree(perm);
         for (int k = 0; k < 2; ++k) { (void)hipFree(tile_cost[k]); (void)hipFree(tile_order[k]); }
         (void)hipFree(kout_d); (void)hipFree(tile_work_d); (void)hipFree(tile_work1_d); (void)hipFree(xcd_clock_d); (void)hipHostFree(xcd_clock_h);
@@ -665,7 +533,9 @@ struct Engine final : EngineBase {
     T kv2() const { return (T)(2.0 * cfg.m0 * cfg.alpha * cfg.c0 * cfg.h); }
     bool kv2_foldable() const { const T k = kv2(); return std::isnormal(k) && std::isfinite(T(1) / k) && std::isnormal(T(1) / k); }
     // … and evaluate Pressure! of a neighbour as ρ⁷·(Cb/γ/ρ₀⁷) − Cb/γ (fp32 kernels: ρ⁷ must stay finite up to 4ρ₀, the constant normal)
-    T cbe7() const { return (T)(((cfg.c0 * cfg.c0 * cfg.rho0) / 7.0) / std::pow(cfg.rho0, 7.0)); }
+    double cb_gamma() const { return (cfg.c0 * cfg.c0 * cfg.rho0) / 7.0; }     // Cb/γ of Pressure!, γ = 7
+    T cbe() const { return (T)cb_gamma(); }
+    T cbe7() const { return (T)(cb_gamma() / std::pow(cfg.rho0, 7.0)); }
     // (fp32: ρ⁷ must neither overflow at 4 ρ₀ nor fall into the subnormals at ρ₀ / 4 — unit systems with ρ₀ ≈ 1e-6 — where ρ⁷·Cbe7 would lose the
     // neighbour pressure without a word; such handles take the run-time variant, which forms (ρ/ρ₀)⁷)
     bool eos_foldable() const { return sizeof(T) == 8 || (std::pow(4.0 * cfg.rho0, 7.0) < 1e37 && std::pow(0.25 * cfg.rho0, 7.0) > 1e-30 && std::isnormal(cbe7())); }
@@ -712,7 +582,7 @@ struct Engine final : EngineBase {
         P.hyd_a = cfg.rho0 * cfg.g / cfg.Cb; P.hyd_b = cfg.rho0;
         P.rho0 = (T)cfg.rho0; P.inv_rho0 = (T)(1.0 / cfg.rho0);
         P.g = (T)cfg.g;
-        P.Cbe = (T)((cfg.c0 * cfg.c0 * cfg.rho0) / 7.0);
+        P.Cbe = cbe();
         P.Cbe7 = eos_foldable() ? cbe7() : T(0);
         return P;
     }
@@ -1245,17 +1115,17 @@ struct Engine final : EngineBase {
         Ev e2 = begin_phase(PH_PASS2);
         launch_force<PASS_CORRECTOR>(P2);                                      // :789-798
         end_phase(e2);
-        if (gf_on) gf_sample(ctrl_cur(), gf_iteration0, gf_steps_base);        // Σ Acceleration of the selected groups → the batch's log
-        if (pr_on) pr_sample(ctrl_cur(), gf_iteration0, gf_steps_base, iB);    // the kernel sums at the probes, on the corrector's output set → the batch's log
+        if (gf_on) gf_sample(ctrl_cur(), obs_iteration0, obs_steps_base);       // Σ Acceleration of the selected groups → the batch's log
+        if (pr_on) pr_sample(ctrl_cur(), obs_iteration0, obs_steps_base, iB);   // the kernel sums at the probes, on the corrector's output set → the batch's log
         std::swap(iA, iB);
     }
 
     void advance(double t_target, int64_t max_steps, sphmi_progress* out) override {
-        if (!uploaded) throw EngineError(SPHMI_ERR_STATE, "sphmi_advance before sphmi_upload");
+        require_uploaded("sphmi_advance");
         HC(hipSetDevice(cfg.device));
         delta_x = 1.0 + cfg.h;                                                // :739
         int64_t steps = 0;
-        gf_iteration0 = iteration;
+        obs_iteration0 = iteration;
         StepCtrl c{};
         c.delta_x = delta_x; c.total_time = total_time; c.t_step_start = total_time; c.t_target = t_target;
         c.max_steps = max_steps; c.last_dt = last_dt;
@@ -1281,14 +1151,14 @@ struct Engine final : EngineBase {
                 if (dx0 >= cfg.h) batch = 1;
                 else if (dx_rate > 0.0) batch = (int)std::max(1.0, std::min((double)kBatch, std::ceil((cfg.h - dx0) / dx_rate) + (fresh ? 2.0 : 1.0)));
                 if (max_steps >= 0) batch = (int)std::min<int64_t>(batch, std::max<int64_t>(max_steps - steps, 1));
-                gf_steps_base = steps;
+                obs_steps_base = steps;
                 for (int k = 0; k < batch; ++k) { batch_step = k; enqueue_step(); iteration += 1; }      // iteration: provisional (event sampling)
                 batch_step = -1;
                 // the block the last queued step wrote, both sets of slots (below: the bad-ρ flag), the counters and the run table of a
                 // device-side rebuild: one copy
                 HC(hipMemcpyAsync(ctl_m, ctl_d, kCtlBytes, hipMemcpyDeviceToHost, stream));
-                if (gf_on) gf_fetch(batch);                                       // … and the group-force records of the batch with it
-                if (pr_on) pr_fetch(batch);                                       // … and the probe records
+                if (gf_on) gf_log.fetch(batch, stream);                                      // … and the group-force records of the batch with it
+                if (pr_on) pr_log.fetch(batch, stream);                                      // … and the probe records
                 // (the XCD finishing times of a sampled launch: the host-side rebuild reads them at its own synchronisation; handles that
                 // rebuild on the device have none — the shares of the next measured-work schedule would never move: 3 % on the 159 k-particle
                 // LaminarSPS case)
@@ -1301,8 +1171,8 @@ struct Engine final : EngineBase {
                 c = *ctrl_h;
                 steps = c.steps_done;
                 const int64_t executed = steps - before;
-                if (gf_on) for (int64_t k = 0; k < executed; ++k) gf_series.push(GroupForceSeries::decode(gf_record(k), gf_table.n));
-                if (pr_on) for (int64_t k = 0; k < executed; ++k) pr_series.push(ProbeSeries::decode(pr_record(k), pr_n));
+                if (gf_on) push_records(gf_series, gf_log, kGfHeader, executed);
+                if (pr_on) push_records(pr_series, pr_log, kPrHeader, executed);
                 // (control inside the predictor: the slots flipped at queue time, once per queued step; what counts is where
                 // the last EXECUTED corrector left its maxima — cancelled steps consume nothing and zero nothing)
                 if (batch_fused) rpar = rpar0 ^ (int)(executed & 1);
@@ -1423,7 +1293,7 @@ struct Engine final : EngineBase {
         hipLaunchKernelGGL(k_iota, dim3(nb256), dim3(256), 0, stream, prow[cur], N);
         // Pressure! (src/SPHCellList.jl:835) and the reductions Δt / update_delta_x! will read first
         hipLaunchKernelGGL(k_eos<T>, dim3(nb256), dim3(256), 0, stream, pk0[iA], pk1[iA], N, (T)cfg.rho0,
-                           (T)(1.0 / cfg.rho0), (T)((cfg.c0 * cfg.c0 * cfg.rho0) / 7.0));
+                           (T)(1.0 / cfg.rho0), cbe());
         hipLaunchKernelGGL(k_init_reduce<T>, dim3(nb256), dim3(256), 0, stream, pk0[iA], pk1[iA], acc[cur], N,
                            (T)cfg.h, (T)cfg.eta2, red_d);
         HC(hipGetLastError());
@@ -1483,7 +1353,7 @@ struct Engine final : EngineBase {
             HC(hipMemsetAsync(key[cur], 0, n * 4, stream)); HC(hipMemsetAsync(red_d, 0, 8 * 8, stream)); cpar = 0; rpar = 0;
             const int nb256 = (N + 255) / 256;
             hipLaunchKernelGGL(k_iota, dim3(nb256), dim3(256), 0, stream, prow[cur], N);
-            hipLaunchKernelGGL(k_eos<T>, dim3(nb256), dim3(256), 0, stream, pk0[iA], pk1[iA], N, (T)cfg.rho0, (T)(1.0 / cfg.rho0), (T)((cfg.c0 * cfg.c0 * cfg.rho0) / 7.0));
+            hipLaunchKernelGGL(k_eos<T>, dim3(nb256), dim3(256), 0, stream, pk0[iA], pk1[iA], N, (T)cfg.rho0, (T)(1.0 / cfg.rho0), cbe());
             hipLaunchKernelGGL(k_init_reduce<T>, dim3(nb256), dim3(256), 0, stream, pk0[iA], pk1[iA], acc[cur], N, (T)cfg.h, (T)cfg.eta2, red_d);
             HC(hipGetLastError());
             HC(hipStreamSynchronize(stream));
@@ -1559,7 +1429,7 @@ struct Engine final : EngineBase {
         char* a_tag = take(dl_tags_host != nullptr && otag[0], n * 8);
         hipLaunchKernelGGL((k_pack_output<T, H>), dim3((N + 255) / 256), dim3(256), 0, stream, pk0[iA], pk1[iA],
                            stepped ? Half<const V4>(pk0[iH]) : Half<const V4>(), acc[cur], ghost[cur], comp[cur], key[cur], N, D, out_comp, grid, have_grid ? 1 : 0,
-                           (T)cfg.rho0, (T)(1.0 / cfg.rho0), (T)((cfg.c0 * cfg.c0 * cfg.rho0) / 7.0), o);
+                           (T)cfg.rho0, (T)(1.0 / cfg.rho0), cbe(), o);
         HC(hipGetLastError());
         if (a_id) HC(hipMemcpyAsync(a_id, id[cur], n * 8, hipMemcpyDeviceToDevice, stream));
         if (a_ty) HC(hipMemcpyAsync(a_ty, type[cur], n, hipMemcpyDeviceToDevice, stream));
@@ -1591,7 +1461,7 @@ struct Engine final : EngineBase {
     }
     void download_begin(void* position, void* velocity, void* acceleration, void* density, void* pressure,
                         int64_t* ids, uint8_t* ty, uint64_t* groups, void* ghost_points, int64_t* cells) override {
-        if (!uploaded) throw EngineError(SPHMI_ERR_STATE, "sphmi_download before sphmi_upload");
+        require_uploaded("sphmi_download");
         HC(hipSetDevice(cfg.device));
         if (cfg.host_float_bytes == 8) download_begin_as<double>(position, velocity, acceleration, density, pressure, ids, ty, groups, ghost_points, cells);
         else download_begin_as<float>(position, velocity, acceleration, density, pressure, ids, ty, groups, ghost_points, cells);
@@ -1626,7 +1496,7 @@ struct Engine final : EngineBase {
     // start counting from the present order.  The reference's sort! permutes all 17 fields of the StructArray
     // (src/SPHCellList.jl:142); the engine carries ten of them, and this is what lets the caller permute the rest.
     void download_permutation(int64_t* prev_row) override {
-        if (!uploaded) throw EngineError(SPHMI_ERR_STATE, "sphmi_download_permutation before sphmi_upload");
+        require_uploaded("sphmi_download_permutation");
         if (!prev_row) throw EngineError(SPHMI_ERR_ARGUMENT, "sphmi_download_permutation: null array");
         HC(hipSetDevice(cfg.device));
         std::vector<int> tmp((size_t)N);
@@ -1656,7 +1526,7 @@ struct Engine final : EngineBase {
         col_store = nullptr; col_base[0] = col_base[1] = nullptr; col_cur = 0; col_table = ColumnTable{};
     }
     void attach_columns(int32_t n_columns, const void* const* columns, const int32_t* row_bytes) override {
-        if (!uploaded) throw EngineError(SPHMI_ERR_STATE, "sphmi_attach_columns before sphmi_upload");
+        require_uploaded("sphmi_attach_columns");
         check_column_table(n_columns, columns, row_bytes);
         HC(hipSetDevice(cfg.device));
         detach_columns();
@@ -1698,7 +1568,7 @@ struct Engine final : EngineBase {
     // sphmi_download_begin it sees the same rows), the device → host copies on the copy stream; a field download in flight is
     // neither waited for nor disturbed (own arena, own list of deferred copies), one download_end completes both.
     void download_columns_begin(void* const* columns_out) override {
-        if (!uploaded) throw EngineError(SPHMI_ERR_STATE, "sphmi_download_columns before sphmi_upload");
+        require_uploaded("sphmi_download_columns");
         if (!col_store) throw EngineError(SPHMI_ERR_STATE, "sphmi_download_columns: no columns attached (sphmi_attach_columns)");
         if (!columns_out) throw EngineError(SPHMI_ERR_ARGUMENT, "sphmi_download_columns: null table");
         HC(hipSetDevice(cfg.device));
@@ -1736,25 +1606,74 @@ struct Engine final : EngineBase {
         }
         columns_pending = true;
     }
+    // ---- what the observers share ---------------------------------------------------------------------------------------------
+    // The device-side log of an observer that records once per executed step: kBatch slots of record_doubles doubles and their
+    // page-locked mirror, fetched with the control block of a batch.  obs_iteration0 / obs_steps_base: the clock of the batch.
+    struct StepLog {
+        static constexpr int slots = kBatch;
+        double *d = nullptr, *m = nullptr;
+        int record_doubles = 0;
+        void alloc(int alloc_record_doubles, int record) {
+            HC(hipMalloc(&d, (size_t)slots * alloc_record_doubles * 8)); HC(hipHostMalloc(&m, (size_t)slots * alloc_record_doubles * 8));
+            record_doubles = record;
+        }
+        void release() { (void)hipFree(d); (void)hipHostFree(m); d = m = nullptr; record_doubles = 0; }
+        void fetch(int batch, hipStream_t s) { HC(hipMemcpyAsync(m, d, (size_t)std::min(batch, slots) * (size_t)record_doubles * 8, hipMemcpyDeviceToHost, s)); }
+        const double* record(int64_t k) const { return m + (size_t)k * (size_t)record_doubles; }      // of the k-th executed step of the fetched batch
+    };
+    int64_t obs_iteration0 = 0, obs_steps_base = 0;
+    // after the synchronisation of a batch: the records of its `executed` steps
+    static void push_records(StepSeries& series, const StepLog& log, int header, int64_t executed) {
+        for (int64_t k = 0; k < executed; ++k) series.push(StepSeries::decode(log.record(k), header, series.values));
+    }
+    // The results of an on-demand sampler: device memory that only grows.
+    struct DeviceArena {
+        double* p = nullptr; size_t doubles = 0;
+        void need(size_t n, const char* fn_name, const char* what, long long count) {
+            if (n <= doubles) return;
+            (void)hipFree(p);
+            p = nullptr; doubles = 0;
+            if (hipMalloc(&p, n * 8) != hipSuccess) {
+                (void)hipGetLastError();
+                char buf[160];
+                snprintf(buf, sizeof(buf), "%s: no device memory for the result arena of %lld %s (%.2f GB)", fn_name, count, what, (double)n * 8.0 / 1e9);
+                throw EngineError(SPHMI_ERR_DEVICE, buf);
+            }
+            doubles = n;
+        }
+    };
+    // a result → host, behind its kernel: directly into memory the caller page-locked — there after the next synchronisation of
+    // the stream — else through the bounce buffer
+    void fetch_result(void* dst, const void* src, size_t bytes) {
+        if (is_registered(dst, bytes)) HC(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, stream));
+        else bounce.d2h(dst, src, bytes, stream);
+    }
+    // the constants of the kernel sums, by member name: every sampler sees the same H, h, αD, m₀ …
+    template <class A> void fill_kernel_consts(A& a) const {
+        a.H_inv = cfg.H_inv; a.H2 = cfg.H2; a.h_inv = cfg.h_inv; a.reach = cfg.H + cfg.h;
+        a.alphaD = cfg.alphaD; a.m0 = cfg.m0;
+    }
+    // … and the samplers that evaluate Pressure! the same equation of state
+    template <class A> void fill_sample_consts(A& a) const {
+        fill_kernel_consts(a);
+        a.rho0 = (T)cfg.rho0; a.inv_rho0 = (T)(1.0 / cfg.rho0); a.Cbe = cbe();
+    }
+
     // ---- per-step force on particle groups (sphmi_group_forces.h) -------------------------------------------------------
     // Off: none of the members below is touched by a step.  On: three launches behind every rebuild that permutes (the row
     // lists), one or two behind every corrector (the sums → the batch's log), one more copy per batch boundary.
-    bool gf_on = false;
     GroupTable gf_table{};
     int *gf_list = nullptr, *gf_counts = nullptr, *gf_offsets = nullptr;
     GroupListMeta* gf_meta = nullptr;
-    double *gf_partial = nullptr, *gf_log_d = nullptr, *gf_log_m = nullptr;
-    int64_t gf_iteration0 = 0, gf_steps_base = 0;
-    GroupForceSeries gf_series;
-    int gf_record_doubles() const { return kGfHeader + 3 * gf_table.n; }
+    double* gf_partial = nullptr;
+    StepLog gf_log;
     int gf_nblk_cap() const { return (cap + 255) / 256; }
     int gf_list_cap() const { return cap + kMaxForceGroups * kGfChunk; }
     int gf_chunk_cap() const { return cap / kGfChunk + kMaxForceGroups + 1; }
-    const double* gf_record(int64_t k) const { return gf_log_m + (size_t)k * (size_t)gf_record_doubles(); }
     void gf_release() {
-        (void)hipFree(gf_list); (void)hipFree(gf_counts); (void)hipFree(gf_offsets); (void)hipFree(gf_meta);
-        (void)hipFree(gf_partial); (void)hipFree(gf_log_d); (void)hipHostFree(gf_log_m);
-        gf_list = gf_counts = gf_offsets = nullptr; gf_meta = nullptr; gf_partial = gf_log_d = gf_log_m = nullptr;
+        (void)hipFree(gf_list); (void)hipFree(gf_counts); (void)hipFree(gf_offsets); (void)hipFree(gf_meta); (void)hipFree(gf_partial);
+        gf_list = gf_counts = gf_offsets = nullptr; gf_meta = nullptr; gf_partial = nullptr;
+        gf_log.release();
     }
     void gf_disable() {
         if (!gf_on) return;
@@ -1762,8 +1681,7 @@ struct Engine final : EngineBase {
         HC(hipStreamSynchronize(stream));
         gf_release();
     }
-    // the device side: what a slab engine of a multi-device handle needs too (the series lives in the handle)
-    void gf_enable_device(int32_t n_groups, const uint64_t* markers) {
+    void gf_enable_device(int32_t n_groups, const uint64_t* markers) override {
         HC(hipSetDevice(cfg.device));
         gf_disable();
         if (n_groups == 0) return;
@@ -1772,7 +1690,7 @@ struct Engine final : EngineBase {
             HC(hipMalloc(&gf_counts, (size_t)kMaxForceGroups * gf_nblk_cap() * 4)); HC(hipMalloc(&gf_offsets, (size_t)kMaxForceGroups * gf_nblk_cap() * 4));
             HC(hipMalloc(&gf_meta, sizeof(GroupListMeta))); HC(hipMemset(gf_meta, 0, sizeof(GroupListMeta)));
             HC(hipMalloc(&gf_partial, (size_t)gf_chunk_cap() * 3 * 8));
-            HC(hipMalloc(&gf_log_d, (size_t)kBatch * kGfRecordMax * 8)); HC(hipHostMalloc(&gf_log_m, (size_t)kBatch * kGfRecordMax * 8));
+            gf_log.alloc(kGfRecordMax, kGfHeader + 3 * n_groups);
         } catch (...) { gf_release(); throw; }
         gf_table.n = n_groups;
         for (int g = 0; g < n_groups; ++g) gf_table.marker[g] = markers[g];
@@ -1791,9 +1709,9 @@ struct Engine final : EngineBase {
     // behind the corrector of a queued step; `ctrl`: the control block that corrector read
     void gf_sample(const StepCtrl* ctrl, int64_t iteration0, int64_t steps_base) {
         GroupSampleArgs A{};
-        A.ctrl = ctrl; A.list = gf_list; A.meta = gf_meta; A.partial = gf_partial; A.log = gf_log_d;
+        A.ctrl = ctrl; A.list = gf_list; A.meta = gf_meta; A.partial = gf_partial; A.log = gf_log.d;
         A.iteration0 = iteration0; A.steps_base = steps_base; A.m0 = cfg.m0;
-        A.n_groups = gf_table.n; A.N = N; A.D = D; A.record = gf_record_doubles(); A.slots = kBatch;
+        A.n_groups = gf_table.n; A.N = N; A.D = D; A.record = gf_log.record_doubles; A.slots = StepLog::slots;
         if (N <= kGfSmallRows) hipLaunchKernelGGL(k_gf_small<T>, dim3(1), dim3(kGfChunk), 0, stream, (const V4*)acc[cur], A);
         else {
             const int max_chunks = std::min(N / kGfChunk + gf_table.n + 1, gf_chunk_cap());
@@ -1802,32 +1720,15 @@ struct Engine final : EngineBase {
         }
         HC(hipGetLastError());
     }
-    void gf_fetch(int batch) {
-        HC(hipMemcpyAsync(gf_log_m, gf_log_d, (size_t)std::min(batch, kBatch) * (size_t)gf_record_doubles() * 8, hipMemcpyDeviceToHost, stream));
-    }
-    void group_forces_enable(int32_t n_groups, const uint64_t* markers, int64_t capacity_steps) override {
-        if (!uploaded) throw EngineError(SPHMI_ERR_STATE, "sphmi_group_forces_enable before sphmi_upload");
-        check_group_table(n_groups, markers, capacity_steps);
-        gf_enable_device(n_groups, markers);
-        gf_series.reset(n_groups, capacity_steps);
-    }
-    void group_forces_read(int64_t capacity, int64_t* iteration_out, double* time, double* dt, double* force, int64_t* n_out, int64_t* n_dropped) override {
-        if (!uploaded) throw EngineError(SPHMI_ERR_STATE, "sphmi_group_forces_read before sphmi_upload");
-        if (!gf_on) throw EngineError(SPHMI_ERR_STATE, "sphmi_group_forces_read: sampling is not enabled (sphmi_group_forces_enable)");
-        gf_series.read(capacity, iteration_out, time, dt, force, n_out, n_dropped);
-    }
 
     // ---- kernel sums at fixed probe points (sphmi_probes.h) -----------------------------------------------------------------
-    // The records of a batch go where the group forces' go: a log of kBatch slots on the device, fetched with the control block
-    // (gf_iteration0 / gf_steps_base: the clock of the batch is the same for both).
-    bool pr_on = false; int pr_n = 0;
-    double *pr_pos_d = nullptr, *pr_log_d = nullptr, *pr_log_m = nullptr;
-    ProbeSeries pr_series;
-    int pr_record_doubles() const { return kPrHeader + kPrValues * pr_n; }
-    const double* pr_record(int64_t k) const { return pr_log_m + (size_t)k * (size_t)pr_record_doubles(); }
+    // The records of a batch go where the group forces' go: a log of kBatch slots on the device, fetched with the control block.
+    int pr_n = 0;
+    double* pr_pos_d = nullptr;
+    StepLog pr_log;
     void pr_release() {
-        (void)hipFree(pr_pos_d); (void)hipFree(pr_log_d); (void)hipHostFree(pr_log_m);
-        pr_pos_d = pr_log_d = pr_log_m = nullptr;
+        (void)hipFree(pr_pos_d); pr_pos_d = nullptr;
+        pr_log.release();
     }
     void pr_disable() {
         if (!pr_on) return;
@@ -1835,18 +1736,16 @@ struct Engine final : EngineBase {
         HC(hipSetDevice(cfg.device)); HC(hipStreamSynchronize(stream));
         pr_release();
     }
-    // the device side of sphmi_probes_enable (a multi-device handle calls it on every slab engine and keeps the series itself)
-    void pr_enable_device(int32_t n_probes, const double* positions) {
+    void pr_enable_device(int32_t n_probes, const double* positions) override {
         HC(hipSetDevice(cfg.device));
         pr_disable();
         if (n_probes == 0) return;
         if (!(cfg.h <= cfg.H)) throw EngineError(SPHMI_ERR_STATE, "sphmi_probes_enable: handles with H < h are not served (the candidate cells of a probe are laid out for H + h <= 2H)");
         std::vector<double> xyz((size_t)3 * n_probes, 0.0);
         for (int p = 0; p < n_probes; ++p) for (int d = 0; d < D; ++d) xyz[3 * (size_t)p + d] = positions[(size_t)p * D + d];
-        const size_t rec_bytes = (size_t)(kPrHeader + kPrValues * n_probes) * 8;
         try {
             HC(hipMalloc(&pr_pos_d, xyz.size() * 8));
-            HC(hipMalloc(&pr_log_d, (size_t)kBatch * rec_bytes)); HC(hipHostMalloc(&pr_log_m, (size_t)kBatch * rec_bytes));
+            pr_log.alloc(kPrHeader + kPrValues * n_probes, kPrHeader + kPrValues * n_probes);
             bounce.h2d(pr_pos_d, xyz.data(), xyz.size() * 8, stream);
         } catch (...) { pr_release(); throw; }
         pr_n = n_probes;
@@ -1856,77 +1755,46 @@ struct Engine final : EngineBase {
     void pr_sample(const StepCtrl* ctrl, int64_t iteration0, int64_t steps_base, int set) {
         ProbeSampleArgs<T> A{};
         A.ctrl = ctrl; A.pk0 = pk0[set]; A.pk1 = pk1[set]; A.half0 = pk0[iH]; A.comp = comp[cur];
-        A.type = dd_slab ? type[cur] : nullptr; A.cstart = cstart; A.pos = pr_pos_d; A.log = pr_log_d; A.g = grid;
+        A.type = dd_slab ? type[cur] : nullptr; A.cstart = cstart; A.pos = pr_pos_d; A.log = pr_log.d; A.g = grid;
         A.iteration0 = iteration0; A.steps_base = steps_base;
-        A.H_inv = cfg.H_inv; A.H2 = cfg.H2; A.h_inv = cfg.h_inv; A.reach = cfg.H + cfg.h;
-        A.alphaD = cfg.alphaD; A.m0 = cfg.m0;
-        A.rho0 = (T)cfg.rho0; A.inv_rho0 = (T)(1.0 / cfg.rho0); A.Cbe = (T)((cfg.c0 * cfg.c0 * cfg.rho0) / 7.0);
-        A.n_probes = pr_n; A.N = N; A.D = D; A.kernel = cfg.kernel; A.record = pr_record_doubles(); A.slots = kBatch;
+        fill_sample_consts(A);
+        A.n_probes = pr_n; A.N = N; A.D = D; A.kernel = cfg.kernel; A.record = pr_log.record_doubles; A.slots = StepLog::slots;
         hipLaunchKernelGGL(k_probe_sample<T>, dim3((pr_n + 3) / 4), dim3(256), 0, stream, A);
         HC(hipGetLastError());
-    }
-    void pr_fetch(int batch) {
-        HC(hipMemcpyAsync(pr_log_m, pr_log_d, (size_t)std::min(batch, kBatch) * (size_t)pr_record_doubles() * 8, hipMemcpyDeviceToHost, stream));
-    }
-    void probes_enable(int32_t n_probes, const double* positions, int64_t capacity_steps) override {
-        if (!uploaded) throw EngineError(SPHMI_ERR_STATE, "sphmi_probes_enable before sphmi_upload");
-        check_probe_table(n_probes, positions, D, capacity_steps);
-        pr_enable_device(n_probes, positions);
-        pr_series.reset(n_probes, capacity_steps);
-    }
-    void probes_read(int64_t capacity, int64_t* iteration_out, double* time, double* dt, double* weight, int64_t* count, double* pressure,
-                     double* density, double* velocity, int64_t* n_out, int64_t* n_dropped) override {
-        if (!uploaded) throw EngineError(SPHMI_ERR_STATE, "sphmi_probes_read before sphmi_upload");
-        if (!pr_on) throw EngineError(SPHMI_ERR_STATE, "sphmi_probes_read: sampling is not enabled (sphmi_probes_enable)");
-        pr_series.read(capacity, iteration_out, time, dt, weight, count, pressure, density, velocity, n_out, n_dropped);
     }
 
     // ---- kernel sums on a regular lattice, on demand (sphmi_field_grid.h) ------------------------------------------------------
     // Reads what sphmi_download reads — the current set, the half-step set, the low words — plus `cstart` and the grid of the last
     // rebuild; writes its own arena and nothing else.  A download in flight keeps out_arena and the copy stream to itself.
-    double* fg_arena = nullptr; size_t fg_arena_doubles = 0;
+    DeviceArena fg_arena;
     bool fg_ready() const { return stepped && have_grid && cstart != nullptr && N > 0; }
     // queue the kernel for the whole lattice on the engine's stream (a multi-device handle calls it on every slab engine)
     void fg_launch(const double* origin, const double* spacing, const int64_t* counts, int64_t nodes) {
         HC(hipSetDevice(cfg.device));
-        const size_t need = (size_t)kFgValues * (size_t)nodes;
-        if (need > fg_arena_doubles) {
-            (void)hipFree(fg_arena);
-            fg_arena = nullptr; fg_arena_doubles = 0;
-            if (hipMalloc(&fg_arena, need * 8) != hipSuccess) {
-                (void)hipGetLastError();
-                char buf[160];
-                snprintf(buf, sizeof(buf), "sphmi_sample_grid: no device memory for the result arena of %lld nodes (%.2f GB)", (long long)nodes, (double)need * 8.0 / 1e9);
-                throw EngineError(SPHMI_ERR_DEVICE, buf);
-            }
-            fg_arena_doubles = need;
-        }
+        fg_arena.need((size_t)kFgValues * (size_t)nodes, "sphmi_sample_grid", "nodes", (long long)nodes);
         FieldGridArgs<T> A{};
         A.pk0 = pk0[iA]; A.pk1 = pk1[iA]; A.half0 = pk0[iH]; A.comp = comp[cur];
-        A.type = dd_slab ? type[cur] : nullptr; A.cstart = cstart; A.out = fg_arena; A.g = grid;
+        A.type = dd_slab ? type[cur] : nullptr; A.cstart = cstart; A.out = fg_arena.p; A.g = grid;
         int64_t c3[3] = {1, 1, 1};
         for (int d = 0; d < 3; ++d) { A.origin[d] = d < D ? origin[d] : 0.0; A.spacing[d] = d < D ? spacing[d] : 1.0; if (d < D) c3[d] = counts[d]; }
         fg_plan_brick(D, A.spacing, c3, A.brick);
         long long nb = 1;
         for (int d = 0; d < 3; ++d) { A.counts[d] = (int)c3[d]; A.nbricks[d] = (int)((c3[d] + A.brick[d] - 1) / A.brick[d]); nb *= A.nbricks[d]; }
         A.nodes = nodes;
-        A.H_inv = cfg.H_inv; A.H2 = cfg.H2; A.h_inv = cfg.h_inv; A.reach = cfg.H + cfg.h;
-        A.alphaD = cfg.alphaD; A.m0 = cfg.m0;
-        A.rho0 = (T)cfg.rho0; A.inv_rho0 = (T)(1.0 / cfg.rho0); A.Cbe = (T)((cfg.c0 * cfg.c0 * cfg.rho0) / 7.0);
+        fill_sample_consts(A);
         A.N = N; A.kernel = cfg.kernel;
         if (D == 3) hipLaunchKernelGGL((k_field_grid<T, 3>), dim3((unsigned)nb), dim3(kFgThreads), 0, stream, A);
         else        hipLaunchKernelGGL((k_field_grid<T, 2>), dim3((unsigned)nb), dim3(kFgThreads), 0, stream, A);
         HC(hipGetLastError());
     }
-    // one raw sum of the lattice → host, behind the kernel: directly into memory the caller page-locked, else through the bounce buffer
-    void fg_fetch(int f, double* dst, int64_t nodes) {
-        const size_t bytes = (size_t)nodes * 8;
-        if (is_registered(dst, bytes)) { HC(hipMemcpyAsync(dst, fg_arena + (size_t)f * (size_t)nodes, bytes, hipMemcpyDeviceToHost, stream)); HC(hipStreamSynchronize(stream)); }
-        else bounce.d2h(dst, fg_arena + (size_t)f * (size_t)nodes, bytes, stream);
-    }
+    // One raw sum of the lattice → host, behind the kernel.  No synchronisation of its own: sample_grid synchronises once before
+    // it forms the means, and the slab engines of a multi-device handle — whose `dst` that handle adds to as soon as this returns —
+    // never hold registered memory (MultiEngine::host_register registers nothing), so there the copy is the bounce buffer's,
+    // which is complete on return.
+    void fg_fetch(int f, double* dst, int64_t nodes) { fetch_result(dst, fg_arena.p + (size_t)f * (size_t)nodes, (size_t)nodes * 8); }
     void sample_grid(const double* origin, const double* spacing, const int64_t* counts, double* weight, int64_t* count, double* pressure,
                      double* density, double* velocity) override {
-        if (!uploaded) throw EngineError(SPHMI_ERR_STATE, "sphmi_sample_grid before sphmi_upload");
+        require_uploaded("sphmi_sample_grid");
         if (!(cfg.h <= cfg.H)) throw EngineError(SPHMI_ERR_STATE, "sphmi_sample_grid: handles with H < h are not served (the candidate cells are laid out for H + h <= 2H)");
         if (!fg_ready()) throw EngineError(SPHMI_ERR_STATE, "sphmi_sample_grid: the handle has not executed a step since the upload (no cell list, no half-step set)");
         const int64_t nodes = check_grid_lattice(origin, spacing, counts, D);
@@ -1939,41 +1807,27 @@ struct Engine final : EngineBase {
 
     // ---- differential fields at the particles, on demand (sphmi_particle_fields.h) -------------------------------------------------
     // Reads the current set, the low words, `cstart` and the grid of the last rebuild; writes its own arena and nothing else.
-    double* pf_arena = nullptr; size_t pf_arena_doubles = 0;
+    DeviceArena pf_arena;
     void particle_fields(int64_t* count, double* shepard, double* normal, double* div_r, double* div_v, double* vorticity) override {
-        if (!uploaded) throw EngineError(SPHMI_ERR_STATE, "sphmi_particle_fields before sphmi_upload");
+        require_uploaded("sphmi_particle_fields");
         if (!(cfg.h <= cfg.H)) throw EngineError(SPHMI_ERR_STATE, "sphmi_particle_fields: handles with H < h are not served (the candidate cells are laid out for H + h <= 2H)");
         if (!fg_ready()) throw EngineError(SPHMI_ERR_STATE, "sphmi_particle_fields: the handle has not executed a step since the upload (no cell list)");
         HC(hipSetDevice(cfg.device));
-        const size_t n = (size_t)N, need = (size_t)kPfValues * n;
-        if (need > pf_arena_doubles) {
-            (void)hipFree(pf_arena);
-            pf_arena = nullptr; pf_arena_doubles = 0;
-            if (hipMalloc(&pf_arena, need * 8) != hipSuccess) {
-                (void)hipGetLastError();
-                char buf[160];
-                snprintf(buf, sizeof(buf), "sphmi_particle_fields: no device memory for the result arena of %d rows (%.2f GB)", N, (double)need * 8.0 / 1e9);
-                throw EngineError(SPHMI_ERR_DEVICE, buf);
-            }
-            pf_arena_doubles = need;
-        }
+        const size_t n = (size_t)N;
+        pf_arena.need((size_t)kPfValues * n, "sphmi_particle_fields", "rows", N);
+        double* const a = pf_arena.p;
         ParticleFieldArgs<T> A{};
         A.pk0 = pk0[iA]; A.pk1 = pk1[iA]; A.comp = comp[cur]; A.cstart = cstart; A.g = grid;
-        A.count = (long long*)pf_arena; A.shepard = pf_arena + n; A.normal = pf_arena + 2 * n; A.div_r = pf_arena + 5 * n;
-        A.div_v = pf_arena + 6 * n; A.vorticity = pf_arena + 7 * n;
-        A.H_inv = cfg.H_inv; A.H2 = cfg.H2; A.h_inv = cfg.h_inv; A.reach = cfg.H + cfg.h;
-        A.alphaD = cfg.alphaD; A.m0 = cfg.m0; A.N = N; A.kernel = cfg.kernel;
+        A.count = (long long*)a; A.shepard = a + n; A.normal = a + 2 * n; A.div_r = a + 5 * n;
+        A.div_v = a + 6 * n; A.vorticity = a + 7 * n;
+        fill_kernel_consts(A);
+        A.N = N; A.kernel = cfg.kernel;
         const unsigned nb = (unsigned)((N + kPfThreads - 1) / kPfThreads);
         if (D == 3) hipLaunchKernelGGL((k_particle_fields<T, 3>), dim3(nb), dim3(kPfThreads), 0, stream, A);
         else        hipLaunchKernelGGL((k_particle_fields<T, 2>), dim3(nb), dim3(kPfThreads), 0, stream, A);
         HC(hipGetLastError());
-        // behind the kernel: directly into memory the caller page-locked, else through the bounce buffer
-        auto fetch = [&](void* dst, const double* src, size_t doubles) {
-            if (!dst) return;
-            if (is_registered(dst, doubles * 8)) HC(hipMemcpyAsync(dst, src, doubles * 8, hipMemcpyDeviceToHost, stream));
-            else bounce.d2h(dst, src, doubles * 8, stream);
-        };
-        fetch(count, pf_arena, n); fetch(shepard, A.shepard, n); fetch(normal, A.normal, 3 * n); fetch(div_r, A.div_r, n);
+        auto fetch = [&](void* dst, const double* src, size_t doubles) { if (dst) fetch_result(dst, src, doubles * 8); };
+        fetch(count, a, n); fetch(shepard, A.shepard, n); fetch(normal, A.normal, 3 * n); fetch(div_r, A.div_r, n);
         fetch(div_v, A.div_v, n); fetch(vorticity, A.vorticity, 3 * n);
         HC(hipStreamSynchronize(stream));
     }
@@ -1984,7 +1838,7 @@ struct Engine final : EngineBase {
     void forces_local(int apply_mdbc, bool all_lists) {
         const int nb256 = (N + 255) / 256;
         hipLaunchKernelGGL(k_eos<T>, dim3(nb256), dim3(256), 0, stream, pk0[iA], pk1[iA], N, (T)cfg.rho0,
-                           (T)(1.0 / cfg.rho0), (T)((cfg.c0 * cfg.c0 * cfg.rho0) / 7.0));
+                           (T)(1.0 / cfg.rho0), cbe());
         if (apply_mdbc && cfg.mdbc == SPHMI_MDBC_SIMPLE) run_mdbc();
         ForceParams<T> P = force_params(iA, iA, iH, 0.0);
         P.accbuf = rec[iB];                       // (scratch: N contiguous packets at the start of the third record array)
@@ -1998,7 +1852,7 @@ struct Engine final : EngineBase {
         }
     }
     void forces_once(int apply_mdbc, void* drhodt, void* acceleration) override {
-        if (!uploaded) throw EngineError(SPHMI_ERR_STATE, "sphmi_forces_once before sphmi_upload");
+        require_uploaded("sphmi_forces_once");
         HC(hipSetDevice(cfg.device));
         rebuild();
         forces_local(apply_mdbc, false);
@@ -2509,7 +2363,7 @@ int sphmi_download_kernel_output(sphmi_handle* h, void* kernel, void* kernel_gra
     SPHMI_GUARD(h, h->e->download_kernel_output(kernel, kernel_gradient));
 }
 int sphmi_download_permutation(sphmi_handle* h, int64_t* prev_row) { SPHMI_GUARD(h, h->e->download_permutation(prev_row)); }
-static_assert(SPHMI_MAX_COLUMNS == sphmi::kMaxColumns && SPHMI_MAX_COLUMN_ROW_BYTES == sphmi::kMaxColumnRowBytes, "sphmi_columns.h and sphmi.h disagree");
+static_assert(SPHMI_MAX_COLUMNS == sphmi::kMaxColumns && SPHMI_MAX_COLUMN_ROW_BYTES == sphmi::kMaxColumnRowBytes, "sphmi_series.h and sphmi.h disagree");
 int sphmi_attach_columns(sphmi_handle* h, int32_t n_columns, const void* const* columns, const int32_t* row_bytes) {
     SPHMI_GUARD(h, h->e->attach_columns(n_columns, columns, row_bytes));
 }
@@ -2517,11 +2371,11 @@ int sphmi_download_columns_begin(sphmi_handle* h, void* const* columns_out) { SP
 int sphmi_download_columns(sphmi_handle* h, void* const* columns_out) {
     SPHMI_GUARD(h, (h->e->download_columns_begin(columns_out), h->e->download_end()));
 }
-static_assert(SPHMI_MAX_FORCE_GROUPS == sphmi::kMaxForceGroups, "sphmi_group_forces.h and sphmi.h disagree");
+static_assert(SPHMI_MAX_FORCE_GROUPS == sphmi::kMaxForceGroups, "sphmi_series.h and sphmi.h disagree");
 int sphmi_group_forces_enable(sphmi_handle* h, int32_t n_groups, const uint64_t* markers, int64_t capacity_steps) {
     SPHMI_GUARD(h, h->e->group_forces_enable(n_groups, markers, capacity_steps));
 }
-static_assert(SPHMI_MAX_PROBES == sphmi::kMaxProbes, "sphmi_probes.h and sphmi.h disagree");
+static_assert(SPHMI_MAX_PROBES == sphmi::kMaxProbes, "sphmi_series.h and sphmi.h disagree");
 int sphmi_probes_enable(sphmi_handle* h, int32_t n_probes, const double* positions, int64_t capacity_steps) {
     SPHMI_GUARD(h, h->e->probes_enable(n_probes, positions, capacity_steps));
 }
@@ -2529,7 +2383,7 @@ int sphmi_probes_read(sphmi_handle* h, int64_t capacity, int64_t* iteration_out,
                       int64_t* count_out, double* pressure_out, double* density_out, double* velocity_out, int64_t* n_out, int64_t* n_dropped) {
     SPHMI_GUARD(h, h->e->probes_read(capacity, iteration_out, time_out, dt_out, weight_out, count_out, pressure_out, density_out, velocity_out, n_out, n_dropped));
 }
-static_assert(SPHMI_MAX_GRID_NODES == sphmi::kMaxGridNodes, "sphmi_field_grid.h and sphmi.h disagree");
+static_assert(SPHMI_MAX_GRID_NODES == sphmi::kMaxGridNodes, "sphmi_series.h and sphmi.h disagree");
 int sphmi_sample_grid(sphmi_handle* h, const double* origin, const double* spacing, const int64_t* counts, double* weight_out, int64_t* count_out,
                       double* pressure_out, double* density_out, double* velocity_out) {
     SPHMI_GUARD(h, h->e->sample_grid(origin, spacing, counts, weight_out, count_out, pressure_out, density_out, velocity_out));

@@ -38,13 +38,12 @@
 #include "sphmi_kernels.h"
 #include "sphmi_rebuild.h"
 #include "sphmi_probes.h"
+#include "sphmi_series.h"       // kFgValues, kMaxGridNodes
 
 namespace sphmi {
 
-constexpr long long kMaxGridNodes = 1ll << 24;   // SPHMI_MAX_GRID_NODES
 constexpr int kFgThreads = 256;                  // nodes of a brick, candidates of a chunk, ranges of a batch
 constexpr int kFgRow = 9;                        // doubles of a staged row: x, y, z, m₀/ρ, P, ρ, v[3]
-constexpr int kFgValues = kPrValues;             // S, SP, Sρ, Sv[3], n
 constexpr size_t kFgLdsBytes = 2 * (size_t)kFgThreads * kFgRow * 8 + 2 * (size_t)kFgThreads * 4 + 64;
 
 template <class T> struct FieldGridArgs {

@@ -27,12 +27,11 @@
 
 #include "sphmi_kernels.h"
 #include "sphmi_rebuild.h"
+#include "sphmi_series.h"       // kMaxForceGroups, kGfHeader
 
 namespace sphmi {
 
-constexpr int kMaxForceGroups = 16;      // SPHMI_MAX_FORCE_GROUPS
 constexpr int kGfChunk = 256;            // list entries per partial sum = threads of the workgroup that forms it
-constexpr int kGfHeader = 3;             // doubles in front of the forces of a record
 constexpr int kGfRecordMax = kGfHeader + 3 * kMaxForceGroups;
 constexpr int kGfSmallChunks = 96;       // k_gf_small keeps the partials in LDS: rows / kGfChunk + n_groups chunks at most
 constexpr int kGfSmallRows = (kGfSmallChunks - kMaxForceGroups) * kGfChunk;

@@ -572,6 +572,11 @@ struct MultiEngine final : EngineBase {
     int world = 1;                     // slabs in total
     std::vector<Rank> R;               // the LOCAL ones (all of them in one-process mode, one in rank mode)
     bool rank_mode = false;            // one local slab, peers in other processes
+    // entry points that merge the rows or the sums of all slabs on the host
+    void require_one_process(const char* fn) const override {
+        if (rank_mode) throw EngineError(SPHMI_ERR_STATE, std::string(fn) + ": one-process handles only (a rank-mode process holds one slab of the rows)");
+        require_uploaded(fn);
+    }
     bool use_rccl = false;
     bool peer_ok = true;               // every pair of this process's devices has peer access: the local transport copies with a kernel
     std::unique_ptr<ShmWorld> shm;     // rank mode with SPHMI_TRANSPORT=shm: peers behind a shared-memory segment instead of RCCL
@@ -1389,7 +1394,7 @@ struct MultiEngine final : EngineBase {
 
     // ---- the SimulationLoop of src/SPHCellList.jl:727-805, over all slabs --------------------------------------------
     void advance(double t_target, int64_t max_steps, sphmi_progress* out) override {
-        if (!uploaded) throw EngineError(SPHMI_ERR_STATE, "sphmi_advance before sphmi_upload");
+        require_uploaded("sphmi_advance");
         double dxl = 1.0 + cfg.h;                                        // :739
         int64_t steps = 0;
         // the first iteration of the loop always rebuilds (:758): run it now when there will be one (StepCtrl::pre_rebuilt) instead of
@@ -1418,8 +1423,8 @@ struct MultiEngine final : EngineBase {
                         if (pr_on) for (auto& r : R) { HC(hipSetDevice(r.device)); r.e->pr_sample(r.e->ctrl_d, iteration, steps0, r.e->iA); }
                     }
                 }
-                if (gf_on) for (auto& r : R) { HC(hipSetDevice(r.device)); r.e->gf_fetch(batch); }
-                if (pr_on) for (auto& r : R) { HC(hipSetDevice(r.device)); r.e->pr_fetch(batch); }
+                if (gf_on) for (auto& r : R) { HC(hipSetDevice(r.device)); r.e->gf_log.fetch(batch, r.e->stream); }
+                if (pr_on) for (auto& r : R) { HC(hipSetDevice(r.device)); r.e->pr_log.fetch(batch, r.e->stream); }
                 for (auto& r : R) {
                     HC(hipSetDevice(r.device)); sphmi_dd_control s{}; r.e->dd_ctrl_sync(&s);
                     if (&r == &R[0]) st = s;
@@ -1434,8 +1439,8 @@ struct MultiEngine final : EngineBase {
                     }
                 }
                 steps = st.steps_done;
-                if (gf_on) gf_collect(steps - steps0);
-                if (pr_on) pr_collect(steps - steps0);
+                if (gf_on) collect_records(gf_series, &Engine<T>::gf_log, kGfHeader, "group forces", steps - steps0);
+                if (pr_on) collect_records(pr_series, &Engine<T>::pr_log, kPrHeader, "probes", steps - steps0);
                 total_time = st.total_time; last_dt = st.last_dt; dxl = st.delta_x;
                 const int64_t grown = (steps - steps0) + (st.need_rebuild ? 1 : 0) - (fresh && steps > steps0 ? 1 : 0);
                 if (steps > steps0) fresh = false;
@@ -1529,7 +1534,7 @@ struct MultiEngine final : EngineBase {
     struct PendingDownload { void *pos, *vel, *acc, *rho, *prs, *gho; int64_t *ids, *cells; uint8_t* ty; uint64_t* grp; bool on = false; } pend{};
     void download_begin(void* position, void* velocity, void* acceleration, void* density, void* pressure, int64_t* ids,
                         uint8_t* ty, uint64_t* groups, void* ghost_points, int64_t* cells) override {
-        if (!uploaded) throw EngineError(SPHMI_ERR_STATE, "sphmi_download before sphmi_upload");
+        require_uploaded("sphmi_download");
         if (pend.on) download_end();
         const size_t hb = (size_t)cfg.host_float_bytes, C = (size_t)out_comp;
         stage.resize(R.size());
@@ -1618,7 +1623,7 @@ struct MultiEngine final : EngineBase {
     // layers from the owners' current state; Pressure! → [mDBC on everything held] → one forces-only pass over the interior
     // AND the slab-edge tiles; rows come back in the order one engine would hold (rank mode: this process's slab).
     void forces_once(int apply_mdbc, void* drhodt, void* acceleration) override {
-        if (!uploaded) throw EngineError(SPHMI_ERR_STATE, "sphmi_forces_once before sphmi_upload");
+        require_uploaded("sphmi_forces_once");
         for (auto& r : R) { HC(hipSetDevice(r.device)); HC(hipStreamSynchronize(r.main)); }
         rebuild_collective();
         for (auto& r : R) { HC(hipSetDevice(r.device)); r.e->forces_local(apply_mdbc, true); }
@@ -1629,7 +1634,7 @@ struct MultiEngine final : EngineBase {
     // StoreKernelOutput (src/SPHCellList.jl:106-116): Σ∇W, ΣW of the last corrector pass, merged like a download
     void download_kernel_output(void* kernel, void* kernel_gradient) override {
         if (cfg.kernel_output != SPHMI_KOUT_STORE) throw EngineError(SPHMI_ERR_STATE, "sphmi_download_kernel_output: the handle was not created with kernel_output = STORE");
-        if (!uploaded) throw EngineError(SPHMI_ERR_STATE, "sphmi_download_kernel_output before sphmi_upload");
+        require_uploaded("sphmi_download_kernel_output");
         packet_src = [](Engine<T>& e) -> const void* { return e.kout_d; };
         put_packets(kernel_gradient, kernel);
     }
@@ -1640,9 +1645,9 @@ struct MultiEngine final : EngineBase {
     // tag like a download; the slabs' columns are then re-numbered with the merged rows.  An asynchronous download in flight is
     // not disturbed.
     void download_permutation(int64_t* prev_row) override {
-        if (!uploaded) throw EngineError(SPHMI_ERR_STATE, "sphmi_download_permutation before sphmi_upload");
+        require_uploaded("sphmi_download_permutation");
         if (!prev_row) throw EngineError(SPHMI_ERR_ARGUMENT, "sphmi_download_permutation: null array");
-        if (rank_mode) throw EngineError(SPHMI_ERR_STATE, "sphmi_download_permutation: one-process handles only (a rank-mode process holds one slab of the rows)");
+        require_one_process("sphmi_download_permutation");
         SlabRows sr;
         fetch_rows("sphmi_download_permutation", sr, prev_row);
         if (!col_data.empty()) {                     // attached columns: their rows are found through the epoch that ends here
@@ -1699,8 +1704,7 @@ struct MultiEngine final : EngineBase {
     // flight is not disturbed (the fetch reads the slabs' live columns, not their staging).
     std::vector<std::vector<char>> col_data; std::vector<int> col_width; std::vector<int64_t> col_base;
     void attach_columns(int32_t n_columns, const void* const* columns, const int32_t* row_bytes) override {
-        if (rank_mode) throw EngineError(SPHMI_ERR_STATE, "sphmi_attach_columns: one-process handles only (a rank-mode process holds one slab of the rows)");
-        if (!uploaded) throw EngineError(SPHMI_ERR_STATE, "sphmi_attach_columns before sphmi_upload");
+        require_one_process("sphmi_attach_columns");
         check_column_table(n_columns, columns, row_bytes);
         col_data.clear(); col_width.clear(); col_base.clear();
         if (n_columns == 0) return;
@@ -1714,65 +1718,33 @@ struct MultiEngine final : EngineBase {
             col_data.emplace_back((const char*)columns[c], (const char*)columns[c] + N * (size_t)row_bytes[c]);
         }
     }
-    // The per-step force on particle groups (sphmi_group_forces.h): every slab engine records the sums over the rows it owns —
-    // ghost copies do not count — and the handle adds the slabs' records of a step in slab order, in fp64.
-    bool gf_on = false; GroupForceSeries gf_series;
-    void group_forces_enable(int32_t n_groups, const uint64_t* markers, int64_t capacity_steps) override {
-        if (rank_mode) throw EngineError(SPHMI_ERR_STATE, "sphmi_group_forces_enable: one-process handles only (a rank-mode process holds one slab of the rows)");
-        if (!uploaded) throw EngineError(SPHMI_ERR_STATE, "sphmi_group_forces_enable before sphmi_upload");
-        check_group_table(n_groups, markers, capacity_steps);
+    // The per-step force on particle groups (sphmi_group_forces.h) and the kernel sums at fixed probe points (sphmi_probes.h):
+    // every slab engine records the sums over the rows it owns — a row sits in exactly one slab, ghost copies do not count — and
+    // the handle adds the slabs' records of a step in slab order, in fp64: the forces, and the RAW sums of the probes (the read
+    // normalises).  The series are EngineBase's.
+    void gf_enable_device(int32_t n_groups, const uint64_t* markers) override {
         gf_on = false; gf_series.reset(0, 0);
         for (auto& r : R) r.e->gf_enable_device(n_groups, markers);
-        if (n_groups == 0) return;
-        gf_series.reset(n_groups, capacity_steps);
-        gf_on = true;
+        gf_on = n_groups > 0;
     }
-    void group_forces_read(int64_t capacity, int64_t* iteration_out, double* time, double* dt, double* force, int64_t* n_out, int64_t* n_dropped) override {
-        if (rank_mode) throw EngineError(SPHMI_ERR_STATE, "sphmi_group_forces_read: one-process handles only (a rank-mode process holds one slab of the rows)");
-        if (!uploaded) throw EngineError(SPHMI_ERR_STATE, "sphmi_group_forces_read before sphmi_upload");
-        if (!gf_on) throw EngineError(SPHMI_ERR_STATE, "sphmi_group_forces_read: sampling is not enabled (sphmi_group_forces_enable)");
-        gf_series.read(capacity, iteration_out, time, dt, force, n_out, n_dropped);
-    }
-    // after the synchronisation of a batch: the records of its `executed` steps, slab by slab
-    void gf_collect(int64_t executed) {
-        const int n = gf_series.n_groups;
-        for (int64_t k = 0; k < executed; ++k) {
-            GroupForceSeries::Sample s = GroupForceSeries::decode(R[0].e->gf_record(k), n);
-            for (size_t q = 1; q < R.size(); ++q) {
-                const GroupForceSeries::Sample o = GroupForceSeries::decode(R[q].e->gf_record(k), n);
-                if (o.iteration != s.iteration) throw EngineError(SPHMI_ERR_STATE, "group forces: the slabs' records of a step do not belong together");
-                for (int c = 0; c < 3 * n; ++c) s.f[c] += o.f[c];
-            }
-            gf_series.push(s);
-        }
-    }
-    // Kernel sums at fixed probe points (sphmi_probes.h): every slab engine sums the rows it owns for every probe — a row sits in
-    // exactly one slab, ghost copies do not count — and the handle adds the slabs' RAW sums of a step in slab order; the read normalises.
-    bool pr_on = false; ProbeSeries pr_series;
-    void probes_enable(int32_t n_probes, const double* positions, int64_t capacity_steps) override {
-        if (rank_mode) throw EngineError(SPHMI_ERR_STATE, "sphmi_probes_enable: one-process handles only (a rank-mode process holds one slab of the rows)");
-        if (!uploaded) throw EngineError(SPHMI_ERR_STATE, "sphmi_probes_enable before sphmi_upload");
-        check_probe_table(n_probes, positions, cfg.dims, capacity_steps);
+    void pr_enable_device(int32_t n_probes, const double* positions) override {
         pr_on = false; pr_series.reset(0, 0);
         for (auto& r : R) r.e->pr_enable_device(n_probes, positions);
-        if (n_probes == 0) return;
-        pr_series.reset(n_probes, capacity_steps);
-        pr_on = true;
-    }
-    void probes_read(int64_t capacity, int64_t* iteration_out, double* time, double* dt, double* weight, int64_t* count, double* pressure,
-                     double* density, double* velocity, int64_t* n_out, int64_t* n_dropped) override {
-        if (rank_mode) throw EngineError(SPHMI_ERR_STATE, "sphmi_probes_read: one-process handles only (a rank-mode process holds one slab of the rows)");
-        if (!uploaded) throw EngineError(SPHMI_ERR_STATE, "sphmi_probes_read before sphmi_upload");
-        if (!pr_on) throw EngineError(SPHMI_ERR_STATE, "sphmi_probes_read: sampling is not enabled (sphmi_probes_enable)");
-        pr_series.read(capacity, iteration_out, time, dt, weight, count, pressure, density, velocity, n_out, n_dropped);
+        pr_on = n_probes > 0;
     }
     // after the synchronisation of a batch: the records of its `executed` steps, slab by slab
+    void collect_records(StepSeries& series, typename Engine<T>::StepLog Engine<T>::*log, int header, const char* what, int64_t executed) {
+        for (int64_t k = 0; k < executed; ++k) {
+            StepSeries::Sample s = StepSeries::decode((R[0].e.get()->*log).record(k), header, series.values);
+            for (size_t q = 1; q < R.size(); ++q) StepSeries::add(s, StepSeries::decode((R[q].e.get()->*log).record(k), header, series.values), what);
+            series.push(std::move(s));
+        }
+    }
     // Kernel sums on a lattice (sphmi_field_grid.h): every slab samples the WHOLE lattice over the rows it owns — the type byte keeps
     // ghost copies out — the handle adds the raw sums in slab order, then normalises, as for the probes.
     void sample_grid(const double* origin, const double* spacing, const int64_t* counts, double* weight, int64_t* count, double* pressure,
                      double* density, double* velocity) override {
-        if (rank_mode) throw EngineError(SPHMI_ERR_STATE, "sphmi_sample_grid: one-process handles only (a rank-mode process holds one slab of the rows)");
-        if (!uploaded) throw EngineError(SPHMI_ERR_STATE, "sphmi_sample_grid before sphmi_upload");
+        require_one_process("sphmi_sample_grid");
         bool any = false;
         for (auto& r : R) any = any || r.e->fg_ready();
         if (!(cfg.h <= cfg.H)) throw EngineError(SPHMI_ERR_STATE, "sphmi_sample_grid: handles with H < h are not served (the candidate cells are laid out for H + h <= 2H)");
@@ -1804,21 +1776,8 @@ struct MultiEngine final : EngineBase {
         if (rank_mode) throw EngineError(SPHMI_ERR_STATE, "sphmi_particle_fields: single-device handles only (a rank-mode process holds one slab of the rows)");
         throw EngineError(SPHMI_ERR_STATE, "sphmi_particle_fields: single-device handles only (a slab's ghost copies hold the half-step state; the halo exchange this needs is not built)");
     }
-    void pr_collect(int64_t executed) {
-        const int n = pr_series.n_probes;
-        for (int64_t k = 0; k < executed; ++k) {
-            ProbeSeries::Sample s = ProbeSeries::decode(R[0].e->pr_record(k), n);
-            for (size_t q = 1; q < R.size(); ++q) {
-                const ProbeSeries::Sample o = ProbeSeries::decode(R[q].e->pr_record(k), n);
-                if (o.iteration != s.iteration) throw EngineError(SPHMI_ERR_STATE, "probes: the slabs' records of a step do not belong together");
-                for (size_t c = 0; c < s.v.size(); ++c) s.v[c] += o.v[c];
-            }
-            pr_series.push(std::move(s));
-        }
-    }
     void download_columns_begin(void* const* columns_out) override {
-        if (rank_mode) throw EngineError(SPHMI_ERR_STATE, "sphmi_download_columns: one-process handles only (a rank-mode process holds one slab of the rows)");
-        if (!uploaded) throw EngineError(SPHMI_ERR_STATE, "sphmi_download_columns before sphmi_upload");
+        require_one_process("sphmi_download_columns");
         if (col_data.empty()) throw EngineError(SPHMI_ERR_STATE, "sphmi_download_columns: no columns attached (sphmi_attach_columns)");
         if (!columns_out) throw EngineError(SPHMI_ERR_ARGUMENT, "sphmi_download_columns: null table");
         const size_t N = (size_t)cfg.n_particles;

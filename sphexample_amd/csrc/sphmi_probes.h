@@ -47,12 +47,11 @@
 #include "sphmi_kernels.h"
 #include "sphmi_rebuild.h"
 #include "sphmi_group_forces.h"
+#include "sphmi_series.h"       // kMaxProbes, kPrValues
 
 namespace sphmi {
 
-constexpr int kMaxProbes = 1024;         // SPHMI_MAX_PROBES
 constexpr int kPrHeader = kGfHeader;     // the same three doubles in front of a record
-constexpr int kPrValues = 7;             // S, SP, Sρ, Sv[3], n
 constexpr int kPrRecordMax = kPrHeader + kPrValues * kMaxProbes;
 constexpr int kPrMaxRows = 25;           // (cy, cz) pairs of a probe: ≤ 5 × 5 — H + h ≤ 2H spans at most five cells per axis
 constexpr int kPrInFlight = 4;           // jobs whose loads are issued before the first is used

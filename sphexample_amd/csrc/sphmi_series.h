@@ -1,0 +1,174 @@
+// sphmi_series.h — the host side the observers share (group forces, probes, lattice, columns): the error type, the limits and
+// record-layout constants host and device agree on, the argument checks every kind of handle reports alike, the per-step series
+// and the means of the kernel sums.  Plain C++17, no HIP: tests/host_series/series_main.cpp compiles it alone.
+#pragma once
+#include <algorithm>
+#include <cmath>
+#include <cstdint>
+#include <cstring>
+#include <deque>
+#include <stdexcept>
+#include <string>
+#include <vector>
+
+#include "../../include/sphmi.h"
+
+namespace sphmi {
+
+struct EngineError : std::runtime_error {
+    int status;
+    EngineError(int s, const std::string& m) : std::runtime_error(m), status(s) {}
+};
+
+constexpr int kMaxColumns = 16;                  // SPHMI_MAX_COLUMNS
+constexpr int kMaxColumnRowBytes = 64;           // SPHMI_MAX_COLUMN_ROW_BYTES
+constexpr int kMaxForceGroups = 16;              // SPHMI_MAX_FORCE_GROUPS
+constexpr int kGfHeader = 3;                     // doubles in front of the payload of a record: iteration (int64 bits), time, Δt
+constexpr int kMaxProbes = 1024;                 // SPHMI_MAX_PROBES
+constexpr int kPrValues = 7;                     // S, SP, Sρ, Sv[3], n
+constexpr int kFgValues = kPrValues;             // S, SP, Sρ, Sv[3], n
+constexpr long long kMaxGridNodes = 1ll << 24;   // SPHMI_MAX_GRID_NODES
+
+// sphmi_attach_columns: the argument errors every kind of handle reports alike
+inline void check_column_table(int32_t n_columns, const void* const* columns, const int32_t* row_bytes) {
+    if (n_columns < 0 || n_columns > kMaxColumns) throw EngineError(SPHMI_ERR_ARGUMENT, "sphmi_attach_columns: n_columns out of range [0, 16]");
+    if (n_columns == 0) return;
+    if (!columns || !row_bytes) throw EngineError(SPHMI_ERR_ARGUMENT, "sphmi_attach_columns: null table");
+    for (int c = 0; c < n_columns; ++c) {
+        if (row_bytes[c] < 1 || row_bytes[c] > kMaxColumnRowBytes) throw EngineError(SPHMI_ERR_ARGUMENT, "sphmi_attach_columns: row_bytes out of range [1, 64]");
+        if (!columns[c]) throw EngineError(SPHMI_ERR_ARGUMENT, "sphmi_attach_columns: null column");
+    }
+}
+
+// sphmi_group_forces_enable: the argument errors every kind of handle reports alike
+inline void check_group_table(int32_t n_groups, const uint64_t* markers, int64_t capacity_steps) {
+    if (n_groups < 0 || n_groups > kMaxForceGroups) throw EngineError(SPHMI_ERR_ARGUMENT, "sphmi_group_forces_enable: n_groups out of range [0, 16]");
+    if (n_groups == 0) return;
+    if (!markers) throw EngineError(SPHMI_ERR_ARGUMENT, "sphmi_group_forces_enable: null table");
+    if (capacity_steps < 1) throw EngineError(SPHMI_ERR_ARGUMENT, "sphmi_group_forces_enable: capacity_steps must be positive");
+    for (int a = 0; a < n_groups; ++a)
+        for (int b = 0; b < a; ++b)
+            if (markers[a] == markers[b]) throw EngineError(SPHMI_ERR_ARGUMENT, "sphmi_group_forces_enable: duplicate marker");
+}
+
+// sphmi_probes_enable: the argument errors every kind of handle reports alike
+inline void check_probe_table(int32_t n_probes, const double* positions, int dims, int64_t capacity_steps) {
+    if (n_probes < 0 || n_probes > kMaxProbes) throw EngineError(SPHMI_ERR_ARGUMENT, "sphmi_probes_enable: n_probes out of range [0, 1024]");
+    if (n_probes == 0) return;
+    if (!positions) throw EngineError(SPHMI_ERR_ARGUMENT, "sphmi_probes_enable: null table");
+    if (capacity_steps < 1) throw EngineError(SPHMI_ERR_ARGUMENT, "sphmi_probes_enable: capacity_steps must be positive");
+    for (int64_t k = 0; k < (int64_t)n_probes * dims; ++k)
+        if (!std::isfinite(positions[k])) throw EngineError(SPHMI_ERR_ARGUMENT, "sphmi_probes_enable: non-finite coordinate");
+}
+
+// sphmi_sample_grid: the argument errors every kind of handle reports alike; returns the number of nodes
+inline int64_t check_grid_lattice(const double* origin, const double* spacing, const int64_t* counts, int dims) {
+    if (!origin || !spacing || !counts) throw EngineError(SPHMI_ERR_ARGUMENT, "sphmi_sample_grid: null origin, spacing or counts");
+    int64_t nodes = 1;
+    for (int d = 0; d < dims; ++d) {
+        if (!std::isfinite(origin[d])) throw EngineError(SPHMI_ERR_ARGUMENT, "sphmi_sample_grid: non-finite origin");
+        if (!std::isfinite(spacing[d]) || !(spacing[d] > 0.0)) throw EngineError(SPHMI_ERR_ARGUMENT, "sphmi_sample_grid: every spacing must be finite and positive");
+        if (counts[d] < 1) throw EngineError(SPHMI_ERR_ARGUMENT, "sphmi_sample_grid: every count must be at least 1");
+        if (counts[d] > kMaxGridNodes || nodes * counts[d] > kMaxGridNodes) throw EngineError(SPHMI_ERR_ARGUMENT, "sphmi_sample_grid: more than SPHMI_MAX_GRID_NODES nodes");
+        nodes *= counts[d];
+    }
+    return nodes;
+}
+
+// The series of an observer that records once per executed step: what the batches delivered since the last read, the newest
+// `capacity` of it.  A sample carries the payload of a device-side record as it is (group forces: 3 per group; probes: the RAW
+// sums, kPrValues per probe); what a read hands out of it is the caller's `deliver`.
+struct StepSeries {
+    struct Sample { int64_t iteration; double time, dt; std::vector<double> v; };
+    int values = 0;                            // doubles of a payload
+    int64_t capacity = 0, dropped = 0;
+    std::deque<Sample> q;
+    void reset(int values_per_step, int64_t cap) { values = values_per_step; capacity = cap; dropped = 0; q.clear(); }
+    void push(Sample&& s) {
+        if ((int64_t)q.size() >= capacity) { q.pop_front(); dropped += 1; }
+        q.push_back(std::move(s));
+    }
+    // one record of a device-side log: `header` doubles { iteration (int64 bits), time, Δt, … }, then the payload
+    static Sample decode(const double* rec, int header, int values) {
+        Sample s{};
+        memcpy(&s.iteration, rec, 8); s.time = rec[1]; s.dt = rec[2];
+        s.v.assign(rec + header, rec + header + values);
+        return s;
+    }
+    // a multi-device handle adds the slabs' records of a step, in slab order
+    static void add(Sample& into, const Sample& other, const char* what) {
+        if (other.iteration != into.iteration) throw EngineError(SPHMI_ERR_STATE, std::string(what) + ": the slabs' records of a step do not belong together");
+        for (size_t c = 0; c < into.v.size(); ++c) into.v[c] += other.v[c];
+    }
+    // the oldest min(cap, waiting) samples leave the series: deliver(k, payload) hands out the k-th of them
+    template <class Deliver>
+    void read(const char* fn_name, int64_t cap, int64_t* iteration, double* time, double* dt, int64_t* n_out, int64_t* n_dropped, Deliver&& deliver) {
+        if (!n_out) throw EngineError(SPHMI_ERR_ARGUMENT, std::string(fn_name) + ": null n_out");
+        if (cap < 0) throw EngineError(SPHMI_ERR_ARGUMENT, std::string(fn_name) + ": negative capacity");
+        if (cap == 0) { *n_out = (int64_t)q.size(); if (n_dropped) *n_dropped = dropped; return; }      // a question: nothing is delivered, nothing cleared
+        const int64_t n = std::min<int64_t>(cap, (int64_t)q.size());
+        for (int64_t k = 0; k < n; ++k) {
+            const Sample& s = q.front();
+            if (iteration) iteration[k] = s.iteration;
+            if (time) time[k] = s.time;
+            if (dt) dt[k] = s.dt;
+            deliver(k, s.v.data());
+            q.pop_front();
+        }
+        *n_out = n;
+        if (n_dropped) *n_dropped = dropped;
+        dropped = 0;
+    }
+};
+
+// sphmi_group_forces_read: the forces of the k-th delivered step, as recorded
+inline void deliver_forces(int n_groups, int64_t k, const double* v, double* force) {
+    if (force) memcpy(force + (size_t)k * 3 * n_groups, v, (size_t)3 * n_groups * 8);
+}
+
+// a mean of the kernel sums (probes and lattice alike); `some`: n > 0 && S > 0, else every value is 0
+inline double kernel_mean(double sum, double S, bool some) { return some ? sum / S : 0.0; }
+
+// sphmi_probes_read: the raw sums { S, SP, Sρ, Sv[3], n } of the k-th delivered step, normalised
+inline void deliver_probe_means(int n_probes, int64_t k, const double* sums, double* weight, int64_t* count, double* pressure, double* density, double* velocity) {
+    for (int p = 0; p < n_probes; ++p) {
+        const double* v = sums + (size_t)kPrValues * p;
+        const size_t at = (size_t)k * n_probes + p;
+        const bool some = v[6] > 0.0 && v[0] > 0.0;
+        if (weight) weight[at] = v[0];
+        if (count) count[at] = (int64_t)v[6];
+        if (pressure) pressure[at] = kernel_mean(v[1], v[0], some);
+        if (density) density[at] = kernel_mean(v[2], v[0], some);
+        if (velocity) for (int d = 0; d < 3; ++d) velocity[3 * at + d] = kernel_mean(v[3 + d], v[0], some);
+    }
+}
+
+// The host side of sphmi_sample_grid: the raw sums { S, SP, Sρ, Sv[3], n } of the lattice (sphmi_field_grid.h), the ones the
+// requested outputs need.  S lands in weight_out itself when that is asked for; the means are formed here, 0 where n == 0.
+struct GridSums {
+    int64_t nodes = 0;
+    double* S = nullptr;                       // weight_out, or s[0]
+    std::vector<double> s[kFgValues];
+    bool want[kFgValues] = {};
+    double* dst(int f) { return f == 0 ? S : s[f].data(); }
+    GridSums(int64_t n, double* weight, const int64_t* count, const double* pressure, const double* density, const double* velocity) : nodes(n) {
+        const bool means = pressure || density || velocity;
+        want[0] = weight || means; want[1] = pressure != nullptr; want[2] = density != nullptr;
+        want[3] = want[4] = want[5] = velocity != nullptr; want[6] = count || means;
+        for (int f = 0; f < kFgValues; ++f) if (want[f] && !(f == 0 && weight)) s[f].assign((size_t)n, 0.0);
+        S = weight ? weight : s[0].data();
+    }
+    void deliver(int64_t* count, double* pressure, double* density, double* velocity) const {
+        const double* n = s[6].data();
+        for (int64_t k = 0; k < nodes; ++k) {
+            if (count) count[k] = (int64_t)n[k];
+            if (!pressure && !density && !velocity) continue;
+            const bool some = n[k] > 0.0 && S[k] > 0.0;
+            if (pressure) pressure[k] = kernel_mean(s[1][k], S[k], some);
+            if (density) density[k] = kernel_mean(s[2][k], S[k], some);
+            if (velocity) for (int d = 0; d < 3; ++d) velocity[3 * k + d] = kernel_mean(s[3 + d][k], S[k], some);
+        }
+    }
+};
+
+}  // namespace sphmi
