@@ -295,6 +295,38 @@ int sphmi_probes_read(sphmi_handle* h, int64_t capacity, int64_t* iteration_out,
                       int64_t* n_out, int64_t* n_dropped);
 
 /*
+ * The global BUDGETS of the fluid at STEP resolution, recorded on the device: the energy, momentum and extent curves of a run - the
+ * wave front of a dam break, the largest speed and the density extremes that show first when a run goes unstable.  For every executed
+ * step, over the rows i of the handle with Type == Fluid, on the state sphmi_download would deliver directly after that step (x, v, rho
+ * the doubles of that download; 2-D handles: z = 0, vz = 0), the raw values
+ *     s0 = n, the number of such rows    s1 = sum 1/2 |v|^2    s2 = sum x_last (the gravity axis)    s3 = sum e(rho)
+ *     s4..6 = sum v    s7..9 = sum x cross v    s10..12 = sum x    s13 = max |v|^2    s14, s15 = min, max rho    s16..18, s19..21 = min, max x
+ * with e(rho) = ((r^6 - 1)/6 + 1/r) - 1, r = rho/rho0: the compressive energy per unit mass of the Tait equation of state the engine
+ * runs (gamma = 7, B = c0^2 rho0 / 7) in units of B/rho0.  Every term is formed in fp64 with one rounding per operation - a host forms
+ * the same doubles from a download - and reduced in an order that depends on the particle order alone, on fp32 and fp64 handles alike:
+ * repeated runs give the same bits.  Off by default; a handle that never enables it launches what it always did.
+ *   enable: after sphmi_upload / sphmi_generate_dam_break_3d, at any later time too.  The handle keeps the newest capacity_steps (>= 1)
+ *     samples that have not been read.  A second call drops the series; capacity_steps = 0 disables.  sphmi_upload and the generator
+ *     disable.  No step waits for the host: the records of a batch of queued steps come back with the control block the host fetches
+ *     anyway.  sphmi_forces_once records nothing.
+ *   read: delivers and clears the oldest `capacity` samples recorded since the last read, oldest first: iteration_out / time_out / dt_out
+ *     [capacity] as sphmi_group_forces_read; count_out [capacity] n; energy_out [capacity x 3] kinetic m0*s1, potential m0*g*s2 and
+ *     compressive m0*(B/rho0)*s3; momentum_out [capacity x 3] m0*s4..6; angular_out [capacity x 3] m0*s7..9, about the origin (2-D
+ *     handles: only the third component is non-zero); centre_out [capacity x 3] s10..12 / n, the centre of mass; extremes_out
+ *     [capacity x 3] the largest speed sqrt(s13), the smallest and the largest density; box_out [capacity x 6] min x[3], max x[3] (2-D
+ *     handles: zero third components) - formed on the host from the raw values, one multiplication or division each; centre, extremes
+ *     and box are 0 where n == 0.  Any output pointer may be NULL.  *n_out, *n_dropped, capacity = 0: as sphmi_group_forces_read.
+ *   SPHMI_ERR_STATE: before the upload; read while disabled; rank-mode handles (a process holds one slab of the rows).
+ *   SPHMI_ERR_ARGUMENT: capacity_steps < 0, negative capacity, null n_out.
+ * Multi-device handles of one process: every slab reduces the rows it owns (ghost copies do not count) and the handle combines the
+ * slabs' raw records in slab order - sums add, extremes take min or max.  Budgets, probes and group forces may be enabled together.
+ */
+int sphmi_budgets_enable(sphmi_handle* h, int64_t capacity_steps);
+int sphmi_budgets_read(sphmi_handle* h, int64_t capacity, int64_t* iteration_out, double* time_out, double* dt_out,
+                       int64_t* count_out, double* energy_out, double* momentum_out, double* angular_out, double* centre_out,
+                       double* extremes_out, double* box_out, int64_t* n_out, int64_t* n_dropped);
+
+/*
  * MotionDetails of the Geometry with this GroupMarker (src/SimulationGeometry.jl:17-22): particles of Type Moving
  * in that group get Velocity = velocity·direction while start_time <= TotalTime <= start_time + duration (0
  * otherwise) and are displaced by Velocity·dt/2 before each neighbour pass — ProgressMotion,

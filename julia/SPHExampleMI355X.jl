@@ -28,6 +28,8 @@
 # device — sphmi_group_forces_enable — and collect the series of a run in SPHExampleMI355X.GROUP_FORCES[SimParticles]).
 # SPHMI_PROBES (unset by default; "x,y,z;x,y,z" = sample pressure, density and velocity at these fixed points at every step on the
 # device — sphmi_probes_enable, `dims` coordinates per point — and collect the series in SPHExampleMI355X.PROBES[SimParticles]).
+# SPHMI_BUDGETS (unset by default; "1" = record the energy, momentum and extent budgets of the fluid at every step on the device —
+# sphmi_budgets_enable — and collect the series in SPHExampleMI355X.BUDGETS[SimParticles]).
 #
 # EXPERIMENTAL: the build image has no Julia, so this file has never been executed.  struct layout and ABI version
 # are asserted against the library at first use (sphmi_create refuses a mismatching struct_size / abi_version).
@@ -127,6 +129,33 @@ function read_probes!(h, pr::ProbeSeries)
     pr.velocity = cat(pr.velocity, v; dims = 3); pr.dropped += dropped[]
     return nothing
 end
+# SPHMI_BUDGETS: the step-resolution budgets of the fluid, bound like GROUP_FORCES — count[s] Fluid rows, energy[:, s] (kinetic, potential,
+# compressive), momentum[:, s], angular[:, s] (about the origin), centre[:, s] (of mass), extremes[:, s] (largest speed, smallest and largest
+# density) and box[:, s] (min x[1:3], max x[1:3]; box[4, :] is the wave front of a dam break that runs towards +x) at sample s
+mutable struct BudgetSeries
+    iteration::Vector{Int64}; time::Vector{Float64}; dt::Vector{Float64}
+    count::Vector{Int64}
+    energy::Matrix{Float64}; momentum::Matrix{Float64}; angular::Matrix{Float64}; centre::Matrix{Float64}; extremes::Matrix{Float64}      # 3 × samples
+    box::Matrix{Float64}                 # 6 × samples
+    dropped::Int64
+end
+const BUDGETS = IdDict{Any,BudgetSeries}()
+budgets_wanted() = !(strip(get(ENV, "SPHMI_BUDGETS", "")) in ("", "0"))
+function read_budgets!(h, bs::BudgetSeries)
+    n = Ref{Int64}(0); dropped = Ref{Int64}(0)
+    check(h, ccall((:sphmi_budgets_read, LIB), Cint, (Ptr{Cvoid}, Int64, Ptr{Int64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ref{Int64}, Ref{Int64}),
+                   h, 0, C_NULL, C_NULL, C_NULL, C_NULL, C_NULL, C_NULL, C_NULL, C_NULL, C_NULL, C_NULL, n, dropped))
+    k = Int(n[]); k == 0 && return nothing
+    it = Vector{Int64}(undef, k); t = Vector{Float64}(undef, k); dt = Vector{Float64}(undef, k); c = Vector{Int64}(undef, k)
+    en = Matrix{Float64}(undef, 3, k); mom = Matrix{Float64}(undef, 3, k); ang = Matrix{Float64}(undef, 3, k); cen = Matrix{Float64}(undef, 3, k)
+    ext = Matrix{Float64}(undef, 3, k); bx = Matrix{Float64}(undef, 6, k)
+    GC.@preserve it t dt c en mom ang cen ext bx check(h, ccall((:sphmi_budgets_read, LIB), Cint, (Ptr{Cvoid}, Int64, Ptr{Int64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ref{Int64}, Ref{Int64}),
+                                                            h, k, pointer(it), pointer(t), pointer(dt), pointer(c), pointer(en), pointer(mom), pointer(ang), pointer(cen), pointer(ext), pointer(bx), n, dropped))
+    append!(bs.iteration, it); append!(bs.time, t); append!(bs.dt, dt); append!(bs.count, c)
+    bs.energy = hcat(bs.energy, en); bs.momentum = hcat(bs.momentum, mom); bs.angular = hcat(bs.angular, ang); bs.centre = hcat(bs.centre, cen)
+    bs.extremes = hcat(bs.extremes, ext); bs.box = hcat(bs.box, bx); bs.dropped += dropped[]
+    return nothing
+end
 # The probes' sums at every node of a regular lattice, evaluated on the state the session holds NOW (sphmi_sample_grid): node (i, j[, k])
 # lies at origin .+ (i, j[, k]) .* spacing, zero-based.  Returns arrays indexed [i, j[, k]] (x fastest: Julia's column-major order IS the
 # node order), velocity as 3 × nx × ny[ × nz].  Call it from an output callback, i.e. between two SimulationLoop calls, after the first step.
@@ -221,6 +250,11 @@ function open_session(SimDensityDiffusion, SimViscosity, SimKernel, SimMetaData:
         PROBES[P] = ProbeSeries(points, Int64[], Float64[], Float64[], zeros(Float64, m, 0), zeros(Int64, m, 0), zeros(Float64, m, 0), zeros(Float64, m, 0),
                                 Array{Float64,3}(undef, 3, m, 0), 0)
     end
+    if budgets_wanted()                            # opt-in as well: SPHMI_BUDGETS
+        check(h, ccall((:sphmi_budgets_enable, LIB), Cint, (Ptr{Cvoid}, Int64), h, 1 << 20))
+        BUDGETS[P] = BudgetSeries(Int64[], Float64[], Float64[], Int64[], zeros(Float64, 3, 0), zeros(Float64, 3, 0), zeros(Float64, 3, 0), zeros(Float64, 3, 0),
+                                  zeros(Float64, 3, 0), zeros(Float64, 6, 0), 0)
+    end
     return Session(h, Vector{Int64}(undef, N), zeros(8), zeros(Int64, 8), Vector{Int}(undef, N), Vector{Int64}(undef, SimMetaData.ExportGridCells ? N * D : 0),
                    columns, colptrs)
     catch
@@ -264,6 +298,7 @@ function SimulationLoop(SimDensityDiffusion::BuiltinDDT, SimViscosity::BuiltinVi
     forward_timers!(SimMetaData.HourGlass, s)
     haskey(GROUP_FORCES, P) && read_group_forces!(h, GROUP_FORCES[P])
     haskey(PROBES, P) && read_probes!(h, PROBES[P])
+    haskey(BUDGETS, P) && read_budgets!(h, BUDGETS[P])
     GC.@preserve P s begin
         # the carried fields: snapshot on the device, copies on a second stream, straight into the StructArray's columns
         # (Cells: a Vector{CartesianIndex{D}} is N·D Int64; Type is a per-particle constant and follows the gather below)

@@ -396,6 +396,35 @@ class Backend:
         self.probes_dropped = dropped.value
         return {key: a[:n.value] for key, a in out.items()}
 
+    # -- the budgets of the fluid at every step (sphmi_budgets_enable / sphmi_budgets_read) ---------------------------------
+    BUDGET_FIELDS = (("count", (), np.int64), ("energy", (3,), np.float64), ("momentum", (3,), np.float64), ("angular", (3,), np.float64),
+                     ("centre", (3,), np.float64), ("extremes", (3,), np.float64), ("box", (6,), np.float64))
+
+    def has_budgets(self) -> bool:
+        return self._has("budgets_enable") and self._has("budgets_read")
+
+    def budgets_enable(self, capacity: int = 4096) -> None:
+        """Record the energy, momentum and extent budgets of the Fluid rows after every executed step, on the device; the newest
+        `capacity` unread samples are kept.  `capacity = 0` disables."""
+        self._fn("budgets_enable").argtypes = [C.c_void_p, C.c_int64]
+        self._check(self._fn("budgets_enable")(self._h, int(capacity)))
+
+    def budgets_read(self) -> dict:
+        """The steps executed since the last read, oldest first, and clears them: a dict of iteration[n], time[n], dt[n], count[n]
+        (Fluid rows), energy[n, 3] (kinetic, potential, compressive), momentum[n, 3], angular[n, 3] (about the origin), centre[n, 3]
+        (of mass), extremes[n, 3] (largest speed, smallest and largest density) and box[n, 6] (min x, max x);
+        `budgets_dropped` holds how many older samples the capacity pushed out."""
+        f = self._fn("budgets_read")
+        f.argtypes = [C.c_void_p, C.c_int64] + [C.c_void_p] * 10 + [C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+        n, dropped = C.c_int64(), C.c_int64()
+        self._check(f(self._h, 0, *[None] * 10, C.byref(n), C.byref(dropped)))                  # capacity 0: how many are waiting
+        k = max(n.value, 1)
+        out = {"iteration": np.zeros(k, dtype=np.int64), "time": np.zeros(k), "dt": np.zeros(k)}
+        out.update({name: np.zeros((k,) + shape, dtype=dtype) for name, shape, dtype in self.BUDGET_FIELDS})
+        self._check(f(self._h, k, *[_ptr(a) for a in out.values()], C.byref(n), C.byref(dropped)))
+        self.budgets_dropped = dropped.value
+        return {key: a[:n.value] for key, a in out.items()}
+
     # -- kernel sums on a regular lattice, on demand (sphmi_sample_grid) -----------------------------------------------------
     GRID_FIELDS = ("weight", "count", "pressure", "density", "velocity")
 

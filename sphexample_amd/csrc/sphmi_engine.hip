@@ -19,6 +19,7 @@
 #include "sphmi_rebuild.h"
 #include "sphmi_columns.h"
 #include "sphmi_group_forces.h"
+#include "sphmi_budgets.h"
 #include "sphmi_probes.h"
 #include "sphmi_field_grid.h"
 #include "sphmi_particle_fields.h"
@@ -122,11 +123,13 @@ struct EngineBase {
     // entry points that need every row in this process: a multi-device handle refuses them in rank mode
     virtual void require_one_process(const char* fn) const { require_uploaded(fn); }
     // The observers' series (sphmi_series.h).  A multi-device handle keeps them itself; those of its slab engines stay empty.
-    bool gf_on = false, pr_on = false;
+    bool gf_on = false, pr_on = false, bg_on = false;
     StepSeries gf_series, pr_series;           // payload: 3 forces per group / the RAW sums, kPrValues per probe (the read normalises)
+    StepSeries bg_series;                      // the RAW budgets of the fluid, kBgValues per step (the read forms energies, momenta, the centre)
     // the device side of an enable: the handle's own sampling, or that of every slab engine of a multi-device handle
     virtual void gf_enable_device(int32_t n_groups, const uint64_t* markers) = 0;
     virtual void pr_enable_device(int32_t n_probes, const double* positions) = 0;
+    virtual void bg_enable_device(bool on) = 0;
     void group_forces_enable(int32_t n_groups, const uint64_t* markers, int64_t capacity_steps) {
         require_one_process("sphmi_group_forces_enable");
         check_group_table(n_groups, markers, capacity_steps);
@@ -138,6 +141,20 @@ struct EngineBase {
         check_probe_table(n_probes, positions, cfg.dims, capacity_steps);
         pr_enable_device(n_probes, positions);
         pr_series.reset(kPrValues * n_probes, capacity_steps);
+    }
+    void budgets_enable(int64_t capacity_steps) {
+        require_one_process("sphmi_budgets_enable");
+        if (capacity_steps < 0) throw EngineError(SPHMI_ERR_ARGUMENT, "sphmi_budgets_enable: negative capacity_steps");
+        bg_enable_device(capacity_steps > 0);
+        bg_series.reset(capacity_steps > 0 ? kBgValues : 0, capacity_steps);
+    }
+    void budgets_read(int64_t capacity, int64_t* iteration_out, double* time, double* dt, int64_t* count, double* energy, double* momentum, double* angular,
+                      double* centre, double* extremes, double* box, int64_t* n_out, int64_t* n_dropped) {
+        require_one_process("sphmi_budgets_read");
+        if (!bg_on) throw EngineError(SPHMI_ERR_STATE, "sphmi_budgets_read: sampling is not enabled (sphmi_budgets_enable)");
+        const BudgetFactors f(cfg.m0, cfg.g, cfg.c0, cfg.rho0);
+        bg_series.read("sphmi_budgets_read", capacity, iteration_out, time, dt, n_out, n_dropped,
+                       [&](int64_t k, const double* v) { deliver_budgets(f, k, v, count, energy, momentum, angular, centre, extremes, box); });
     }
     void group_forces_read(int64_t capacity, int64_t* iteration_out, double* time, double* dt, double* force, int64_t* n_out, int64_t* n_dropped) {
         require_one_process("sphmi_group_forces_read");
@@ -442,7 +459,7 @@ struct Engine final : EngineBase {
         for (auto& e : host_pinned) (void)hipHostUnregister(e.first);
         (void)hipFree(out_arena);
         (void)hipFree(col_arena); (void)hipFree(col_store); (void)hipFree(col_base[0]); (void)hipFree(col_base[1]);
-        gf_release(); pr_release(); (void)hipFree(fg_arena.p); (void)hipFree(pf_arena.p);
+        gf_release(); pr_release(); bg_release(); (void)hipFree(fg_arena.p); (void)hipFree(pf_arena.p);
         (void)hipFree(slot); (void)hipFree(tmp_idx); (void)hipFree(perm);
         for (int k = 0; k < 2; ++k) { (void)hipFree(tile_cost[k]); (void)hipFree(tile_order[k]); }
         (void)hipFree(kout_d); (void)hipFree(tile_work_d); (void)hipFree(tile_work1_d); (void)hipFree(xcd_clock_d); (void)hipHostFree(xcd_clock_h);
@@ -1117,6 +1134,7 @@ struct Engine final : EngineBase {
         end_phase(e2);
         if (gf_on) gf_sample(ctrl_cur(), obs_iteration0, obs_steps_base);       // Σ Acceleration of the selected groups → the batch's log
         if (pr_on) pr_sample(ctrl_cur(), obs_iteration0, obs_steps_base, iB);   // the kernel sums at the probes, on the corrector's output set → the batch's log
+        if (bg_on) bg_sample(ctrl_cur(), obs_iteration0, obs_steps_base, iB);   // the budgets of the fluid, on the same set → the batch's log
         std::swap(iA, iB);
     }
 
@@ -1159,6 +1177,7 @@ struct Engine final : EngineBase {
                 HC(hipMemcpyAsync(ctl_m, ctl_d, kCtlBytes, hipMemcpyDeviceToHost, stream));
                 if (gf_on) gf_log.fetch(batch, stream);                                      // … and the group-force records of the batch with it
                 if (pr_on) pr_log.fetch(batch, stream);                                      // … and the probe records
+                if (bg_on) bg_log.fetch(batch, stream);                                      // … and the budgets
                 // (the XCD finishing times of a sampled launch: the host-side rebuild reads them at its own synchronisation; handles that
                 // rebuild on the device have none — the shares of the next measured-work schedule would never move: 3 % on the 159 k-particle
                 // LaminarSPS case)
@@ -1173,6 +1192,7 @@ struct Engine final : EngineBase {
                 const int64_t executed = steps - before;
                 if (gf_on) push_records(gf_series, gf_log, kGfHeader, executed);
                 if (pr_on) push_records(pr_series, pr_log, kPrHeader, executed);
+                if (bg_on) push_records(bg_series, bg_log, kGfHeader, executed);
                 // (control inside the predictor: the slots flipped at queue time, once per queued step; what counts is where
                 // the last EXECUTED corrector left its maxima — cancelled steps consume nothing and zero nothing)
                 if (batch_fused) rpar = rpar0 ^ (int)(executed & 1);
@@ -1267,6 +1287,7 @@ struct Engine final : EngineBase {
         detach_columns();                          // a new particle set: the attached columns described the old one
         gf_disable();                              // … and so did the selected groups' row lists
         pr_disable();                              // … and the probes go with them
+        bg_disable();                              // … and the budgets
         iA = 0; iH = 1; iB = 2; cur = 0;
         ghost_given = ghost_points != nullptr;
         {
@@ -1328,6 +1349,7 @@ struct Engine final : EngineBase {
             detach_columns();
             gf_disable();
             pr_disable();
+            bg_disable();
             iA = 0; iH = 1; iB = 2; cur = 0; ghost_given = false; mdbc_n_list = 0; mdbc_list_valid = false;
             int base = 0;
             const unsigned nbM = (unsigned)((M + 255) / 256);
@@ -1760,6 +1782,50 @@ struct Engine final : EngineBase {
         fill_sample_consts(A);
         A.n_probes = pr_n; A.N = N; A.D = D; A.kernel = cfg.kernel; A.record = pr_log.record_doubles; A.slots = StepLog::slots;
         hipLaunchKernelGGL(k_probe_sample<T>, dim3((pr_n + 3) / 4), dim3(256), 0, stream, A);
+        HC(hipGetLastError());
+    }
+
+    // ---- the budgets of the fluid at every step (sphmi_budgets.h) ----------------------------------------------------------------
+    // No row lists: every launch looks at every row, so rebuilds need no hook.  One launch behind every corrector on handles of at
+    // most bg_small_rows rows, two above; the records of a batch go where the group forces' go.
+    double* bg_partial = nullptr;
+    StepLog bg_log;
+    int bg_small_rows = kBgSmallRows;          // $SPHMI_BUDGETS_SMALL_ROWS, read at enable (0: always two stages)
+    int bg_nblk_cap() const { return (cap + kBgBlock - 1) / kBgBlock; }
+    void bg_release() {
+        (void)hipFree(bg_partial); bg_partial = nullptr;
+        bg_log.release();
+    }
+    void bg_disable() {
+        if (!bg_on) return;
+        bg_on = false; bg_series.reset(0, 0);
+        HC(hipSetDevice(cfg.device)); HC(hipStreamSynchronize(stream));
+        bg_release();
+    }
+    void bg_enable_device(bool on) override {
+        HC(hipSetDevice(cfg.device));
+        bg_disable();
+        if (!on) return;
+        bg_small_rows = kBgSmallRows;
+        if (const char* e = getenv("SPHMI_BUDGETS_SMALL_ROWS")) bg_small_rows = (int)std::min<long long>(std::max<long long>(atoll(e), 0), kBgSmallRowsMax);
+        try {
+            HC(hipMalloc(&bg_partial, (size_t)std::max(bg_nblk_cap(), 1) * kBgValues * 8));
+            bg_log.alloc(kBgRecord, kBgRecord);
+        } catch (...) { bg_release(); throw; }
+        bg_on = true;
+    }
+    // queued behind the corrector of a step; `set`: the state set that corrector wrote
+    void bg_sample(const StepCtrl* ctrl, int64_t iteration0, int64_t steps_base, int set) {
+        BudgetArgs<T> A{};
+        A.ctrl = ctrl; A.pk0 = pk0[set]; A.pk1 = pk1[set]; A.comp = comp[cur];
+        A.type = dd_slab ? type[cur] : nullptr; A.partial = bg_partial; A.log = bg_log.d;
+        A.iteration0 = iteration0; A.steps_base = steps_base; A.rho0 = cfg.rho0;
+        A.N = N; A.D = D; A.nblk = std::min((N + kBgBlock - 1) / kBgBlock, bg_nblk_cap()); A.slots = StepLog::slots;
+        if (N <= bg_small_rows) hipLaunchKernelGGL(k_bg_small<T>, dim3(1), dim3(kBgBlock), 0, stream, A);
+        else {
+            hipLaunchKernelGGL(k_bg_partial<T>, dim3(std::min(A.nblk, 1 << 20)), dim3(kBgBlock), 0, stream, A);
+            hipLaunchKernelGGL(k_bg_final<T>, dim3(1), dim3(64), 0, stream, A);
+        }
         HC(hipGetLastError());
     }
 
@@ -2395,6 +2461,13 @@ int sphmi_particle_fields(sphmi_handle* h, int64_t* count_out, double* shepard_o
 int sphmi_group_forces_read(sphmi_handle* h, int64_t capacity, int64_t* iteration_out, double* time_out, double* dt_out, double* force_out,
                             int64_t* n_out, int64_t* n_dropped) {
     SPHMI_GUARD(h, h->e->group_forces_read(capacity, iteration_out, time_out, dt_out, force_out, n_out, n_dropped));
+}
+int sphmi_budgets_enable(sphmi_handle* h, int64_t capacity_steps) { SPHMI_GUARD(h, h->e->budgets_enable(capacity_steps)); }
+int sphmi_budgets_read(sphmi_handle* h, int64_t capacity, int64_t* iteration_out, double* time_out, double* dt_out, int64_t* count_out,
+                       double* energy_out, double* momentum_out, double* angular_out, double* centre_out, double* extremes_out, double* box_out,
+                       int64_t* n_out, int64_t* n_dropped) {
+    SPHMI_GUARD(h, h->e->budgets_read(capacity, iteration_out, time_out, dt_out, count_out, energy_out, momentum_out, angular_out, centre_out, extremes_out,
+                                      box_out, n_out, n_dropped));
 }
 int sphmi_set_motion(sphmi_handle* h, uint64_t group_marker, double velocity, double start_time, double duration,
                      const double* direction) {

@@ -914,6 +914,7 @@ struct MultiEngine final : EngineBase {
         col_data.clear(); col_width.clear(); col_base.clear();     // a new particle set: the attached columns described the old one
         gf_on = false; gf_series.reset(0, 0);                      // … and the selected groups (the slab engines are made anew below)
         pr_on = false; pr_series.reset(0, 0);                      // … and the probes
+        bg_on = false; bg_series.reset(0, 0);                      // … and the budgets
         SlabSetup S;
         plan_slabs(cfg, position, ghost_points, N, world, cfg.slab_axis - 1, given_plan.world() == world ? &given_plan : nullptr, 1.6, S);
         axis = S.axis; halo_width = S.halo_width; plan = S.plan;
@@ -1421,10 +1422,12 @@ struct MultiEngine final : EngineBase {
                         if (gf_on) for (auto& r : R) { HC(hipSetDevice(r.device)); r.e->gf_sample(r.e->ctrl_d, iteration, steps0); }
                         // … and the kernel sums at the probes (the corrector's output set is iA here: dd_pass has rotated the sets)
                         if (pr_on) for (auto& r : R) { HC(hipSetDevice(r.device)); r.e->pr_sample(r.e->ctrl_d, iteration, steps0, r.e->iA); }
+                        if (bg_on) for (auto& r : R) { HC(hipSetDevice(r.device)); r.e->bg_sample(r.e->ctrl_d, iteration, steps0, r.e->iA); }
                     }
                 }
                 if (gf_on) for (auto& r : R) { HC(hipSetDevice(r.device)); r.e->gf_log.fetch(batch, r.e->stream); }
                 if (pr_on) for (auto& r : R) { HC(hipSetDevice(r.device)); r.e->pr_log.fetch(batch, r.e->stream); }
+                if (bg_on) for (auto& r : R) { HC(hipSetDevice(r.device)); r.e->bg_log.fetch(batch, r.e->stream); }
                 for (auto& r : R) {
                     HC(hipSetDevice(r.device)); sphmi_dd_control s{}; r.e->dd_ctrl_sync(&s);
                     if (&r == &R[0]) st = s;
@@ -1441,6 +1444,7 @@ struct MultiEngine final : EngineBase {
                 steps = st.steps_done;
                 if (gf_on) collect_records(gf_series, &Engine<T>::gf_log, kGfHeader, "group forces", steps - steps0);
                 if (pr_on) collect_records(pr_series, &Engine<T>::pr_log, kPrHeader, "probes", steps - steps0);
+                if (bg_on) collect_records(bg_series, &Engine<T>::bg_log, kGfHeader, "budgets", steps - steps0, bg_rule);
                 total_time = st.total_time; last_dt = st.last_dt; dxl = st.delta_x;
                 const int64_t grown = (steps - steps0) + (st.need_rebuild ? 1 : 0) - (fresh && steps > steps0 ? 1 : 0);
                 if (steps > steps0) fresh = false;
@@ -1732,11 +1736,22 @@ struct MultiEngine final : EngineBase {
         for (auto& r : R) r.e->pr_enable_device(n_probes, positions);
         pr_on = n_probes > 0;
     }
-    // after the synchronisation of a batch: the records of its `executed` steps, slab by slab
-    void collect_records(StepSeries& series, typename Engine<T>::StepLog Engine<T>::*log, int header, const char* what, int64_t executed) {
+    // The budgets of the fluid (sphmi_budgets.h): every slab reduces the rows it owns, the handle combines the slabs' raw records of a
+    // step in slab order — sums add, extremes take min or max (bg_rule); the read forms the delivered values from the combined record.
+    void bg_enable_device(bool on) override {
+        bg_on = false; bg_series.reset(0, 0);
+        for (auto& r : R) r.e->bg_enable_device(on);
+        bg_on = on;
+    }
+    // after the synchronisation of a batch: the records of its `executed` steps, slab by slab (every slot a sum, or combined by `rule`)
+    void collect_records(StepSeries& series, typename Engine<T>::StepLog Engine<T>::*log, int header, const char* what, int64_t executed,
+                         int (*rule)(int) = nullptr) {
         for (int64_t k = 0; k < executed; ++k) {
             StepSeries::Sample s = StepSeries::decode((R[0].e.get()->*log).record(k), header, series.values);
-            for (size_t q = 1; q < R.size(); ++q) StepSeries::add(s, StepSeries::decode((R[q].e.get()->*log).record(k), header, series.values), what);
+            for (size_t q = 1; q < R.size(); ++q) {
+                const StepSeries::Sample o = StepSeries::decode((R[q].e.get()->*log).record(k), header, series.values);
+                if (rule) StepSeries::combine(s, o, what, rule); else StepSeries::add(s, o, what);
+            }
             series.push(std::move(s));
         }
     }

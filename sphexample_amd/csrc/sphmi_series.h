@@ -1,4 +1,4 @@
-// sphmi_series.h — the host side the observers share (group forces, probes, lattice, columns): the error type, the limits and
+// sphmi_series.h — the host side the observers share (group forces, probes, budgets, lattice, columns): the error type, the limits and
 // record-layout constants host and device agree on, the argument checks every kind of handle reports alike, the per-step series
 // and the means of the kernel sums.  Plain C++17, no HIP: tests/host_series/series_main.cpp compiles it alone.
 #pragma once
@@ -28,6 +28,11 @@ constexpr int kMaxProbes = 1024;                 // SPHMI_MAX_PROBES
 constexpr int kPrValues = 7;                     // S, SP, Sρ, Sv[3], n
 constexpr int kFgValues = kPrValues;             // S, SP, Sρ, Sv[3], n
 constexpr long long kMaxGridNodes = 1ll << 24;   // SPHMI_MAX_GRID_NODES
+constexpr int kBgValues = 22;                    // the raw budgets of the fluid (sphmi_budgets.h): thirteen sums, nine extremes
+
+// How two values of slot `slot` of a budget record combine: 0 sum (slots 0 … 12), 1 min, 2 max (13 max |v|², 14 / 15 min / max ρ,
+// 16 … 18 / 19 … 21 min / max x per axis).  The kernels and the host side of a multi-device handle use the same rule.
+constexpr int bg_rule(int slot) { return slot < 13 ? 0 : (slot == 14 || (slot >= 16 && slot <= 18)) ? 1 : 2; }
 
 // sphmi_attach_columns: the argument errors every kind of handle reports alike
 inline void check_column_table(int32_t n_columns, const void* const* columns, const int32_t* row_bytes) {
@@ -100,6 +105,15 @@ struct StepSeries {
         if (other.iteration != into.iteration) throw EngineError(SPHMI_ERR_STATE, std::string(what) + ": the slabs' records of a step do not belong together");
         for (size_t c = 0; c < into.v.size(); ++c) into.v[c] += other.v[c];
     }
+    // … or combines them slot by slot where not every slot is a sum: rule(slot) = 0 sum, 1 min, 2 max (bg_rule)
+    template <class Rule>
+    static void combine(Sample& into, const Sample& other, const char* what, Rule&& rule) {
+        if (other.iteration != into.iteration) throw EngineError(SPHMI_ERR_STATE, std::string(what) + ": the slabs' records of a step do not belong together");
+        for (size_t c = 0; c < into.v.size(); ++c) {
+            const int r = rule((int)c);
+            into.v[c] = r == 0 ? into.v[c] + other.v[c] : r == 1 ? std::fmin(into.v[c], other.v[c]) : std::fmax(into.v[c], other.v[c]);
+        }
+    }
     // the oldest min(cap, waiting) samples leave the series: deliver(k, payload) hands out the k-th of them
     template <class Deliver>
     void read(const char* fn_name, int64_t cap, int64_t* iteration, double* time, double* dt, int64_t* n_out, int64_t* n_dropped, Deliver&& deliver) {
@@ -141,6 +155,26 @@ inline void deliver_probe_means(int n_probes, int64_t k, const double* sums, dou
         if (density) density[at] = kernel_mean(v[2], v[0], some);
         if (velocity) for (int d = 0; d < 3; ++d) velocity[3 * at + d] = kernel_mean(v[3 + d], v[0], some);
     }
+}
+
+// sphmi_budgets_read: what turns the raw budgets into energies and momenta.  B = c₀²ρ₀/7 is the Cb/γ of the Tait equation the
+// engine runs (γ = 7); the kernels record Σ e(ρ) in units of B/ρ₀.
+struct BudgetFactors {
+    double mass, potential, internal;          // m₀,  m₀·g,  m₀·(B/ρ₀)
+    BudgetFactors(double m0, double g, double c0, double rho0) : mass(m0), potential(m0 * g), internal(m0 * (((c0 * c0 * rho0) / 7.0) / rho0)) {}
+};
+// … the raw record { n, Σ½v², Σx_last, Σe, Σv[3], Σx×v[3], Σx[3], max v², min ρ, max ρ, min x[3], max x[3] } of the k-th delivered
+// step: one multiplication or division per value; a step without Fluid rows (n = 0: ±inf in the extremes) delivers zeros
+inline void deliver_budgets(const BudgetFactors& f, int64_t k, const double* v, int64_t* count, double* energy, double* momentum, double* angular,
+                            double* centre, double* extremes, double* box) {
+    const bool some = v[0] > 0.0;
+    if (count) count[k] = (int64_t)v[0];
+    if (energy) { energy[3 * k] = f.mass * v[1]; energy[3 * k + 1] = f.potential * v[2]; energy[3 * k + 2] = f.internal * v[3]; }
+    if (momentum) for (int d = 0; d < 3; ++d) momentum[3 * k + d] = f.mass * v[4 + d];
+    if (angular) for (int d = 0; d < 3; ++d) angular[3 * k + d] = f.mass * v[7 + d];
+    if (centre) for (int d = 0; d < 3; ++d) centre[3 * k + d] = some ? v[10 + d] / v[0] : 0.0;
+    if (extremes) { extremes[3 * k] = some ? std::sqrt(v[13]) : 0.0; extremes[3 * k + 1] = some ? v[14] : 0.0; extremes[3 * k + 2] = some ? v[15] : 0.0; }
+    if (box) for (int d = 0; d < 6; ++d) box[6 * k + d] = some ? v[16 + d] : 0.0;
 }
 
 // The host side of sphmi_sample_grid: the raw sums { S, SP, Sρ, Sv[3], n } of the lattice (sphmi_field_grid.h), the ones the

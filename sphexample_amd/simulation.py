@@ -17,6 +17,7 @@ import numpy as np
 from ._abi import make_config
 from .config import (SimulationConstants, SimulationMetaData, SPHDensityDiffusion, SPHKernelInstance,
                      SPHViscosity, next_output_time)
+from .budgets import empty_budgets
 from .engine import Engine
 from .preprocess import LoadMDBCNormals, SimParticles
 
@@ -43,7 +44,7 @@ def RunSimulation(*, SimGeometry=None, SimMetaData: SimulationMetaData, SimConst
                   on_output: Optional[Callable[[SimulationMetaData, SimParticles], None]] = None,
                   device_float_bytes: int = 0, device: int = 0, backend_factory=None,
                   async_output: bool = False, group_forces=None, probes=None, field_grid=None,
-                  particle_fields=None) -> List[float]:
+                  particle_fields=None, budgets: bool = False) -> List[float]:
     """Same keyword signature as the reference (src/SPHCellList.jl:808-817); returns the list of
     time steps the reference collects in ``TimeSteps`` (:823,:884).  ``SimParticles`` is updated in
     place at every output time, in the engine's cell-sorted order, as the reference's is.
@@ -68,7 +69,12 @@ def RunSimulation(*, SimGeometry=None, SimMetaData: SimulationMetaData, SimConst
     receives the dict as one more argument, behind group forces, probes and the field grid when those are on (``None`` at the
     first call).  It is taken at the same point as the snapshot: row i is particle i of that output
     (``sphexample_amd.fields.free_surface_mask`` reads a free surface off ``div_r``).  ``None`` (default): nothing is evaluated
-    and the callback keeps its arguments."""
+    and the callback keeps its arguments.
+
+    ``budgets=True``: the energy, momentum and extent budgets of the fluid are recorded on the device at every step
+    (``Backend.budgets_enable``; ``sphexample_amd.budgets`` adds up a total energy and reads a wave front off the box) and
+    ``on_output`` receives the samples of the interval, the dict of ``Backend.budgets_read``, as its last argument (empty
+    arrays at the first call).  ``False`` (default): nothing is recorded and the callback keeps its arguments."""
     if SimMetaData.BMode.__name__ == "SimpleMDBC":
         LoadMDBCNormals(SimParticles, ParticleNormalsPath)                       # :827
     host_bytes = SimParticles.Position.dtype.itemsize
@@ -112,6 +118,9 @@ def RunSimulation(*, SimGeometry=None, SimMetaData: SimulationMetaData, SimConst
     if particle_fields is not None:
         names = tuple(particle_fields)
         extras.append((None, lambda: eng.particle_fields(names)))                # (the rows of this output: no step lies between it and the download)
+    if budgets:
+        eng.budgets_enable(capacity=1 << 20)
+        extras.append((empty_budgets(), eng.budgets_read))
     none_yet = tuple(first for first, _ in extras)
     emit = lambda meta, samples: on_output(meta, SimParticles, *samples)         # noqa: E731
     if on_output:

@@ -1,0 +1,176 @@
+// The host side of the budgets of the fluid (sphexample_amd/csrc/sphmi_series.h: deliver_budgets, BudgetFactors, bg_rule and
+// StepSeries::combine) on hand-made records: built with the host compiler and the address / undefined-behaviour sanitizers by
+// tests/test_budgets_host.py, run as a child process.  Exit code 0 and "ok" on the last line: every check held.
+#include <cmath>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <limits>
+#include <string>
+#include <vector>
+
+#include "sphmi_series.h"
+
+using namespace sphmi;
+
+static int g_checks = 0;
+#define CHECK(cond)                                                                   \
+    do {                                                                              \
+        ++g_checks;                                                                   \
+        if (!(cond)) { printf("FAILED %s:%d: %s\n", __FILE__, __LINE__, #cond); exit(1); } \
+    } while (0)
+
+static const char* kFn = "sphmi_budgets_read";
+static const double kInf = std::numeric_limits<double>::infinity();
+
+// the record of a step without Fluid rows, as the kernels write it: 0 in the sum slots, +inf in the min slots, −inf in the max slots
+static std::vector<double> empty_record(int64_t it) {
+    std::vector<double> r((size_t)kGfHeader + kBgValues, 0.0);
+    memcpy(&r[0], &it, 8);
+    r[1] = 0.5 * (double)it; r[2] = 0.125;
+    for (int c = 0; c < kBgValues; ++c) r[(size_t)kGfHeader + c] = bg_rule(c) == 0 ? 0.0 : (bg_rule(c) == 1 ? kInf : -kInf);
+    return r;
+}
+// … and one of `n` rows: slot c holds base + c (the min slots below, the max slots above what `other` holds when base differs)
+static std::vector<double> filled_record(int64_t it, double n, double base) {
+    std::vector<double> r = empty_record(it);
+    for (int c = 0; c < kBgValues; ++c) r[(size_t)kGfHeader + c] = base + c;
+    r[kGfHeader] = n;
+    return r;
+}
+static StepSeries::Sample sample(const std::vector<double>& rec) { return StepSeries::decode(rec.data(), kGfHeader, kBgValues); }
+
+// the arrays of one read, exactly `cap` samples long (the sanitizer sees a write past them)
+struct Got {
+    std::vector<int64_t> it, count;
+    std::vector<double> t, dt, energy, momentum, angular, centre, extremes, box;
+    int64_t n = -7, dropped = -7;
+    explicit Got(int64_t cap)
+        : it((size_t)cap, -1), count((size_t)cap, -1), t((size_t)cap, -1.0), dt((size_t)cap, -1.0), energy((size_t)cap * 3, -1.0), momentum((size_t)cap * 3, -1.0),
+          angular((size_t)cap * 3, -1.0), centre((size_t)cap * 3, -1.0), extremes((size_t)cap * 3, -1.0), box((size_t)cap * 6, -1.0) {}
+};
+static Got read(StepSeries& s, const BudgetFactors& f, int64_t cap) {
+    Got g(cap);
+    s.read(kFn, cap, g.it.data(), g.t.data(), g.dt.data(), &g.n, &g.dropped, [&](int64_t k, const double* v) {
+        deliver_budgets(f, k, v, g.count.data(), g.energy.data(), g.momentum.data(), g.angular.data(), g.centre.data(), g.extremes.data(), g.box.data());
+    });
+    return g;
+}
+
+static void test_rule() {
+    int sums = 0, mins = 0, maxs = 0;
+    for (int c = 0; c < kBgValues; ++c) { sums += bg_rule(c) == 0; mins += bg_rule(c) == 1; maxs += bg_rule(c) == 2; }
+    CHECK(kBgValues == 22 && sums == 13 && mins == 4 && maxs == 5);
+    for (int c = 0; c < 13; ++c) CHECK(bg_rule(c) == 0);
+    CHECK(bg_rule(13) == 2 && bg_rule(14) == 1 && bg_rule(15) == 2);
+    for (int c = 16; c < 19; ++c) CHECK(bg_rule(c) == 1 && bg_rule(c + 3) == 2);
+}
+
+static void test_factors_and_delivery() {
+    const double m0 = 0.008, g = 9.81, c0 = 88.14, rho0 = 1000.0;
+    const BudgetFactors f(m0, g, c0, rho0);
+    CHECK(f.mass == m0 && f.potential == m0 * g && f.internal == m0 * (((c0 * c0 * rho0) / 7.0) / rho0));
+    StepSeries s;
+    s.reset(kBgValues, 4);
+    std::vector<double> rec = filled_record(3, 5.0, 0.5);
+    rec[kGfHeader + 13] = 6.25;
+    s.push(sample(rec));
+    s.push(sample(empty_record(4)));
+    Got got = read(s, f, 2);
+    CHECK(got.n == 2 && got.dropped == 0 && got.it[0] == 3 && got.it[1] == 4 && got.t[0] == 1.5 && got.dt[1] == 0.125);
+    const double* v = &rec[kGfHeader];
+    CHECK(got.count[0] == 5);
+    CHECK(got.energy[0] == m0 * v[1] && got.energy[1] == (m0 * g) * v[2] && got.energy[2] == f.internal * v[3]);
+    for (int d = 0; d < 3; ++d) {
+        CHECK(got.momentum[(size_t)d] == m0 * v[4 + d] && got.angular[(size_t)d] == m0 * v[7 + d]);
+        CHECK(got.centre[(size_t)d] == v[10 + d] / 5.0);
+    }
+    CHECK(got.extremes[0] == 2.5 && got.extremes[1] == v[14] && got.extremes[2] == v[15]);
+    for (int d = 0; d < 6; ++d) CHECK(got.box[(size_t)d] == v[16 + d]);
+    // a record with n = 0 delivers zeros, not inf or NaN
+    CHECK(got.count[1] == 0);
+    for (size_t d = 3; d < 6; ++d) CHECK(got.energy[d] == 0.0 && got.momentum[d] == 0.0 && got.angular[d] == 0.0 && got.centre[d] == 0.0 && got.extremes[d] == 0.0);
+    for (size_t d = 6; d < 12; ++d) CHECK(got.box[d] == 0.0);
+    // every output null: the samples still leave the series
+    s.push(sample(rec));
+    int64_t n = -1;
+    s.read(kFn, 1, nullptr, nullptr, nullptr, &n, nullptr, [&](int64_t k, const double* p) {
+        deliver_budgets(f, k, p, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
+    });
+    CHECK(n == 1 && s.q.empty());
+}
+
+// two slabs whose extremes lie in different slabs; a slab without Fluid rows; records of different steps
+static void test_combine() {
+    // slab A holds the smallest values of slots 14, 16, 17 and the largest of 13, 19; slab B the others
+    std::vector<double> ra = filled_record(9, 3.0, 1.0), rb = filled_record(9, 4.0, 2.0);
+    double* a = &ra[kGfHeader]; double* b = &rb[kGfHeader];
+    a[13] = 50.0; b[13] = 40.0;     // max |v|²: in A
+    a[18] = 7.5; b[18] = -7.5;      // min z: in B
+    a[19] = 90.0; b[19] = 80.0;     // max x: in A
+    a[20] = -3.0; b[20] = -2.0;     // max y: in B
+    StepSeries::Sample s = sample(ra);
+    const StepSeries::Sample s0 = s, o = sample(rb);
+    StepSeries::combine(s, o, "budgets", bg_rule);
+    for (int c = 0; c < 13; ++c) CHECK(s.v[(size_t)c] == s0.v[(size_t)c] + o.v[(size_t)c]);
+    CHECK(s.v[0] == 7.0);
+    CHECK(s.v[13] == 50.0 && s.v[14] == a[14] && s.v[15] == b[15]);
+    CHECK(s.v[16] == a[16] && s.v[17] == a[17] && s.v[18] == -7.5);
+    CHECK(s.v[19] == 90.0 && s.v[20] == -2.0 && s.v[21] == b[21]);
+    CHECK(s.iteration == 9 && s.time == s0.time && s.dt == s0.dt);
+    // the other way round: min and max do not depend on the order of the slabs
+    StepSeries::Sample r = sample(rb);
+    StepSeries::combine(r, s0, "budgets", bg_rule);
+    for (int c = 13; c < kBgValues; ++c) CHECK(r.v[(size_t)c] == s.v[(size_t)c]);
+    // a slab without Fluid rows changes nothing, on either side
+    StepSeries::Sample e = sample(empty_record(9)), t = s0;
+    StepSeries::combine(t, e, "budgets", bg_rule);
+    CHECK(t.v == s0.v);
+    StepSeries::combine(e, s0, "budgets", bg_rule);
+    CHECK(e.v == s0.v);
+    // two empty slabs stay the empty record, which delivers zeros
+    StepSeries::Sample e1 = sample(empty_record(9));
+    StepSeries::combine(e1, sample(empty_record(9)), "budgets", bg_rule);
+    CHECK(e1.v == sample(empty_record(9)).v);
+    // records of different steps do not combine, and nothing is touched
+    StepSeries::Sample before = s;
+    try { StepSeries::combine(s, sample(filled_record(10, 1.0, 0.0)), "budgets", bg_rule); CHECK(false); }
+    catch (const EngineError& err) {
+        CHECK(err.status == SPHMI_ERR_STATE && std::string(err.what()) == "budgets: the slabs' records of a step do not belong together");
+    }
+    CHECK(s.v == before.v);
+}
+
+// a read with capacity = 0 clears nothing; samples beyond capacity_steps are dropped and counted
+static void test_capacity() {
+    const BudgetFactors f(1.0, 1.0, 7.0, 1.0);
+    StepSeries s;
+    s.reset(kBgValues, 6);
+    for (int64_t it = 1; it <= 50; ++it) s.push(sample(filled_record(it, 2.0, (double)it)));
+    for (int rep = 0; rep < 2; ++rep) {
+        int64_t n = -1, d = -1;
+        s.read(kFn, 0, nullptr, nullptr, nullptr, &n, &d, [&](int64_t, const double*) { CHECK(false); });
+        CHECK(n == 6 && d == 44 && s.q.size() == 6 && s.dropped == 44);
+    }
+    Got got = read(s, f, 7);
+    CHECK(got.n == 6 && got.dropped == 44);
+    for (int64_t k = 0; k < 6; ++k) CHECK(got.it[(size_t)k] == 45 + k && got.count[(size_t)k] == 2 && got.box[(size_t)(6 * k)] == (double)(45 + k) + 16.0);
+    CHECK(got.it[6] == -1 && got.count[6] == -1 && got.box[36] == -1.0);          // nothing behind the delivered ones
+    got = read(s, f, 7);
+    CHECK(got.n == 0 && got.dropped == 0);
+    // the argument errors are the series' own
+    int64_t n = -1;
+    try { s.read(kFn, 1, nullptr, nullptr, nullptr, nullptr, nullptr, [&](int64_t, const double*) {}); CHECK(false); }
+    catch (const EngineError& err) { CHECK(err.status == SPHMI_ERR_ARGUMENT && std::string(err.what()) == "sphmi_budgets_read: null n_out"); }
+    try { s.read(kFn, -1, nullptr, nullptr, nullptr, &n, nullptr, [&](int64_t, const double*) {}); CHECK(false); }
+    catch (const EngineError& err) { CHECK(err.status == SPHMI_ERR_ARGUMENT && std::string(err.what()) == "sphmi_budgets_read: negative capacity"); }
+}
+
+int main() {
+    test_rule();
+    test_factors_and_delivery();
+    test_combine();
+    test_capacity();
+    printf("%d checks\nok\n", g_checks);
+    return 0;
+}
