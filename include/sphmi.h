@@ -475,6 +475,36 @@ int sphmi_particle_fields(sphmi_handle* h,
         double*  div_v_out,      /* [n]      div v     */
         double*  vorticity_out); /* [n x 3]  w_i       */
 
+/*
+ * The neighbour list of every row in CSR form, built on the device on demand: who the neighbours ARE, for the pair sums the library does
+ * not define - a user viscosity or diffusion term, a pair statistic - formed on the host from the list and one download, without a
+ * neighbour search there (csrc/sphmi_neighbor_list.h).
+ *   sphmi_neighbors_build is synchronous and called between sphmi_advance calls like sphmi_particle_fields; it changes no state a later
+ *   step, download, column download, series read, sphmi_sample_grid or sphmi_particle_fields reads, and leaves a download begun with
+ *   sphmi_download_begin alone.  n_rows = sphmi_owned_count rows; row i is row i of what sphmi_download delivers now.
+ *   Row i, of any Type, lists every row j != i of any Type with r^2 = ((dx^2 + dy^2) + dz^2) <= H^2 - inclusive, not fused, on the
+ *   Position doubles sphmi_download would deliver now (fp32 handles: record + low word), however stale the cell list: the cut of
+ *   sphmi_particle_fields, which a host reproduces bit for bit; its count_out is the length of every row.  Coincident rows are listed;
+ *   j = i is excluded by row index.  SPHMI_NEIGHBORS_FULL lists both (i, j) and (j, i); SPHMI_NEIGHBORS_HALF keeps j > i, every pair once.
+ *   The list of a row is strictly ascending in j and no atomics decide an entry's place: repeated calls give the same bytes.
+ *   The entries of row i are neighbors[offsets[i] .. offsets[i + 1]), 0-based, offsets[0] = 0, offsets[n_rows] = n_pairs.  Offsets are
+ *   int64 and the scan that forms them sums in 64 bits: at the per-device particle limit the total passes 2^31.  (That is reviewed, not
+ *   exercised: offsets beyond 2^31 need more than 10^7 rows.)
+ *   The result stays in a device arena of the handle until the next build, sphmi_neighbors_release (which gives the memory back) or
+ *   sphmi_destroy.  sphmi_advance, sphmi_upload, sphmi_generate_dam_break_3d and sphmi_forces_once mark it stale: rows may have moved.
+ *   sphmi_neighbors_read copies the offsets [n_rows + 1] and the entries [n_pairs] to host arrays; either pointer may be NULL.
+ *   SPHMI_ERR_STATE: before the upload; before the handle has executed its first step since the upload or generator (no cell list);
+ *     handles with H < h; rank-mode handles; multi-device handles (single-device handles only, as for sphmi_particle_fields);
+ *     sphmi_neighbors_read without a build, or of a stale result.
+ *   SPHMI_ERR_ARGUMENT: an unknown mode; a null n_pairs_out (n_rows_out may be NULL).
+ *   SPHMI_ERR_DEVICE: the device cannot hold the arena (4 bytes per entry); the message gives the pair count and the bytes, and the
+ *     handle stays usable.
+ */
+enum { SPHMI_NEIGHBORS_FULL = 0, SPHMI_NEIGHBORS_HALF = 1 };
+int sphmi_neighbors_build(sphmi_handle* h, int32_t mode, int64_t* n_rows_out, int64_t* n_pairs_out);
+int sphmi_neighbors_read(sphmi_handle* h, int64_t* offsets_out /* [n_rows + 1] */, int32_t* neighbors_out /* [n_pairs] */);
+int sphmi_neighbors_release(sphmi_handle* h);
+
 #ifdef __cplusplus
 }
 #endif

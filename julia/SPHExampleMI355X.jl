@@ -180,6 +180,18 @@ function particle_fields(P)
                                                 h, pointer(c), pointer(s), pointer(nrm), pointer(dr), pointer(dv), pointer(w)))
     return (count = c, shepard = s, normal = nrm, div_r = dr, div_v = dv, vorticity = w)
 end
+# The neighbour list of every row on the state the session holds NOW (sphmi_neighbors_build / _read / _release): row i (1-based) of the
+# next download lists neighbors[offsets[i] + 1 : offsets[i + 1]], every other row within H, ascending.  Both arrays are the library's RAW
+# 0-BASED values — offsets[1] == 0 and an entry j names row j + 1 of the StructArray.  Single-device sessions; from an output callback.
+function neighbor_list(P; half::Bool = false)
+    h = SESSIONS[P].h
+    rows = Ref{Int64}(0); pairs = Ref{Int64}(0)
+    check(h, ccall((:sphmi_neighbors_build, LIB), Cint, (Ptr{Cvoid}, Int32, Ref{Int64}, Ref{Int64}), h, half ? 1 : 0, rows, pairs))
+    offsets = Vector{Int64}(undef, rows[] + 1); neighbors = Vector{Int32}(undef, pairs[])
+    GC.@preserve offsets neighbors check(h, ccall((:sphmi_neighbors_read, LIB), Cint, (Ptr{Cvoid}, Ptr{Int64}, Ptr{Int32}), h, pointer(offsets), pointer(neighbors)))
+    check(h, ccall((:sphmi_neighbors_release, LIB), Cint, (Ptr{Cvoid},), h))
+    return (offsets = offsets, neighbors = neighbors)
+end
 atexit(() -> foreach(s -> ccall((:sphmi_destroy, LIB), Cint, (Ptr{Cvoid},), s.h), values(SESSIONS)))
 
 function check(h, rc)

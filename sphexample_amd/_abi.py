@@ -20,6 +20,7 @@ MAX_COLUMN_ROW_BYTES = 64
 MAX_FORCE_GROUPS = 16
 MAX_PROBES = 1024
 MAX_GRID_NODES = 1 << 24
+NEIGHBORS_FULL, NEIGHBORS_HALF = 0, 1
 
 OK, ERR_ARGUMENT, ERR_DEVICE, ERR_NUMERIC, ERR_DOMAIN, ERR_STATE = range(6)
 
@@ -481,6 +482,56 @@ class Backend:
                for k in self.PARTICLE_FIELDS}
         self._check(f(self._h, *[_ptr(out[k]) for k in self.PARTICLE_FIELDS]))
         return {k: v for k, v in out.items() if v is not None}
+
+    # -- the neighbour list of every row, on demand (sphmi_neighbors_build / _read / _release) ----------------------------------
+    def has_neighbor_list(self) -> bool:
+        return all(self._has(n) for n in ("neighbors_build", "neighbors_read", "neighbors_release"))
+
+    def neighbors_build(self, half: bool = False):
+        """Build the CSR neighbour list of every row on the device and keep it there: (n_rows, n_pairs).  `half`: only j > i,
+        every pair once.  It stays until the next build, `neighbors_release` or `close`; a step, an upload or `forces_once`
+        marks it stale."""
+        f = self._fn("neighbors_build")
+        f.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+        rows, pairs = C.c_int64(), C.c_int64()
+        self._neighbor_shape = None                                               # (a refused build leaves nothing this object may read)
+        self._check(f(self._h, NEIGHBORS_HALF if half else NEIGHBORS_FULL, C.byref(rows), C.byref(pairs)))
+        self._neighbor_shape = (rows.value, pairs.value)
+        return self._neighbor_shape
+
+    def neighbors_read(self, offsets: bool = True, neighbors: bool = True):
+        """(offsets int64 [n_rows + 1], neighbors int32 [n_pairs]) of the list built last; False skips one (None in its place).
+        sphmi_neighbors_read takes no capacities: the arrays are sized from what THIS object's `neighbors_build` reported, so a
+        list built through the raw entry point behind its back must not be read here.  Without a build of its own the library
+        is asked with both pointers NULL — it words the refusal — and a list it then turns out to hold is refused here."""
+        f = self._fn("neighbors_read")
+        f.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        shape = getattr(self, "_neighbor_shape", None)
+        if shape is None:
+            self._check(f(self._h, None, None))
+            raise RuntimeError("neighbors_read: the handle holds a list this object did not build; call neighbors_build first")
+        rows, pairs = shape
+        off = np.zeros(rows + 1, dtype=np.int64) if offsets else None
+        nbr = np.zeros(pairs, dtype=np.int32) if neighbors else None
+        self._check(f(self._h, _ptr(off), _ptr(nbr)))
+        return off, nbr
+
+    def neighbors_release(self) -> None:
+        f = self._fn("neighbors_release")
+        f.argtypes = [C.c_void_p]
+        self._check(f(self._h))
+        self._neighbor_shape = None
+
+    def neighbor_list(self, half: bool = False):
+        """The neighbour list of every row, evaluated now: (offsets int64 [n + 1], neighbors int32 [total]); row i — row i of what
+        `download` delivers now — lists neighbors[offsets[i]:offsets[i + 1]], every row j != i within H on the current positions,
+        ascending (`half`: only j > i).  `sphexample_amd.neighbors` forms pair sums from it.  Single-device handles; call it
+        between `advance` calls, after the first executed step.  The device memory is given back before it returns."""
+        self.neighbors_build(half)
+        try:
+            return self.neighbors_read()
+        finally:
+            self.neighbors_release()
 
     def forces_once(self, apply_mdbc: bool = False):
         drho = np.empty(self.N, dtype=self._ft)

@@ -23,6 +23,7 @@
 #include "sphmi_probes.h"
 #include "sphmi_field_grid.h"
 #include "sphmi_particle_fields.h"
+#include "sphmi_neighbor_list.h"
 
 namespace sphmi {
 
@@ -188,6 +189,14 @@ struct EngineBase {
     virtual void sample_grid(const double* origin, const double* spacing, const int64_t* counts, double* weight, int64_t* count, double* pressure,
                              double* density, double* velocity) = 0;
     virtual void particle_fields(int64_t* count, double* shepard, double* normal, double* div_r, double* div_v, double* vorticity) = 0;
+    // The neighbour list (sphmi_neighbor_list.h).  nl_state: whether a built list matches the rows; sphmi_advance, sphmi_upload, the
+    // generator and sphmi_forces_once turn NL_VALID into NL_STALE at the C boundary.
+    enum { NL_NONE = 0, NL_VALID, NL_STALE };
+    int nl_state = NL_NONE;
+    void neighbors_stale() { if (nl_state == NL_VALID) nl_state = NL_STALE; }
+    virtual void neighbors_build(int32_t mode, int64_t* n_rows_out, int64_t* n_pairs_out) = 0;
+    virtual void neighbors_read(int64_t*, int32_t*) { throw EngineError(SPHMI_ERR_STATE, "sphmi_neighbors_read: no neighbour list is held (sphmi_neighbors_build)"); }
+    virtual void neighbors_release() {}
     virtual void unique_cells(int64_t* out, int64_t cap, int64_t* n) = 0;
     virtual void timers(int32_t cap, const char** names, double* secs, int64_t* calls, int32_t* n) = 0;
     virtual void force_stats(int reset, double* avg_ms, int64_t* launches) = 0;
@@ -459,7 +468,7 @@ struct Engine final : EngineBase {
         for (auto& e : host_pinned) (void)hipHostUnregister(e.first);
         (void)hipFree(out_arena);
         (void)hipFree(col_arena); (void)hipFree(col_store); (void)hipFree(col_base[0]); (void)hipFree(col_base[1]);
-        gf_release(); pr_release(); bg_release(); (void)hipFree(fg_arena.p); (void)hipFree(pf_arena.p);
+        gf_release(); pr_release(); bg_release(); (void)hipFree(fg_arena.p); (void)hipFree(pf_arena.p); nl_free();
         (void)hipFree(slot); (void)hipFree(tmp_idx); (void)hipFree(perm);
         for (int k = 0; k < 2; ++k) { (void)hipFree(tile_cost[k]); (void)hipFree(tile_order[k]); }
         (void)hipFree(kout_d); (void)hipFree(tile_work_d); (void)hipFree(tile_work1_d); (void)hipFree(xcd_clock_d); (void)hipHostFree(xcd_clock_h);
@@ -1898,6 +1907,105 @@ struct Engine final : EngineBase {
         HC(hipStreamSynchronize(stream));
     }
 
+    // ---- the neighbour list of every row, on demand (sphmi_neighbor_list.h) -----------------------------------------------------------
+    // Reads the current set's positions, the low words, `cstart` and the grid of the last rebuild; writes its own arena and nothing
+    // else.  The arena: counts [N] int32, tile sums, offsets [N + 1] int64 — they grow with N — and the entries, which grow with the
+    // pair count and go back to the device at sphmi_neighbors_release.  nl_state (EngineBase) tells whether it matches the rows.
+    int *nl_counts = nullptr, *nl_entries = nullptr;
+    long long *nl_offsets = nullptr, *nl_tsum = nullptr;
+    size_t nl_rows_cap = 0, nl_entries_cap = 0;
+    int64_t nl_rows = 0, nl_pairs = 0;
+    void nl_free() {
+        (void)hipFree(nl_counts); (void)hipFree(nl_entries); (void)hipFree(nl_offsets); (void)hipFree(nl_tsum);
+        nl_counts = nl_entries = nullptr; nl_offsets = nl_tsum = nullptr;
+        nl_rows_cap = nl_entries_cap = 0; nl_rows = nl_pairs = 0;
+        nl_state = NL_NONE;
+    }
+    void nl_alloc(void** p, size_t bytes, long long pairs) {
+        if (hipMalloc(p, bytes) == hipSuccess) return;
+        (void)hipGetLastError();
+        *p = nullptr;
+        char buf[200];
+        snprintf(buf, sizeof(buf), "sphmi_neighbors_build: no device memory for the arena of %lld pairs over %d rows (%.2f GB)", pairs, N, (double)bytes / 1e9);
+        throw EngineError(SPHMI_ERR_DEVICE, buf);
+    }
+    void neighbors_build(int32_t mode, int64_t* n_rows_out, int64_t* n_pairs_out) override {
+        require_uploaded("sphmi_neighbors_build");
+        if (mode != SPHMI_NEIGHBORS_FULL && mode != SPHMI_NEIGHBORS_HALF) throw EngineError(SPHMI_ERR_ARGUMENT, "sphmi_neighbors_build: unknown mode");
+        if (!n_pairs_out) throw EngineError(SPHMI_ERR_ARGUMENT, "sphmi_neighbors_build: null n_pairs_out");
+        if (!(cfg.h <= cfg.H)) throw EngineError(SPHMI_ERR_STATE, "sphmi_neighbors_build: handles with H < h are not served (the candidate cells are laid out for H + h <= 2H)");
+        if (!fg_ready()) throw EngineError(SPHMI_ERR_STATE, "sphmi_neighbors_build: the handle has not executed a step since the upload (no cell list)");
+        HC(hipSetDevice(cfg.device));
+        nl_state = NL_NONE; nl_rows = nl_pairs = 0;                        // the result of the build before is gone, whatever happens below
+        const size_t n = (size_t)N;
+        const int ntiles = (N + kNlScanTile - 1) / kNlScanTile;
+        if (n > nl_rows_cap) {
+            nl_free();
+            try {
+                nl_alloc((void**)&nl_counts, n * 4, 0); nl_alloc((void**)&nl_tsum, (size_t)ntiles * 8, 0); nl_alloc((void**)&nl_offsets, (n + 1) * 8, 0);
+            } catch (...) { nl_free(); throw; }
+            nl_rows_cap = n;
+        }
+        NeighborListArgs<T> A{};
+        A.pk0 = pk0[iA]; A.comp = comp[cur]; A.cstart = cstart; A.g = grid;
+        A.counts = nl_counts; A.offsets = nl_offsets;
+        A.H_inv = cfg.H_inv; A.H2 = cfg.H2; A.reach = cfg.H + cfg.h;
+        A.N = N; A.half = mode == SPHMI_NEIGHBORS_HALF ? 1 : 0;
+        // $SPHMI_NEIGHBORS_TIMING=1: the device time of every pass goes to stderr (tools/neighbor_list_cost.py)
+        const bool timing = getenv("SPHMI_NEIGHBORS_TIMING") != nullptr;
+        hipEvent_t ev[4] = {};
+        auto mark = [&](int k) { if (timing) { if (!ev[k]) HC(hipEventCreate(&ev[k])); HC(hipEventRecord(ev[k], stream)); } };
+        auto drop = [&]() { for (auto& e : ev) if (e) { (void)hipEventDestroy(e); e = nullptr; } };
+        try {
+            const unsigned nb = (unsigned)((N + kNlThreads - 1) / kNlThreads);
+            mark(0);
+            if (D == 3) hipLaunchKernelGGL((k_neighbor_count<T, 3>), dim3(nb), dim3(kNlThreads), 0, stream, A);
+            else        hipLaunchKernelGGL((k_neighbor_count<T, 2>), dim3(nb), dim3(kNlThreads), 0, stream, A);
+            mark(1);
+            hipLaunchKernelGGL(k_nl_tile_sums, dim3(ntiles), dim3(kNlScanThreads), 0, stream, (const int*)nl_counts, N, nl_tsum);
+            hipLaunchKernelGGL(k_nl_scan_tiles, dim3(1), dim3(1024), 0, stream, nl_tsum, ntiles, nl_offsets + n);
+            hipLaunchKernelGGL(k_nl_offsets, dim3(ntiles), dim3(kNlScanThreads), 0, stream, (const int*)nl_counts, N, (const long long*)nl_tsum, nl_offsets);
+            HC(hipGetLastError());
+            long long pairs = 0;
+            bounce.d2h(&pairs, nl_offsets + n, 8, stream);                 // (complete on return: the call is synchronous anyway)
+            mark(2);
+            if ((size_t)pairs > nl_entries_cap) {
+                (void)hipFree(nl_entries); nl_entries = nullptr; nl_entries_cap = 0;
+                nl_alloc((void**)&nl_entries, (size_t)pairs * 4, pairs);
+                nl_entries_cap = (size_t)pairs;
+            }
+            A.neighbors = nl_entries;
+            if (pairs > 0) {
+                if (D == 3) hipLaunchKernelGGL((k_neighbor_fill<T, 3>), dim3(nb), dim3(kNlThreads), 0, stream, A);
+                else        hipLaunchKernelGGL((k_neighbor_fill<T, 2>), dim3(nb), dim3(kNlThreads), 0, stream, A);
+                HC(hipGetLastError());
+            }
+            mark(3);
+            HC(hipStreamSynchronize(stream));
+            if (timing) {
+                float ms[3] = {};
+                for (int k = 0; k < 3; ++k) HC(hipEventElapsedTime(&ms[k], ev[k], ev[k + 1]));
+                fprintf(stderr, "sphmi_neighbors_build: %d rows, %lld pairs: count %.3f ms, scan %.3f ms, fill %.3f ms\n", N, pairs, ms[0], ms[1], ms[2]);
+            }
+            drop();
+            nl_rows = N; nl_pairs = pairs; nl_state = NL_VALID;
+        } catch (...) { drop(); throw; }
+        if (n_rows_out) *n_rows_out = nl_rows;
+        *n_pairs_out = nl_pairs;
+    }
+    void neighbors_read(int64_t* offsets_out, int32_t* neighbors_out) override {
+        if (nl_state == NL_STALE) throw EngineError(SPHMI_ERR_STATE, "sphmi_neighbors_read: the neighbour list is stale (rows may have moved since sphmi_neighbors_build)");
+        if (nl_state != NL_VALID) throw EngineError(SPHMI_ERR_STATE, "sphmi_neighbors_read: no neighbour list is held (sphmi_neighbors_build)");
+        HC(hipSetDevice(cfg.device));
+        if (offsets_out) fetch_result(offsets_out, nl_offsets, (size_t)(nl_rows + 1) * 8);
+        if (neighbors_out && nl_pairs > 0) fetch_result(neighbors_out, nl_entries, (size_t)nl_pairs * 4);
+        HC(hipStreamSynchronize(stream));
+    }
+    void neighbors_release() override {
+        HC(hipSetDevice(cfg.device));
+        nl_free();
+    }
+
     // Pressure! + [mDBC] + ONE forces-only neighbour pass on the current cell list; {a, dρ/dt} of every particle held are left
     // in the scratch record array rec[iB] (N contiguous packets), SimParticles.Acceleration survives.  all_lists: a slab
     // engine runs its interior and its slab-edge tiles (the ghost layers must be current: the caller has just rebuilt).
@@ -2310,7 +2418,7 @@ int sphmi_dam_break_3d_count(double dp, int64_t* n_bound_out, int64_t* n_fluid_o
     if (n_fluid_out) *n_fluid_out = (rnd(0.38 / dp) + 1) * (rnd(0.62 / dp) + 1) * (rnd(0.28 / dp) + 1);
     return SPHMI_OK;
 }
-int sphmi_generate_dam_break_3d(sphmi_handle* h, double dp) { SPHMI_GUARD(h, h->e->generate_dam_break_3d(dp)); }
+int sphmi_generate_dam_break_3d(sphmi_handle* h, double dp) { SPHMI_GUARD(h, (h->e->neighbors_stale(), h->e->generate_dam_break_3d(dp))); }
 int sphmi_owned_count(sphmi_handle* h, int64_t* n_out) {
     if (!n_out) return SPHMI_ERR_ARGUMENT;
     SPHMI_GUARD(h, *n_out = h->e->owned_count());
@@ -2412,7 +2520,7 @@ int sphmi_destroy(sphmi_handle* h) {
 int sphmi_upload(sphmi_handle* h, const void* position, const void* velocity, const void* acceleration,
                  const void* density, const uint8_t* type, const int64_t* id, const uint64_t* group_marker,
                  const void* ghost_points) {
-    SPHMI_GUARD(h, (h->e->reset_count(), h->e->upload(position, velocity, acceleration, density, type, id, group_marker, ghost_points)));
+    SPHMI_GUARD(h, (h->e->neighbors_stale(), h->e->reset_count(), h->e->upload(position, velocity, acceleration, density, type, id, group_marker, ghost_points)));
 }
 
 int sphmi_download_begin(sphmi_handle* h, void* position, void* velocity, void* acceleration, void* density,
@@ -2458,6 +2566,11 @@ int sphmi_particle_fields(sphmi_handle* h, int64_t* count_out, double* shepard_o
                           double* vorticity_out) {
     SPHMI_GUARD(h, h->e->particle_fields(count_out, shepard_out, normal_out, div_r_out, div_v_out, vorticity_out));
 }
+int sphmi_neighbors_build(sphmi_handle* h, int32_t mode, int64_t* n_rows_out, int64_t* n_pairs_out) {
+    SPHMI_GUARD(h, h->e->neighbors_build(mode, n_rows_out, n_pairs_out));
+}
+int sphmi_neighbors_read(sphmi_handle* h, int64_t* offsets_out, int32_t* neighbors_out) { SPHMI_GUARD(h, h->e->neighbors_read(offsets_out, neighbors_out)); }
+int sphmi_neighbors_release(sphmi_handle* h) { SPHMI_GUARD(h, h->e->neighbors_release()); }
 int sphmi_group_forces_read(sphmi_handle* h, int64_t capacity, int64_t* iteration_out, double* time_out, double* dt_out, double* force_out,
                             int64_t* n_out, int64_t* n_dropped) {
     SPHMI_GUARD(h, h->e->group_forces_read(capacity, iteration_out, time_out, dt_out, force_out, n_out, n_dropped));
@@ -2478,7 +2591,7 @@ int sphmi_set_clock(sphmi_handle* h, int64_t iteration, double total_time) {
 }
 
 int sphmi_advance(sphmi_handle* h, double t_target, int64_t max_steps, sphmi_progress* out) {
-    SPHMI_GUARD(h, h->e->advance(t_target, max_steps, out));
+    SPHMI_GUARD(h, (h->e->neighbors_stale(), h->e->advance(t_target, max_steps, out)));
 }
 
 int sphmi_download(sphmi_handle* h, void* position, void* velocity, void* acceleration, void* density,
@@ -2489,7 +2602,7 @@ int sphmi_download(sphmi_handle* h, void* position, void* velocity, void* accele
 }
 
 int sphmi_forces_once(sphmi_handle* h, int apply_mdbc, void* drhodt, void* acceleration) {
-    SPHMI_GUARD(h, h->e->forces_once(apply_mdbc, drhodt, acceleration));
+    SPHMI_GUARD(h, (h->e->neighbors_stale(), h->e->forces_once(apply_mdbc, drhodt, acceleration)));
 }
 
 int sphmi_unique_cells(sphmi_handle* h, int64_t* cells_out, int64_t capacity, int64_t* n_out) {

@@ -1791,6 +1791,11 @@ struct MultiEngine final : EngineBase {
         if (rank_mode) throw EngineError(SPHMI_ERR_STATE, "sphmi_particle_fields: single-device handles only (a rank-mode process holds one slab of the rows)");
         throw EngineError(SPHMI_ERR_STATE, "sphmi_particle_fields: single-device handles only (a slab's ghost copies hold the half-step state; the halo exchange this needs is not built)");
     }
+    // The neighbour list (sphmi_neighbor_list.h): single-device handles only, for the same reason.
+    void neighbors_build(int32_t, int64_t*, int64_t*) override {
+        if (rank_mode) throw EngineError(SPHMI_ERR_STATE, "sphmi_neighbors_build: single-device handles only (a rank-mode process holds one slab of the rows)");
+        throw EngineError(SPHMI_ERR_STATE, "sphmi_neighbors_build: single-device handles only (a slab's ghost copies hold the half-step state; the halo exchange this needs is not built)");
+    }
     void download_columns_begin(void* const* columns_out) override {
         require_one_process("sphmi_download_columns");
         if (col_data.empty()) throw EngineError(SPHMI_ERR_STATE, "sphmi_download_columns: no columns attached (sphmi_attach_columns)");

@@ -44,7 +44,7 @@ def RunSimulation(*, SimGeometry=None, SimMetaData: SimulationMetaData, SimConst
                   on_output: Optional[Callable[[SimulationMetaData, SimParticles], None]] = None,
                   device_float_bytes: int = 0, device: int = 0, backend_factory=None,
                   async_output: bool = False, group_forces=None, probes=None, field_grid=None,
-                  particle_fields=None, budgets: bool = False) -> List[float]:
+                  particle_fields=None, budgets: bool = False, neighbor_list: bool = False) -> List[float]:
     """Same keyword signature as the reference (src/SPHCellList.jl:808-817); returns the list of
     time steps the reference collects in ``TimeSteps`` (:823,:884).  ``SimParticles`` is updated in
     place at every output time, in the engine's cell-sorted order, as the reference's is.
@@ -69,6 +69,12 @@ def RunSimulation(*, SimGeometry=None, SimMetaData: SimulationMetaData, SimConst
     receives the dict as one more argument, behind group forces, probes and the field grid when those are on (``None`` at the
     first call).  It is taken at the same point as the snapshot: row i is particle i of that output
     (``sphexample_amd.fields.free_surface_mask`` reads a free surface off ``div_r``).  ``None`` (default): nothing is evaluated
+    and the callback keeps its arguments.
+
+    ``neighbor_list=True``: at every output the CSR neighbour list of ``Backend.neighbor_list`` is built on the device and
+    ``on_output`` receives ``(offsets, neighbors)`` as one more argument, behind the differential fields and before the budgets
+    (``None`` at the first call).  It is taken at the same point as the snapshot, with no step between it and the download: row i
+    is particle i of that output (``sphexample_amd.neighbors`` forms pair sums from it).  ``False`` (default): nothing is built
     and the callback keeps its arguments.
 
     ``budgets=True``: the energy, momentum and extent budgets of the fluid are recorded on the device at every step
@@ -118,6 +124,8 @@ def RunSimulation(*, SimGeometry=None, SimMetaData: SimulationMetaData, SimConst
     if particle_fields is not None:
         names = tuple(particle_fields)
         extras.append((None, lambda: eng.particle_fields(names)))                # (the rows of this output: no step lies between it and the download)
+    if neighbor_list:
+        extras.append((None, lambda: eng.neighbor_list()))                       # (the rows of this output, like the fields above)
     if budgets:
         eng.budgets_enable(capacity=1 << 20)
         extras.append((empty_budgets(), eng.budgets_read))
