@@ -505,6 +505,52 @@ int sphmi_neighbors_build(sphmi_handle* h, int32_t mode, int64_t* n_rows_out, in
 int sphmi_neighbors_read(sphmi_handle* h, int64_t* offsets_out /* [n_rows + 1] */, int32_t* neighbors_out /* [n_pairs] */);
 int sphmi_neighbors_release(sphmi_handle* h);
 
+/*
+ * The free surface as GEOMETRY, extracted on the device on demand: the surface S = level of the Shepard sum of sphmi_sample_grid's
+ * lattice - about 1 in the fluid, 1/2 at the surface, 0 in air - as a triangle mesh (3-D handles) or a contour polyline (2-D handles):
+ * an overturning wave, a splash, a cavity behind an obstacle, which a height map cannot hold (csrc/sphmi_isosurface.h,
+ * csrc/sphmi_iso_core.h).  Only the mesh crosses the bus; nothing of S does.
+ *   sphmi_isosurface_build is synchronous and called between sphmi_advance calls like sphmi_sample_grid, with the same lattice
+ *   arguments; it changes no state a later step, download, column download, series read, sphmi_sample_grid, sphmi_particle_fields or
+ *   neighbour list reads, and leaves a download begun with sphmi_download_begin alone.
+ *   Node n is INSIDE iff S[n] >= level.  Every cell - named by its lowest node, x fastest - is cut into D! Kuhn simplices along its main
+ *   diagonal: for an axis permutation p, w_0 = the lowest corner, w_k = w_(k-1) + e_p(k); neighbouring cells agree on every face
+ *   diagonal, so the surface is watertight by construction.  A lattice with a count of 1 along an axis has no cells: an empty mesh.
+ *   Edges: node a to b = a + m, m in 1 .. 2^D - 1 a bitmask of unit steps (bit d: a step along axis d); a owns the edge in slot m - 1;
+ *   it exists if b is on the lattice and crosses iff exactly one end is inside.
+ *   Vertices: one per crossing edge, at x_a + t (x_b - x_a) with t = (level - S_a) / (S_b - S_a), always from the owner a, the node
+ *   coordinates formed as sphmi_sample_grid forms them, every operation in fp64 and rounded once (not fused): a host forms the same
+ *   doubles.  Order: owner ascending, then slot ascending.  vertices_out is [n_vertices x 3]; 2-D handles: an exact zero third component.
+ *   Elements: int32 triples (3-D) or pairs (2-D) of vertex indices; cell ascending, within a cell the simplices in the lexicographic
+ *   order of p, within a simplex (corners named by their position 0 .. D in w):
+ *     3-D, one corner inside or one corner outside: that corner a; the triangle of the edges (a, b), b != a ascending.
+ *     3-D, two inside a < b, two outside c < d: the triangles [(a,c), (a,d), (b,d)] and then [(a,c), (b,d), (b,c)].
+ *     In every 3-D case the first vertex stays and the other two are swapped where needed so that the normal (v1 - v0) x (v2 - v0)
+ *     points from the inside corners to the outside ones, out of the fluid.
+ *     2-D: the segment between the two crossing edges, directed so that the inside lies to its left.
+ *   Degenerate elements (t = 0: a node exactly at the level) are legal and kept.  No hash table and no atomics place a vertex or an
+ *   element: repeated calls give the same bytes.
+ *   Attributes: pressure_out [n_vertices] and velocity_out [n_vertices x 3] are A_a + t (A_b - A_a), the same t, not fused, of the means
+ *   SP / S and Sv / S sphmi_sample_grid delivers (one division each, 0 where n == 0); if exactly one end has n == 0 the other end's
+ *   mean is taken unmixed.  They are always formed at the build (4 doubles per vertex); the read delivers what is asked for.
+ *   The result stays in a device arena of its own until the next build, sphmi_isosurface_release (which gives the memory back) or
+ *   sphmi_destroy; a later sphmi_sample_grid does not touch it.  sphmi_advance, sphmi_upload, sphmi_generate_dam_break_3d and
+ *   sphmi_forces_once mark it stale: rows may have moved.  sphmi_isosurface_read copies the mesh to host arrays; any pointer may be NULL.
+ *   SPHMI_ERR_STATE: before the upload; before the handle has executed its first step since the upload or generator (no cell list, no
+ *     half-step set); handles with H < h; rank-mode handles; multi-device handles (single-device handles only: a multi-device handle
+ *     adds the slabs' lattice sums on the host, no device holds S); sphmi_isosurface_read without a build, or of a stale or released
+ *     result.
+ *   SPHMI_ERR_ARGUMENT: everything sphmi_sample_grid reports of a lattice; a level that is not finite and positive; a null
+ *     n_vertices_out or n_elements_out.
+ *   SPHMI_ERR_DEVICE: the device cannot hold the arena (25 bytes per node, 56 per vertex, 4 D per element); the message gives the
+ *     counts and the bytes, and the handle stays usable.
+ */
+int sphmi_isosurface_build(sphmi_handle* h, const double* origin, const double* spacing, const int64_t* counts,
+                           double level, int64_t* n_vertices_out, int64_t* n_elements_out);
+int sphmi_isosurface_read(sphmi_handle* h, double* vertices_out /* [nv x 3] */, int32_t* elements_out /* [ne x dims] */,
+                          double* pressure_out /* [nv] */, double* velocity_out /* [nv x 3] */);
+int sphmi_isosurface_release(sphmi_handle* h);
+
 #ifdef __cplusplus
 }
 #endif

@@ -192,6 +192,22 @@ function neighbor_list(P; half::Bool = false)
     check(h, ccall((:sphmi_neighbors_release, LIB), Cint, (Ptr{Cvoid},), h))
     return (offsets = offsets, neighbors = neighbors)
 end
+# The free surface as a mesh on the state the session holds NOW (sphmi_isosurface_build / _read / _release): the surface S == level of
+# the Shepard sum on the lattice sample_grid takes.  vertices is 3 × nv, elements D × ne — triangles in 3-D (normals out of the fluid),
+# segments in 2-D (the fluid to the left) — with the library's RAW 0-BASED vertex indices; pressure [nv] and velocity 3 × nv are the
+# lattice means interpolated to the vertices.  Single-device sessions; from an output callback, after the first step.
+function isosurface(P, origin::Vector{Float64}, spacing::Vector{Float64}, counts::Vector{Int64}; level::Float64 = 0.5)
+    h = SESSIONS[P].h
+    nv = Ref{Int64}(0); ne = Ref{Int64}(0)
+    GC.@preserve origin spacing counts check(h, ccall((:sphmi_isosurface_build, LIB), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Int64}, Float64, Ref{Int64}, Ref{Int64}),
+                                                       h, pointer(origin), pointer(spacing), pointer(counts), level, nv, ne))
+    vertices = Matrix{Float64}(undef, 3, nv[]); elements = Matrix{Int32}(undef, length(counts), ne[])
+    pp = Vector{Float64}(undef, nv[]); v = Matrix{Float64}(undef, 3, nv[])
+    GC.@preserve vertices elements pp v check(h, ccall((:sphmi_isosurface_read, LIB), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Int32}, Ptr{Float64}, Ptr{Float64}),
+                                                        h, pointer(vertices), pointer(elements), pointer(pp), pointer(v)))
+    check(h, ccall((:sphmi_isosurface_release, LIB), Cint, (Ptr{Cvoid},), h))
+    return (vertices = vertices, elements = elements, pressure = pp, velocity = v)
+end
 atexit(() -> foreach(s -> ccall((:sphmi_destroy, LIB), Cint, (Ptr{Cvoid},), s.h), values(SESSIONS)))
 
 function check(h, rc)

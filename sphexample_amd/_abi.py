@@ -533,6 +533,64 @@ class Backend:
         finally:
             self.neighbors_release()
 
+    # -- the free surface as a mesh, on demand (sphmi_isosurface_build / _read / _release) ---------------------------------------
+    def has_isosurface(self) -> bool:
+        return all(self._has(n) for n in ("isosurface_build", "isosurface_read", "isosurface_release"))
+
+    def isosurface_build(self, origin, spacing, counts, level: float = 0.5):
+        """Sample the Shepard sum on the lattice of `sample_grid` and extract the surface ``S == level`` on the device, where it
+        stays: (n_vertices, n_elements).  It is held until the next build, `isosurface_release` or `close`; a step, an upload or
+        `forces_once` marks it stale."""
+        D = self.D
+        o = np.ascontiguousarray(origin, dtype=np.float64).reshape(-1)
+        s = np.ascontiguousarray(spacing, dtype=np.float64).reshape(-1)
+        c = np.ascontiguousarray(counts, dtype=np.int64).reshape(-1)
+        if not (len(o) == len(s) == len(c) == D):
+            raise ValueError(f"isosurface_build: origin, spacing and counts hold {D} entries each")
+        f = self._fn("isosurface_build")
+        f.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+        nv, ne = C.c_int64(), C.c_int64()
+        self._isosurface_shape = None                                             # (a refused build leaves nothing this object may read)
+        self._check(f(self._h, _ptr(o), _ptr(s), _ptr(c), float(level), C.byref(nv), C.byref(ne)))
+        self._isosurface_shape = (nv.value, ne.value)
+        return self._isosurface_shape
+
+    def isosurface_read(self, vertices: bool = True, elements: bool = True, pressure: bool = False, velocity: bool = False):
+        """(vertices float64 [nv, 3], elements int32 [ne, D], pressure [nv], velocity [nv, 3]) of the mesh built last; False skips
+        one (None in its place).  sphmi_isosurface_read takes no capacities: the arrays are sized from what THIS object's
+        `isosurface_build` reported, so a mesh built through the raw entry point behind its back must not be read here."""
+        f = self._fn("isosurface_read")
+        f.argtypes = [C.c_void_p] * 5
+        shape = getattr(self, "_isosurface_shape", None)
+        if shape is None:
+            self._check(f(self._h, None, None, None, None))                        # the library words the refusal
+            raise RuntimeError("isosurface_read: the handle holds a mesh this object did not build; call isosurface_build first")
+        nv, ne = shape
+        out = (np.zeros((nv, 3)) if vertices else None, np.zeros((ne, self.D), dtype=np.int32) if elements else None,
+               np.zeros(nv) if pressure else None, np.zeros((nv, 3)) if velocity else None)
+        self._check(f(self._h, *[_ptr(a) for a in out]))
+        return out
+
+    def isosurface_release(self) -> None:
+        f = self._fn("isosurface_release")
+        f.argtypes = [C.c_void_p]
+        self._check(f(self._h))
+        self._isosurface_shape = None
+
+    def isosurface(self, origin, spacing, counts, level: float = 0.5, attributes: bool = False):
+        """The free surface as a mesh, evaluated now: ``(vertices [nv, 3], elements [ne, D] int32)`` — triangles on 3-D handles,
+        the segments of a contour polyline on 2-D handles (a zero third coordinate), normals out of the fluid / the fluid to the
+        left — of the surface ``S == level`` of the Shepard sum on the lattice `sample_grid` takes; `attributes` adds the pressure
+        [nv] and velocity [nv, 3] interpolated to the vertices.  `sphexample_amd.isosurface` restates the extraction in numpy and
+        measures the result.  Single-device handles; call it between `advance` calls, after the first executed step.  The device
+        memory is given back before it returns."""
+        self.isosurface_build(origin, spacing, counts, level)
+        try:
+            got = self.isosurface_read(pressure=attributes, velocity=attributes)
+            return got if attributes else got[:2]
+        finally:
+            self.isosurface_release()
+
     def forces_once(self, apply_mdbc: bool = False):
         drho = np.empty(self.N, dtype=self._ft)
         acc = np.empty((self.N, self.D), dtype=self._ft)

@@ -24,6 +24,7 @@
 #include "sphmi_field_grid.h"
 #include "sphmi_particle_fields.h"
 #include "sphmi_neighbor_list.h"
+#include "sphmi_isosurface.h"
 
 namespace sphmi {
 
@@ -197,6 +198,12 @@ struct EngineBase {
     virtual void neighbors_build(int32_t mode, int64_t* n_rows_out, int64_t* n_pairs_out) = 0;
     virtual void neighbors_read(int64_t*, int32_t*) { throw EngineError(SPHMI_ERR_STATE, "sphmi_neighbors_read: no neighbour list is held (sphmi_neighbors_build)"); }
     virtual void neighbors_release() {}
+    // The free surface as a mesh (sphmi_isosurface.h): the same lifetime, the same calls mark it stale.
+    int iso_state = NL_NONE;
+    void results_stale() { neighbors_stale(); if (iso_state == NL_VALID) iso_state = NL_STALE; }
+    virtual void isosurface_build(const double* origin, const double* spacing, const int64_t* counts, double level, int64_t* n_vertices_out, int64_t* n_elements_out) = 0;
+    virtual void isosurface_read(double*, int32_t*, double*, double*) { throw EngineError(SPHMI_ERR_STATE, "sphmi_isosurface_read: no mesh is held (sphmi_isosurface_build)"); }
+    virtual void isosurface_release() {}
     virtual void unique_cells(int64_t* out, int64_t cap, int64_t* n) = 0;
     virtual void timers(int32_t cap, const char** names, double* secs, int64_t* calls, int32_t* n) = 0;
     virtual void force_stats(int reset, double* avg_ms, int64_t* launches) = 0;
@@ -468,7 +475,7 @@ struct Engine final : EngineBase {
         for (auto& e : host_pinned) (void)hipHostUnregister(e.first);
         (void)hipFree(out_arena);
         (void)hipFree(col_arena); (void)hipFree(col_store); (void)hipFree(col_base[0]); (void)hipFree(col_base[1]);
-        gf_release(); pr_release(); bg_release(); (void)hipFree(fg_arena.p); (void)hipFree(pf_arena.p); nl_free();
+        gf_release(); pr_release(); bg_release(); (void)hipFree(fg_arena.p); (void)hipFree(pf_arena.p); nl_free(); iso_free();
         (void)hipFree(slot); (void)hipFree(tmp_idx); (void)hipFree(perm);
         for (int k = 0; k < 2; ++k) { (void)hipFree(tile_cost[k]); (void)hipFree(tile_order[k]); }
         (void)hipFree(kout_d); (void)hipFree(tile_work_d); (void)hipFree(tile_work1_d); (void)hipFree(xcd_clock_d); (void)hipHostFree(xcd_clock_h);
@@ -2006,6 +2013,135 @@ struct Engine final : EngineBase {
         nl_free();
     }
 
+    // ---- the free surface as a mesh, on demand (sphmi_isosurface.h) -----------------------------------------------------------------
+    // Samples the lattice with fg_launch into fg_arena — nothing of S goes to the host — and extracts the mesh of S = level into an
+    // arena of its own, which holds everything a read needs: a later sphmi_sample_grid may reuse fg_arena.  Per node: the two bytes,
+    // the two counts and the two offset arrays (they grow with the lattice); the vertices, their attributes and the elements grow
+    // with the mesh and go back to the device at sphmi_isosurface_release.  iso_state (EngineBase) tells whether it matches the rows.
+    unsigned char *iso_mask = nullptr, *iso_corners = nullptr;
+    int *iso_vcount = nullptr, *iso_ecount = nullptr, *iso_elements = nullptr;
+    long long *iso_voff = nullptr, *iso_eoff = nullptr, *iso_tsum = nullptr;
+    double* iso_vertices = nullptr;            // [nv × 3], then the pressure [nv], then the velocity [nv × 3]
+    size_t iso_nodes_cap = 0, iso_vertices_cap = 0, iso_elements_cap = 0;
+    int64_t iso_nv = 0, iso_ne = 0;
+    void iso_free() {
+        (void)hipFree(iso_mask); (void)hipFree(iso_corners); (void)hipFree(iso_vcount); (void)hipFree(iso_ecount); (void)hipFree(iso_elements);
+        (void)hipFree(iso_voff); (void)hipFree(iso_eoff); (void)hipFree(iso_tsum); (void)hipFree(iso_vertices);
+        iso_mask = iso_corners = nullptr; iso_vcount = iso_ecount = iso_elements = nullptr; iso_voff = iso_eoff = iso_tsum = nullptr; iso_vertices = nullptr;
+        iso_nodes_cap = iso_vertices_cap = iso_elements_cap = 0; iso_nv = iso_ne = 0;
+        iso_state = NL_NONE;
+    }
+    void iso_alloc(void** p, size_t bytes, long long nodes, long long nv, long long ne) {
+        if (hipMalloc(p, std::max<size_t>(bytes, 8)) == hipSuccess) return;
+        (void)hipGetLastError();
+        *p = nullptr;
+        char buf[240];
+        snprintf(buf, sizeof(buf), "sphmi_isosurface_build: no device memory for the arena of %lld vertices and %lld elements over %lld nodes (%.2f GB)", nv, ne, nodes, (double)bytes / 1e9);
+        throw EngineError(SPHMI_ERR_DEVICE, buf);
+    }
+    void isosurface_build(const double* origin, const double* spacing, const int64_t* counts, double level, int64_t* n_vertices_out, int64_t* n_elements_out) override {
+        require_uploaded("sphmi_isosurface_build");
+        if (!(cfg.h <= cfg.H)) throw EngineError(SPHMI_ERR_STATE, "sphmi_isosurface_build: handles with H < h are not served (the candidate cells are laid out for H + h <= 2H)");
+        if (!fg_ready()) throw EngineError(SPHMI_ERR_STATE, "sphmi_isosurface_build: the handle has not executed a step since the upload (no cell list, no half-step set)");
+        const int64_t nodes = check_grid_lattice(origin, spacing, counts, D);
+        if (!std::isfinite(level) || !(level > 0.0)) throw EngineError(SPHMI_ERR_ARGUMENT, "sphmi_isosurface_build: the level must be finite and positive");
+        if (!n_vertices_out || !n_elements_out) throw EngineError(SPHMI_ERR_ARGUMENT, "sphmi_isosurface_build: null n_vertices_out or n_elements_out");
+        HC(hipSetDevice(cfg.device));
+        iso_state = NL_NONE; iso_nv = iso_ne = 0;                          // the mesh of the build before is gone, whatever happens below
+        const size_t n = (size_t)nodes;
+        const int ntiles = (int)((nodes + kNlScanTile - 1) / kNlScanTile);
+        // $SPHMI_ISOSURFACE_TIMING: the device time of every pass goes to stderr (tools/isosurface_cost.py)
+        const bool timing = getenv("SPHMI_ISOSURFACE_TIMING") != nullptr;
+        hipEvent_t ev[6] = {};
+        auto mark = [&](int k) { if (timing) { if (!ev[k]) HC(hipEventCreate(&ev[k])); HC(hipEventRecord(ev[k], stream)); } };
+        auto drop = [&]() { for (auto& e : ev) if (e) { (void)hipEventDestroy(e); e = nullptr; } };
+        try {
+            mark(0);
+            fg_launch(origin, spacing, counts, nodes);
+            mark(1);
+            if (n > iso_nodes_cap) {
+                iso_free();
+                try {
+                    iso_alloc((void**)&iso_mask, n, nodes, 0, 0); iso_alloc((void**)&iso_corners, n, nodes, 0, 0);
+                    iso_alloc((void**)&iso_vcount, n * 4, nodes, 0, 0); iso_alloc((void**)&iso_ecount, n * 4, nodes, 0, 0);
+                    iso_alloc((void**)&iso_voff, (n + 1) * 8, nodes, 0, 0); iso_alloc((void**)&iso_eoff, (n + 1) * 8, nodes, 0, 0);
+                    iso_alloc((void**)&iso_tsum, (size_t)ntiles * 8, nodes, 0, 0);
+                } catch (...) { iso_free(); throw; }
+                iso_nodes_cap = n;
+            }
+            IsoArgs A{};
+            A.sums = fg_arena.p;
+            for (int d = 0; d < 3; ++d) { A.origin[d] = d < D ? origin[d] : 0.0; A.spacing[d] = d < D ? spacing[d] : 1.0; A.counts[d] = d < D ? (int)counts[d] : 1; }
+            A.level = level; A.nodes = (int)nodes;
+            A.mask = iso_mask; A.corners = iso_corners; A.vcount = iso_vcount; A.ecount = iso_ecount; A.voff = iso_voff; A.eoff = iso_eoff;
+            const unsigned nb = (unsigned)((nodes + kIsoThreads - 1) / kIsoThreads);
+            if (D == 3) hipLaunchKernelGGL(k_iso_classify<3>, dim3(nb), dim3(kIsoThreads), 0, stream, A);
+            else        hipLaunchKernelGGL(k_iso_classify<2>, dim3(nb), dim3(kIsoThreads), 0, stream, A);
+            mark(2);
+            for (int pass = 0; pass < 2; ++pass) {
+                const int* cnt = pass ? iso_ecount : iso_vcount;
+                long long* off = pass ? iso_eoff : iso_voff;
+                hipLaunchKernelGGL(k_nl_tile_sums, dim3(ntiles), dim3(kNlScanThreads), 0, stream, cnt, (int)nodes, iso_tsum);
+                hipLaunchKernelGGL(k_nl_scan_tiles, dim3(1), dim3(1024), 0, stream, iso_tsum, ntiles, off + n);
+                hipLaunchKernelGGL(k_nl_offsets, dim3(ntiles), dim3(kNlScanThreads), 0, stream, cnt, (int)nodes, (const long long*)iso_tsum, off);
+            }
+            HC(hipGetLastError());
+            long long nv = 0, ne = 0;
+            bounce.d2h(&nv, iso_voff + n, 8, stream);                      // (complete on return: the call is synchronous anyway)
+            bounce.d2h(&ne, iso_eoff + n, 8, stream);
+            mark(3);
+            if ((size_t)nv > iso_vertices_cap) {
+                (void)hipFree(iso_vertices); iso_vertices = nullptr; iso_vertices_cap = 0;
+                iso_alloc((void**)&iso_vertices, (size_t)nv * 7 * 8, nodes, nv, ne);
+                iso_vertices_cap = (size_t)nv;
+            }
+            if ((size_t)ne > iso_elements_cap) {
+                (void)hipFree(iso_elements); iso_elements = nullptr; iso_elements_cap = 0;
+                iso_alloc((void**)&iso_elements, (size_t)ne * D * 4, nodes, nv, ne);
+                iso_elements_cap = (size_t)ne;
+            }
+            A.vertices = iso_vertices; A.pressure = iso_vertices + 3 * (size_t)nv; A.velocity = iso_vertices + 4 * (size_t)nv; A.elements = iso_elements;
+            if (nv > 0) {
+                if (D == 3) hipLaunchKernelGGL(k_iso_vertices<3>, dim3(nb), dim3(kIsoThreads), 0, stream, A);
+                else        hipLaunchKernelGGL(k_iso_vertices<2>, dim3(nb), dim3(kIsoThreads), 0, stream, A);
+            }
+            mark(4);
+            if (ne > 0) {
+                if (D == 3) hipLaunchKernelGGL(k_iso_elements<3>, dim3(nb), dim3(kIsoThreads), 0, stream, A);
+                else        hipLaunchKernelGGL(k_iso_elements<2>, dim3(nb), dim3(kIsoThreads), 0, stream, A);
+            }
+            HC(hipGetLastError());
+            mark(5);
+            HC(hipStreamSynchronize(stream));
+            if (timing) {
+                float ms[5] = {};
+                for (int k = 0; k < 5; ++k) HC(hipEventElapsedTime(&ms[k], ev[k], ev[k + 1]));
+                fprintf(stderr, "sphmi_isosurface_build: %lld nodes, %lld vertices, %lld elements: sample %.3f ms, classify %.3f ms, scans %.3f ms, vertices %.3f ms, elements %.3f ms\n",
+                        (long long)nodes, nv, ne, ms[0], ms[1], ms[2], ms[3], ms[4]);
+            }
+            drop();
+            iso_nv = nv; iso_ne = ne; iso_state = NL_VALID;
+        } catch (...) { drop(); throw; }
+        *n_vertices_out = iso_nv; *n_elements_out = iso_ne;
+    }
+    void isosurface_read(double* vertices_out, int32_t* elements_out, double* pressure_out, double* velocity_out) override {
+        if (iso_state == NL_STALE) throw EngineError(SPHMI_ERR_STATE, "sphmi_isosurface_read: the mesh is stale (rows may have moved since sphmi_isosurface_build)");
+        if (iso_state != NL_VALID) throw EngineError(SPHMI_ERR_STATE, "sphmi_isosurface_read: no mesh is held (sphmi_isosurface_build)");
+        HC(hipSetDevice(cfg.device));
+        const size_t nv = (size_t)iso_nv;
+        if (nv > 0) {
+            if (vertices_out) fetch_result(vertices_out, iso_vertices, nv * 3 * 8);
+            if (pressure_out) fetch_result(pressure_out, iso_vertices + 3 * nv, nv * 8);
+            if (velocity_out) fetch_result(velocity_out, iso_vertices + 4 * nv, nv * 3 * 8);
+        }
+        if (elements_out && iso_ne > 0) fetch_result(elements_out, iso_elements, (size_t)iso_ne * D * 4);
+        HC(hipStreamSynchronize(stream));
+    }
+    void isosurface_release() override {
+        HC(hipSetDevice(cfg.device));
+        iso_free();
+    }
+
     // Pressure! + [mDBC] + ONE forces-only neighbour pass on the current cell list; {a, dρ/dt} of every particle held are left
     // in the scratch record array rec[iB] (N contiguous packets), SimParticles.Acceleration survives.  all_lists: a slab
     // engine runs its interior and its slab-edge tiles (the ghost layers must be current: the caller has just rebuilt).
@@ -2418,7 +2554,7 @@ int sphmi_dam_break_3d_count(double dp, int64_t* n_bound_out, int64_t* n_fluid_o
     if (n_fluid_out) *n_fluid_out = (rnd(0.38 / dp) + 1) * (rnd(0.62 / dp) + 1) * (rnd(0.28 / dp) + 1);
     return SPHMI_OK;
 }
-int sphmi_generate_dam_break_3d(sphmi_handle* h, double dp) { SPHMI_GUARD(h, (h->e->neighbors_stale(), h->e->generate_dam_break_3d(dp))); }
+int sphmi_generate_dam_break_3d(sphmi_handle* h, double dp) { SPHMI_GUARD(h, (h->e->results_stale(), h->e->generate_dam_break_3d(dp))); }
 int sphmi_owned_count(sphmi_handle* h, int64_t* n_out) {
     if (!n_out) return SPHMI_ERR_ARGUMENT;
     SPHMI_GUARD(h, *n_out = h->e->owned_count());
@@ -2520,7 +2656,7 @@ int sphmi_destroy(sphmi_handle* h) {
 int sphmi_upload(sphmi_handle* h, const void* position, const void* velocity, const void* acceleration,
                  const void* density, const uint8_t* type, const int64_t* id, const uint64_t* group_marker,
                  const void* ghost_points) {
-    SPHMI_GUARD(h, (h->e->neighbors_stale(), h->e->reset_count(), h->e->upload(position, velocity, acceleration, density, type, id, group_marker, ghost_points)));
+    SPHMI_GUARD(h, (h->e->results_stale(), h->e->reset_count(), h->e->upload(position, velocity, acceleration, density, type, id, group_marker, ghost_points)));
 }
 
 int sphmi_download_begin(sphmi_handle* h, void* position, void* velocity, void* acceleration, void* density,
@@ -2558,6 +2694,7 @@ int sphmi_probes_read(sphmi_handle* h, int64_t capacity, int64_t* iteration_out,
     SPHMI_GUARD(h, h->e->probes_read(capacity, iteration_out, time_out, dt_out, weight_out, count_out, pressure_out, density_out, velocity_out, n_out, n_dropped));
 }
 static_assert(SPHMI_MAX_GRID_NODES == sphmi::kMaxGridNodes, "sphmi_series.h and sphmi.h disagree");
+static_assert(7ll * SPHMI_MAX_GRID_NODES < (1ll << 31) && 12ll * SPHMI_MAX_GRID_NODES < (1ll << 31), "sphmi_isosurface_build: the vertices (at most 7 per node) and the elements (at most 12 per cell) fit int32 indices");
 int sphmi_sample_grid(sphmi_handle* h, const double* origin, const double* spacing, const int64_t* counts, double* weight_out, int64_t* count_out,
                       double* pressure_out, double* density_out, double* velocity_out) {
     SPHMI_GUARD(h, h->e->sample_grid(origin, spacing, counts, weight_out, count_out, pressure_out, density_out, velocity_out));
@@ -2571,6 +2708,14 @@ int sphmi_neighbors_build(sphmi_handle* h, int32_t mode, int64_t* n_rows_out, in
 }
 int sphmi_neighbors_read(sphmi_handle* h, int64_t* offsets_out, int32_t* neighbors_out) { SPHMI_GUARD(h, h->e->neighbors_read(offsets_out, neighbors_out)); }
 int sphmi_neighbors_release(sphmi_handle* h) { SPHMI_GUARD(h, h->e->neighbors_release()); }
+int sphmi_isosurface_build(sphmi_handle* h, const double* origin, const double* spacing, const int64_t* counts, double level, int64_t* n_vertices_out,
+                           int64_t* n_elements_out) {
+    SPHMI_GUARD(h, h->e->isosurface_build(origin, spacing, counts, level, n_vertices_out, n_elements_out));
+}
+int sphmi_isosurface_read(sphmi_handle* h, double* vertices_out, int32_t* elements_out, double* pressure_out, double* velocity_out) {
+    SPHMI_GUARD(h, h->e->isosurface_read(vertices_out, elements_out, pressure_out, velocity_out));
+}
+int sphmi_isosurface_release(sphmi_handle* h) { SPHMI_GUARD(h, h->e->isosurface_release()); }
 int sphmi_group_forces_read(sphmi_handle* h, int64_t capacity, int64_t* iteration_out, double* time_out, double* dt_out, double* force_out,
                             int64_t* n_out, int64_t* n_dropped) {
     SPHMI_GUARD(h, h->e->group_forces_read(capacity, iteration_out, time_out, dt_out, force_out, n_out, n_dropped));
@@ -2591,7 +2736,7 @@ int sphmi_set_clock(sphmi_handle* h, int64_t iteration, double total_time) {
 }
 
 int sphmi_advance(sphmi_handle* h, double t_target, int64_t max_steps, sphmi_progress* out) {
-    SPHMI_GUARD(h, (h->e->neighbors_stale(), h->e->advance(t_target, max_steps, out)));
+    SPHMI_GUARD(h, (h->e->results_stale(), h->e->advance(t_target, max_steps, out)));
 }
 
 int sphmi_download(sphmi_handle* h, void* position, void* velocity, void* acceleration, void* density,
@@ -2602,7 +2747,7 @@ int sphmi_download(sphmi_handle* h, void* position, void* velocity, void* accele
 }
 
 int sphmi_forces_once(sphmi_handle* h, int apply_mdbc, void* drhodt, void* acceleration) {
-    SPHMI_GUARD(h, (h->e->neighbors_stale(), h->e->forces_once(apply_mdbc, drhodt, acceleration)));
+    SPHMI_GUARD(h, (h->e->results_stale(), h->e->forces_once(apply_mdbc, drhodt, acceleration)));
 }
 
 int sphmi_unique_cells(sphmi_handle* h, int64_t* cells_out, int64_t capacity, int64_t* n_out) {

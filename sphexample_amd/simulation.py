@@ -44,7 +44,7 @@ def RunSimulation(*, SimGeometry=None, SimMetaData: SimulationMetaData, SimConst
                   on_output: Optional[Callable[[SimulationMetaData, SimParticles], None]] = None,
                   device_float_bytes: int = 0, device: int = 0, backend_factory=None,
                   async_output: bool = False, group_forces=None, probes=None, field_grid=None,
-                  particle_fields=None, budgets: bool = False, neighbor_list: bool = False) -> List[float]:
+                  particle_fields=None, budgets: bool = False, neighbor_list: bool = False, isosurface=None) -> List[float]:
     """Same keyword signature as the reference (src/SPHCellList.jl:808-817); returns the list of
     time steps the reference collects in ``TimeSteps`` (:823,:884).  ``SimParticles`` is updated in
     place at every output time, in the engine's cell-sorted order, as the reference's is.
@@ -76,6 +76,11 @@ def RunSimulation(*, SimGeometry=None, SimMetaData: SimulationMetaData, SimConst
     (``None`` at the first call).  It is taken at the same point as the snapshot, with no step between it and the download: row i
     is particle i of that output (``sphexample_amd.neighbors`` forms pair sums from it).  ``False`` (default): nothing is built
     and the callback keeps its arguments.
+
+    ``isosurface=(origin, spacing, counts[, level])``: at every output the free surface is extracted on the device as a mesh
+    (``Backend.isosurface`` on that lattice, level 0.5 unless given; ``sphexample_amd.isosurface`` measures it) and ``on_output``
+    receives ``(vertices, elements)`` as one more argument, behind the neighbour list and before the budgets (``None`` at the
+    first call), the way ``field_grid=`` hands over its fields.  ``None`` (default): nothing is extracted.
 
     ``budgets=True``: the energy, momentum and extent budgets of the fluid are recorded on the device at every step
     (``Backend.budgets_enable``; ``sphexample_amd.budgets`` adds up a total energy and reads a wave front off the box) and
@@ -126,6 +131,9 @@ def RunSimulation(*, SimGeometry=None, SimMetaData: SimulationMetaData, SimConst
         extras.append((None, lambda: eng.particle_fields(names)))                # (the rows of this output: no step lies between it and the download)
     if neighbor_list:
         extras.append((None, lambda: eng.neighbor_list()))                       # (the rows of this output, like the fields above)
+    if isosurface is not None:
+        surface = tuple(isosurface)
+        extras.append((None, lambda: eng.isosurface(*surface)))                  # (the state of this output, like the field grid)
     if budgets:
         eng.budgets_enable(capacity=1 << 20)
         extras.append((empty_budgets(), eng.budgets_read))
