@@ -551,6 +551,40 @@ int sphmi_isosurface_read(sphmi_handle* h, double* vertices_out /* [nv x 3] */, 
                           double* pressure_out /* [nv] */, double* velocity_out /* [nv x 3] */);
 int sphmi_isosurface_release(sphmi_handle* h);
 
+/*
+ * The connected bodies of the fluid, labelled on the device on demand: which rows still belong to the main body of water and which are
+ * spray - droplet count, size distribution, the mass detached from the bulk - without a connected-components search on the host
+ * (csrc/sphmi_components.h).
+ *   sphmi_components_build is synchronous and called between sphmi_advance calls like sphmi_neighbors_build; it changes no state a later
+ *   step, download, column download, series read, sphmi_sample_grid, sphmi_particle_fields, neighbour list or mesh reads, and leaves a
+ *   download begun with sphmi_download_begin alone.  n_rows = sphmi_owned_count rows; row i is row i of what sphmi_download delivers now.
+ *   Rows: a row is SELECTED iff bit Type of type_mask is set - Fluid = 1, Fixed = 2, Moving = 3: 1u << 1 selects the fluid.
+ *   Edges: two selected rows i != j are linked iff r^2 = ((dx^2 + dy^2) + dz^2) <= link * link, the product formed once on the host in
+ *   fp64; r^2 exactly as the neighbour list forms it - on the Position doubles sphmi_download would deliver now (fp32 handles: record +
+ *   low word), term by term, not fused, inclusive, however stale the cell list.  Coincident rows are linked.
+ *   Components: a component is a connected set of selected rows; its FIRST ROW is its smallest row index; components are numbered
+ *   0 .. C - 1 in ascending first row.
+ *   Outputs: label_out[i] is the component number of row i, or -1 if row i is not selected; first_row_out[c] the component's first row;
+ *   count_out[c] its number of rows; box_out[c] = { min x, min y, min z, max x, max y, max z } of those Position doubles (2-D handles:
+ *   the z entries are exact zeros).  Every output is a function of the state alone: the union-find's compare-and-swap decides the shape
+ *   of a forest, never a value, the table is formed with integer add / min / max; repeated builds give the same bytes.
+ *   Any pointer of sphmi_components_read may be NULL.
+ *   The result stays in a device arena of its own until the next build, sphmi_components_release (which gives the memory back) or
+ *   sphmi_destroy.  sphmi_advance, sphmi_upload, sphmi_generate_dam_break_3d and sphmi_forces_once mark it stale: rows may have moved.
+ *   SPHMI_ERR_STATE: before the upload; before the handle has executed its first step since the upload or generator (no cell list);
+ *     handles with H < h; rank-mode handles; multi-device handles (single-device handles only, as for the neighbour list);
+ *     sphmi_components_read without a build, or of a stale or released result.
+ *   SPHMI_ERR_ARGUMENT: a link that is not finite, not positive or greater than H (the walk reaches no further); a type_mask with none
+ *     of the bits 1 - 3 set, or with any other bit set; a null n_components_out (n_rows_out may be NULL).
+ *   SPHMI_ERR_DEVICE: the device cannot hold the arena (24 bytes per row, 56 per component) - the handle stays usable; or the
+ *     union-find left the bounds every one of its loops carries (a defect, reported instead of a hung device).
+ */
+int sphmi_components_build(sphmi_handle* h, double link, uint32_t type_mask,
+                           int64_t* n_rows_out, int64_t* n_components_out);
+int sphmi_components_read(sphmi_handle* h, int32_t* label_out /* [n_rows] */, int32_t* first_row_out /* [C] */,
+                          int32_t* count_out /* [C] */, double* box_out /* [C x 6] */);
+int sphmi_components_release(sphmi_handle* h);
+
 #ifdef __cplusplus
 }
 #endif

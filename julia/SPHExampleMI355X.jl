@@ -208,6 +208,24 @@ function isosurface(P, origin::Vector{Float64}, spacing::Vector{Float64}, counts
     check(h, ccall((:sphmi_isosurface_release, LIB), Cint, (Ptr{Cvoid},), h))
     return (vertices = vertices, elements = elements, pressure = pp, velocity = v)
 end
+# The connected bodies of the fluid on the state the session holds NOW (sphmi_components_build / _read / _release): rows of the Types
+# named (Fluid = 1, Fixed = 2, Moving = 3) are linked within `link` (at most SimKernel.H); label[i] is the component of row i of the next
+# download or -1, first_row / count / box (6 × C: min x, y, z, max x, y, z) describe the components, numbered in ascending first row.
+# label and first_row are the library's RAW 0-BASED values.  Single-device sessions; from an output callback, after the first step.
+# (The build goes through @ccall: its mask is the header's only 32-bit unsigned argument, a width the table of
+# tests/test_julia_shim.py does not hold; tests/test_components_host.py holds this call to its prototype.)
+function components(P, link::Float64; types = (1,))
+    h = SESSIONS[P].h
+    mask = reduce(|, (UInt32(1) << t for t in types); init = UInt32(0))
+    rows = Ref{Int64}(0); comps = Ref{Int64}(0)
+    check(h, @ccall LIB.sphmi_components_build(h::Ptr{Cvoid}, link::Float64, mask::UInt32, rows::Ref{Int64}, comps::Ref{Int64})::Cint)
+    label = Vector{Int32}(undef, rows[]); first_row = Vector{Int32}(undef, comps[]); count = Vector{Int32}(undef, comps[])
+    box = Matrix{Float64}(undef, 6, comps[])
+    GC.@preserve label first_row count box check(h, ccall((:sphmi_components_read, LIB), Cint, (Ptr{Cvoid}, Ptr{Int32}, Ptr{Int32}, Ptr{Int32}, Ptr{Float64}),
+                                                            h, pointer(label), pointer(first_row), pointer(count), pointer(box)))
+    check(h, ccall((:sphmi_components_release, LIB), Cint, (Ptr{Cvoid},), h))
+    return (label = label, first_row = first_row, count = count, box = box)
+end
 atexit(() -> foreach(s -> ccall((:sphmi_destroy, LIB), Cint, (Ptr{Cvoid},), s.h), values(SESSIONS)))
 
 function check(h, rc)

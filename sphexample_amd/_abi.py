@@ -591,6 +591,69 @@ class Backend:
         finally:
             self.isosurface_release()
 
+    # -- the connected bodies of selected rows, on demand (sphmi_components_build / _read / _release) ----------------------------
+    COMPONENT_TYPES = {"Fluid": 1, "Fixed": 2, "Moving": 3}
+
+    def has_components(self) -> bool:
+        return all(self._has(n) for n in ("components_build", "components_read", "components_release"))
+
+    def _type_mask(self, types) -> int:
+        if isinstance(types, (str, int, np.integer)):
+            types = (types,)
+        mask = 0
+        for t in types:
+            if isinstance(t, str) and t not in self.COMPONENT_TYPES:
+                raise ValueError(f"components: unknown type {t!r} (one of {sorted(self.COMPONENT_TYPES)})")
+            mask |= 1 << (self.COMPONENT_TYPES[t] if isinstance(t, str) else int(t))
+        return mask
+
+    def components_build(self, link=None, types=("Fluid",)):
+        """Label the connected bodies of the rows of `types` ("Fluid", "Fixed", "Moving", or their Type numbers) on the device and
+        keep the result there: (n_rows, n_components).  Two selected rows are linked iff r^2 <= link^2 on the current positions;
+        `link=None` means H, the longest the library serves.  It stays until the next build, `components_release` or `close`; a
+        step, an upload or `forces_once` marks it stale."""
+        f = self._fn("components_build")
+        f.argtypes = [C.c_void_p, C.c_double, C.c_uint32, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+        rows, comps = C.c_int64(), C.c_int64()
+        self._components_shape = None                                             # (a refused build leaves nothing this object may read)
+        self._check(f(self._h, float(self.cfg.H if link is None else link), self._type_mask(types), C.byref(rows), C.byref(comps)))
+        self._components_shape = (rows.value, comps.value)
+        return self._components_shape
+
+    def components_read(self, label: bool = True, first_row: bool = True, count: bool = True, box: bool = True):
+        """(label int32 [n_rows], first_row int32 [C], count int32 [C], box float64 [C, 6]) of the components built last; False
+        skips one (None in its place).  sphmi_components_read takes no capacities: the arrays are sized from what THIS object's
+        `components_build` reported, so a result built through the raw entry point behind its back must not be read here."""
+        f = self._fn("components_read")
+        f.argtypes = [C.c_void_p] * 5
+        shape = getattr(self, "_components_shape", None)
+        if shape is None:
+            self._check(f(self._h, None, None, None, None))                        # the library words the refusal
+            raise RuntimeError("components_read: the handle holds components this object did not build; call components_build first")
+        rows, comps = shape
+        out = (np.zeros(rows, dtype=np.int32) if label else None, np.zeros(comps, dtype=np.int32) if first_row else None,
+               np.zeros(comps, dtype=np.int32) if count else None, np.zeros((comps, 6)) if box else None)
+        self._check(f(self._h, *[_ptr(a) for a in out]))
+        return out
+
+    def components_release(self) -> None:
+        f = self._fn("components_release")
+        f.argtypes = [C.c_void_p]
+        self._check(f(self._h))
+        self._components_shape = None
+
+    def components(self, link=None, types=("Fluid",)) -> dict:
+        """The connected bodies of the rows of `types`, evaluated now: a dict of `label` int32 [n] (the component of row i — row i of
+        what `download` delivers now — or -1 if it is not selected), `first_row`, `count` int32 [C] and `box` float64 [C, 6]
+        (min x, y, z, max x, y, z); components are numbered in ascending first (smallest) row.  `sphexample_amd.components` finds
+        the main body, tabulates the droplets and restates the labelling in numpy.  Single-device handles; call it between
+        `advance` calls, after the first executed step.  The device memory is given back before it returns."""
+        self.components_build(link, types)
+        try:
+            return dict(zip(("label", "first_row", "count", "box"), self.components_read()))
+        finally:
+            self.components_release()
+
     def forces_once(self, apply_mdbc: bool = False):
         drho = np.empty(self.N, dtype=self._ft)
         acc = np.empty((self.N, self.D), dtype=self._ft)

@@ -24,6 +24,7 @@
 #include "sphmi_field_grid.h"
 #include "sphmi_particle_fields.h"
 #include "sphmi_neighbor_list.h"
+#include "sphmi_components.h"
 #include "sphmi_isosurface.h"
 
 namespace sphmi {
@@ -200,10 +201,15 @@ struct EngineBase {
     virtual void neighbors_release() {}
     // The free surface as a mesh (sphmi_isosurface.h): the same lifetime, the same calls mark it stale.
     int iso_state = NL_NONE;
-    void results_stale() { neighbors_stale(); if (iso_state == NL_VALID) iso_state = NL_STALE; }
+    void results_stale() { neighbors_stale(); if (iso_state == NL_VALID) iso_state = NL_STALE; if (cc_state == NL_VALID) cc_state = NL_STALE; }
     virtual void isosurface_build(const double* origin, const double* spacing, const int64_t* counts, double level, int64_t* n_vertices_out, int64_t* n_elements_out) = 0;
     virtual void isosurface_read(double*, int32_t*, double*, double*) { throw EngineError(SPHMI_ERR_STATE, "sphmi_isosurface_read: no mesh is held (sphmi_isosurface_build)"); }
     virtual void isosurface_release() {}
+    // The connected bodies of selected rows (sphmi_components.h): the same lifetime, the same calls mark it stale.
+    int cc_state = NL_NONE;
+    virtual void components_build(double link, uint32_t type_mask, int64_t* n_rows_out, int64_t* n_components_out) = 0;
+    virtual void components_read(int32_t*, int32_t*, int32_t*, double*) { throw EngineError(SPHMI_ERR_STATE, "sphmi_components_read: no components are held (sphmi_components_build)"); }
+    virtual void components_release() {}
     virtual void unique_cells(int64_t* out, int64_t cap, int64_t* n) = 0;
     virtual void timers(int32_t cap, const char** names, double* secs, int64_t* calls, int32_t* n) = 0;
     virtual void force_stats(int reset, double* avg_ms, int64_t* launches) = 0;
@@ -475,7 +481,7 @@ struct Engine final : EngineBase {
         for (auto& e : host_pinned) (void)hipHostUnregister(e.first);
         (void)hipFree(out_arena);
         (void)hipFree(col_arena); (void)hipFree(col_store); (void)hipFree(col_base[0]); (void)hipFree(col_base[1]);
-        gf_release(); pr_release(); bg_release(); (void)hipFree(fg_arena.p); (void)hipFree(pf_arena.p); nl_free(); iso_free();
+        gf_release(); pr_release(); bg_release(); (void)hipFree(fg_arena.p); (void)hipFree(pf_arena.p); nl_free(); iso_free(); cc_free();
         (void)hipFree(slot); (void)hipFree(tmp_idx); (void)hipFree(perm);
         for (int k = 0; k < 2; ++k) { (void)hipFree(tile_cost[k]); (void)hipFree(tile_order[k]); }
         (void)hipFree(kout_d); (void)hipFree(tile_work_d); (void)hipFree(tile_work1_d); (void)hipFree(xcd_clock_d); (void)hipHostFree(xcd_clock_h);
@@ -2013,6 +2019,133 @@ struct Engine final : EngineBase {
         nl_free();
     }
 
+    // ---- the connected bodies of selected rows, on demand (sphmi_components.h) ----------------------------------------------------------
+    // Reads the current set's positions, the low words, the types, `cstart` and the grid of the last rebuild; writes its own arena and
+    // nothing else.  The arena: parent, root, flag, label [N] int32, the scan's tile sums and dense [N + 1] int64, the error word —
+    // they grow with N — and first_row, count, box, which grow with the number of components.  cc_state (EngineBase) tells whether it
+    // matches the rows.
+    int *cc_parent = nullptr, *cc_root = nullptr, *cc_flag = nullptr, *cc_label = nullptr, *cc_first = nullptr, *cc_count = nullptr, *cc_err = nullptr;
+    long long *cc_dense = nullptr, *cc_tsum = nullptr;
+    unsigned long long* cc_box = nullptr;
+    size_t cc_rows_cap = 0, cc_comp_cap = 0;
+    int64_t cc_rows = 0, cc_n = 0;
+    void cc_free() {
+        (void)hipFree(cc_parent); (void)hipFree(cc_root); (void)hipFree(cc_flag); (void)hipFree(cc_label); (void)hipFree(cc_first); (void)hipFree(cc_count);
+        (void)hipFree(cc_err); (void)hipFree(cc_dense); (void)hipFree(cc_tsum); (void)hipFree(cc_box);
+        cc_parent = cc_root = cc_flag = cc_label = cc_first = cc_count = cc_err = nullptr; cc_dense = cc_tsum = nullptr; cc_box = nullptr;
+        cc_rows_cap = cc_comp_cap = 0; cc_rows = cc_n = 0;
+        cc_state = NL_NONE;
+    }
+    void cc_alloc(void** p, size_t bytes, long long comps) {
+        if (hipMalloc(p, std::max<size_t>(bytes, 8)) == hipSuccess) return;
+        (void)hipGetLastError();
+        *p = nullptr;
+        char buf[200];
+        snprintf(buf, sizeof(buf), "sphmi_components_build: no device memory for the arena of %lld components over %d rows (%.2f GB)", comps, N, (double)bytes / 1e9);
+        throw EngineError(SPHMI_ERR_DEVICE, buf);
+    }
+    void components_build(double link, uint32_t type_mask, int64_t* n_rows_out, int64_t* n_components_out) override {
+        require_uploaded("sphmi_components_build");
+        if (!std::isfinite(link) || !(link > 0.0) || !(link <= cfg.H)) throw EngineError(SPHMI_ERR_ARGUMENT, "sphmi_components_build: the link length must be finite, positive and at most H");
+        if ((type_mask & ~0xeu) || !(type_mask & 0xeu)) throw EngineError(SPHMI_ERR_ARGUMENT, "sphmi_components_build: the type mask must name at least one of the bits 1 (Fluid), 2 (Fixed), 3 (Moving) and no other");
+        if (!n_components_out) throw EngineError(SPHMI_ERR_ARGUMENT, "sphmi_components_build: null n_components_out");
+        if (!(cfg.h <= cfg.H)) throw EngineError(SPHMI_ERR_STATE, "sphmi_components_build: handles with H < h are not served (the candidate cells are laid out for H + h <= 2H)");
+        if (!fg_ready()) throw EngineError(SPHMI_ERR_STATE, "sphmi_components_build: the handle has not executed a step since the upload (no cell list)");
+        HC(hipSetDevice(cfg.device));
+        cc_state = NL_NONE; cc_rows = cc_n = 0;                            // the result of the build before is gone, whatever happens below
+        const size_t n = (size_t)N;
+        const int ntiles = (N + kNlScanTile - 1) / kNlScanTile;
+        if (n > cc_rows_cap) {
+            cc_free();
+            try {
+                cc_alloc((void**)&cc_parent, n * 4, 0); cc_alloc((void**)&cc_root, n * 4, 0); cc_alloc((void**)&cc_flag, n * 4, 0); cc_alloc((void**)&cc_label, n * 4, 0);
+                cc_alloc((void**)&cc_tsum, (size_t)ntiles * 8, 0); cc_alloc((void**)&cc_dense, (n + 1) * 8, 0); cc_alloc((void**)&cc_err, 8, 0);
+            } catch (...) { cc_free(); throw; }
+            cc_rows_cap = n;
+        }
+        NeighborListArgs<T> A{};
+        A.pk0 = pk0[iA]; A.comp = comp[cur]; A.cstart = cstart; A.g = grid;
+        A.H_inv = cfg.H_inv; A.H2 = link * link; A.reach = cfg.H + cfg.h;   // the cells are walked as for the neighbour list; only the cut is shorter
+        A.N = N; A.half = 1;
+        ComponentArgs K{};
+        K.type = type[cur]; K.parent = cc_parent; K.root = cc_root; K.flag = cc_flag; K.dense = cc_dense; K.label = cc_label; K.err = cc_err;
+        K.N = N; K.type_mask = type_mask;
+        // $SPHMI_COMPONENTS_TIMING=1: the device time of every pass goes to stderr (tools/components_cost.py)
+        const bool timing = getenv("SPHMI_COMPONENTS_TIMING") != nullptr;
+        hipEvent_t ev[6] = {};
+        auto mark = [&](int k) { if (timing) { if (!ev[k]) HC(hipEventCreate(&ev[k])); HC(hipEventRecord(ev[k], stream)); } };
+        auto drop = [&]() { for (auto& e : ev) if (e) { (void)hipEventDestroy(e); e = nullptr; } };
+        auto check_err = [&](int e) {
+            if (!e) return;
+            char buf[200];
+            snprintf(buf, sizeof(buf), "sphmi_components_build: the union-find left its bounds (error word %d: 1 = climb, 2 = retry, 4 = parent out of range); no result is held", e);
+            throw EngineError(SPHMI_ERR_DEVICE, buf);
+        };
+        try {
+            const unsigned nb = (unsigned)((N + kCcThreads - 1) / kCcThreads);
+            HC(hipMemsetAsync(cc_err, 0, 8, stream));
+            mark(0);
+            hipLaunchKernelGGL(k_cc_init, dim3(nb), dim3(kCcThreads), 0, stream, K);
+            mark(1);
+            if (D == 3) hipLaunchKernelGGL((k_cc_hook<T, 3>), dim3(nb), dim3(kNlThreads), 0, stream, A, K);
+            else        hipLaunchKernelGGL((k_cc_hook<T, 2>), dim3(nb), dim3(kNlThreads), 0, stream, A, K);
+            mark(2);
+            hipLaunchKernelGGL(k_cc_flatten, dim3(nb), dim3(kCcThreads), 0, stream, K);
+            mark(3);
+            hipLaunchKernelGGL(k_nl_tile_sums, dim3(ntiles), dim3(kNlScanThreads), 0, stream, (const int*)cc_flag, N, cc_tsum);
+            hipLaunchKernelGGL(k_nl_scan_tiles, dim3(1), dim3(1024), 0, stream, cc_tsum, ntiles, cc_dense + n);
+            hipLaunchKernelGGL(k_nl_offsets, dim3(ntiles), dim3(kNlScanThreads), 0, stream, (const int*)cc_flag, N, (const long long*)cc_tsum, cc_dense);
+            HC(hipGetLastError());
+            long long comps = 0; int err = 0;
+            bounce.d2h(&comps, cc_dense + n, 8, stream);                   // (complete on return: the call is synchronous anyway)
+            bounce.d2h(&err, cc_err, 4, stream);
+            check_err(err);
+            if (comps < 0 || comps > (long long)N) throw EngineError(SPHMI_ERR_DEVICE, "sphmi_components_build: the scan of the roots left its bounds; no result is held");
+            if ((size_t)comps > cc_comp_cap) {
+                (void)hipFree(cc_first); (void)hipFree(cc_count); (void)hipFree(cc_box); cc_first = cc_count = nullptr; cc_box = nullptr; cc_comp_cap = 0;
+                cc_alloc((void**)&cc_first, (size_t)comps * 4, comps); cc_alloc((void**)&cc_count, (size_t)comps * 4, comps); cc_alloc((void**)&cc_box, (size_t)comps * 48, comps);
+                cc_comp_cap = (size_t)comps;
+            }
+            K.first_row = cc_first; K.count = cc_count; K.box = cc_box; K.C = (int)comps;
+            hipLaunchKernelGGL(k_cc_label, dim3(nb), dim3(kCcThreads), 0, stream, K);
+            mark(4);
+            if (comps > 0) {
+                const unsigned nbt = (unsigned)((6 * comps + kCcThreads - 1) / kCcThreads);
+                hipLaunchKernelGGL(k_cc_table_init, dim3(nbt), dim3(kCcThreads), 0, stream, K);
+                if (D == 3) { hipLaunchKernelGGL((k_cc_table<T, 3>), dim3(nb), dim3(kCcThreads), 0, stream, A, K); hipLaunchKernelGGL(k_cc_box_decode<3>, dim3(nbt), dim3(kCcThreads), 0, stream, K); }
+                else        { hipLaunchKernelGGL((k_cc_table<T, 2>), dim3(nb), dim3(kCcThreads), 0, stream, A, K); hipLaunchKernelGGL(k_cc_box_decode<2>, dim3(nbt), dim3(kCcThreads), 0, stream, K); }
+            }
+            HC(hipGetLastError());
+            mark(5);
+            HC(hipStreamSynchronize(stream));
+            if (timing) {
+                float ms[5] = {};
+                for (int k = 0; k < 5; ++k) HC(hipEventElapsedTime(&ms[k], ev[k], ev[k + 1]));
+                fprintf(stderr, "sphmi_components_build: %d rows, %lld components: init %.3f ms, hook %.3f ms, flatten %.3f ms, number %.3f ms, table %.3f ms\n", N, comps, ms[0], ms[1], ms[2], ms[3], ms[4]);
+            }
+            drop();
+            cc_rows = N; cc_n = comps; cc_state = NL_VALID;
+        } catch (...) { drop(); throw; }
+        if (n_rows_out) *n_rows_out = cc_rows;
+        *n_components_out = cc_n;
+    }
+    void components_read(int32_t* label_out, int32_t* first_row_out, int32_t* count_out, double* box_out) override {
+        if (cc_state == NL_STALE) throw EngineError(SPHMI_ERR_STATE, "sphmi_components_read: the components are stale (rows may have moved since sphmi_components_build)");
+        if (cc_state != NL_VALID) throw EngineError(SPHMI_ERR_STATE, "sphmi_components_read: no components are held (sphmi_components_build)");
+        HC(hipSetDevice(cfg.device));
+        if (label_out && cc_rows > 0) fetch_result(label_out, cc_label, (size_t)cc_rows * 4);
+        if (cc_n > 0) {
+            if (first_row_out) fetch_result(first_row_out, cc_first, (size_t)cc_n * 4);
+            if (count_out) fetch_result(count_out, cc_count, (size_t)cc_n * 4);
+            if (box_out) fetch_result(box_out, cc_box, (size_t)cc_n * 48);
+        }
+        HC(hipStreamSynchronize(stream));
+    }
+    void components_release() override {
+        HC(hipSetDevice(cfg.device));
+        cc_free();
+    }
+
     // ---- the free surface as a mesh, on demand (sphmi_isosurface.h) -----------------------------------------------------------------
     // Samples the lattice with fg_launch into fg_arena — nothing of S goes to the host — and extracts the mesh of S = level into an
     // arena of its own, which holds everything a read needs: a later sphmi_sample_grid may reuse fg_arena.  Per node: the two bytes,
@@ -2716,6 +2849,13 @@ int sphmi_isosurface_read(sphmi_handle* h, double* vertices_out, int32_t* elemen
     SPHMI_GUARD(h, h->e->isosurface_read(vertices_out, elements_out, pressure_out, velocity_out));
 }
 int sphmi_isosurface_release(sphmi_handle* h) { SPHMI_GUARD(h, h->e->isosurface_release()); }
+int sphmi_components_build(sphmi_handle* h, double link, uint32_t type_mask, int64_t* n_rows_out, int64_t* n_components_out) {
+    SPHMI_GUARD(h, h->e->components_build(link, type_mask, n_rows_out, n_components_out));
+}
+int sphmi_components_read(sphmi_handle* h, int32_t* label_out, int32_t* first_row_out, int32_t* count_out, double* box_out) {
+    SPHMI_GUARD(h, h->e->components_read(label_out, first_row_out, count_out, box_out));
+}
+int sphmi_components_release(sphmi_handle* h) { SPHMI_GUARD(h, h->e->components_release()); }
 int sphmi_group_forces_read(sphmi_handle* h, int64_t capacity, int64_t* iteration_out, double* time_out, double* dt_out, double* force_out,
                             int64_t* n_out, int64_t* n_dropped) {
     SPHMI_GUARD(h, h->e->group_forces_read(capacity, iteration_out, time_out, dt_out, force_out, n_out, n_dropped));

@@ -1796,6 +1796,11 @@ struct MultiEngine final : EngineBase {
         if (rank_mode) throw EngineError(SPHMI_ERR_STATE, "sphmi_neighbors_build: single-device handles only (a rank-mode process holds one slab of the rows)");
         throw EngineError(SPHMI_ERR_STATE, "sphmi_neighbors_build: single-device handles only (a slab's ghost copies hold the half-step state; the halo exchange this needs is not built)");
     }
+    // The connected bodies (sphmi_components.h): single-device handles only, as for the neighbour list.
+    void components_build(double, uint32_t, int64_t*, int64_t*) override {
+        if (rank_mode) throw EngineError(SPHMI_ERR_STATE, "sphmi_components_build: single-device handles only (a rank-mode process holds one slab of the rows)");
+        throw EngineError(SPHMI_ERR_STATE, "sphmi_components_build: single-device handles only (a slab's ghost copies hold the half-step state; the halo exchange this needs is not built)");
+    }
     // The free surface as a mesh (sphmi_isosurface.h): single-device handles only — a multi-device handle adds the slabs' sums on the host.
     void isosurface_build(const double*, const double*, const int64_t*, double, int64_t*, int64_t*) override {
         if (rank_mode) throw EngineError(SPHMI_ERR_STATE, "sphmi_isosurface_build: single-device handles only (a rank-mode process holds one slab of the rows)");

@@ -44,7 +44,7 @@ def RunSimulation(*, SimGeometry=None, SimMetaData: SimulationMetaData, SimConst
                   on_output: Optional[Callable[[SimulationMetaData, SimParticles], None]] = None,
                   device_float_bytes: int = 0, device: int = 0, backend_factory=None,
                   async_output: bool = False, group_forces=None, probes=None, field_grid=None,
-                  particle_fields=None, budgets: bool = False, neighbor_list: bool = False, isosurface=None) -> List[float]:
+                  particle_fields=None, budgets: bool = False, neighbor_list: bool = False, isosurface=None, components=None) -> List[float]:
     """Same keyword signature as the reference (src/SPHCellList.jl:808-817); returns the list of
     time steps the reference collects in ``TimeSteps`` (:823,:884).  ``SimParticles`` is updated in
     place at every output time, in the engine's cell-sorted order, as the reference's is.
@@ -81,6 +81,13 @@ def RunSimulation(*, SimGeometry=None, SimMetaData: SimulationMetaData, SimConst
     (``Backend.isosurface`` on that lattice, level 0.5 unless given; ``sphexample_amd.isosurface`` measures it) and ``on_output``
     receives ``(vertices, elements)`` as one more argument, behind the neighbour list and before the budgets (``None`` at the
     first call), the way ``field_grid=`` hands over its fields.  ``None`` (default): nothing is extracted.
+
+    ``components=True | link | (link, types)``: at every output the connected bodies of the fluid are labelled on the device
+    (``Backend.components``: rows linked within `link`, H unless given, among the rows of `types`, the fluid unless given;
+    ``sphexample_amd.components`` finds the main body and tabulates the droplets) and ``on_output`` receives the dict of
+    ``label``, ``first_row``, ``count`` and ``box`` as one more argument, behind the mesh and before the budgets (``None`` at the
+    first call).  Row i is particle i of that output.  ``None`` or ``False`` (default): nothing is built and the callback keeps
+    its arguments.
 
     ``budgets=True``: the energy, momentum and extent budgets of the fluid are recorded on the device at every step
     (``Backend.budgets_enable``; ``sphexample_amd.budgets`` adds up a total energy and reads a wave front off the box) and
@@ -134,6 +141,9 @@ def RunSimulation(*, SimGeometry=None, SimMetaData: SimulationMetaData, SimConst
     if isosurface is not None:
         surface = tuple(isosurface)
         extras.append((None, lambda: eng.isosurface(*surface)))                  # (the state of this output, like the field grid)
+    if components is not None and components is not False:
+        asked = () if components is True else tuple(components) if isinstance(components, (tuple, list)) else (components,)
+        extras.append((None, lambda: eng.components(*asked)))                    # (the rows of this output, like the neighbour list)
     if budgets:
         eng.budgets_enable(capacity=1 << 20)
         extras.append((empty_budgets(), eng.budgets_read))
