@@ -327,6 +327,46 @@ int sphmi_budgets_read(sphmi_handle* h, int64_t capacity, int64_t* iteration_out
                        double* extremes_out, double* box_out, int64_t* n_out, int64_t* n_dropped);
 
 /*
+ * The FLOW through control boxes at STEP resolution, recorded on the device: how much fluid a region holds and how much went in or
+ * out - the discharge through a section of a channel, the volume that has passed an obstacle, overtopping of a wall, the filling
+ * curve of a compartment.  A box is axis-aligned and half-open: row i is INSIDE box b iff lo[b][d] <= x_i[d] < hi[b][d] for every
+ * d < dims, compared in fp64 on the Position doubles sphmi_download would deliver - adjacent boxes partition space without a gap or
+ * an overlap.  lo = -inf and hi = +inf are legal: a box unbounded along the other axes is a gate across a channel, and the box
+ * [c, +inf) along x counts the crossings of the plane x = c, `entered` in the +x direction, `left` in the -x direction.  Boxes may
+ * overlap and may be empty of fluid.  For every executed step and every box, over the rows i of the handle with Type == Fluid, the
+ * raw values
+ *     s0 = n_after, the rows inside on the state sphmi_download would deliver directly after that step
+ *     s1 = sum 1/rho over those rows (one fp64 division per row)    s2..4 = sum v over those rows (2-D handles: an exact zero third)
+ *     s5 = entered, the rows NOT inside on the state at the START of that step and inside after it
+ *     s6 = left, the rows inside at the start of that step and not inside after it
+ * The state at the start of a step is what sphmi_download would have delivered before it, the after-state of the step before: for
+ * consecutive samples n_after[k] - n_after[k-1] == entered[k] - left[k] holds exactly, across rebuilds and sphmi_advance calls.  The
+ * start state is marked on the device as the first launch of a step (the corrector of an fp32 handle updates positions in place);
+ * every crossing between two outputs is counted, one that comes back included.  Sums are reduced in an order that depends on the
+ * particle order alone: repeated runs give the same bits.  Off by default; a handle that never enables it launches what it always did.
+ *   enable: after sphmi_upload / sphmi_generate_dam_break_3d, at any later time too.  1 <= n_boxes <= SPHMI_MAX_FLOW_BOXES boxes, lo
+ *     and hi `dims` doubles per box.  The handle keeps the newest capacity_steps (>= 1) samples that have not been read.  A second
+ *     call replaces the boxes and drops the series; n_boxes = 0 disables.  sphmi_upload and the generator disable.  No step waits for
+ *     the host: the records of a batch of queued steps come back with the control block the host fetches anyway.  sphmi_forces_once
+ *     records nothing.
+ *   read: delivers and clears the oldest `capacity` samples recorded since the last read, oldest first: iteration_out / time_out / dt_out
+ *     [capacity] as sphmi_group_forces_read; count_out [capacity x n_boxes] n_after; volume_out [capacity x n_boxes] m0*s1;
+ *     momentum_out [capacity x n_boxes x 3] m0*s2..4; entered_out, left_out [capacity x n_boxes] - volume and momentum formed on the
+ *     host, one multiplication each.  Any output pointer may be NULL.  *n_out, *n_dropped, capacity = 0: as sphmi_group_forces_read.
+ *   SPHMI_ERR_STATE: before the upload; read while disabled; rank-mode handles (a process holds one slab of the rows).
+ *   SPHMI_ERR_ARGUMENT: a null table, n_boxes out of [0, SPHMI_MAX_FLOW_BOXES], a NaN bound, !(lo < hi) on any axis of any box,
+ *     capacity_steps < 1, negative capacity, null n_out.
+ * Multi-device handles of one process: every slab marks and samples the rows it owns (ghost copies do not count; rows migrate in the
+ * collective rebuild, between steps, so a row's start and end state lie in the same slab) and the handle adds the slabs' records in
+ * slab order.  Flow, budgets, probes and group forces may be enabled together.
+ */
+#define SPHMI_MAX_FLOW_BOXES 16
+int sphmi_flow_enable(sphmi_handle* h, int32_t n_boxes, const double* lo, const double* hi, int64_t capacity_steps);
+int sphmi_flow_read(sphmi_handle* h, int64_t capacity, int64_t* iteration_out, double* time_out, double* dt_out,
+                    int64_t* count_out, double* volume_out, double* momentum_out, int64_t* entered_out, int64_t* left_out,
+                    int64_t* n_out, int64_t* n_dropped);
+
+/*
  * MotionDetails of the Geometry with this GroupMarker (src/SimulationGeometry.jl:17-22): particles of Type Moving
  * in that group get Velocity = velocity·direction while start_time <= TotalTime <= start_time + duration (0
  * otherwise) and are displaced by Velocity·dt/2 before each neighbour pass — ProgressMotion,

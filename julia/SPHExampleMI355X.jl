@@ -30,6 +30,9 @@
 # device — sphmi_probes_enable, `dims` coordinates per point — and collect the series in SPHExampleMI355X.PROBES[SimParticles]).
 # SPHMI_BUDGETS (unset by default; "1" = record the energy, momentum and extent budgets of the fluid at every step on the device —
 # sphmi_budgets_enable — and collect the series in SPHExampleMI355X.BUDGETS[SimParticles]).
+# SPHMI_FLOW_BOXES (unset by default; "lo,lo,lo:hi,hi,hi;…" = record the flow through these half-open control boxes, `dims` bounds on
+# either side of the colon, "-Inf" / "Inf" allowed, at every step on the device — sphmi_flow_enable — and collect the series in
+# SPHExampleMI355X.FLOW[SimParticles]).
 #
 # EXPERIMENTAL: the build image has no Julia, so this file has never been executed.  struct layout and ABI version
 # are asserted against the library at first use (sphmi_create refuses a mismatching struct_size / abi_version).
@@ -154,6 +157,36 @@ function read_budgets!(h, bs::BudgetSeries)
     append!(bs.iteration, it); append!(bs.time, t); append!(bs.dt, dt); append!(bs.count, c)
     bs.energy = hcat(bs.energy, en); bs.momentum = hcat(bs.momentum, mom); bs.angular = hcat(bs.angular, ang); bs.centre = hcat(bs.centre, cen)
     bs.extremes = hcat(bs.extremes, ext); bs.box = hcat(bs.box, bx); bs.dropped += dropped[]
+    return nothing
+end
+# SPHMI_FLOW_BOXES: the step-resolution flow through control boxes, bound like BUDGETS — count[b, s] Fluid rows inside box b after sample s,
+# volume[b, s], momentum[:, b, s], entered[b, s] and left[b, s] (rows that crossed into / out of the box during the step)
+mutable struct FlowSeries
+    lo::Matrix{Float64}; hi::Matrix{Float64}            # dims × boxes
+    iteration::Vector{Int64}; time::Vector{Float64}; dt::Vector{Float64}
+    count::Matrix{Int64}; volume::Matrix{Float64}; momentum::Array{Float64,3}; entered::Matrix{Int64}; left::Matrix{Int64}
+    dropped::Int64
+end
+const FLOW = IdDict{Any,FlowSeries}()
+function flow_boxes(D)
+    sides = [[parse.(Float64, strip.(split(side, ","))) for side in split(b, ":")] for b in split(get(ENV, "SPHMI_FLOW_BOXES", ""), ";") if !isempty(strip(b))]
+    all(b -> length(b) == 2 && length(b[1]) == D && length(b[2]) == D, sides) || error("SPHMI_FLOW_BOXES: every box is \"lo:hi\" with $D bounds on either side")
+    isempty(sides) && return zeros(Float64, D, 0), zeros(Float64, D, 0)
+    return reduce(hcat, [b[1] for b in sides]), reduce(hcat, [b[2] for b in sides])
+end
+function read_flow!(h, fs::FlowSeries)
+    n = Ref{Int64}(0); dropped = Ref{Int64}(0)
+    check(h, ccall((:sphmi_flow_read, LIB), Cint, (Ptr{Cvoid}, Int64, Ptr{Int64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int64}, Ptr{Int64}, Ref{Int64}, Ref{Int64}),
+                   h, 0, C_NULL, C_NULL, C_NULL, C_NULL, C_NULL, C_NULL, C_NULL, C_NULL, n, dropped))
+    k = Int(n[]); k == 0 && return nothing
+    m = size(fs.lo, 2)
+    it = Vector{Int64}(undef, k); t = Vector{Float64}(undef, k); dt = Vector{Float64}(undef, k)
+    c = Matrix{Int64}(undef, m, k); vol = Matrix{Float64}(undef, m, k); mom = Array{Float64,3}(undef, 3, m, k); en = Matrix{Int64}(undef, m, k); le = Matrix{Int64}(undef, m, k)
+    GC.@preserve it t dt c vol mom en le check(h, ccall((:sphmi_flow_read, LIB), Cint, (Ptr{Cvoid}, Int64, Ptr{Int64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int64}, Ptr{Int64}, Ref{Int64}, Ref{Int64}),
+                                                       h, k, pointer(it), pointer(t), pointer(dt), pointer(c), pointer(vol), pointer(mom), pointer(en), pointer(le), n, dropped))
+    append!(fs.iteration, it); append!(fs.time, t); append!(fs.dt, dt)
+    fs.count = hcat(fs.count, c); fs.volume = hcat(fs.volume, vol); fs.momentum = cat(fs.momentum, mom; dims = 3)
+    fs.entered = hcat(fs.entered, en); fs.left = hcat(fs.left, le); fs.dropped += dropped[]
     return nothing
 end
 # The probes' sums at every node of a regular lattice, evaluated on the state the session holds NOW (sphmi_sample_grid): node (i, j[, k])
@@ -301,6 +334,14 @@ function open_session(SimDensityDiffusion, SimViscosity, SimKernel, SimMetaData:
         BUDGETS[P] = BudgetSeries(Int64[], Float64[], Float64[], Int64[], zeros(Float64, 3, 0), zeros(Float64, 3, 0), zeros(Float64, 3, 0), zeros(Float64, 3, 0),
                                   zeros(Float64, 3, 0), zeros(Float64, 6, 0), 0)
     end
+    box_lo, box_hi = flow_boxes(D)                 # opt-in as well: SPHMI_FLOW_BOXES
+    if !isempty(box_lo)
+        m = size(box_lo, 2)
+        GC.@preserve box_lo box_hi check(h, ccall((:sphmi_flow_enable, LIB), Cint, (Ptr{Cvoid}, Int32, Ptr{Float64}, Ptr{Float64}, Int64),
+                                                  h, Int32(m), pointer(box_lo), pointer(box_hi), 1 << 20))
+        FLOW[P] = FlowSeries(box_lo, box_hi, Int64[], Float64[], Float64[], zeros(Int64, m, 0), zeros(Float64, m, 0), Array{Float64,3}(undef, 3, m, 0),
+                             zeros(Int64, m, 0), zeros(Int64, m, 0), 0)
+    end
     return Session(h, Vector{Int64}(undef, N), zeros(8), zeros(Int64, 8), Vector{Int}(undef, N), Vector{Int64}(undef, SimMetaData.ExportGridCells ? N * D : 0),
                    columns, colptrs)
     catch
@@ -345,6 +386,7 @@ function SimulationLoop(SimDensityDiffusion::BuiltinDDT, SimViscosity::BuiltinVi
     haskey(GROUP_FORCES, P) && read_group_forces!(h, GROUP_FORCES[P])
     haskey(PROBES, P) && read_probes!(h, PROBES[P])
     haskey(BUDGETS, P) && read_budgets!(h, BUDGETS[P])
+    haskey(FLOW, P) && read_flow!(h, FLOW[P])
     GC.@preserve P s begin
         # the carried fields: snapshot on the device, copies on a second stream, straight into the StructArray's columns
         # (Cells: a Vector{CartesianIndex{D}} is N·D Int64; Type is a per-particle constant and follows the gather below)

@@ -426,6 +426,42 @@ class Backend:
         self.budgets_dropped = dropped.value
         return {key: a[:n.value] for key, a in out.items()}
 
+    # -- the flow through control boxes at every step (sphmi_flow_enable / sphmi_flow_read) ----------------------------------
+    FLOW_FIELDS = (("count", (), np.int64), ("volume", (), np.float64), ("momentum", (3,), np.float64), ("entered", (), np.int64),
+                   ("left", (), np.int64))
+
+    def has_flow(self) -> bool:
+        return self._has("flow_enable") and self._has("flow_read")
+
+    def flow_enable(self, lo, hi, capacity: int = 4096) -> None:
+        """Record, after every executed step and on the device, how many Fluid rows lie in each of the half-open boxes
+        ``lo[b] <= x < hi[b]`` (`lo`, `hi` [n, dims], at most 16, -inf / +inf allowed), their volume and momentum, and how many
+        entered and left during that step; the newest `capacity` unread samples are kept.  Empty arrays disable."""
+        a = np.ascontiguousarray(lo, dtype=np.float64).reshape(-1, self.D)
+        b = np.ascontiguousarray(hi, dtype=np.float64).reshape(-1, self.D)
+        if a.shape != b.shape:
+            raise ValueError("flow_enable: lo and hi hold one row of `dims` bounds per box each")
+        self._fn("flow_enable").argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64]
+        self._check(self._fn("flow_enable")(self._h, len(a), _ptr(a) if len(a) else None, _ptr(b) if len(b) else None, int(capacity)))
+        self._flow_boxes = len(a)
+
+    def flow_read(self) -> dict:
+        """The steps executed since the last read, oldest first, and clears them: a dict of iteration[n], time[n], dt[n],
+        count[n, boxes] (Fluid rows inside after the step), volume[n, boxes] (m0 * sum 1/rho), momentum[n, boxes, 3],
+        entered[n, boxes] and left[n, boxes] (rows that crossed into / out of the box during the step);
+        `flow_dropped` holds how many older samples the capacity pushed out."""
+        f = self._fn("flow_read")
+        f.argtypes = [C.c_void_p, C.c_int64] + [C.c_void_p] * 8 + [C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+        n, dropped = C.c_int64(), C.c_int64()
+        self._check(f(self._h, 0, *[None] * 8, C.byref(n), C.byref(dropped)))                   # capacity 0: how many are waiting
+        m = int(getattr(self, "_flow_boxes", 0))
+        k = max(n.value, 1)
+        out = {"iteration": np.zeros(k, dtype=np.int64), "time": np.zeros(k), "dt": np.zeros(k)}
+        out.update({name: np.zeros((k, m) + shape, dtype=dtype) for name, shape, dtype in self.FLOW_FIELDS})
+        self._check(f(self._h, k, *[_ptr(a) for a in out.values()], C.byref(n), C.byref(dropped)))
+        self.flow_dropped = dropped.value
+        return {key: a[:n.value] for key, a in out.items()}
+
     # -- kernel sums on a regular lattice, on demand (sphmi_sample_grid) -----------------------------------------------------
     GRID_FIELDS = ("weight", "count", "pressure", "density", "velocity")
 

@@ -10,7 +10,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc")
 LIB = os.path.join(_HERE, "libsphmi.so")
 SOURCES = ["sphmi_engine.hip"]
-HEADERS = ["sphmi_kernels.h", "sphmi_rebuild.h", "sphmi_columns.h", "sphmi_group_forces.h", "sphmi_probes.h", "sphmi_budgets.h", "sphmi_field_grid.h", "sphmi_particle_fields.h", "sphmi_neighbor_list.h", "sphmi_components.h", "sphmi_isosurface.h", "sphmi_iso_core.h", "sphmi_multi.h", "sphmi_shm.h", "sphmi_series.h", os.path.join("..", "..", "include", "sphmi.h")]
+HEADERS = ["sphmi_kernels.h", "sphmi_rebuild.h", "sphmi_columns.h", "sphmi_group_forces.h", "sphmi_probes.h", "sphmi_budgets.h", "sphmi_flow.h", "sphmi_field_grid.h", "sphmi_particle_fields.h", "sphmi_neighbor_list.h", "sphmi_components.h", "sphmi_isosurface.h", "sphmi_iso_core.h", "sphmi_multi.h", "sphmi_shm.h", "sphmi_series.h", os.path.join("..", "..", "include", "sphmi.h")]
 
 
 def hipcc() -> str:

@@ -20,6 +20,7 @@
 #include "sphmi_columns.h"
 #include "sphmi_group_forces.h"
 #include "sphmi_budgets.h"
+#include "sphmi_flow.h"
 #include "sphmi_probes.h"
 #include "sphmi_field_grid.h"
 #include "sphmi_particle_fields.h"
@@ -126,13 +127,29 @@ struct EngineBase {
     // entry points that need every row in this process: a multi-device handle refuses them in rank mode
     virtual void require_one_process(const char* fn) const { require_uploaded(fn); }
     // The observers' series (sphmi_series.h).  A multi-device handle keeps them itself; those of its slab engines stay empty.
-    bool gf_on = false, pr_on = false, bg_on = false;
+    bool gf_on = false, pr_on = false, bg_on = false, fl_on = false;
     StepSeries gf_series, pr_series;           // payload: 3 forces per group / the RAW sums, kPrValues per probe (the read normalises)
     StepSeries bg_series;                      // the RAW budgets of the fluid, kBgValues per step (the read forms energies, momenta, the centre)
     // the device side of an enable: the handle's own sampling, or that of every slab engine of a multi-device handle
     virtual void gf_enable_device(int32_t n_groups, const uint64_t* markers) = 0;
     virtual void pr_enable_device(int32_t n_probes, const double* positions) = 0;
     virtual void bg_enable_device(bool on) = 0;
+    StepSeries fl_series;                      // the RAW flow records, kFlValues per control box (the read multiplies by m₀)
+    virtual void fl_enable_device(int32_t n_boxes, const double* lo, const double* hi) = 0;
+    void flow_enable(int32_t n_boxes, const double* lo, const double* hi, int64_t capacity_steps) {
+        require_one_process("sphmi_flow_enable");
+        check_flow_table(n_boxes, lo, hi, cfg.dims, capacity_steps);
+        fl_enable_device(n_boxes, lo, hi);
+        fl_series.reset(kFlValues * n_boxes, n_boxes > 0 ? capacity_steps : 0);
+    }
+    void flow_read(int64_t capacity, int64_t* iteration_out, double* time, double* dt, int64_t* count, double* volume, double* momentum, int64_t* entered,
+                   int64_t* left, int64_t* n_out, int64_t* n_dropped) {
+        require_one_process("sphmi_flow_read");
+        if (!fl_on) throw EngineError(SPHMI_ERR_STATE, "sphmi_flow_read: sampling is not enabled (sphmi_flow_enable)");
+        fl_series.read("sphmi_flow_read", capacity, iteration_out, time, dt, n_out, n_dropped, [&](int64_t k, const double* v) {
+            deliver_flow(cfg.m0, fl_series.values / kFlValues, k, v, count, volume, momentum, entered, left);
+        });
+    }
     void group_forces_enable(int32_t n_groups, const uint64_t* markers, int64_t capacity_steps) {
         require_one_process("sphmi_group_forces_enable");
         check_group_table(n_groups, markers, capacity_steps);
@@ -481,7 +498,7 @@ struct Engine final : EngineBase {
         for (auto& e : host_pinned) (void)hipHostUnregister(e.first);
         (void)hipFree(out_arena);
         (void)hipFree(col_arena); (void)hipFree(col_store); (void)hipFree(col_base[0]); (void)hipFree(col_base[1]);
-        gf_release(); pr_release(); bg_release(); (void)hipFree(fg_arena.p); (void)hipFree(pf_arena.p); nl_free(); iso_free(); cc_free();
+        gf_release(); pr_release(); bg_release(); fl_release(); (void)hipFree(fg_arena.p); (void)hipFree(pf_arena.p); nl_free(); iso_free(); cc_free();
         (void)hipFree(slot); (void)hipFree(tmp_idx); (void)hipFree(perm);
         for (int k = 0; k < 2; ++k) { (void)hipFree(tile_cost[k]); (void)hipFree(tile_order[k]); }
         (void)hipFree(kout_d); (void)hipFree(tile_work_d); (void)hipFree(tile_work1_d); (void)hipFree(xcd_clock_d); (void)hipHostFree(xcd_clock_h);
@@ -1121,6 +1138,7 @@ struct Engine final : EngineBase {
     }
     void enqueue_step() {
         serve_reschedules();
+        if (fl_on) fl_mark();                                                  // the boxes every row is inside of BEFORE the step (the corrector updates the low words in place)
         const bool fused = batch_fused;
         if (!fused) {
             Ev ev = begin_phase(PH_TIMESTEP);
@@ -1157,6 +1175,7 @@ struct Engine final : EngineBase {
         if (gf_on) gf_sample(ctrl_cur(), obs_iteration0, obs_steps_base);       // Σ Acceleration of the selected groups → the batch's log
         if (pr_on) pr_sample(ctrl_cur(), obs_iteration0, obs_steps_base, iB);   // the kernel sums at the probes, on the corrector's output set → the batch's log
         if (bg_on) bg_sample(ctrl_cur(), obs_iteration0, obs_steps_base, iB);   // the budgets of the fluid, on the same set → the batch's log
+        if (fl_on) fl_sample(ctrl_cur(), obs_iteration0, obs_steps_base, iB);   // the flow through the control boxes: that set against this step's marks
         std::swap(iA, iB);
     }
 
@@ -1200,6 +1219,7 @@ struct Engine final : EngineBase {
                 if (gf_on) gf_log.fetch(batch, stream);                                      // … and the group-force records of the batch with it
                 if (pr_on) pr_log.fetch(batch, stream);                                      // … and the probe records
                 if (bg_on) bg_log.fetch(batch, stream);                                      // … and the budgets
+                if (fl_on) fl_log.fetch(batch, stream);                                      // … and the flow records
                 // (the XCD finishing times of a sampled launch: the host-side rebuild reads them at its own synchronisation; handles that
                 // rebuild on the device have none — the shares of the next measured-work schedule would never move: 3 % on the 159 k-particle
                 // LaminarSPS case)
@@ -1215,6 +1235,7 @@ struct Engine final : EngineBase {
                 if (gf_on) push_records(gf_series, gf_log, kGfHeader, executed);
                 if (pr_on) push_records(pr_series, pr_log, kPrHeader, executed);
                 if (bg_on) push_records(bg_series, bg_log, kGfHeader, executed);
+                if (fl_on) push_records(fl_series, fl_log, kGfHeader, executed);
                 // (control inside the predictor: the slots flipped at queue time, once per queued step; what counts is where
                 // the last EXECUTED corrector left its maxima — cancelled steps consume nothing and zero nothing)
                 if (batch_fused) rpar = rpar0 ^ (int)(executed & 1);
@@ -1310,6 +1331,7 @@ struct Engine final : EngineBase {
         gf_disable();                              // … and so did the selected groups' row lists
         pr_disable();                              // … and the probes go with them
         bg_disable();                              // … and the budgets
+        fl_disable();                              // … and the control boxes
         iA = 0; iH = 1; iB = 2; cur = 0;
         ghost_given = ghost_points != nullptr;
         {
@@ -1372,6 +1394,7 @@ struct Engine final : EngineBase {
             gf_disable();
             pr_disable();
             bg_disable();
+            fl_disable();
             iA = 0; iH = 1; iB = 2; cur = 0; ghost_given = false; mdbc_n_list = 0; mdbc_list_valid = false;
             int base = 0;
             const unsigned nbM = (unsigned)((M + 255) / 256);
@@ -1847,6 +1870,75 @@ struct Engine final : EngineBase {
         else {
             hipLaunchKernelGGL(k_bg_partial<T>, dim3(std::min(A.nblk, 1 << 20)), dim3(kBgBlock), 0, stream, A);
             hipLaunchKernelGGL(k_bg_final<T>, dim3(1), dim3(64), 0, stream, A);
+        }
+        HC(hipGetLastError());
+    }
+
+    // ---- the flow through control boxes at every step (sphmi_flow.h) -----------------------------------------------------------
+    // Two streaming passes per step: the marks before anything of the step runs, the sample behind its corrector (one launch on
+    // handles of at most fl_small_rows rows, two above).  No row lists, so rebuilds have no hook: they run between steps.
+    uint16_t* fl_mark_d = nullptr;
+    double* fl_partial = nullptr;
+    StepLog fl_log;
+    FlowBoxes fl_boxes{};
+    int fl_small_rows = kFlSmallRows;          // $SPHMI_FLOW_SMALL_ROWS, read at enable (0: always two stages)
+    int fl_nblk_cap() const { return (cap + kFlBlock - 1) / kFlBlock; }
+    void fl_release() {
+        (void)hipFree(fl_mark_d); fl_mark_d = nullptr;
+        (void)hipFree(fl_partial); fl_partial = nullptr;
+        fl_log.release();
+    }
+    void fl_disable() {
+        if (!fl_on) return;
+        fl_on = false; fl_boxes.n = 0; fl_series.reset(0, 0);
+        HC(hipSetDevice(cfg.device)); HC(hipStreamSynchronize(stream));
+        fl_release();
+    }
+    void fl_enable_device(int32_t n_boxes, const double* lo, const double* hi) override {
+        HC(hipSetDevice(cfg.device));
+        fl_disable();
+        if (n_boxes == 0) return;
+        const double inf = std::numeric_limits<double>::infinity();
+        for (int b = 0; b < n_boxes; ++b)
+            for (int d = 0; d < 3; ++d) {
+                fl_boxes.lo[b][d] = d < D ? lo[(size_t)b * D + d] : -inf;
+                fl_boxes.hi[b][d] = d < D ? hi[(size_t)b * D + d] : inf;
+            }
+        fl_small_rows = kFlSmallRows;
+        if (const char* e = getenv("SPHMI_FLOW_SMALL_ROWS")) fl_small_rows = (int)std::min<long long>(std::max<long long>(atoll(e), 0), kFlSmallRowsMax);
+        const int record = kGfHeader + kFlValues * n_boxes;
+        try {
+            HC(hipMalloc(&fl_mark_d, (size_t)std::max(cap, 1) * sizeof(uint16_t)));
+            HC(hipMalloc(&fl_partial, (size_t)std::max(fl_nblk_cap(), 1) * n_boxes * kFlValues * 8));
+            fl_log.alloc(record, record);
+        } catch (...) { fl_release(); throw; }
+        fl_boxes.n = n_boxes;
+        fl_on = true;
+    }
+    template <class A> void fl_fill(A& a, int set) const {
+        a.pk0 = pk0[set]; a.pk1 = pk1[set]; a.comp = comp[cur];
+        a.type = dd_slab ? type[cur] : nullptr; a.mark = fl_mark_d; a.partial = fl_partial; a.log = fl_log.d;
+        a.N = N; a.D = D; a.nblk = std::min((N + kFlBlock - 1) / kFlBlock, fl_nblk_cap()); a.slots = StepLog::slots;
+        a.box = fl_boxes;
+    }
+    // queued in front of everything else of a step: the current set + low words
+    void fl_mark() {
+        if (N <= 0) return;
+        FlowArgs<T> A{};
+        fl_fill(A, iA);
+        hipLaunchKernelGGL(k_fl_mark<T>, dim3(A.nblk), dim3(kFlBlock), 0, stream, A);
+        HC(hipGetLastError());
+    }
+    // queued behind the corrector of a step; `set`: the state set that corrector wrote
+    void fl_sample(const StepCtrl* ctrl, int64_t iteration0, int64_t steps_base, int set) {
+        FlowArgs<T> A{};
+        fl_fill(A, set);
+        A.ctrl = ctrl; A.iteration0 = iteration0; A.steps_base = steps_base;
+        // (a slab that holds no row still writes its record — zeros under the step's header — for the handle to add: one workgroup does)
+        if (N <= fl_small_rows || N <= 0) hipLaunchKernelGGL(k_fl_small<T>, dim3(1), dim3(kFlBlock), 0, stream, A);
+        else {
+            hipLaunchKernelGGL(k_fl_partial<T>, dim3(std::min(A.nblk, 1 << 20)), dim3(kFlBlock), 0, stream, A);
+            hipLaunchKernelGGL(k_fl_final<T>, dim3(fl_boxes.n), dim3(64), 0, stream, A);
         }
         HC(hipGetLastError());
     }
@@ -2866,6 +2958,13 @@ int sphmi_budgets_read(sphmi_handle* h, int64_t capacity, int64_t* iteration_out
                        int64_t* n_out, int64_t* n_dropped) {
     SPHMI_GUARD(h, h->e->budgets_read(capacity, iteration_out, time_out, dt_out, count_out, energy_out, momentum_out, angular_out, centre_out, extremes_out,
                                       box_out, n_out, n_dropped));
+}
+int sphmi_flow_enable(sphmi_handle* h, int32_t n_boxes, const double* lo, const double* hi, int64_t capacity_steps) {
+    SPHMI_GUARD(h, h->e->flow_enable(n_boxes, lo, hi, capacity_steps));
+}
+int sphmi_flow_read(sphmi_handle* h, int64_t capacity, int64_t* iteration_out, double* time_out, double* dt_out, int64_t* count_out, double* volume_out,
+                    double* momentum_out, int64_t* entered_out, int64_t* left_out, int64_t* n_out, int64_t* n_dropped) {
+    SPHMI_GUARD(h, h->e->flow_read(capacity, iteration_out, time_out, dt_out, count_out, volume_out, momentum_out, entered_out, left_out, n_out, n_dropped));
 }
 int sphmi_set_motion(sphmi_handle* h, uint64_t group_marker, double velocity, double start_time, double duration,
                      const double* direction) {

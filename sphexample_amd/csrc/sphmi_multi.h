@@ -915,6 +915,7 @@ struct MultiEngine final : EngineBase {
         gf_on = false; gf_series.reset(0, 0);                      // … and the selected groups (the slab engines are made anew below)
         pr_on = false; pr_series.reset(0, 0);                      // … and the probes
         bg_on = false; bg_series.reset(0, 0);                      // … and the budgets
+        fl_on = false; fl_series.reset(0, 0);                      // … and the control boxes
         SlabSetup S;
         plan_slabs(cfg, position, ghost_points, N, world, cfg.slab_axis - 1, given_plan.world() == world ? &given_plan : nullptr, 1.6, S);
         axis = S.axis; halo_width = S.halo_width; plan = S.plan;
@@ -1417,17 +1418,21 @@ struct MultiEngine final : EngineBase {
                 for (int k = 0; k < batch; ++k) {
                     reductions_and_control();
                     if (have_halo) {                                     // before the first rebuild there is no ghost layer to exchange
+                        // the boxes every owned row is inside of BEFORE the step: the corrector updates the low words in place (sphmi_flow.h)
+                        if (fl_on) for (auto& r : R) { HC(hipSetDevice(r.device)); r.e->fl_mark(); }
                         pass(1); pass(2);
                         // every slab sums its OWNED rows behind its corrector (the edge tiles have joined `main`)
                         if (gf_on) for (auto& r : R) { HC(hipSetDevice(r.device)); r.e->gf_sample(r.e->ctrl_d, iteration, steps0); }
                         // … and the kernel sums at the probes (the corrector's output set is iA here: dd_pass has rotated the sets)
                         if (pr_on) for (auto& r : R) { HC(hipSetDevice(r.device)); r.e->pr_sample(r.e->ctrl_d, iteration, steps0, r.e->iA); }
                         if (bg_on) for (auto& r : R) { HC(hipSetDevice(r.device)); r.e->bg_sample(r.e->ctrl_d, iteration, steps0, r.e->iA); }
+                        if (fl_on) for (auto& r : R) { HC(hipSetDevice(r.device)); r.e->fl_sample(r.e->ctrl_d, iteration, steps0, r.e->iA); }
                     }
                 }
                 if (gf_on) for (auto& r : R) { HC(hipSetDevice(r.device)); r.e->gf_log.fetch(batch, r.e->stream); }
                 if (pr_on) for (auto& r : R) { HC(hipSetDevice(r.device)); r.e->pr_log.fetch(batch, r.e->stream); }
                 if (bg_on) for (auto& r : R) { HC(hipSetDevice(r.device)); r.e->bg_log.fetch(batch, r.e->stream); }
+                if (fl_on) for (auto& r : R) { HC(hipSetDevice(r.device)); r.e->fl_log.fetch(batch, r.e->stream); }
                 for (auto& r : R) {
                     HC(hipSetDevice(r.device)); sphmi_dd_control s{}; r.e->dd_ctrl_sync(&s);
                     if (&r == &R[0]) st = s;
@@ -1445,6 +1450,7 @@ struct MultiEngine final : EngineBase {
                 if (gf_on) collect_records(gf_series, &Engine<T>::gf_log, kGfHeader, "group forces", steps - steps0);
                 if (pr_on) collect_records(pr_series, &Engine<T>::pr_log, kPrHeader, "probes", steps - steps0);
                 if (bg_on) collect_records(bg_series, &Engine<T>::bg_log, kGfHeader, "budgets", steps - steps0, bg_rule);
+                if (fl_on) collect_records(fl_series, &Engine<T>::fl_log, kGfHeader, "flow", steps - steps0);
                 total_time = st.total_time; last_dt = st.last_dt; dxl = st.delta_x;
                 const int64_t grown = (steps - steps0) + (st.need_rebuild ? 1 : 0) - (fresh && steps > steps0 ? 1 : 0);
                 if (steps > steps0) fresh = false;
@@ -1742,6 +1748,14 @@ struct MultiEngine final : EngineBase {
         bg_on = false; bg_series.reset(0, 0);
         for (auto& r : R) r.e->bg_enable_device(on);
         bg_on = on;
+    }
+    // The flow through control boxes (sphmi_flow.h): every slab marks and samples the rows it owns — migration happens in the collective
+    // rebuild, between steps, so a row's start state and end state lie in the same slab — and the handle adds the slabs' records of a
+    // step in slab order: every slot is a sum.
+    void fl_enable_device(int32_t n_boxes, const double* lo, const double* hi) override {
+        fl_on = false; fl_series.reset(0, 0);
+        for (auto& r : R) r.e->fl_enable_device(n_boxes, lo, hi);
+        fl_on = n_boxes > 0;
     }
     // after the synchronisation of a batch: the records of its `executed` steps, slab by slab (every slot a sum, or combined by `rule`)
     void collect_records(StepSeries& series, typename Engine<T>::StepLog Engine<T>::*log, int header, const char* what, int64_t executed,

@@ -1,4 +1,4 @@
-// sphmi_series.h — the host side the observers share (group forces, probes, budgets, lattice, columns): the error type, the limits and
+// sphmi_series.h — the host side the observers share (group forces, probes, budgets, flow, lattice, columns): the error type, the limits and
 // record-layout constants host and device agree on, the argument checks every kind of handle reports alike, the per-step series
 // and the means of the kernel sums.  Plain C++17, no HIP: tests/host_series/series_main.cpp compiles it alone.
 #pragma once
@@ -33,6 +33,8 @@ constexpr int kBgValues = 22;                    // the raw budgets of the fluid
 // How two values of slot `slot` of a budget record combine: 0 sum (slots 0 … 12), 1 min, 2 max (13 max |v|², 14 / 15 min / max ρ,
 // 16 … 18 / 19 … 21 min / max x per axis).  The kernels and the host side of a multi-device handle use the same rule.
 constexpr int bg_rule(int slot) { return slot < 13 ? 0 : (slot == 14 || (slot >= 16 && slot <= 18)) ? 1 : 2; }
+constexpr int kMaxFlowBoxes = 16;                // SPHMI_MAX_FLOW_BOXES
+constexpr int kFlValues = 7;                     // per control box (sphmi_flow.h): n_after, Σ1/ρ, Σv[3], entered, left — every slot a sum
 
 // sphmi_attach_columns: the argument errors every kind of handle reports alike
 inline void check_column_table(int32_t n_columns, const void* const* columns, const int32_t* row_bytes) {
@@ -64,6 +66,19 @@ inline void check_probe_table(int32_t n_probes, const double* positions, int dim
     if (capacity_steps < 1) throw EngineError(SPHMI_ERR_ARGUMENT, "sphmi_probes_enable: capacity_steps must be positive");
     for (int64_t k = 0; k < (int64_t)n_probes * dims; ++k)
         if (!std::isfinite(positions[k])) throw EngineError(SPHMI_ERR_ARGUMENT, "sphmi_probes_enable: non-finite coordinate");
+}
+
+// sphmi_flow_enable: the argument errors every kind of handle reports alike.  A box is half-open, lo <= x < hi per axis; -inf and
+// +inf are bounds like any other, NaN is none, and a box with !(lo < hi) on an axis could hold no row.
+inline void check_flow_table(int32_t n_boxes, const double* lo, const double* hi, int dims, int64_t capacity_steps) {
+    if (n_boxes < 0 || n_boxes > kMaxFlowBoxes) throw EngineError(SPHMI_ERR_ARGUMENT, "sphmi_flow_enable: n_boxes out of range [0, 16]");
+    if (n_boxes == 0) return;
+    if (!lo || !hi) throw EngineError(SPHMI_ERR_ARGUMENT, "sphmi_flow_enable: null table");
+    if (capacity_steps < 1) throw EngineError(SPHMI_ERR_ARGUMENT, "sphmi_flow_enable: capacity_steps must be positive");
+    for (int64_t k = 0; k < (int64_t)n_boxes * dims; ++k) {
+        if (std::isnan(lo[k]) || std::isnan(hi[k])) throw EngineError(SPHMI_ERR_ARGUMENT, "sphmi_flow_enable: NaN bound");
+        if (!(lo[k] < hi[k])) throw EngineError(SPHMI_ERR_ARGUMENT, "sphmi_flow_enable: every box needs lo < hi on every axis");
+    }
 }
 
 // sphmi_sample_grid: the argument errors every kind of handle reports alike; returns the number of nodes
@@ -175,6 +190,21 @@ inline void deliver_budgets(const BudgetFactors& f, int64_t k, const double* v, 
     if (centre) for (int d = 0; d < 3; ++d) centre[3 * k + d] = some ? v[10 + d] / v[0] : 0.0;
     if (extremes) { extremes[3 * k] = some ? std::sqrt(v[13]) : 0.0; extremes[3 * k + 1] = some ? v[14] : 0.0; extremes[3 * k + 2] = some ? v[15] : 0.0; }
     if (box) for (int d = 0; d < 6; ++d) box[6 * k + d] = some ? v[16 + d] : 0.0;
+}
+
+// sphmi_flow_read: the raw record { n_after, Σ1/ρ, Σv[3], entered, left } per box of the k-th delivered step: the counts as they are
+// (exact integers carried in doubles), volume and momentum one multiplication by m₀ each
+inline void deliver_flow(double m0, int n_boxes, int64_t k, const double* raw, int64_t* count, double* volume, double* momentum, int64_t* entered,
+                         int64_t* left) {
+    for (int b = 0; b < n_boxes; ++b) {
+        const double* v = raw + (size_t)kFlValues * b;
+        const size_t at = (size_t)k * n_boxes + b;
+        if (count) count[at] = (int64_t)v[0];
+        if (volume) volume[at] = m0 * v[1];
+        if (momentum) for (int d = 0; d < 3; ++d) momentum[3 * at + d] = m0 * v[2 + d];
+        if (entered) entered[at] = (int64_t)v[5];
+        if (left) left[at] = (int64_t)v[6];
+    }
 }
 
 // The host side of sphmi_sample_grid: the raw sums { S, SP, Sρ, Sv[3], n } of the lattice (sphmi_field_grid.h), the ones the

@@ -18,6 +18,7 @@ from ._abi import make_config
 from .config import (SimulationConstants, SimulationMetaData, SPHDensityDiffusion, SPHKernelInstance,
                      SPHViscosity, next_output_time)
 from .budgets import empty_budgets
+from .flow import empty_flow
 from .engine import Engine
 from .preprocess import LoadMDBCNormals, SimParticles
 
@@ -44,7 +45,8 @@ def RunSimulation(*, SimGeometry=None, SimMetaData: SimulationMetaData, SimConst
                   on_output: Optional[Callable[[SimulationMetaData, SimParticles], None]] = None,
                   device_float_bytes: int = 0, device: int = 0, backend_factory=None,
                   async_output: bool = False, group_forces=None, probes=None, field_grid=None,
-                  particle_fields=None, budgets: bool = False, neighbor_list: bool = False, isosurface=None, components=None) -> List[float]:
+                  particle_fields=None, budgets: bool = False, neighbor_list: bool = False, isosurface=None, components=None,
+                  flow_boxes=None) -> List[float]:
     """Same keyword signature as the reference (src/SPHCellList.jl:808-817); returns the list of
     time steps the reference collects in ``TimeSteps`` (:823,:884).  ``SimParticles`` is updated in
     place at every output time, in the engine's cell-sorted order, as the reference's is.
@@ -92,7 +94,13 @@ def RunSimulation(*, SimGeometry=None, SimMetaData: SimulationMetaData, SimConst
     ``budgets=True``: the energy, momentum and extent budgets of the fluid are recorded on the device at every step
     (``Backend.budgets_enable``; ``sphexample_amd.budgets`` adds up a total energy and reads a wave front off the box) and
     ``on_output`` receives the samples of the interval, the dict of ``Backend.budgets_read``, as its last argument (empty
-    arrays at the first call).  ``False`` (default): nothing is recorded and the callback keeps its arguments."""
+    arrays at the first call).  ``False`` (default): nothing is recorded and the callback keeps its arguments.
+
+    ``flow_boxes=[(lo, hi), …]``: the flow through those half-open control boxes (``lo <= x < hi`` per axis, ``dims`` bounds each,
+    ``±inf`` allowed; ``sphexample_amd.flow.strips`` tiles an axis) is recorded on the device at every step
+    (``Backend.flow_enable``; ``sphexample_amd.flow`` forms discharges and cumulative counts) and ``on_output`` receives the
+    samples of the interval, the dict of ``Backend.flow_read``, as one more argument behind the budgets (empty arrays at the
+    first call).  ``None`` (default): nothing is recorded and the callback keeps its arguments."""
     if SimMetaData.BMode.__name__ == "SimpleMDBC":
         LoadMDBCNormals(SimParticles, ParticleNormalsPath)                       # :827
     host_bytes = SimParticles.Position.dtype.itemsize
@@ -147,6 +155,12 @@ def RunSimulation(*, SimGeometry=None, SimMetaData: SimulationMetaData, SimConst
     if budgets:
         eng.budgets_enable(capacity=1 << 20)
         extras.append((empty_budgets(), eng.budgets_read))
+    if flow_boxes is not None:
+        if len(flow_boxes) == 0:
+            raise ValueError("RunSimulation: flow_boxes holds no box (pass None to record nothing)")
+        boxes = [(np.asarray(lo, dtype=np.float64), np.asarray(hi, dtype=np.float64)) for lo, hi in flow_boxes]
+        eng.flow_enable([lo for lo, _ in boxes], [hi for _, hi in boxes], capacity=1 << 20)
+        extras.append((empty_flow(len(boxes)), eng.flow_read))
     none_yet = tuple(first for first, _ in extras)
     emit = lambda meta, samples: on_output(meta, SimParticles, *samples)         # noqa: E731
     if on_output:
