@@ -10,7 +10,9 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc")
 LIB = os.path.join(_HERE, "libsphmi.so")
 SOURCES = ["sphmi_engine.hip"]
-HEADERS = ["sphmi_kernels.h", "sphmi_rebuild.h", "sphmi_columns.h", "sphmi_group_forces.h", "sphmi_probes.h", "sphmi_budgets.h", "sphmi_flow.h", "sphmi_field_grid.h", "sphmi_particle_fields.h", "sphmi_neighbor_list.h", "sphmi_components.h", "sphmi_isosurface.h", "sphmi_iso_core.h", "sphmi_multi.h", "sphmi_shm.h", "sphmi_series.h", os.path.join("..", "..", "include", "sphmi.h")]
+# every header of the library, by directory: whatever is added there makes the built library stale
+INCLUDE = os.path.join(os.path.dirname(_HERE), "include")
+HEADERS = sorted(f for f in os.listdir(CSRC) if f.endswith(".h")) + sorted(os.path.join("..", "..", "include", f) for f in os.listdir(INCLUDE) if f.endswith(".h"))
 
 
 def hipcc() -> str:

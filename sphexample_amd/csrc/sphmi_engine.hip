@@ -99,6 +99,10 @@ struct HostBounce {
     }
 };
 
+}  // namespace sphmi
+#include "sphmi_results.h"                     // (behind HC and HostBounce, which it uses)
+namespace sphmi {
+
 // Phase labels follow the reference's TimerOutputs sections (src/SPHCellList.jl:748-800).
 enum Phase { PH_TIMESTEP = 0, PH_REBUILD, PH_MDBC, PH_PASS1, PH_PASS2, PH_COUNT, PH_PASS1_EDGE, PH_PASS2_EDGE, PH_REBUILD_DEVICE };
 static const char* kPhaseNames[PH_COUNT] = {
@@ -126,6 +130,13 @@ struct EngineBase {
     }
     // entry points that need every row in this process: a multi-device handle refuses them in rank mode
     virtual void require_one_process(const char* fn) const { require_uploaded(fn); }
+    // what every on-demand sampler asks for: every row in this process, h <= H, and a cell list (`cell_list`) — which the first step
+    // after an upload leaves; `tail` names what else that step leaves and the caller reads
+    void require_cell_list(const char* fn, bool cell_list, const char* tail = "(no cell list)") const {
+        require_one_process(fn);
+        if (!(cfg.h <= cfg.H)) throw EngineError(SPHMI_ERR_STATE, std::string(fn) + ": handles with H < h are not served (the candidate cells are laid out for H + h <= 2H)");
+        if (!cell_list) throw EngineError(SPHMI_ERR_STATE, std::string(fn) + ": the handle has not executed a step since the upload " + tail);
+    }
     // The observers' series (sphmi_series.h).  A multi-device handle keeps them itself; those of its slab engines stay empty.
     bool gf_on = false, pr_on = false, bg_on = false, fl_on = false;
     StepSeries gf_series, pr_series;           // payload: 3 forces per group / the RAW sums, kPrValues per probe (the read normalises)
@@ -208,25 +219,33 @@ struct EngineBase {
     virtual void sample_grid(const double* origin, const double* spacing, const int64_t* counts, double* weight, int64_t* count, double* pressure,
                              double* density, double* velocity) = 0;
     virtual void particle_fields(int64_t* count, double* shepard, double* normal, double* div_r, double* div_v, double* vorticity) = 0;
-    // The neighbour list (sphmi_neighbor_list.h).  nl_state: whether a built list matches the rows; sphmi_advance, sphmi_upload, the
-    // generator and sphmi_forces_once turn NL_VALID into NL_STALE at the C boundary.
-    enum { NL_NONE = 0, NL_VALID, NL_STALE };
-    int nl_state = NL_NONE;
-    void neighbors_stale() { if (nl_state == NL_VALID) nl_state = NL_STALE; }
+    // The results a handle holds between calls (HeldResult, sphmi_results.h): the neighbour list (sphmi_neighbor_list.h), the free
+    // surface as a mesh (sphmi_isosurface.h) and the connected bodies of selected rows (sphmi_components.h).  sphmi_advance,
+    // sphmi_upload, the generator and sphmi_forces_once call results_stale() at the C boundary.  A read checks the state here and
+    // then asks the engine for the arrays; only an engine that built a result is ever asked.
+    HeldResult nl_held, iso_held, cc_held;
+    void results_stale() { for (HeldResult* r : {&nl_held, &iso_held, &cc_held}) r->stale(); }
     virtual void neighbors_build(int32_t mode, int64_t* n_rows_out, int64_t* n_pairs_out) = 0;
-    virtual void neighbors_read(int64_t*, int32_t*) { throw EngineError(SPHMI_ERR_STATE, "sphmi_neighbors_read: no neighbour list is held (sphmi_neighbors_build)"); }
+    virtual void neighbors_fetch(int64_t*, int32_t*) {}
     virtual void neighbors_release() {}
-    // The free surface as a mesh (sphmi_isosurface.h): the same lifetime, the same calls mark it stale.
-    int iso_state = NL_NONE;
-    void results_stale() { neighbors_stale(); if (iso_state == NL_VALID) iso_state = NL_STALE; if (cc_state == NL_VALID) cc_state = NL_STALE; }
+    void neighbors_read(int64_t* offsets_out, int32_t* neighbors_out) {
+        nl_held.require_readable("sphmi_neighbors_read", "no neighbour list is held (sphmi_neighbors_build)", "the neighbour list is stale (rows may have moved since sphmi_neighbors_build)");
+        neighbors_fetch(offsets_out, neighbors_out);
+    }
     virtual void isosurface_build(const double* origin, const double* spacing, const int64_t* counts, double level, int64_t* n_vertices_out, int64_t* n_elements_out) = 0;
-    virtual void isosurface_read(double*, int32_t*, double*, double*) { throw EngineError(SPHMI_ERR_STATE, "sphmi_isosurface_read: no mesh is held (sphmi_isosurface_build)"); }
+    virtual void isosurface_fetch(double*, int32_t*, double*, double*) {}
     virtual void isosurface_release() {}
-    // The connected bodies of selected rows (sphmi_components.h): the same lifetime, the same calls mark it stale.
-    int cc_state = NL_NONE;
+    void isosurface_read(double* vertices_out, int32_t* elements_out, double* pressure_out, double* velocity_out) {
+        iso_held.require_readable("sphmi_isosurface_read", "no mesh is held (sphmi_isosurface_build)", "the mesh is stale (rows may have moved since sphmi_isosurface_build)");
+        isosurface_fetch(vertices_out, elements_out, pressure_out, velocity_out);
+    }
     virtual void components_build(double link, uint32_t type_mask, int64_t* n_rows_out, int64_t* n_components_out) = 0;
-    virtual void components_read(int32_t*, int32_t*, int32_t*, double*) { throw EngineError(SPHMI_ERR_STATE, "sphmi_components_read: no components are held (sphmi_components_build)"); }
+    virtual void components_fetch(int32_t*, int32_t*, int32_t*, double*) {}
     virtual void components_release() {}
+    void components_read(int32_t* label_out, int32_t* first_row_out, int32_t* count_out, double* box_out) {
+        cc_held.require_readable("sphmi_components_read", "no components are held (sphmi_components_build)", "the components are stale (rows may have moved since sphmi_components_build)");
+        components_fetch(label_out, first_row_out, count_out, box_out);
+    }
     virtual void unique_cells(int64_t* out, int64_t cap, int64_t* n) = 0;
     virtual void timers(int32_t cap, const char** names, double* secs, int64_t* calls, int32_t* n) = 0;
     virtual void force_stats(int reset, double* avg_ms, int64_t* launches) = 0;
@@ -498,7 +517,7 @@ struct Engine final : EngineBase {
         for (auto& e : host_pinned) (void)hipHostUnregister(e.first);
         (void)hipFree(out_arena);
         (void)hipFree(col_arena); (void)hipFree(col_store); (void)hipFree(col_base[0]); (void)hipFree(col_base[1]);
-        gf_release(); pr_release(); bg_release(); fl_release(); (void)hipFree(fg_arena.p); (void)hipFree(pf_arena.p); nl_free(); iso_free(); cc_free();
+        gf_release(); pr_release(); bg_release(); fl_release(); fg_arena.free(); pf_arena.free(); nl_free(); iso_free(); cc_free();
         (void)hipFree(slot); (void)hipFree(tmp_idx); (void)hipFree(perm);
         for (int k = 0; k < 2; ++k) { (void)hipFree(tile_cost[k]); (void)hipFree(tile_order[k]); }
         (void)hipFree(kout_d); (void)hipFree(tile_work_d); (void)hipFree(tile_work1_d); (void)hipFree(xcd_clock_d); (void)hipHostFree(xcd_clock_h);
@@ -1678,14 +1697,15 @@ struct Engine final : EngineBase {
     // page-locked mirror, fetched with the control block of a batch.  obs_iteration0 / obs_steps_base: the clock of the batch.
     struct StepLog {
         static constexpr int slots = kBatch;
-        double *d = nullptr, *m = nullptr;
+        DeviceBuf<double> d;
+        double* m = nullptr;
         int record_doubles = 0;
-        void alloc(int alloc_record_doubles, int record) {
-            HC(hipMalloc(&d, (size_t)slots * alloc_record_doubles * 8)); HC(hipHostMalloc(&m, (size_t)slots * alloc_record_doubles * 8));
+        void alloc(int alloc_record_doubles, int record) {          // (of a released log)
+            d.need((size_t)slots * alloc_record_doubles); HC(hipHostMalloc(&m, (size_t)slots * alloc_record_doubles * 8));
             record_doubles = record;
         }
-        void release() { (void)hipFree(d); (void)hipHostFree(m); d = m = nullptr; record_doubles = 0; }
-        void fetch(int batch, hipStream_t s) { HC(hipMemcpyAsync(m, d, (size_t)std::min(batch, slots) * (size_t)record_doubles * 8, hipMemcpyDeviceToHost, s)); }
+        void release() { d.free(); (void)hipHostFree(m); m = nullptr; record_doubles = 0; }
+        void fetch(int batch, hipStream_t s) { HC(hipMemcpyAsync(m, d.p, (size_t)std::min(batch, slots) * (size_t)record_doubles * 8, hipMemcpyDeviceToHost, s)); }
         const double* record(int64_t k) const { return m + (size_t)k * (size_t)record_doubles; }      // of the k-th executed step of the fetched batch
     };
     int64_t obs_iteration0 = 0, obs_steps_base = 0;
@@ -1693,22 +1713,20 @@ struct Engine final : EngineBase {
     static void push_records(StepSeries& series, const StepLog& log, int header, int64_t executed) {
         for (int64_t k = 0; k < executed; ++k) series.push(StepSeries::decode(log.record(k), header, series.values));
     }
-    // The results of an on-demand sampler: device memory that only grows.
-    struct DeviceArena {
-        double* p = nullptr; size_t doubles = 0;
-        void need(size_t n, const char* fn_name, const char* what, long long count) {
-            if (n <= doubles) return;
-            (void)hipFree(p);
-            p = nullptr; doubles = 0;
-            if (hipMalloc(&p, n * 8) != hipSuccess) {
-                (void)hipGetLastError();
-                char buf[160];
-                snprintf(buf, sizeof(buf), "%s: no device memory for the result arena of %lld %s (%.2f GB)", fn_name, count, what, (double)n * 8.0 / 1e9);
-                throw EngineError(SPHMI_ERR_DEVICE, buf);
-            }
-            doubles = n;
+    // Switching an observer off, the part all four share: nothing is sampled from here on, the series is empty, and once the stream
+    // has drained the device side goes back (`release`, which also clears the observer's table).  Not on: only the release, so that
+    // an enable that failed half way leaves nothing behind for the next one.
+    void observer_off(bool& on, StepSeries& series, void (Engine::*release)()) {
+        if (on) {
+            on = false; series.reset(0, 0);
+            HC(hipSetDevice(cfg.device)); HC(hipStreamSynchronize(stream));
         }
-    };
+        (this->*release)();
+    }
+    // The <T, 3> / <T, 2> instantiation of a kernel by the handle's D: f(std::integral_constant<int, D>) makes the launch.
+    template <class F> void by_dims(F&& f) const {
+        if (D == 3) f(std::integral_constant<int, 3>{}); else f(std::integral_constant<int, 2>{});
+    }
     // a result → host, behind its kernel: directly into memory the caller page-locked — there after the next synchronisation of
     // the stream — else through the bounce buffer
     void fetch_result(void* dst, const void* src, size_t bytes) {
@@ -1730,35 +1748,27 @@ struct Engine final : EngineBase {
     // Off: none of the members below is touched by a step.  On: three launches behind every rebuild that permutes (the row
     // lists), one or two behind every corrector (the sums → the batch's log), one more copy per batch boundary.
     GroupTable gf_table{};
-    int *gf_list = nullptr, *gf_counts = nullptr, *gf_offsets = nullptr;
-    GroupListMeta* gf_meta = nullptr;
-    double* gf_partial = nullptr;
+    DeviceBuf<int> gf_list, gf_counts, gf_offsets;
+    DeviceBuf<GroupListMeta> gf_meta;
+    DeviceBuf<double> gf_partial;
     StepLog gf_log;
     int gf_nblk_cap() const { return (cap + 255) / 256; }
     int gf_list_cap() const { return cap + kMaxForceGroups * kGfChunk; }
     int gf_chunk_cap() const { return cap / kGfChunk + kMaxForceGroups + 1; }
     void gf_release() {
-        (void)hipFree(gf_list); (void)hipFree(gf_counts); (void)hipFree(gf_offsets); (void)hipFree(gf_meta); (void)hipFree(gf_partial);
-        gf_list = gf_counts = gf_offsets = nullptr; gf_meta = nullptr; gf_partial = nullptr;
-        gf_log.release();
+        gf_list.free(); gf_counts.free(); gf_offsets.free(); gf_meta.free(); gf_partial.free(); gf_log.release();
+        gf_table = GroupTable{};
     }
-    void gf_disable() {
-        if (!gf_on) return;
-        gf_on = false; gf_table = GroupTable{}; gf_series.reset(0, 0);
-        HC(hipStreamSynchronize(stream));
-        gf_release();
-    }
+    void gf_disable() { observer_off(gf_on, gf_series, &Engine::gf_release); }
     void gf_enable_device(int32_t n_groups, const uint64_t* markers) override {
         HC(hipSetDevice(cfg.device));
         gf_disable();
         if (n_groups == 0) return;
-        try {
-            HC(hipMalloc(&gf_list, (size_t)gf_list_cap() * 4));
-            HC(hipMalloc(&gf_counts, (size_t)kMaxForceGroups * gf_nblk_cap() * 4)); HC(hipMalloc(&gf_offsets, (size_t)kMaxForceGroups * gf_nblk_cap() * 4));
-            HC(hipMalloc(&gf_meta, sizeof(GroupListMeta))); HC(hipMemset(gf_meta, 0, sizeof(GroupListMeta)));
-            HC(hipMalloc(&gf_partial, (size_t)gf_chunk_cap() * 3 * 8));
-            gf_log.alloc(kGfRecordMax, kGfHeader + 3 * n_groups);
-        } catch (...) { gf_release(); throw; }
+        gf_list.need((size_t)gf_list_cap());
+        gf_counts.need((size_t)kMaxForceGroups * gf_nblk_cap()); gf_offsets.need((size_t)kMaxForceGroups * gf_nblk_cap());
+        gf_meta.need(1); HC(hipMemset(gf_meta.p, 0, sizeof(GroupListMeta)));
+        gf_partial.need((size_t)gf_chunk_cap() * 3);
+        gf_log.alloc(kGfRecordMax, kGfHeader + 3 * n_groups);
         gf_table.n = n_groups;
         for (int g = 0; g < n_groups; ++g) gf_table.marker[g] = markers[g];
         gf_on = true;
@@ -1767,16 +1777,16 @@ struct Engine final : EngineBase {
     }
     void gf_build_lists() {
         const int nblk = (N + 255) / 256;
-        hipLaunchKernelGGL(k_gf_count, dim3(nblk), dim3(256), 0, stream, (const unsigned long long*)grp[cur], (const uint8_t*)type[cur], N, gf_table, nblk, gf_counts);
-        hipLaunchKernelGGL(k_gf_offsets, dim3(1), dim3(1024), 0, stream, (const int*)gf_counts, nblk, gf_table.n, gf_offsets, gf_meta);
+        hipLaunchKernelGGL(k_gf_count, dim3(nblk), dim3(256), 0, stream, (const unsigned long long*)grp[cur], (const uint8_t*)type[cur], N, gf_table, nblk, gf_counts.p);
+        hipLaunchKernelGGL(k_gf_offsets, dim3(1), dim3(1024), 0, stream, (const int*)gf_counts.p, nblk, gf_table.n, gf_offsets.p, gf_meta.p);
         hipLaunchKernelGGL(k_gf_fill, dim3(nblk), dim3(256), 0, stream, (const unsigned long long*)grp[cur], (const uint8_t*)type[cur], N, gf_table, nblk,
-                           (const int*)gf_offsets, gf_list, gf_list_cap());
+                           (const int*)gf_offsets.p, gf_list.p, gf_list_cap());
         HC(hipGetLastError());
     }
     // behind the corrector of a queued step; `ctrl`: the control block that corrector read
     void gf_sample(const StepCtrl* ctrl, int64_t iteration0, int64_t steps_base) {
         GroupSampleArgs A{};
-        A.ctrl = ctrl; A.list = gf_list; A.meta = gf_meta; A.partial = gf_partial; A.log = gf_log.d;
+        A.ctrl = ctrl; A.list = gf_list.p; A.meta = gf_meta.p; A.partial = gf_partial.p; A.log = gf_log.d.p;
         A.iteration0 = iteration0; A.steps_base = steps_base; A.m0 = cfg.m0;
         A.n_groups = gf_table.n; A.N = N; A.D = D; A.record = gf_log.record_doubles; A.slots = StepLog::slots;
         if (N <= kGfSmallRows) hipLaunchKernelGGL(k_gf_small<T>, dim3(1), dim3(kGfChunk), 0, stream, (const V4*)acc[cur], A);
@@ -1791,18 +1801,10 @@ struct Engine final : EngineBase {
     // ---- kernel sums at fixed probe points (sphmi_probes.h) -----------------------------------------------------------------
     // The records of a batch go where the group forces' go: a log of kBatch slots on the device, fetched with the control block.
     int pr_n = 0;
-    double* pr_pos_d = nullptr;
+    DeviceBuf<double> pr_pos_d;
     StepLog pr_log;
-    void pr_release() {
-        (void)hipFree(pr_pos_d); pr_pos_d = nullptr;
-        pr_log.release();
-    }
-    void pr_disable() {
-        if (!pr_on) return;
-        pr_on = false; pr_n = 0; pr_series.reset(0, 0);
-        HC(hipSetDevice(cfg.device)); HC(hipStreamSynchronize(stream));
-        pr_release();
-    }
+    void pr_release() { pr_pos_d.free(); pr_log.release(); pr_n = 0; }
+    void pr_disable() { observer_off(pr_on, pr_series, &Engine::pr_release); }
     void pr_enable_device(int32_t n_probes, const double* positions) override {
         HC(hipSetDevice(cfg.device));
         pr_disable();
@@ -1810,11 +1812,9 @@ struct Engine final : EngineBase {
         if (!(cfg.h <= cfg.H)) throw EngineError(SPHMI_ERR_STATE, "sphmi_probes_enable: handles with H < h are not served (the candidate cells of a probe are laid out for H + h <= 2H)");
         std::vector<double> xyz((size_t)3 * n_probes, 0.0);
         for (int p = 0; p < n_probes; ++p) for (int d = 0; d < D; ++d) xyz[3 * (size_t)p + d] = positions[(size_t)p * D + d];
-        try {
-            HC(hipMalloc(&pr_pos_d, xyz.size() * 8));
-            pr_log.alloc(kPrHeader + kPrValues * n_probes, kPrHeader + kPrValues * n_probes);
-            bounce.h2d(pr_pos_d, xyz.data(), xyz.size() * 8, stream);
-        } catch (...) { pr_release(); throw; }
+        pr_pos_d.need(xyz.size());
+        pr_log.alloc(kPrHeader + kPrValues * n_probes, kPrHeader + kPrValues * n_probes);
+        bounce.h2d(pr_pos_d.p, xyz.data(), xyz.size() * 8, stream);
         pr_n = n_probes;
         pr_on = true;
     }
@@ -1822,7 +1822,7 @@ struct Engine final : EngineBase {
     void pr_sample(const StepCtrl* ctrl, int64_t iteration0, int64_t steps_base, int set) {
         ProbeSampleArgs<T> A{};
         A.ctrl = ctrl; A.pk0 = pk0[set]; A.pk1 = pk1[set]; A.half0 = pk0[iH]; A.comp = comp[cur];
-        A.type = dd_slab ? type[cur] : nullptr; A.cstart = cstart; A.pos = pr_pos_d; A.log = pr_log.d; A.g = grid;
+        A.type = dd_slab ? type[cur] : nullptr; A.cstart = cstart; A.pos = pr_pos_d.p; A.log = pr_log.d.p; A.g = grid;
         A.iteration0 = iteration0; A.steps_base = steps_base;
         fill_sample_consts(A);
         A.n_probes = pr_n; A.N = N; A.D = D; A.kernel = cfg.kernel; A.record = pr_log.record_doubles; A.slots = StepLog::slots;
@@ -1833,37 +1833,27 @@ struct Engine final : EngineBase {
     // ---- the budgets of the fluid at every step (sphmi_budgets.h) ----------------------------------------------------------------
     // No row lists: every launch looks at every row, so rebuilds need no hook.  One launch behind every corrector on handles of at
     // most bg_small_rows rows, two above; the records of a batch go where the group forces' go.
-    double* bg_partial = nullptr;
+    DeviceBuf<double> bg_partial;
     StepLog bg_log;
     int bg_small_rows = kBgSmallRows;          // $SPHMI_BUDGETS_SMALL_ROWS, read at enable (0: always two stages)
     int bg_nblk_cap() const { return (cap + kBgBlock - 1) / kBgBlock; }
-    void bg_release() {
-        (void)hipFree(bg_partial); bg_partial = nullptr;
-        bg_log.release();
-    }
-    void bg_disable() {
-        if (!bg_on) return;
-        bg_on = false; bg_series.reset(0, 0);
-        HC(hipSetDevice(cfg.device)); HC(hipStreamSynchronize(stream));
-        bg_release();
-    }
+    void bg_release() { bg_partial.free(); bg_log.release(); }
+    void bg_disable() { observer_off(bg_on, bg_series, &Engine::bg_release); }
     void bg_enable_device(bool on) override {
         HC(hipSetDevice(cfg.device));
         bg_disable();
         if (!on) return;
         bg_small_rows = kBgSmallRows;
         if (const char* e = getenv("SPHMI_BUDGETS_SMALL_ROWS")) bg_small_rows = (int)std::min<long long>(std::max<long long>(atoll(e), 0), kBgSmallRowsMax);
-        try {
-            HC(hipMalloc(&bg_partial, (size_t)std::max(bg_nblk_cap(), 1) * kBgValues * 8));
-            bg_log.alloc(kBgRecord, kBgRecord);
-        } catch (...) { bg_release(); throw; }
+        bg_partial.need((size_t)bg_nblk_cap() * kBgValues);
+        bg_log.alloc(kBgRecord, kBgRecord);
         bg_on = true;
     }
     // queued behind the corrector of a step; `set`: the state set that corrector wrote
     void bg_sample(const StepCtrl* ctrl, int64_t iteration0, int64_t steps_base, int set) {
         BudgetArgs<T> A{};
         A.ctrl = ctrl; A.pk0 = pk0[set]; A.pk1 = pk1[set]; A.comp = comp[cur];
-        A.type = dd_slab ? type[cur] : nullptr; A.partial = bg_partial; A.log = bg_log.d;
+        A.type = dd_slab ? type[cur] : nullptr; A.partial = bg_partial.p; A.log = bg_log.d.p;
         A.iteration0 = iteration0; A.steps_base = steps_base; A.rho0 = cfg.rho0;
         A.N = N; A.D = D; A.nblk = std::min((N + kBgBlock - 1) / kBgBlock, bg_nblk_cap()); A.slots = StepLog::slots;
         if (N <= bg_small_rows) hipLaunchKernelGGL(k_bg_small<T>, dim3(1), dim3(kBgBlock), 0, stream, A);
@@ -1877,23 +1867,14 @@ struct Engine final : EngineBase {
     // ---- the flow through control boxes at every step (sphmi_flow.h) -----------------------------------------------------------
     // Two streaming passes per step: the marks before anything of the step runs, the sample behind its corrector (one launch on
     // handles of at most fl_small_rows rows, two above).  No row lists, so rebuilds have no hook: they run between steps.
-    uint16_t* fl_mark_d = nullptr;
-    double* fl_partial = nullptr;
+    DeviceBuf<uint16_t> fl_mark_d;
+    DeviceBuf<double> fl_partial;
     StepLog fl_log;
     FlowBoxes fl_boxes{};
     int fl_small_rows = kFlSmallRows;          // $SPHMI_FLOW_SMALL_ROWS, read at enable (0: always two stages)
     int fl_nblk_cap() const { return (cap + kFlBlock - 1) / kFlBlock; }
-    void fl_release() {
-        (void)hipFree(fl_mark_d); fl_mark_d = nullptr;
-        (void)hipFree(fl_partial); fl_partial = nullptr;
-        fl_log.release();
-    }
-    void fl_disable() {
-        if (!fl_on) return;
-        fl_on = false; fl_boxes.n = 0; fl_series.reset(0, 0);
-        HC(hipSetDevice(cfg.device)); HC(hipStreamSynchronize(stream));
-        fl_release();
-    }
+    void fl_release() { fl_mark_d.free(); fl_partial.free(); fl_log.release(); fl_boxes.n = 0; }
+    void fl_disable() { observer_off(fl_on, fl_series, &Engine::fl_release); }
     void fl_enable_device(int32_t n_boxes, const double* lo, const double* hi) override {
         HC(hipSetDevice(cfg.device));
         fl_disable();
@@ -1907,17 +1888,15 @@ struct Engine final : EngineBase {
         fl_small_rows = kFlSmallRows;
         if (const char* e = getenv("SPHMI_FLOW_SMALL_ROWS")) fl_small_rows = (int)std::min<long long>(std::max<long long>(atoll(e), 0), kFlSmallRowsMax);
         const int record = kGfHeader + kFlValues * n_boxes;
-        try {
-            HC(hipMalloc(&fl_mark_d, (size_t)std::max(cap, 1) * sizeof(uint16_t)));
-            HC(hipMalloc(&fl_partial, (size_t)std::max(fl_nblk_cap(), 1) * n_boxes * kFlValues * 8));
-            fl_log.alloc(record, record);
-        } catch (...) { fl_release(); throw; }
+        fl_mark_d.need((size_t)cap);
+        fl_partial.need((size_t)fl_nblk_cap() * n_boxes * kFlValues);
+        fl_log.alloc(record, record);
         fl_boxes.n = n_boxes;
         fl_on = true;
     }
     template <class A> void fl_fill(A& a, int set) const {
         a.pk0 = pk0[set]; a.pk1 = pk1[set]; a.comp = comp[cur];
-        a.type = dd_slab ? type[cur] : nullptr; a.mark = fl_mark_d; a.partial = fl_partial; a.log = fl_log.d;
+        a.type = dd_slab ? type[cur] : nullptr; a.mark = fl_mark_d.p; a.partial = fl_partial.p; a.log = fl_log.d.p;
         a.N = N; a.D = D; a.nblk = std::min((N + kFlBlock - 1) / kFlBlock, fl_nblk_cap()); a.slots = StepLog::slots;
         a.box = fl_boxes;
     }
@@ -1946,12 +1925,14 @@ struct Engine final : EngineBase {
     // ---- kernel sums on a regular lattice, on demand (sphmi_field_grid.h) ------------------------------------------------------
     // Reads what sphmi_download reads — the current set, the half-step set, the low words — plus `cstart` and the grid of the last
     // rebuild; writes its own arena and nothing else.  A download in flight keeps out_arena and the copy stream to itself.
-    DeviceArena fg_arena;
+    DeviceBuf<double> fg_arena;
     bool fg_ready() const { return stepped && have_grid && cstart != nullptr && N > 0; }
     // queue the kernel for the whole lattice on the engine's stream (a multi-device handle calls it on every slab engine)
     void fg_launch(const double* origin, const double* spacing, const int64_t* counts, int64_t nodes) {
         HC(hipSetDevice(cfg.device));
-        fg_arena.need((size_t)kFgValues * (size_t)nodes, "sphmi_sample_grid", "nodes", (long long)nodes);
+        fg_arena.need((size_t)kFgValues * (size_t)nodes, [&](size_t bytes) {
+            return text("sphmi_sample_grid: no device memory for the result arena of %lld nodes (%.2f GB)", (long long)nodes, (double)bytes / 1e9);
+        });
         FieldGridArgs<T> A{};
         A.pk0 = pk0[iA]; A.pk1 = pk1[iA]; A.half0 = pk0[iH]; A.comp = comp[cur];
         A.type = dd_slab ? type[cur] : nullptr; A.cstart = cstart; A.out = fg_arena.p; A.g = grid;
@@ -1963,8 +1944,7 @@ struct Engine final : EngineBase {
         A.nodes = nodes;
         fill_sample_consts(A);
         A.N = N; A.kernel = cfg.kernel;
-        if (D == 3) hipLaunchKernelGGL((k_field_grid<T, 3>), dim3((unsigned)nb), dim3(kFgThreads), 0, stream, A);
-        else        hipLaunchKernelGGL((k_field_grid<T, 2>), dim3((unsigned)nb), dim3(kFgThreads), 0, stream, A);
+        by_dims([&](auto d) { hipLaunchKernelGGL((k_field_grid<T, decltype(d)::value>), dim3((unsigned)nb), dim3(kFgThreads), 0, stream, A); });
         HC(hipGetLastError());
     }
     // One raw sum of the lattice → host, behind the kernel.  No synchronisation of its own: sample_grid synchronises once before
@@ -1974,9 +1954,7 @@ struct Engine final : EngineBase {
     void fg_fetch(int f, double* dst, int64_t nodes) { fetch_result(dst, fg_arena.p + (size_t)f * (size_t)nodes, (size_t)nodes * 8); }
     void sample_grid(const double* origin, const double* spacing, const int64_t* counts, double* weight, int64_t* count, double* pressure,
                      double* density, double* velocity) override {
-        require_uploaded("sphmi_sample_grid");
-        if (!(cfg.h <= cfg.H)) throw EngineError(SPHMI_ERR_STATE, "sphmi_sample_grid: handles with H < h are not served (the candidate cells are laid out for H + h <= 2H)");
-        if (!fg_ready()) throw EngineError(SPHMI_ERR_STATE, "sphmi_sample_grid: the handle has not executed a step since the upload (no cell list, no half-step set)");
+        require_cell_list("sphmi_sample_grid", fg_ready(), "(no cell list, no half-step set)");
         const int64_t nodes = check_grid_lattice(origin, spacing, counts, D);
         fg_launch(origin, spacing, counts, nodes);
         GridSums G(nodes, weight, count, pressure, density, velocity);
@@ -1987,14 +1965,14 @@ struct Engine final : EngineBase {
 
     // ---- differential fields at the particles, on demand (sphmi_particle_fields.h) -------------------------------------------------
     // Reads the current set, the low words, `cstart` and the grid of the last rebuild; writes its own arena and nothing else.
-    DeviceArena pf_arena;
+    DeviceBuf<double> pf_arena;
     void particle_fields(int64_t* count, double* shepard, double* normal, double* div_r, double* div_v, double* vorticity) override {
-        require_uploaded("sphmi_particle_fields");
-        if (!(cfg.h <= cfg.H)) throw EngineError(SPHMI_ERR_STATE, "sphmi_particle_fields: handles with H < h are not served (the candidate cells are laid out for H + h <= 2H)");
-        if (!fg_ready()) throw EngineError(SPHMI_ERR_STATE, "sphmi_particle_fields: the handle has not executed a step since the upload (no cell list)");
+        require_cell_list("sphmi_particle_fields", fg_ready());
         HC(hipSetDevice(cfg.device));
         const size_t n = (size_t)N;
-        pf_arena.need((size_t)kPfValues * n, "sphmi_particle_fields", "rows", N);
+        pf_arena.need((size_t)kPfValues * n, [&](size_t bytes) {
+            return text("sphmi_particle_fields: no device memory for the result arena of %lld rows (%.2f GB)", (long long)N, (double)bytes / 1e9);
+        });
         double* const a = pf_arena.p;
         ParticleFieldArgs<T> A{};
         A.pk0 = pk0[iA]; A.pk1 = pk1[iA]; A.comp = comp[cur]; A.cstart = cstart; A.g = grid;
@@ -2003,8 +1981,7 @@ struct Engine final : EngineBase {
         fill_kernel_consts(A);
         A.N = N; A.kernel = cfg.kernel;
         const unsigned nb = (unsigned)((N + kPfThreads - 1) / kPfThreads);
-        if (D == 3) hipLaunchKernelGGL((k_particle_fields<T, 3>), dim3(nb), dim3(kPfThreads), 0, stream, A);
-        else        hipLaunchKernelGGL((k_particle_fields<T, 2>), dim3(nb), dim3(kPfThreads), 0, stream, A);
+        by_dims([&](auto d) { hipLaunchKernelGGL((k_particle_fields<T, decltype(d)::value>), dim3(nb), dim3(kPfThreads), 0, stream, A); });
         HC(hipGetLastError());
         auto fetch = [&](void* dst, const double* src, size_t doubles) { if (dst) fetch_result(dst, src, doubles * 8); };
         fetch(count, a, n); fetch(shepard, A.shepard, n); fetch(normal, A.normal, 3 * n); fetch(div_r, A.div_r, n);
@@ -2013,97 +1990,59 @@ struct Engine final : EngineBase {
     }
 
     // ---- the neighbour list of every row, on demand (sphmi_neighbor_list.h) -----------------------------------------------------------
-    // Reads the current set's positions, the low words, `cstart` and the grid of the last rebuild; writes its own arena and nothing
-    // else.  The arena: counts [N] int32, tile sums, offsets [N + 1] int64 — they grow with N — and the entries, which grow with the
-    // pair count and go back to the device at sphmi_neighbors_release.  nl_state (EngineBase) tells whether it matches the rows.
-    int *nl_counts = nullptr, *nl_entries = nullptr;
-    long long *nl_offsets = nullptr, *nl_tsum = nullptr;
-    size_t nl_rows_cap = 0, nl_entries_cap = 0;
+    // Reads the current set's positions, the low words, `cstart` and the grid of the last rebuild; writes its own buffers and nothing
+    // else: counts [N] int32, the scan's tile sums, offsets [N + 1] int64 — they grow with N — and the entries, which grow with the
+    // pair count.  All go back to the device at sphmi_neighbors_release.  nl_held (EngineBase) tells whether they match the rows.
+    DeviceBuf<int> nl_counts, nl_entries;
+    DeviceBuf<long long> nl_offsets, nl_tsum;
     int64_t nl_rows = 0, nl_pairs = 0;
     void nl_free() {
-        (void)hipFree(nl_counts); (void)hipFree(nl_entries); (void)hipFree(nl_offsets); (void)hipFree(nl_tsum);
-        nl_counts = nl_entries = nullptr; nl_offsets = nl_tsum = nullptr;
-        nl_rows_cap = nl_entries_cap = 0; nl_rows = nl_pairs = 0;
-        nl_state = NL_NONE;
-    }
-    void nl_alloc(void** p, size_t bytes, long long pairs) {
-        if (hipMalloc(p, bytes) == hipSuccess) return;
-        (void)hipGetLastError();
-        *p = nullptr;
-        char buf[200];
-        snprintf(buf, sizeof(buf), "sphmi_neighbors_build: no device memory for the arena of %lld pairs over %d rows (%.2f GB)", pairs, N, (double)bytes / 1e9);
-        throw EngineError(SPHMI_ERR_DEVICE, buf);
+        nl_counts.free(); nl_entries.free(); nl_offsets.free(); nl_tsum.free();
+        nl_rows = nl_pairs = 0;
+        nl_held.drop();
     }
     void neighbors_build(int32_t mode, int64_t* n_rows_out, int64_t* n_pairs_out) override {
         require_uploaded("sphmi_neighbors_build");
         if (mode != SPHMI_NEIGHBORS_FULL && mode != SPHMI_NEIGHBORS_HALF) throw EngineError(SPHMI_ERR_ARGUMENT, "sphmi_neighbors_build: unknown mode");
         if (!n_pairs_out) throw EngineError(SPHMI_ERR_ARGUMENT, "sphmi_neighbors_build: null n_pairs_out");
-        if (!(cfg.h <= cfg.H)) throw EngineError(SPHMI_ERR_STATE, "sphmi_neighbors_build: handles with H < h are not served (the candidate cells are laid out for H + h <= 2H)");
-        if (!fg_ready()) throw EngineError(SPHMI_ERR_STATE, "sphmi_neighbors_build: the handle has not executed a step since the upload (no cell list)");
+        require_cell_list("sphmi_neighbors_build", fg_ready());
         HC(hipSetDevice(cfg.device));
-        nl_state = NL_NONE; nl_rows = nl_pairs = 0;                        // the result of the build before is gone, whatever happens below
+        nl_held.drop(); nl_rows = nl_pairs = 0;                           // the result of the build before is gone, whatever happens below
         const size_t n = (size_t)N;
-        const int ntiles = (N + kNlScanTile - 1) / kNlScanTile;
-        if (n > nl_rows_cap) {
-            nl_free();
-            try {
-                nl_alloc((void**)&nl_counts, n * 4, 0); nl_alloc((void**)&nl_tsum, (size_t)ntiles * 8, 0); nl_alloc((void**)&nl_offsets, (n + 1) * 8, 0);
-            } catch (...) { nl_free(); throw; }
-            nl_rows_cap = n;
-        }
+        long long pairs = 0;
+        auto no_memory = [&](size_t bytes) {
+            return text("sphmi_neighbors_build: no device memory for the arena of %lld pairs over %d rows (%.2f GB)", pairs, N, (double)bytes / 1e9);
+        };
+        nl_counts.need(n, no_memory); nl_offsets.need(n + 1, no_memory);
         NeighborListArgs<T> A{};
         A.pk0 = pk0[iA]; A.comp = comp[cur]; A.cstart = cstart; A.g = grid;
-        A.counts = nl_counts; A.offsets = nl_offsets;
+        A.counts = nl_counts.p; A.offsets = nl_offsets.p;
         A.H_inv = cfg.H_inv; A.H2 = cfg.H2; A.reach = cfg.H + cfg.h;
         A.N = N; A.half = mode == SPHMI_NEIGHBORS_HALF ? 1 : 0;
-        // $SPHMI_NEIGHBORS_TIMING=1: the device time of every pass goes to stderr (tools/neighbor_list_cost.py)
-        const bool timing = getenv("SPHMI_NEIGHBORS_TIMING") != nullptr;
-        hipEvent_t ev[4] = {};
-        auto mark = [&](int k) { if (timing) { if (!ev[k]) HC(hipEventCreate(&ev[k])); HC(hipEventRecord(ev[k], stream)); } };
-        auto drop = [&]() { for (auto& e : ev) if (e) { (void)hipEventDestroy(e); e = nullptr; } };
-        try {
-            const unsigned nb = (unsigned)((N + kNlThreads - 1) / kNlThreads);
-            mark(0);
-            if (D == 3) hipLaunchKernelGGL((k_neighbor_count<T, 3>), dim3(nb), dim3(kNlThreads), 0, stream, A);
-            else        hipLaunchKernelGGL((k_neighbor_count<T, 2>), dim3(nb), dim3(kNlThreads), 0, stream, A);
-            mark(1);
-            hipLaunchKernelGGL(k_nl_tile_sums, dim3(ntiles), dim3(kNlScanThreads), 0, stream, (const int*)nl_counts, N, nl_tsum);
-            hipLaunchKernelGGL(k_nl_scan_tiles, dim3(1), dim3(1024), 0, stream, nl_tsum, ntiles, nl_offsets + n);
-            hipLaunchKernelGGL(k_nl_offsets, dim3(ntiles), dim3(kNlScanThreads), 0, stream, (const int*)nl_counts, N, (const long long*)nl_tsum, nl_offsets);
+        PassClock clock("SPHMI_NEIGHBORS_TIMING", stream);                 // the device time of every pass → stderr (tools/neighbor_list_cost.py)
+        const unsigned nb = (unsigned)((N + kNlThreads - 1) / kNlThreads);
+        clock.mark();
+        by_dims([&](auto d) { hipLaunchKernelGGL((k_neighbor_count<T, decltype(d)::value>), dim3(nb), dim3(kNlThreads), 0, stream, A); });
+        clock.mark();
+        pairs = scan64(nl_counts.p, N, nl_tsum, nl_offsets.p, bounce, stream, no_memory);
+        clock.mark();
+        nl_entries.need((size_t)pairs, no_memory);
+        A.neighbors = nl_entries.p;
+        if (pairs > 0) {
+            by_dims([&](auto d) { hipLaunchKernelGGL((k_neighbor_fill<T, decltype(d)::value>), dim3(nb), dim3(kNlThreads), 0, stream, A); });
             HC(hipGetLastError());
-            long long pairs = 0;
-            bounce.d2h(&pairs, nl_offsets + n, 8, stream);                 // (complete on return: the call is synchronous anyway)
-            mark(2);
-            if ((size_t)pairs > nl_entries_cap) {
-                (void)hipFree(nl_entries); nl_entries = nullptr; nl_entries_cap = 0;
-                nl_alloc((void**)&nl_entries, (size_t)pairs * 4, pairs);
-                nl_entries_cap = (size_t)pairs;
-            }
-            A.neighbors = nl_entries;
-            if (pairs > 0) {
-                if (D == 3) hipLaunchKernelGGL((k_neighbor_fill<T, 3>), dim3(nb), dim3(kNlThreads), 0, stream, A);
-                else        hipLaunchKernelGGL((k_neighbor_fill<T, 2>), dim3(nb), dim3(kNlThreads), 0, stream, A);
-                HC(hipGetLastError());
-            }
-            mark(3);
-            HC(hipStreamSynchronize(stream));
-            if (timing) {
-                float ms[3] = {};
-                for (int k = 0; k < 3; ++k) HC(hipEventElapsedTime(&ms[k], ev[k], ev[k + 1]));
-                fprintf(stderr, "sphmi_neighbors_build: %d rows, %lld pairs: count %.3f ms, scan %.3f ms, fill %.3f ms\n", N, pairs, ms[0], ms[1], ms[2]);
-            }
-            drop();
-            nl_rows = N; nl_pairs = pairs; nl_state = NL_VALID;
-        } catch (...) { drop(); throw; }
+        }
+        clock.mark();
+        HC(hipStreamSynchronize(stream));
+        clock.report(text("sphmi_neighbors_build: %d rows, %lld pairs:", N, pairs), {"count", "scan", "fill"});
+        nl_rows = N; nl_pairs = pairs; nl_held.set_valid();
         if (n_rows_out) *n_rows_out = nl_rows;
         *n_pairs_out = nl_pairs;
     }
-    void neighbors_read(int64_t* offsets_out, int32_t* neighbors_out) override {
-        if (nl_state == NL_STALE) throw EngineError(SPHMI_ERR_STATE, "sphmi_neighbors_read: the neighbour list is stale (rows may have moved since sphmi_neighbors_build)");
-        if (nl_state != NL_VALID) throw EngineError(SPHMI_ERR_STATE, "sphmi_neighbors_read: no neighbour list is held (sphmi_neighbors_build)");
+    void neighbors_fetch(int64_t* offsets_out, int32_t* neighbors_out) override {
         HC(hipSetDevice(cfg.device));
-        if (offsets_out) fetch_result(offsets_out, nl_offsets, (size_t)(nl_rows + 1) * 8);
-        if (neighbors_out && nl_pairs > 0) fetch_result(neighbors_out, nl_entries, (size_t)nl_pairs * 4);
+        if (offsets_out) fetch_result(offsets_out, nl_offsets.p, (size_t)(nl_rows + 1) * 8);
+        if (neighbors_out && nl_pairs > 0) fetch_result(neighbors_out, nl_entries.p, (size_t)nl_pairs * 4);
         HC(hipStreamSynchronize(stream));
     }
     void neighbors_release() override {
@@ -2112,124 +2051,84 @@ struct Engine final : EngineBase {
     }
 
     // ---- the connected bodies of selected rows, on demand (sphmi_components.h) ----------------------------------------------------------
-    // Reads the current set's positions, the low words, the types, `cstart` and the grid of the last rebuild; writes its own arena and
-    // nothing else.  The arena: parent, root, flag, label [N] int32, the scan's tile sums and dense [N + 1] int64, the error word —
-    // they grow with N — and first_row, count, box, which grow with the number of components.  cc_state (EngineBase) tells whether it
-    // matches the rows.
-    int *cc_parent = nullptr, *cc_root = nullptr, *cc_flag = nullptr, *cc_label = nullptr, *cc_first = nullptr, *cc_count = nullptr, *cc_err = nullptr;
-    long long *cc_dense = nullptr, *cc_tsum = nullptr;
-    unsigned long long* cc_box = nullptr;
-    size_t cc_rows_cap = 0, cc_comp_cap = 0;
+    // Reads the current set's positions, the low words, the types, `cstart` and the grid of the last rebuild; writes its own buffers and
+    // nothing else: parent, root, flag, label [N] int32, the scan's tile sums and dense [N + 1] int64, the error word — they grow with
+    // N — and first_row, count, box, which grow with the number of components.  cc_held (EngineBase) tells whether they match the rows.
+    DeviceBuf<int> cc_parent, cc_root, cc_flag, cc_label, cc_first, cc_count, cc_err;
+    DeviceBuf<long long> cc_dense, cc_tsum;
+    DeviceBuf<unsigned long long> cc_box;      // 6 words per component
     int64_t cc_rows = 0, cc_n = 0;
     void cc_free() {
-        (void)hipFree(cc_parent); (void)hipFree(cc_root); (void)hipFree(cc_flag); (void)hipFree(cc_label); (void)hipFree(cc_first); (void)hipFree(cc_count);
-        (void)hipFree(cc_err); (void)hipFree(cc_dense); (void)hipFree(cc_tsum); (void)hipFree(cc_box);
-        cc_parent = cc_root = cc_flag = cc_label = cc_first = cc_count = cc_err = nullptr; cc_dense = cc_tsum = nullptr; cc_box = nullptr;
-        cc_rows_cap = cc_comp_cap = 0; cc_rows = cc_n = 0;
-        cc_state = NL_NONE;
-    }
-    void cc_alloc(void** p, size_t bytes, long long comps) {
-        if (hipMalloc(p, std::max<size_t>(bytes, 8)) == hipSuccess) return;
-        (void)hipGetLastError();
-        *p = nullptr;
-        char buf[200];
-        snprintf(buf, sizeof(buf), "sphmi_components_build: no device memory for the arena of %lld components over %d rows (%.2f GB)", comps, N, (double)bytes / 1e9);
-        throw EngineError(SPHMI_ERR_DEVICE, buf);
+        for (DeviceBuf<int>* b : {&cc_parent, &cc_root, &cc_flag, &cc_label, &cc_first, &cc_count, &cc_err}) b->free();
+        cc_dense.free(); cc_tsum.free(); cc_box.free();
+        cc_rows = cc_n = 0;
+        cc_held.drop();
     }
     void components_build(double link, uint32_t type_mask, int64_t* n_rows_out, int64_t* n_components_out) override {
         require_uploaded("sphmi_components_build");
         if (!std::isfinite(link) || !(link > 0.0) || !(link <= cfg.H)) throw EngineError(SPHMI_ERR_ARGUMENT, "sphmi_components_build: the link length must be finite, positive and at most H");
         if ((type_mask & ~0xeu) || !(type_mask & 0xeu)) throw EngineError(SPHMI_ERR_ARGUMENT, "sphmi_components_build: the type mask must name at least one of the bits 1 (Fluid), 2 (Fixed), 3 (Moving) and no other");
         if (!n_components_out) throw EngineError(SPHMI_ERR_ARGUMENT, "sphmi_components_build: null n_components_out");
-        if (!(cfg.h <= cfg.H)) throw EngineError(SPHMI_ERR_STATE, "sphmi_components_build: handles with H < h are not served (the candidate cells are laid out for H + h <= 2H)");
-        if (!fg_ready()) throw EngineError(SPHMI_ERR_STATE, "sphmi_components_build: the handle has not executed a step since the upload (no cell list)");
+        require_cell_list("sphmi_components_build", fg_ready());
         HC(hipSetDevice(cfg.device));
-        cc_state = NL_NONE; cc_rows = cc_n = 0;                            // the result of the build before is gone, whatever happens below
+        cc_held.drop(); cc_rows = cc_n = 0;                               // the result of the build before is gone, whatever happens below
         const size_t n = (size_t)N;
-        const int ntiles = (N + kNlScanTile - 1) / kNlScanTile;
-        if (n > cc_rows_cap) {
-            cc_free();
-            try {
-                cc_alloc((void**)&cc_parent, n * 4, 0); cc_alloc((void**)&cc_root, n * 4, 0); cc_alloc((void**)&cc_flag, n * 4, 0); cc_alloc((void**)&cc_label, n * 4, 0);
-                cc_alloc((void**)&cc_tsum, (size_t)ntiles * 8, 0); cc_alloc((void**)&cc_dense, (n + 1) * 8, 0); cc_alloc((void**)&cc_err, 8, 0);
-            } catch (...) { cc_free(); throw; }
-            cc_rows_cap = n;
-        }
+        long long comps = 0;
+        auto no_memory = [&](size_t bytes) {
+            return text("sphmi_components_build: no device memory for the arena of %lld components over %d rows (%.2f GB)", comps, N, (double)bytes / 1e9);
+        };
+        for (DeviceBuf<int>* b : {&cc_parent, &cc_root, &cc_flag, &cc_label}) b->need(n, no_memory);
+        cc_dense.need(n + 1, no_memory); cc_err.need(2, no_memory);
         NeighborListArgs<T> A{};
         A.pk0 = pk0[iA]; A.comp = comp[cur]; A.cstart = cstart; A.g = grid;
         A.H_inv = cfg.H_inv; A.H2 = link * link; A.reach = cfg.H + cfg.h;   // the cells are walked as for the neighbour list; only the cut is shorter
         A.N = N; A.half = 1;
         ComponentArgs K{};
-        K.type = type[cur]; K.parent = cc_parent; K.root = cc_root; K.flag = cc_flag; K.dense = cc_dense; K.label = cc_label; K.err = cc_err;
+        K.type = type[cur]; K.parent = cc_parent.p; K.root = cc_root.p; K.flag = cc_flag.p; K.dense = cc_dense.p; K.label = cc_label.p; K.err = cc_err.p;
         K.N = N; K.type_mask = type_mask;
-        // $SPHMI_COMPONENTS_TIMING=1: the device time of every pass goes to stderr (tools/components_cost.py)
-        const bool timing = getenv("SPHMI_COMPONENTS_TIMING") != nullptr;
-        hipEvent_t ev[6] = {};
-        auto mark = [&](int k) { if (timing) { if (!ev[k]) HC(hipEventCreate(&ev[k])); HC(hipEventRecord(ev[k], stream)); } };
-        auto drop = [&]() { for (auto& e : ev) if (e) { (void)hipEventDestroy(e); e = nullptr; } };
-        auto check_err = [&](int e) {
-            if (!e) return;
-            char buf[200];
-            snprintf(buf, sizeof(buf), "sphmi_components_build: the union-find left its bounds (error word %d: 1 = climb, 2 = retry, 4 = parent out of range); no result is held", e);
-            throw EngineError(SPHMI_ERR_DEVICE, buf);
-        };
-        try {
-            const unsigned nb = (unsigned)((N + kCcThreads - 1) / kCcThreads);
-            HC(hipMemsetAsync(cc_err, 0, 8, stream));
-            mark(0);
-            hipLaunchKernelGGL(k_cc_init, dim3(nb), dim3(kCcThreads), 0, stream, K);
-            mark(1);
-            if (D == 3) hipLaunchKernelGGL((k_cc_hook<T, 3>), dim3(nb), dim3(kNlThreads), 0, stream, A, K);
-            else        hipLaunchKernelGGL((k_cc_hook<T, 2>), dim3(nb), dim3(kNlThreads), 0, stream, A, K);
-            mark(2);
-            hipLaunchKernelGGL(k_cc_flatten, dim3(nb), dim3(kCcThreads), 0, stream, K);
-            mark(3);
-            hipLaunchKernelGGL(k_nl_tile_sums, dim3(ntiles), dim3(kNlScanThreads), 0, stream, (const int*)cc_flag, N, cc_tsum);
-            hipLaunchKernelGGL(k_nl_scan_tiles, dim3(1), dim3(1024), 0, stream, cc_tsum, ntiles, cc_dense + n);
-            hipLaunchKernelGGL(k_nl_offsets, dim3(ntiles), dim3(kNlScanThreads), 0, stream, (const int*)cc_flag, N, (const long long*)cc_tsum, cc_dense);
-            HC(hipGetLastError());
-            long long comps = 0; int err = 0;
-            bounce.d2h(&comps, cc_dense + n, 8, stream);                   // (complete on return: the call is synchronous anyway)
-            bounce.d2h(&err, cc_err, 4, stream);
-            check_err(err);
-            if (comps < 0 || comps > (long long)N) throw EngineError(SPHMI_ERR_DEVICE, "sphmi_components_build: the scan of the roots left its bounds; no result is held");
-            if ((size_t)comps > cc_comp_cap) {
-                (void)hipFree(cc_first); (void)hipFree(cc_count); (void)hipFree(cc_box); cc_first = cc_count = nullptr; cc_box = nullptr; cc_comp_cap = 0;
-                cc_alloc((void**)&cc_first, (size_t)comps * 4, comps); cc_alloc((void**)&cc_count, (size_t)comps * 4, comps); cc_alloc((void**)&cc_box, (size_t)comps * 48, comps);
-                cc_comp_cap = (size_t)comps;
-            }
-            K.first_row = cc_first; K.count = cc_count; K.box = cc_box; K.C = (int)comps;
-            hipLaunchKernelGGL(k_cc_label, dim3(nb), dim3(kCcThreads), 0, stream, K);
-            mark(4);
-            if (comps > 0) {
-                const unsigned nbt = (unsigned)((6 * comps + kCcThreads - 1) / kCcThreads);
-                hipLaunchKernelGGL(k_cc_table_init, dim3(nbt), dim3(kCcThreads), 0, stream, K);
-                if (D == 3) { hipLaunchKernelGGL((k_cc_table<T, 3>), dim3(nb), dim3(kCcThreads), 0, stream, A, K); hipLaunchKernelGGL(k_cc_box_decode<3>, dim3(nbt), dim3(kCcThreads), 0, stream, K); }
-                else        { hipLaunchKernelGGL((k_cc_table<T, 2>), dim3(nb), dim3(kCcThreads), 0, stream, A, K); hipLaunchKernelGGL(k_cc_box_decode<2>, dim3(nbt), dim3(kCcThreads), 0, stream, K); }
-            }
-            HC(hipGetLastError());
-            mark(5);
-            HC(hipStreamSynchronize(stream));
-            if (timing) {
-                float ms[5] = {};
-                for (int k = 0; k < 5; ++k) HC(hipEventElapsedTime(&ms[k], ev[k], ev[k + 1]));
-                fprintf(stderr, "sphmi_components_build: %d rows, %lld components: init %.3f ms, hook %.3f ms, flatten %.3f ms, number %.3f ms, table %.3f ms\n", N, comps, ms[0], ms[1], ms[2], ms[3], ms[4]);
-            }
-            drop();
-            cc_rows = N; cc_n = comps; cc_state = NL_VALID;
-        } catch (...) { drop(); throw; }
+        PassClock clock("SPHMI_COMPONENTS_TIMING", stream);                // the device time of every pass → stderr (tools/components_cost.py)
+        const unsigned nb = (unsigned)((N + kCcThreads - 1) / kCcThreads);
+        HC(hipMemsetAsync(cc_err.p, 0, 8, stream));
+        clock.mark();
+        hipLaunchKernelGGL(k_cc_init, dim3(nb), dim3(kCcThreads), 0, stream, K);
+        clock.mark();
+        by_dims([&](auto d) { hipLaunchKernelGGL((k_cc_hook<T, decltype(d)::value>), dim3(nb), dim3(kNlThreads), 0, stream, A, K); });
+        clock.mark();
+        hipLaunchKernelGGL(k_cc_flatten, dim3(nb), dim3(kCcThreads), 0, stream, K);
+        clock.mark();
+        comps = scan64(cc_flag.p, N, cc_tsum, cc_dense.p, bounce, stream, no_memory);
+        int err = 0;
+        bounce.d2h(&err, cc_err.p, 4, stream);
+        if (err)
+            throw EngineError(SPHMI_ERR_DEVICE, text("sphmi_components_build: the union-find left its bounds (error word %d: 1 = climb, 2 = retry, 4 = parent out of range); no result is held", err));
+        if (comps < 0 || comps > (long long)N) throw EngineError(SPHMI_ERR_DEVICE, "sphmi_components_build: the scan of the roots left its bounds; no result is held");
+        cc_first.need((size_t)comps, no_memory); cc_count.need((size_t)comps, no_memory); cc_box.need((size_t)comps * 6, no_memory);
+        K.first_row = cc_first.p; K.count = cc_count.p; K.box = cc_box.p; K.C = (int)comps;
+        hipLaunchKernelGGL(k_cc_label, dim3(nb), dim3(kCcThreads), 0, stream, K);
+        clock.mark();
+        if (comps > 0) {
+            const unsigned nbt = (unsigned)((6 * comps + kCcThreads - 1) / kCcThreads);
+            hipLaunchKernelGGL(k_cc_table_init, dim3(nbt), dim3(kCcThreads), 0, stream, K);
+            by_dims([&](auto d) {
+                hipLaunchKernelGGL((k_cc_table<T, decltype(d)::value>), dim3(nb), dim3(kCcThreads), 0, stream, A, K);
+                hipLaunchKernelGGL(k_cc_box_decode<decltype(d)::value>, dim3(nbt), dim3(kCcThreads), 0, stream, K);
+            });
+        }
+        HC(hipGetLastError());
+        clock.mark();
+        HC(hipStreamSynchronize(stream));
+        clock.report(text("sphmi_components_build: %d rows, %lld components:", N, comps), {"init", "hook", "flatten", "number", "table"});
+        cc_rows = N; cc_n = comps; cc_held.set_valid();
         if (n_rows_out) *n_rows_out = cc_rows;
         *n_components_out = cc_n;
     }
-    void components_read(int32_t* label_out, int32_t* first_row_out, int32_t* count_out, double* box_out) override {
-        if (cc_state == NL_STALE) throw EngineError(SPHMI_ERR_STATE, "sphmi_components_read: the components are stale (rows may have moved since sphmi_components_build)");
-        if (cc_state != NL_VALID) throw EngineError(SPHMI_ERR_STATE, "sphmi_components_read: no components are held (sphmi_components_build)");
+    void components_fetch(int32_t* label_out, int32_t* first_row_out, int32_t* count_out, double* box_out) override {
         HC(hipSetDevice(cfg.device));
-        if (label_out && cc_rows > 0) fetch_result(label_out, cc_label, (size_t)cc_rows * 4);
+        if (label_out && cc_rows > 0) fetch_result(label_out, cc_label.p, (size_t)cc_rows * 4);
         if (cc_n > 0) {
-            if (first_row_out) fetch_result(first_row_out, cc_first, (size_t)cc_n * 4);
-            if (count_out) fetch_result(count_out, cc_count, (size_t)cc_n * 4);
-            if (box_out) fetch_result(box_out, cc_box, (size_t)cc_n * 48);
+            if (first_row_out) fetch_result(first_row_out, cc_first.p, (size_t)cc_n * 4);
+            if (count_out) fetch_result(count_out, cc_count.p, (size_t)cc_n * 4);
+            if (box_out) fetch_result(box_out, cc_box.p, (size_t)cc_n * 48);
         }
         HC(hipStreamSynchronize(stream));
     }
@@ -2239,127 +2138,71 @@ struct Engine final : EngineBase {
     }
 
     // ---- the free surface as a mesh, on demand (sphmi_isosurface.h) -----------------------------------------------------------------
-    // Samples the lattice with fg_launch into fg_arena — nothing of S goes to the host — and extracts the mesh of S = level into an
-    // arena of its own, which holds everything a read needs: a later sphmi_sample_grid may reuse fg_arena.  Per node: the two bytes,
+    // Samples the lattice with fg_launch into fg_arena — nothing of S goes to the host — and extracts the mesh of S = level into
+    // buffers of its own, which hold everything a read needs: a later sphmi_sample_grid may reuse fg_arena.  Per node: the two bytes,
     // the two counts and the two offset arrays (they grow with the lattice); the vertices, their attributes and the elements grow
-    // with the mesh and go back to the device at sphmi_isosurface_release.  iso_state (EngineBase) tells whether it matches the rows.
-    unsigned char *iso_mask = nullptr, *iso_corners = nullptr;
-    int *iso_vcount = nullptr, *iso_ecount = nullptr, *iso_elements = nullptr;
-    long long *iso_voff = nullptr, *iso_eoff = nullptr, *iso_tsum = nullptr;
-    double* iso_vertices = nullptr;            // [nv × 3], then the pressure [nv], then the velocity [nv × 3]
-    size_t iso_nodes_cap = 0, iso_vertices_cap = 0, iso_elements_cap = 0;
+    // with the mesh.  All go back to the device at sphmi_isosurface_release.  iso_held (EngineBase) tells whether they match the rows.
+    DeviceBuf<unsigned char> iso_mask, iso_corners;
+    DeviceBuf<int> iso_vcount, iso_ecount, iso_elements;
+    DeviceBuf<long long> iso_voff, iso_eoff, iso_tsum;
+    DeviceBuf<double> iso_vertices;            // [nv × 3], then the pressure [nv], then the velocity [nv × 3]
     int64_t iso_nv = 0, iso_ne = 0;
     void iso_free() {
-        (void)hipFree(iso_mask); (void)hipFree(iso_corners); (void)hipFree(iso_vcount); (void)hipFree(iso_ecount); (void)hipFree(iso_elements);
-        (void)hipFree(iso_voff); (void)hipFree(iso_eoff); (void)hipFree(iso_tsum); (void)hipFree(iso_vertices);
-        iso_mask = iso_corners = nullptr; iso_vcount = iso_ecount = iso_elements = nullptr; iso_voff = iso_eoff = iso_tsum = nullptr; iso_vertices = nullptr;
-        iso_nodes_cap = iso_vertices_cap = iso_elements_cap = 0; iso_nv = iso_ne = 0;
-        iso_state = NL_NONE;
-    }
-    void iso_alloc(void** p, size_t bytes, long long nodes, long long nv, long long ne) {
-        if (hipMalloc(p, std::max<size_t>(bytes, 8)) == hipSuccess) return;
-        (void)hipGetLastError();
-        *p = nullptr;
-        char buf[240];
-        snprintf(buf, sizeof(buf), "sphmi_isosurface_build: no device memory for the arena of %lld vertices and %lld elements over %lld nodes (%.2f GB)", nv, ne, nodes, (double)bytes / 1e9);
-        throw EngineError(SPHMI_ERR_DEVICE, buf);
+        iso_mask.free(); iso_corners.free(); iso_vcount.free(); iso_ecount.free(); iso_elements.free();
+        iso_voff.free(); iso_eoff.free(); iso_tsum.free(); iso_vertices.free();
+        iso_nv = iso_ne = 0;
+        iso_held.drop();
     }
     void isosurface_build(const double* origin, const double* spacing, const int64_t* counts, double level, int64_t* n_vertices_out, int64_t* n_elements_out) override {
-        require_uploaded("sphmi_isosurface_build");
-        if (!(cfg.h <= cfg.H)) throw EngineError(SPHMI_ERR_STATE, "sphmi_isosurface_build: handles with H < h are not served (the candidate cells are laid out for H + h <= 2H)");
-        if (!fg_ready()) throw EngineError(SPHMI_ERR_STATE, "sphmi_isosurface_build: the handle has not executed a step since the upload (no cell list, no half-step set)");
+        require_cell_list("sphmi_isosurface_build", fg_ready(), "(no cell list, no half-step set)");
         const int64_t nodes = check_grid_lattice(origin, spacing, counts, D);
         if (!std::isfinite(level) || !(level > 0.0)) throw EngineError(SPHMI_ERR_ARGUMENT, "sphmi_isosurface_build: the level must be finite and positive");
         if (!n_vertices_out || !n_elements_out) throw EngineError(SPHMI_ERR_ARGUMENT, "sphmi_isosurface_build: null n_vertices_out or n_elements_out");
         HC(hipSetDevice(cfg.device));
-        iso_state = NL_NONE; iso_nv = iso_ne = 0;                          // the mesh of the build before is gone, whatever happens below
+        iso_held.drop(); iso_nv = iso_ne = 0;                             // the mesh of the build before is gone, whatever happens below
         const size_t n = (size_t)nodes;
-        const int ntiles = (int)((nodes + kNlScanTile - 1) / kNlScanTile);
-        // $SPHMI_ISOSURFACE_TIMING: the device time of every pass goes to stderr (tools/isosurface_cost.py)
-        const bool timing = getenv("SPHMI_ISOSURFACE_TIMING") != nullptr;
-        hipEvent_t ev[6] = {};
-        auto mark = [&](int k) { if (timing) { if (!ev[k]) HC(hipEventCreate(&ev[k])); HC(hipEventRecord(ev[k], stream)); } };
-        auto drop = [&]() { for (auto& e : ev) if (e) { (void)hipEventDestroy(e); e = nullptr; } };
-        try {
-            mark(0);
-            fg_launch(origin, spacing, counts, nodes);
-            mark(1);
-            if (n > iso_nodes_cap) {
-                iso_free();
-                try {
-                    iso_alloc((void**)&iso_mask, n, nodes, 0, 0); iso_alloc((void**)&iso_corners, n, nodes, 0, 0);
-                    iso_alloc((void**)&iso_vcount, n * 4, nodes, 0, 0); iso_alloc((void**)&iso_ecount, n * 4, nodes, 0, 0);
-                    iso_alloc((void**)&iso_voff, (n + 1) * 8, nodes, 0, 0); iso_alloc((void**)&iso_eoff, (n + 1) * 8, nodes, 0, 0);
-                    iso_alloc((void**)&iso_tsum, (size_t)ntiles * 8, nodes, 0, 0);
-                } catch (...) { iso_free(); throw; }
-                iso_nodes_cap = n;
-            }
-            IsoArgs A{};
-            A.sums = fg_arena.p;
-            for (int d = 0; d < 3; ++d) { A.origin[d] = d < D ? origin[d] : 0.0; A.spacing[d] = d < D ? spacing[d] : 1.0; A.counts[d] = d < D ? (int)counts[d] : 1; }
-            A.level = level; A.nodes = (int)nodes;
-            A.mask = iso_mask; A.corners = iso_corners; A.vcount = iso_vcount; A.ecount = iso_ecount; A.voff = iso_voff; A.eoff = iso_eoff;
-            const unsigned nb = (unsigned)((nodes + kIsoThreads - 1) / kIsoThreads);
-            if (D == 3) hipLaunchKernelGGL(k_iso_classify<3>, dim3(nb), dim3(kIsoThreads), 0, stream, A);
-            else        hipLaunchKernelGGL(k_iso_classify<2>, dim3(nb), dim3(kIsoThreads), 0, stream, A);
-            mark(2);
-            for (int pass = 0; pass < 2; ++pass) {
-                const int* cnt = pass ? iso_ecount : iso_vcount;
-                long long* off = pass ? iso_eoff : iso_voff;
-                hipLaunchKernelGGL(k_nl_tile_sums, dim3(ntiles), dim3(kNlScanThreads), 0, stream, cnt, (int)nodes, iso_tsum);
-                hipLaunchKernelGGL(k_nl_scan_tiles, dim3(1), dim3(1024), 0, stream, iso_tsum, ntiles, off + n);
-                hipLaunchKernelGGL(k_nl_offsets, dim3(ntiles), dim3(kNlScanThreads), 0, stream, cnt, (int)nodes, (const long long*)iso_tsum, off);
-            }
-            HC(hipGetLastError());
-            long long nv = 0, ne = 0;
-            bounce.d2h(&nv, iso_voff + n, 8, stream);                      // (complete on return: the call is synchronous anyway)
-            bounce.d2h(&ne, iso_eoff + n, 8, stream);
-            mark(3);
-            if ((size_t)nv > iso_vertices_cap) {
-                (void)hipFree(iso_vertices); iso_vertices = nullptr; iso_vertices_cap = 0;
-                iso_alloc((void**)&iso_vertices, (size_t)nv * 7 * 8, nodes, nv, ne);
-                iso_vertices_cap = (size_t)nv;
-            }
-            if ((size_t)ne > iso_elements_cap) {
-                (void)hipFree(iso_elements); iso_elements = nullptr; iso_elements_cap = 0;
-                iso_alloc((void**)&iso_elements, (size_t)ne * D * 4, nodes, nv, ne);
-                iso_elements_cap = (size_t)ne;
-            }
-            A.vertices = iso_vertices; A.pressure = iso_vertices + 3 * (size_t)nv; A.velocity = iso_vertices + 4 * (size_t)nv; A.elements = iso_elements;
-            if (nv > 0) {
-                if (D == 3) hipLaunchKernelGGL(k_iso_vertices<3>, dim3(nb), dim3(kIsoThreads), 0, stream, A);
-                else        hipLaunchKernelGGL(k_iso_vertices<2>, dim3(nb), dim3(kIsoThreads), 0, stream, A);
-            }
-            mark(4);
-            if (ne > 0) {
-                if (D == 3) hipLaunchKernelGGL(k_iso_elements<3>, dim3(nb), dim3(kIsoThreads), 0, stream, A);
-                else        hipLaunchKernelGGL(k_iso_elements<2>, dim3(nb), dim3(kIsoThreads), 0, stream, A);
-            }
-            HC(hipGetLastError());
-            mark(5);
-            HC(hipStreamSynchronize(stream));
-            if (timing) {
-                float ms[5] = {};
-                for (int k = 0; k < 5; ++k) HC(hipEventElapsedTime(&ms[k], ev[k], ev[k + 1]));
-                fprintf(stderr, "sphmi_isosurface_build: %lld nodes, %lld vertices, %lld elements: sample %.3f ms, classify %.3f ms, scans %.3f ms, vertices %.3f ms, elements %.3f ms\n",
-                        (long long)nodes, nv, ne, ms[0], ms[1], ms[2], ms[3], ms[4]);
-            }
-            drop();
-            iso_nv = nv; iso_ne = ne; iso_state = NL_VALID;
-        } catch (...) { drop(); throw; }
+        long long nv = 0, ne = 0;
+        auto no_memory = [&](size_t bytes) {
+            return text("sphmi_isosurface_build: no device memory for the arena of %lld vertices and %lld elements over %lld nodes (%.2f GB)", nv, ne, (long long)nodes, (double)bytes / 1e9);
+        };
+        PassClock clock("SPHMI_ISOSURFACE_TIMING", stream);                // the device time of every pass → stderr (tools/isosurface_cost.py)
+        clock.mark();
+        fg_launch(origin, spacing, counts, nodes);
+        clock.mark();
+        iso_mask.need(n, no_memory); iso_corners.need(n, no_memory); iso_vcount.need(n, no_memory); iso_ecount.need(n, no_memory);
+        iso_voff.need(n + 1, no_memory); iso_eoff.need(n + 1, no_memory);
+        IsoArgs A{};
+        A.sums = fg_arena.p;
+        for (int d = 0; d < 3; ++d) { A.origin[d] = d < D ? origin[d] : 0.0; A.spacing[d] = d < D ? spacing[d] : 1.0; A.counts[d] = d < D ? (int)counts[d] : 1; }
+        A.level = level; A.nodes = (int)nodes;
+        A.mask = iso_mask.p; A.corners = iso_corners.p; A.vcount = iso_vcount.p; A.ecount = iso_ecount.p; A.voff = iso_voff.p; A.eoff = iso_eoff.p;
+        const unsigned nb = (unsigned)((nodes + kIsoThreads - 1) / kIsoThreads);
+        by_dims([&](auto d) { hipLaunchKernelGGL(k_iso_classify<decltype(d)::value>, dim3(nb), dim3(kIsoThreads), 0, stream, A); });
+        clock.mark();
+        nv = scan64(iso_vcount.p, (int)nodes, iso_tsum, iso_voff.p, bounce, stream, no_memory);
+        ne = scan64(iso_ecount.p, (int)nodes, iso_tsum, iso_eoff.p, bounce, stream, no_memory);
+        clock.mark();
+        iso_vertices.need((size_t)nv * 7, no_memory); iso_elements.need((size_t)ne * D, no_memory);
+        A.vertices = iso_vertices.p; A.pressure = iso_vertices.p + 3 * (size_t)nv; A.velocity = iso_vertices.p + 4 * (size_t)nv; A.elements = iso_elements.p;
+        if (nv > 0) by_dims([&](auto d) { hipLaunchKernelGGL(k_iso_vertices<decltype(d)::value>, dim3(nb), dim3(kIsoThreads), 0, stream, A); });
+        clock.mark();
+        if (ne > 0) by_dims([&](auto d) { hipLaunchKernelGGL(k_iso_elements<decltype(d)::value>, dim3(nb), dim3(kIsoThreads), 0, stream, A); });
+        HC(hipGetLastError());
+        clock.mark();
+        HC(hipStreamSynchronize(stream));
+        clock.report(text("sphmi_isosurface_build: %lld nodes, %lld vertices, %lld elements:", (long long)nodes, nv, ne), {"sample", "classify", "scans", "vertices", "elements"});
+        iso_nv = nv; iso_ne = ne; iso_held.set_valid();
         *n_vertices_out = iso_nv; *n_elements_out = iso_ne;
     }
-    void isosurface_read(double* vertices_out, int32_t* elements_out, double* pressure_out, double* velocity_out) override {
-        if (iso_state == NL_STALE) throw EngineError(SPHMI_ERR_STATE, "sphmi_isosurface_read: the mesh is stale (rows may have moved since sphmi_isosurface_build)");
-        if (iso_state != NL_VALID) throw EngineError(SPHMI_ERR_STATE, "sphmi_isosurface_read: no mesh is held (sphmi_isosurface_build)");
+    void isosurface_fetch(double* vertices_out, int32_t* elements_out, double* pressure_out, double* velocity_out) override {
         HC(hipSetDevice(cfg.device));
         const size_t nv = (size_t)iso_nv;
         if (nv > 0) {
-            if (vertices_out) fetch_result(vertices_out, iso_vertices, nv * 3 * 8);
-            if (pressure_out) fetch_result(pressure_out, iso_vertices + 3 * nv, nv * 8);
-            if (velocity_out) fetch_result(velocity_out, iso_vertices + 4 * nv, nv * 3 * 8);
+            if (vertices_out) fetch_result(vertices_out, iso_vertices.p, nv * 3 * 8);
+            if (pressure_out) fetch_result(pressure_out, iso_vertices.p + 3 * nv, nv * 8);
+            if (velocity_out) fetch_result(velocity_out, iso_vertices.p + 4 * nv, nv * 3 * 8);
         }
-        if (elements_out && iso_ne > 0) fetch_result(elements_out, iso_elements, (size_t)iso_ne * D * 4);
+        if (elements_out && iso_ne > 0) fetch_result(elements_out, iso_elements.p, (size_t)iso_ne * D * 4);
         HC(hipStreamSynchronize(stream));
     }
     void isosurface_release() override {

@@ -1776,8 +1776,7 @@ struct MultiEngine final : EngineBase {
         require_one_process("sphmi_sample_grid");
         bool any = false;
         for (auto& r : R) any = any || r.e->fg_ready();
-        if (!(cfg.h <= cfg.H)) throw EngineError(SPHMI_ERR_STATE, "sphmi_sample_grid: handles with H < h are not served (the candidate cells are laid out for H + h <= 2H)");
-        if (!any) throw EngineError(SPHMI_ERR_STATE, "sphmi_sample_grid: the handle has not executed a step since the upload (no cell list, no half-step set)");
+        require_cell_list("sphmi_sample_grid", any, "(no cell list, no half-step set)");
         const int64_t nodes = check_grid_lattice(origin, spacing, counts, D);
         for (auto& r : R) if (r.e->fg_ready()) r.e->fg_launch(origin, spacing, counts, nodes);        // all slabs at once, each on its device
         GridSums G(nodes, weight, count, pressure, density, velocity);
