@@ -367,6 +367,51 @@ int sphmi_flow_read(sphmi_handle* h, int64_t capacity, int64_t* iteration_out, d
                     int64_t* n_out, int64_t* n_dropped);
 
 /*
+ * ENVELOPES: what every single particle has experienced over time, accumulated on the device at EVERY step - the peak pressure
+ * every wall particle of an obstacle has seen, when the wave reached it and the pressure impulse it took (the load MAP of a
+ * structure, not only its total), the largest speed every fluid particle ever had.  Such peaks last a few steps and an output
+ * interval holds hundreds; without this a caller gets them only by downloading every step.  With, "after a step", the state
+ * sphmi_download would deliver directly after that step - P its Pressure, v its Velocity (2-D handles: vz = 0; the device values
+ * widened to fp64: a handle with host_float_bytes = 4 on an fp64 device rounds its downloads, the envelopes do not), t =
+ * TotalTime at the end of the step, dt its time step - every selected row keeps eight doubles, updated per EXECUTED step:
+ *     p_max, t_p_max   start -inf, 0    if (P > p_max) { p_max = P; t_p_max = t; }     strict: the first attainment keeps its time
+ *     p_min            start +inf       if (P < p_min) p_min = P
+ *     impulse          start 0          impulse = impulse + P * dt
+ *     square           start 0          square = square + (P * P) * dt
+ *     loaded           start 0          if (P > 0) loaded = loaded + dt
+ *     speed2_max       start 0          s = (vx*vx + vy*vy) + vz*vz; if (s > speed2_max) speed2_max = s
+ *     t_arrival        start +inf       if (P > 0 && t_arrival == inf) t_arrival = t
+ * Every operation is fp64, rounded once, never contracted: a host that downloads after every step forms the same doubles, bit for
+ * bit (sphexample_amd/envelopes.py: update).  A NaN never wins a comparison and poisons the sums.  The window is kept with them:
+ * steps (executed steps since the enable), t_begin (TotalTime at the enable), t_end, duration = sum dt in step order.  The records
+ * follow the PARTICLE, not the row: the sort moves rows at every rebuild, the records stay where they were at the enable and are
+ * found through the row column the sorts carry anyway and a map of their own, composed in sphmi_download_permutation as the map of
+ * the attached columns is - attaching or detaching columns does not disturb the envelopes, nor the other way round.  No atomics: a
+ * record has one writer.  Off by default; a handle that never enables it launches what it always did.
+ *   enable: after sphmi_upload / sphmi_generate_dam_break_3d, at any later time too: steps executed before it are not seen.  Bit
+ *     Type of type_mask selects the rows of that Type (Fluid = 1, Fixed = 2, Moving = 3, as in sphmi_components_build); rows of
+ *     other types keep the start record.  A second call replaces the selection and restarts the window (start records, steps = 0,
+ *     t_begin = the TotalTime now); type_mask = 0 disables and frees the memory.  sphmi_upload and the generator disable.  Cancelled
+ *     steps add nothing; sphmi_forces_once records nothing.
+ *   read: synchronous, between sphmi_advance calls.  *steps_out; window_out[3] = { t_begin, t_end, duration }; then eight arrays of
+ *     n = sphmi_owned_count doubles - doubles whatever host_float_bytes is - row i being row i of what sphmi_download delivers
+ *     NOW: p_max, t_p_max, p_min, impulse, square, loaded, speed_max = sqrt(speed2_max) (the one sqrt, formed on the host) and
+ *     t_arrival (+inf: never loaded).  Any output pointer may be NULL.  It clears nothing: the envelopes keep growing across
+ *     sphmi_advance calls, downloads, column downloads, sphmi_download_permutation and the on-demand results.
+ *   SPHMI_ERR_STATE: before the upload; read while disabled; rank-mode and multi-device handles (rows migrate between slabs, and
+ *     carrying their records along is not built).
+ *   SPHMI_ERR_ARGUMENT: a type_mask with a bit other than 1, 2, 3 set (the mask travels as an int32_t - the same register as the
+ *     uint32_t of sphmi_components_build - so that the Julia shim's prototype check, which knows no uint32_t, covers the binding; a
+ *     negative value has bit 31 set and is refused like any other stray bit).
+ *   SPHMI_ERR_DEVICE: the device cannot hold the 68 bytes per row (64 of record, 4 of map; the first sphmi_download_permutation
+ *     adds 4 more, a read 8 per requested array); the message gives the bytes, nothing is held and the handle stays usable.
+ */
+int sphmi_envelopes_enable(sphmi_handle* h, int32_t type_mask);
+int sphmi_envelopes_read(sphmi_handle* h, int64_t* steps_out, double* window_out /* [3] t_begin, t_end, duration */,
+                         double* p_max_out, double* t_p_max_out, double* p_min_out, double* impulse_out, double* square_out,
+                         double* loaded_out, double* speed_max_out, double* t_arrival_out /* each [n] */);
+
+/*
  * MotionDetails of the Geometry with this GroupMarker (src/SimulationGeometry.jl:17-22): particles of Type Moving
  * in that group get Velocity = velocity·direction while start_time <= TotalTime <= start_time + duration (0
  * otherwise) and are displaced by Velocity·dt/2 before each neighbour pass — ProgressMotion,

@@ -33,6 +33,9 @@
 # SPHMI_FLOW_BOXES (unset by default; "lo,lo,lo:hi,hi,hi;…" = record the flow through these half-open control boxes, `dims` bounds on
 # either side of the colon, "-Inf" / "Inf" allowed, at every step on the device — sphmi_flow_enable — and collect the series in
 # SPHExampleMI355X.FLOW[SimParticles]).
+# SPHMI_ENVELOPES (unset by default; "1" = the fluid, or a list of "Fluid", "Fixed", "Moving" = accumulate per particle, at every step on the
+# device, the pressure and speed envelopes of the rows of those types — sphmi_envelopes_enable — and keep the newest read, in the row
+# order of that output, in SPHExampleMI355X.ENVELOPES[SimParticles]).
 #
 # EXPERIMENTAL: the build image has no Julia, so this file has never been executed.  struct layout and ABI version
 # are asserted against the library at first use (sphmi_create refuses a mismatching struct_size / abi_version).
@@ -189,6 +192,41 @@ function read_flow!(h, fs::FlowSeries)
     fs.entered = hcat(fs.entered, en); fs.left = hcat(fs.left, le); fs.dropped += dropped[]
     return nothing
 end
+# SPHMI_ENVELOPES: what every particle has experienced since the session opened, bound like FLOW — but a state, not a series: every output
+# REPLACES the arrays (row i is particle i of that output): p_max, t_p_max, p_min, impulse (Σ P·dt), square (Σ P²·dt), loaded (Σ dt over
+# steps with P > 0), speed_max and t_arrival (Inf: never loaded); steps, t_begin, t_end, duration describe the window
+mutable struct Envelopes
+    mask::Int32
+    steps::Int64; t_begin::Float64; t_end::Float64; duration::Float64
+    p_max::Vector{Float64}; t_p_max::Vector{Float64}; p_min::Vector{Float64}; impulse::Vector{Float64}; square::Vector{Float64}
+    loaded::Vector{Float64}; speed_max::Vector{Float64}; t_arrival::Vector{Float64}
+end
+const ENVELOPES = IdDict{Any,Envelopes}()
+const ENVELOPE_TYPES = Dict("fluid" => 1, "fixed" => 2, "moving" => 3)
+function envelopes_mask()
+    asked = lowercase.(strip.(split(get(ENV, "SPHMI_ENVELOPES", ""), ",")))
+    asked = [a for a in asked if !(a in ("", "0"))]
+    isempty(asked) && return Int32(0)
+    all(a -> a == "1" || haskey(ENVELOPE_TYPES, a), asked) || error("SPHMI_ENVELOPES: \"1\" (the fluid) or a list of Fluid, Fixed, Moving")
+    return Int32(reduce(|, [1 << (a == "1" ? 1 : ENVELOPE_TYPES[a]) for a in asked]))
+end
+function envelopes_enable(h, mask::Integer)
+    check(h, ccall((:sphmi_envelopes_enable, LIB), Cint, (Ptr{Cvoid}, Int32), h, Int32(mask)))
+    return nothing
+end
+function envelopes_read(h, n::Integer)
+    steps = Ref{Int64}(0); window = zeros(3)
+    a = [Vector{Float64}(undef, n) for _ in 1:8]
+    GC.@preserve window a check(h, ccall((:sphmi_envelopes_read, LIB), Cint, (Ptr{Cvoid}, Ref{Int64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+                                         h, steps, pointer(window), pointer(a[1]), pointer(a[2]), pointer(a[3]), pointer(a[4]), pointer(a[5]), pointer(a[6]), pointer(a[7]), pointer(a[8])))
+    return steps[], window, a
+end
+function read_envelopes!(h, en::Envelopes, n::Integer)
+    en.steps, w, a = envelopes_read(h, n)
+    en.t_begin, en.t_end, en.duration = w
+    en.p_max, en.t_p_max, en.p_min, en.impulse, en.square, en.loaded, en.speed_max, en.t_arrival = a
+    return nothing
+end
 # The probes' sums at every node of a regular lattice, evaluated on the state the session holds NOW (sphmi_sample_grid): node (i, j[, k])
 # lies at origin .+ (i, j[, k]) .* spacing, zero-based.  Returns arrays indexed [i, j[, k]] (x fastest: Julia's column-major order IS the
 # node order), velocity as 3 × nx × ny[ × nz].  Call it from an output callback, i.e. between two SimulationLoop calls, after the first step.
@@ -342,6 +380,11 @@ function open_session(SimDensityDiffusion, SimViscosity, SimKernel, SimMetaData:
         FLOW[P] = FlowSeries(box_lo, box_hi, Int64[], Float64[], Float64[], zeros(Int64, m, 0), zeros(Float64, m, 0), Array{Float64,3}(undef, 3, m, 0),
                              zeros(Int64, m, 0), zeros(Int64, m, 0), 0)
     end
+    mask = envelopes_mask()                        # opt-in as well: SPHMI_ENVELOPES
+    if mask != 0
+        envelopes_enable(h, mask)
+        ENVELOPES[P] = Envelopes(mask, 0, 0.0, 0.0, 0.0, Float64[], Float64[], Float64[], Float64[], Float64[], Float64[], Float64[], Float64[])
+    end
     return Session(h, Vector{Int64}(undef, N), zeros(8), zeros(Int64, 8), Vector{Int}(undef, N), Vector{Int64}(undef, SimMetaData.ExportGridCells ? N * D : 0),
                    columns, colptrs)
     catch
@@ -387,6 +430,7 @@ function SimulationLoop(SimDensityDiffusion::BuiltinDDT, SimViscosity::BuiltinVi
     haskey(PROBES, P) && read_probes!(h, PROBES[P])
     haskey(BUDGETS, P) && read_budgets!(h, BUDGETS[P])
     haskey(FLOW, P) && read_flow!(h, FLOW[P])
+    haskey(ENVELOPES, P) && read_envelopes!(h, ENVELOPES[P], length(P))
     GC.@preserve P s begin
         # the carried fields: snapshot on the device, copies on a second stream, straight into the StructArray's columns
         # (Cells: a Vector{CartesianIndex{D}} is N·D Int64; Type is a per-particle constant and follows the gather below)

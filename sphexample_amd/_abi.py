@@ -462,6 +462,33 @@ class Backend:
         self.flow_dropped = dropped.value
         return {key: a[:n.value] for key, a in out.items()}
 
+    # -- per-particle pressure and speed envelopes at every step (sphmi_envelopes_enable / sphmi_envelopes_read) ---------------
+    ENVELOPE_FIELDS = ("p_max", "t_p_max", "p_min", "impulse", "square", "loaded", "speed_max", "t_arrival")
+
+    def has_envelopes(self) -> bool:
+        return self._has("envelopes_enable") and self._has("envelopes_read")
+
+    def envelopes_enable(self, types=("Fluid",)) -> None:
+        """Accumulate, after every executed step and on the device, what each row of `types` ("Fluid", "Fixed", "Moving", or their
+        Type numbers) experiences: the largest and smallest pressure, when the largest occurred, the pressure impulse, the time
+        under load, the largest speed and the arrival time of the first positive pressure.  The records follow the particle
+        through every sort.  A second call replaces the selection and restarts the window; an empty `types` disables."""
+        f = self._fn("envelopes_enable")
+        f.argtypes = [C.c_void_p, C.c_int32]
+        self._check(f(self._h, self._type_mask(types)))
+
+    def envelopes_read(self) -> dict:
+        """The envelopes as they stand, without clearing them: `steps` (executed steps since the enable), `t_begin`, `t_end`,
+        `duration` (sum of dt) and float64 [n] arrays `p_max`, `t_p_max`, `p_min`, `impulse` (sum P dt), `square` (sum P^2 dt),
+        `loaded` (sum dt over steps with P > 0), `speed_max` and `t_arrival` (+inf: never loaded); row i is row i of what `download`
+        delivers now.  Rows of a type that is not selected hold the start record (-inf, 0, +inf, 0, 0, 0, 0, +inf)."""
+        f = self._fn("envelopes_read")
+        f.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.c_void_p] + [C.c_void_p] * 8
+        steps, window = C.c_int64(), np.zeros(3)
+        out = {name: np.zeros(self.N) for name in self.ENVELOPE_FIELDS}
+        self._check(f(self._h, C.byref(steps), _ptr(window), *[_ptr(a) for a in out.values()]))
+        return {"steps": int(steps.value), "t_begin": float(window[0]), "t_end": float(window[1]), "duration": float(window[2]), **out}
+
     # -- kernel sums on a regular lattice, on demand (sphmi_sample_grid) -----------------------------------------------------
     GRID_FIELDS = ("weight", "count", "pressure", "density", "velocity")
 

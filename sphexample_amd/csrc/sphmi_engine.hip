@@ -21,6 +21,7 @@
 #include "sphmi_group_forces.h"
 #include "sphmi_budgets.h"
 #include "sphmi_flow.h"
+#include "sphmi_envelopes.h"
 #include "sphmi_probes.h"
 #include "sphmi_field_grid.h"
 #include "sphmi_particle_fields.h"
@@ -160,6 +161,16 @@ struct EngineBase {
         fl_series.read("sphmi_flow_read", capacity, iteration_out, time, dt, n_out, n_dropped, [&](int64_t k, const double* v) {
             deliver_flow(cfg.m0, fl_series.values / kFlValues, k, v, count, volume, momentum, entered, left);
         });
+    }
+    // The per-particle envelopes (sphmi_envelopes.h) live in the rows' own device: a handle of one device overrides the pair.  Rows of
+    // a multi-device handle migrate between slabs, and carrying the records along is not built.
+    virtual void envelopes_enable(uint32_t) {
+        require_uploaded("sphmi_envelopes_enable");
+        throw EngineError(SPHMI_ERR_STATE, "sphmi_envelopes_enable: single-device handles only (rows migrate between slabs; their records are not carried along)");
+    }
+    virtual void envelopes_read(int64_t*, double*, double*, double*, double*, double*, double*, double*, double*, double*) {
+        require_uploaded("sphmi_envelopes_read");
+        throw EngineError(SPHMI_ERR_STATE, "sphmi_envelopes_read: single-device handles only");
     }
     void group_forces_enable(int32_t n_groups, const uint64_t* markers, int64_t capacity_steps) {
         require_one_process("sphmi_group_forces_enable");
@@ -517,7 +528,7 @@ struct Engine final : EngineBase {
         for (auto& e : host_pinned) (void)hipHostUnregister(e.first);
         (void)hipFree(out_arena);
         (void)hipFree(col_arena); (void)hipFree(col_store); (void)hipFree(col_base[0]); (void)hipFree(col_base[1]);
-        gf_release(); pr_release(); bg_release(); fl_release(); fg_arena.free(); pf_arena.free(); nl_free(); iso_free(); cc_free();
+        gf_release(); pr_release(); bg_release(); fl_release(); en_release(); fg_arena.free(); pf_arena.free(); nl_free(); iso_free(); cc_free();
         (void)hipFree(slot); (void)hipFree(tmp_idx); (void)hipFree(perm);
         for (int k = 0; k < 2; ++k) { (void)hipFree(tile_cost[k]); (void)hipFree(tile_order[k]); }
         (void)hipFree(kout_d); (void)hipFree(tile_work_d); (void)hipFree(tile_work1_d); (void)hipFree(xcd_clock_d); (void)hipHostFree(xcd_clock_h);
@@ -1195,6 +1206,7 @@ struct Engine final : EngineBase {
         if (pr_on) pr_sample(ctrl_cur(), obs_iteration0, obs_steps_base, iB);   // the kernel sums at the probes, on the corrector's output set → the batch's log
         if (bg_on) bg_sample(ctrl_cur(), obs_iteration0, obs_steps_base, iB);   // the budgets of the fluid, on the same set → the batch's log
         if (fl_on) fl_sample(ctrl_cur(), obs_iteration0, obs_steps_base, iB);   // the flow through the control boxes: that set against this step's marks
+        if (en_mask) en_update(ctrl_cur(), iB);                                 // the per-particle envelopes: that set and the half step's density → the rows' records
         std::swap(iA, iB);
     }
 
@@ -1351,6 +1363,7 @@ struct Engine final : EngineBase {
         pr_disable();                              // … and the probes go with them
         bg_disable();                              // … and the budgets
         fl_disable();                              // … and the control boxes
+        en_disable();                              // … and the envelopes of the old rows
         iA = 0; iH = 1; iB = 2; cur = 0;
         ghost_given = ghost_points != nullptr;
         {
@@ -1414,6 +1427,7 @@ struct Engine final : EngineBase {
             pr_disable();
             bg_disable();
             fl_disable();
+            en_disable();
             iA = 0; iH = 1; iB = 2; cur = 0; ghost_given = false; mdbc_n_list = 0; mdbc_list_valid = false;
             int base = 0;
             const unsigned nbM = (unsigned)((M + 255) / 256);
@@ -1587,6 +1601,13 @@ struct Engine final : EngineBase {
         HC(hipSetDevice(cfg.device));
         std::vector<int> tmp((size_t)N);
         bounce.d2h(tmp.data(), prow[cur], (size_t)N * 4, stream);
+        if (en_mask) en_base[en_cur ^ 1].need((size_t)N, [&](size_t bytes) {      // (before anything of the epoch changes: a refusal leaves it as it was)
+            return text("sphmi_download_permutation: no device memory for the envelopes' second row map (%zu bytes)", bytes);
+        });
+        if (en_mask) {                                 // the envelopes' records are found the same way, through a map of their own
+            hipLaunchKernelGGL(k_columns_base_compose, dim3((N + 255) / 256), dim3(256), 0, stream, (const int*)en_base[en_cur].p, (const int*)prow[cur], en_base[en_cur ^ 1].p, N);
+            en_cur ^= 1;
+        }
         if (col_store) {                               // attached columns: their records are found through the epoch that ends here
             hipLaunchKernelGGL(k_columns_base_compose, dim3((N + 255) / 256), dim3(256), 0, stream, (const int*)col_base[col_cur], (const int*)prow[cur], col_base[col_cur ^ 1], N);
             col_cur ^= 1;
@@ -1920,6 +1941,94 @@ struct Engine final : EngineBase {
             hipLaunchKernelGGL(k_fl_final<T>, dim3(fl_boxes.n), dim3(64), 0, stream, A);
         }
         HC(hipGetLastError());
+    }
+
+    // ---- per-particle pressure and speed envelopes at every step (sphmi_envelopes.h) -----------------------------------------------
+    // One streaming launch behind every corrector.  The records never move: row i finds its own at en_base[en_cur][prow[i]], the
+    // columns' indirection with a map of its own, so attaching or detaching columns and enabling or disabling envelopes do not touch
+    // each other.  No series, no log: the records ARE the result, gathered into the current order by a read.
+    uint32_t en_mask = 0;                      // bit Type; 0: off, and no step launches anything for it
+    DeviceBuf<double2> en_store;               // N records of kEnValues doubles, then the window header (kEnHeader doubles)
+    DeviceBuf<int> en_base[2];                 // row at the last permutation epoch → record; [en_cur] is live, the other one grows at the first permutation
+    int en_cur = 0;
+    DeviceBuf<double> en_arena;                // a read: one array per requested value, in the current order
+    double* en_header() const { return (double*)(en_store.p + (size_t)N * (kEnValues / 2)); }
+    void en_release() { en_store.free(); en_base[0].free(); en_base[1].free(); en_arena.free(); en_cur = 0; }
+    void en_disable() {
+        if (en_mask) {
+            en_mask = 0;
+            HC(hipSetDevice(cfg.device)); HC(hipStreamSynchronize(stream));
+        }
+        en_release();
+    }
+    void envelopes_enable(uint32_t type_mask) override {
+        require_uploaded("sphmi_envelopes_enable");
+        if (dd_slab) throw EngineError(SPHMI_ERR_STATE, "sphmi_envelopes_enable: single-device handles only");
+        check_envelope_mask(type_mask);
+        HC(hipSetDevice(cfg.device));
+        en_disable();
+        if (type_mask == 0) return;
+        const size_t n = (size_t)N;
+        auto no_memory = [&](size_t) {
+            return text("sphmi_envelopes_enable: no device memory for the records of %lld rows (%zu bytes, 68 per row)", (long long)N,
+                        n * (kEnValues * 8 + 4) + kEnHeader * 8);
+        };
+        try {
+            en_store.need(n * (kEnValues / 2) + kEnHeader / 2, no_memory);
+            en_base[0].need(n, no_memory);
+        } catch (...) { en_release(); throw; }
+        const int blocks = std::max((N + kEnBlock - 1) / kEnBlock, 1);
+        hipLaunchKernelGGL(k_en_fill, dim3(blocks), dim3(kEnBlock), 0, stream, en_store.p, en_header(), N, total_time);
+        // record i belongs to row i of the present order: its row at the last epoch is prow[i]
+        hipLaunchKernelGGL(k_columns_base_init, dim3(blocks), dim3(256), 0, stream, (const int*)prow[cur], en_base[0].p, N);
+        HC(hipGetLastError());
+        HC(hipStreamSynchronize(stream));
+        en_mask = type_mask;
+    }
+    // queued behind the corrector of a step; `set`: the state set that corrector wrote
+    void en_update(const StepCtrl* ctrl, int set) {
+        if (N <= 0) return;
+        EnvelopeArgs<T> A{};
+        A.ctrl = ctrl; A.pk0 = pk0[set]; A.pk1 = pk1[set]; A.half0 = pk0[iH];
+        A.prow = prow[cur]; A.base = en_base[en_cur].p; A.store = en_store.p; A.header = en_header();
+        A.rho0 = (T)cfg.rho0; A.inv_rho0 = (T)(1.0 / cfg.rho0); A.Cbe = cbe();
+        A.type_mask = en_mask;
+        // Fluid is told off the sign of the ρ·s slot; only a mask that separates Fixed from Moving needs the type byte
+        A.type = ((en_mask >> 2) & 1u) != ((en_mask >> 3) & 1u) ? type[cur] : nullptr;
+        A.N = N; A.D = D;
+        hipLaunchKernelGGL(k_en_update<T>, dim3((N + kEnBlock - 1) / kEnBlock), dim3(kEnBlock), 0, stream, A);
+        HC(hipGetLastError());
+    }
+    void envelopes_read(int64_t* steps_out, double* window_out, double* p_max, double* t_p_max, double* p_min, double* impulse, double* square, double* loaded,
+                        double* speed_max, double* t_arrival) override {
+        require_uploaded("sphmi_envelopes_read");
+        if (!en_mask) throw EngineError(SPHMI_ERR_STATE, "sphmi_envelopes_read: envelopes are not enabled (sphmi_envelopes_enable)");
+        HC(hipSetDevice(cfg.device));
+        double* const outs[kEnValues] = {p_max, t_p_max, p_min, impulse, square, loaded, speed_max, t_arrival};
+        const size_t n = (size_t)N, per = (n * 8 + 255) / 256 * 32;            // doubles per delivered array, a multiple of 256 bytes
+        size_t wanted = 0;
+        for (double* o : outs) wanted += o ? 1 : 0;
+        ColumnTable t{};
+        t.n_columns = kEnValues; t.stride = kEnValues * 8; t.rows_per_block = gather_rows_per_block(t.stride);
+        if (wanted) {
+            en_arena.need(wanted * per, [&](size_t bytes) {
+                return text("sphmi_envelopes_read: no device memory for %zu arrays of %lld rows (%zu bytes)", wanted, (long long)N, bytes);
+            });
+            size_t at = 0;
+            for (int c = 0; c < kEnValues; ++c) {
+                t.offset[c] = 8 * c; t.width[c] = 8;
+                t.out[c] = outs[c] ? (char*)(en_arena.p + per * at++) : nullptr;
+            }
+            const int blocks = (N + t.rows_per_block - 1) / t.rows_per_block;
+            hipLaunchKernelGGL(k_gather_columns, dim3(blocks), dim3(kGatherThreads), gather_lds_bytes(t), stream, (const uint4*)en_store.p,
+                               (const int*)en_base[en_cur].p, (const int*)prow[cur], N, t);
+            HC(hipGetLastError());
+        }
+        double header[kEnHeader];
+        bounce.d2h(header, en_header(), sizeof(header), stream);
+        for (int c = 0; c < kEnValues; ++c) if (outs[c]) bounce.d2h(outs[c], t.out[c], n * 8, stream);
+        deliver_envelope_window(header, steps_out, window_out);
+        deliver_envelope_speed((int64_t)N, speed_max);
     }
 
     // ---- kernel sums on a regular lattice, on demand (sphmi_field_grid.h) ------------------------------------------------------
@@ -2808,6 +2917,12 @@ int sphmi_flow_enable(sphmi_handle* h, int32_t n_boxes, const double* lo, const 
 int sphmi_flow_read(sphmi_handle* h, int64_t capacity, int64_t* iteration_out, double* time_out, double* dt_out, int64_t* count_out, double* volume_out,
                     double* momentum_out, int64_t* entered_out, int64_t* left_out, int64_t* n_out, int64_t* n_dropped) {
     SPHMI_GUARD(h, h->e->flow_read(capacity, iteration_out, time_out, dt_out, count_out, volume_out, momentum_out, entered_out, left_out, n_out, n_dropped));
+}
+int sphmi_envelopes_enable(sphmi_handle* h, int32_t type_mask) { SPHMI_GUARD(h, h->e->envelopes_enable((uint32_t)type_mask)); }
+int sphmi_envelopes_read(sphmi_handle* h, int64_t* steps_out, double* window_out, double* p_max_out, double* t_p_max_out, double* p_min_out,
+                         double* impulse_out, double* square_out, double* loaded_out, double* speed_max_out, double* t_arrival_out) {
+    SPHMI_GUARD(h, h->e->envelopes_read(steps_out, window_out, p_max_out, t_p_max_out, p_min_out, impulse_out, square_out, loaded_out, speed_max_out,
+                                        t_arrival_out));
 }
 int sphmi_set_motion(sphmi_handle* h, uint64_t group_marker, double velocity, double start_time, double duration,
                      const double* direction) {

@@ -1227,10 +1227,7 @@ __global__ void __launch_bounds__(256) k_pack_output(Half<const typename Vec4<T>
     }
     if (o.press && half0) {
         // SimParticles.Pressure holds Pressure!(ρₙ⁺) of the last step (src/SPHCellList.jl:789)
-        const T w = half0[i].w;
-        const T rr = sizeof(T) == 8 ? w / rho0 : w * inv_rho0;
-        const T r2 = rr * rr, r4 = r2 * r2;
-        o.press[i] = (H)(Cbe * (r4 * r2 * rr - T(1)));
+        o.press[i] = (H)eos7<T>(half0[i].w, rho0, inv_rho0, Cbe);     // (k_en_update forms the same value: sphmi_envelopes.h)
     }
     if (o.acc) { const auto q = accv[i]; o.acc[b] = (H)q.x; o.acc[b + 1] = (H)q.y; if (C == 3) o.acc[b + 2] = (H)q.z; }
     if (o.ghost) { const auto q = ghostv[i]; o.ghost[b] = (H)q.x; o.ghost[b + 1] = (H)q.y; if (C == 3) o.ghost[b + 2] = (H)q.z; }

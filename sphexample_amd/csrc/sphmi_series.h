@@ -1,4 +1,4 @@
-// sphmi_series.h — the host side the observers share (group forces, probes, budgets, flow, lattice, columns): the error type, the limits and
+// sphmi_series.h — the host side the observers share (group forces, probes, budgets, flow, envelopes, lattice, columns): the error type, the limits and
 // record-layout constants host and device agree on, the argument checks every kind of handle reports alike, the per-step series
 // and the means of the kernel sums.  Plain C++17, no HIP: tests/host_series/series_main.cpp compiles it alone.
 #pragma once
@@ -35,6 +35,8 @@ constexpr int kBgValues = 22;                    // the raw budgets of the fluid
 constexpr int bg_rule(int slot) { return slot < 13 ? 0 : (slot == 14 || (slot >= 16 && slot <= 18)) ? 1 : 2; }
 constexpr int kMaxFlowBoxes = 16;                // SPHMI_MAX_FLOW_BOXES
 constexpr int kFlValues = 7;                     // per control box (sphmi_flow.h): n_after, Σ1/ρ, Σv[3], entered, left — every slot a sum
+constexpr int kEnValues = 8;                     // per row (sphmi_envelopes.h): p_max, t_p_max, p_min, impulse, square, loaded, speed2_max, t_arrival
+constexpr int kEnHeader = 4;                     // the window of the envelopes: steps (int64 bits), t_begin, t_end, duration
 
 // sphmi_attach_columns: the argument errors every kind of handle reports alike
 inline void check_column_table(int32_t n_columns, const void* const* columns, const int32_t* row_bytes) {
@@ -79,6 +81,12 @@ inline void check_flow_table(int32_t n_boxes, const double* lo, const double* hi
         if (std::isnan(lo[k]) || std::isnan(hi[k])) throw EngineError(SPHMI_ERR_ARGUMENT, "sphmi_flow_enable: NaN bound");
         if (!(lo[k] < hi[k])) throw EngineError(SPHMI_ERR_ARGUMENT, "sphmi_flow_enable: every box needs lo < hi on every axis");
     }
+}
+
+// sphmi_envelopes_enable: bit Type of the mask selects the rows of that Type (Fluid = 1, Fixed = 2, Moving = 3), as in
+// sphmi_components_build; 0 disables; any other bit is an argument error
+inline void check_envelope_mask(uint32_t type_mask) {
+    if (type_mask & ~0xEu) throw EngineError(SPHMI_ERR_ARGUMENT, "sphmi_envelopes_enable: type_mask has a bit other than 1 (Fluid), 2 (Fixed), 3 (Moving) set");
 }
 
 // sphmi_sample_grid: the argument errors every kind of handle reports alike; returns the number of nodes
@@ -205,6 +213,17 @@ inline void deliver_flow(double m0, int n_boxes, int64_t k, const double* raw, i
         if (entered) entered[at] = (int64_t)v[5];
         if (left) left[at] = (int64_t)v[6];
     }
+}
+
+// sphmi_envelopes_read: the window header as the device keeps it { steps (int64 bits), t_begin, t_end, duration } → the caller's
+// steps_out and window_out[3]
+inline void deliver_envelope_window(const double* header, int64_t* steps_out, double* window_out) {
+    if (steps_out) memcpy(steps_out, header, 8);
+    if (window_out) for (int k = 0; k < 3; ++k) window_out[k] = header[1 + k];
+}
+// … and the largest speed of every row from max |v|² (slot 6), in place: the one sqrt, on the host (NaN stays NaN)
+inline void deliver_envelope_speed(int64_t n, double* speed) {
+    if (speed) for (int64_t i = 0; i < n; ++i) speed[i] = std::sqrt(speed[i]);
 }
 
 // The host side of sphmi_sample_grid: the raw sums { S, SP, Sρ, Sv[3], n } of the lattice (sphmi_field_grid.h), the ones the

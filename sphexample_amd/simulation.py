@@ -46,7 +46,7 @@ def RunSimulation(*, SimGeometry=None, SimMetaData: SimulationMetaData, SimConst
                   device_float_bytes: int = 0, device: int = 0, backend_factory=None,
                   async_output: bool = False, group_forces=None, probes=None, field_grid=None,
                   particle_fields=None, budgets: bool = False, neighbor_list: bool = False, isosurface=None, components=None,
-                  flow_boxes=None) -> List[float]:
+                  flow_boxes=None, envelopes=None) -> List[float]:
     """Same keyword signature as the reference (src/SPHCellList.jl:808-817); returns the list of
     time steps the reference collects in ``TimeSteps`` (:823,:884).  ``SimParticles`` is updated in
     place at every output time, in the engine's cell-sorted order, as the reference's is.
@@ -100,7 +100,14 @@ def RunSimulation(*, SimGeometry=None, SimMetaData: SimulationMetaData, SimConst
     ``±inf`` allowed; ``sphexample_amd.flow.strips`` tiles an axis) is recorded on the device at every step
     (``Backend.flow_enable``; ``sphexample_amd.flow`` forms discharges and cumulative counts) and ``on_output`` receives the
     samples of the interval, the dict of ``Backend.flow_read``, as one more argument behind the budgets (empty arrays at the
-    first call).  ``None`` (default): nothing is recorded and the callback keeps its arguments."""
+    first call).  ``None`` (default): nothing is recorded and the callback keeps its arguments.
+
+    ``envelopes=True | types``: what every particle of `types` (the fluid for ``True``; ``"Fluid"``, ``"Fixed"``, ``"Moving"`` or a
+    tuple of them) experiences is accumulated on the device at every step (``Backend.envelopes_enable``: peak pressure and its
+    time, impulse, time under load, largest speed, arrival time; ``sphexample_amd.envelopes`` forms means and an arrival map) and
+    ``on_output`` receives the dict of ``Backend.envelopes_read`` as its last argument, the way ``particle_fields=`` hands over its
+    fields (``None`` at the first call).  The envelopes keep growing over the whole run; row i is particle i of that output.
+    ``None`` or ``False`` (default): nothing is accumulated and the callback keeps its arguments."""
     if SimMetaData.BMode.__name__ == "SimpleMDBC":
         LoadMDBCNormals(SimParticles, ParticleNormalsPath)                       # :827
     host_bytes = SimParticles.Position.dtype.itemsize
@@ -161,6 +168,9 @@ def RunSimulation(*, SimGeometry=None, SimMetaData: SimulationMetaData, SimConst
         boxes = [(np.asarray(lo, dtype=np.float64), np.asarray(hi, dtype=np.float64)) for lo, hi in flow_boxes]
         eng.flow_enable([lo for lo, _ in boxes], [hi for _, hi in boxes], capacity=1 << 20)
         extras.append((empty_flow(len(boxes)), eng.flow_read))
+    if envelopes is not None and envelopes is not False:
+        eng.envelopes_enable(("Fluid",) if envelopes is True else envelopes)
+        extras.append((None, eng.envelopes_read))                                # (the rows of this output: no step lies between it and the download)
     none_yet = tuple(first for first, _ in extras)
     emit = lambda meta, samples: on_output(meta, SimParticles, *samples)         # noqa: E731
     if on_output:
