@@ -36,6 +36,9 @@
 # SPHMI_ENVELOPES (unset by default; "1" = the fluid, or a list of "Fluid", "Fixed", "Moving" = accumulate per particle, at every step on the
 # device, the pressure and speed envelopes of the rows of those types — sphmi_envelopes_enable — and keep the newest read, in the row
 # order of that output, in SPHExampleMI355X.ENVELOPES[SimParticles]).
+# SPHMI_MAPS (unset by default; "origin:spacing:counts[:up_axis]", `dims` numbers per part, "Inf" allowed as a spacing next to a count of 1,
+# up_axis zero-based = accumulate per bin of that lattice, at every step on the device, crest, arrival time, wet duration, fill, flux and
+# the largest bin-mean speed — sphmi_maps_enable — and keep the newest read in SPHExampleMI355X.MAPS[SimParticles]).
 #
 # EXPERIMENTAL: the build image has no Julia, so this file has never been executed.  struct layout and ABI version
 # are asserted against the library at first use (sphmi_create refuses a mismatching struct_size / abi_version).
@@ -227,6 +230,50 @@ function read_envelopes!(h, en::Envelopes, n::Integer)
     en.p_max, en.t_p_max, en.p_min, en.impulse, en.square, en.loaded, en.speed_max, en.t_arrival = a
     return nothing
 end
+# SPHMI_MAPS: what every bin of a lattice has experienced since the session opened, bound like ENVELOPES — a state, not a series: every
+# output REPLACES the arrays.  Arrays are indexed [k0, k1[, k2]] (x fastest: Julia's column-major order IS the bin order), flux and
+# last_velocity_sum as 3 × counts…; speed2_max is the SQUARE of the largest bin-mean speed; t_arrival is Inf in a bin that never got wet
+mutable struct Maps
+    origin::Vector{Float64}; spacing::Vector{Float64}; counts::Vector{Int64}; up_axis::Int32
+    steps::Int64; t_begin::Float64; t_end::Float64; duration::Float64
+    top_max::Array{Float64}; t_top_max::Array{Float64}; bottom_min::Array{Float64}; t_arrival::Array{Float64}; wet::Array{Float64}; fill::Array{Float64}
+    flux::Array{Float64}; speed2_max::Array{Float64}; t_speed2_max::Array{Float64}; n_max::Array{Float64}
+    last_n::Array{Int64}; last_top::Array{Float64}; last_bottom::Array{Float64}; last_velocity_sum::Array{Float64}
+end
+const MAPS = IdDict{Any,Maps}()
+function maps_lattice(D)
+    parts = [strip.(split(part, ",")) for part in split(get(ENV, "SPHMI_MAPS", ""), ":") if !isempty(strip(part))]
+    isempty(parts) && return nothing
+    (length(parts) in (3, 4) && all(k -> length(parts[k]) == D, 1:3) && (length(parts) == 3 || length(parts[4]) == 1)) ||
+        error("SPHMI_MAPS: \"origin:spacing:counts[:up_axis]\" with $D numbers in each of the first three parts")
+    up = length(parts) == 4 ? parse(Int32, parts[4][1]) : Int32(D - 1)
+    return parse.(Float64, parts[1]), parse.(Float64, parts[2]), parse.(Int64, parts[3]), up
+end
+function maps_enable(h, origin::Vector{Float64}, spacing::Vector{Float64}, counts::Vector{Int64}, up_axis::Integer)
+    GC.@preserve origin spacing counts check(h, ccall((:sphmi_maps_enable, LIB), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Int64}, Int32),
+                                                       h, pointer(origin), pointer(spacing), pointer(counts), Int32(up_axis)))
+    return nothing
+end
+function maps_disable(h)
+    check(h, ccall((:sphmi_maps_disable, LIB), Cint, (Ptr{Cvoid},), h))
+    return nothing
+end
+function maps_read(h, counts::Vector{Int64})
+    dims = Tuple(Int.(counts))
+    steps = Ref{Int64}(0); window = zeros(3)
+    a = [Array{Float64}(undef, k == 7 ? (3, dims...) : dims) for k in 1:10]
+    ln = Array{Int64}(undef, dims); lt = Array{Float64}(undef, dims); lb = Array{Float64}(undef, dims); ls = Array{Float64}(undef, (3, dims...))
+    GC.@preserve window a ln lt lb ls check(h, ccall((:sphmi_maps_read, LIB), Cint, (Ptr{Cvoid}, Ref{Int64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+                                                     h, steps, pointer(window), pointer(a[1]), pointer(a[2]), pointer(a[3]), pointer(a[4]), pointer(a[5]), pointer(a[6]), pointer(a[7]), pointer(a[8]), pointer(a[9]), pointer(a[10]), pointer(ln), pointer(lt), pointer(lb), pointer(ls)))
+    return steps[], window, a, (ln, lt, lb, ls)
+end
+function read_maps!(h, mp::Maps)
+    mp.steps, w, a, last = maps_read(h, mp.counts)
+    mp.t_begin, mp.t_end, mp.duration = w
+    mp.top_max, mp.t_top_max, mp.bottom_min, mp.t_arrival, mp.wet, mp.fill, mp.flux, mp.speed2_max, mp.t_speed2_max, mp.n_max = a
+    mp.last_n, mp.last_top, mp.last_bottom, mp.last_velocity_sum = last
+    return nothing
+end
 # The probes' sums at every node of a regular lattice, evaluated on the state the session holds NOW (sphmi_sample_grid): node (i, j[, k])
 # lies at origin .+ (i, j[, k]) .* spacing, zero-based.  Returns arrays indexed [i, j[, k]] (x fastest: Julia's column-major order IS the
 # node order), velocity as 3 × nx × ny[ × nz].  Call it from an output callback, i.e. between two SimulationLoop calls, after the first step.
@@ -385,6 +432,12 @@ function open_session(SimDensityDiffusion, SimViscosity, SimKernel, SimMetaData:
         envelopes_enable(h, mask)
         ENVELOPES[P] = Envelopes(mask, 0, 0.0, 0.0, 0.0, Float64[], Float64[], Float64[], Float64[], Float64[], Float64[], Float64[], Float64[])
     end
+    lattice = maps_lattice(D)                      # opt-in as well: SPHMI_MAPS
+    if lattice !== nothing
+        maps_enable(h, lattice...)
+        e = Float64[]
+        MAPS[P] = Maps(lattice..., 0, 0.0, 0.0, 0.0, e, e, e, e, e, e, e, e, e, e, Int64[], e, e, e)
+    end
     return Session(h, Vector{Int64}(undef, N), zeros(8), zeros(Int64, 8), Vector{Int}(undef, N), Vector{Int64}(undef, SimMetaData.ExportGridCells ? N * D : 0),
                    columns, colptrs)
     catch
@@ -431,6 +484,7 @@ function SimulationLoop(SimDensityDiffusion::BuiltinDDT, SimViscosity::BuiltinVi
     haskey(BUDGETS, P) && read_budgets!(h, BUDGETS[P])
     haskey(FLOW, P) && read_flow!(h, FLOW[P])
     haskey(ENVELOPES, P) && read_envelopes!(h, ENVELOPES[P], length(P))
+    haskey(MAPS, P) && read_maps!(h, MAPS[P])
     GC.@preserve P s begin
         # the carried fields: snapshot on the device, copies on a second stream, straight into the StructArray's columns
         # (Cells: a Vector{CartesianIndex{D}} is N·D Int64; Type is a per-particle constant and follows the gather below)

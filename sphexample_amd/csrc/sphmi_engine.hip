@@ -22,6 +22,7 @@
 #include "sphmi_budgets.h"
 #include "sphmi_flow.h"
 #include "sphmi_envelopes.h"
+#include "sphmi_maps.h"
 #include "sphmi_probes.h"
 #include "sphmi_field_grid.h"
 #include "sphmi_particle_fields.h"
@@ -171,6 +172,20 @@ struct EngineBase {
     virtual void envelopes_read(int64_t*, double*, double*, double*, double*, double*, double*, double*, double*, double*) {
         require_uploaded("sphmi_envelopes_read");
         throw EngineError(SPHMI_ERR_STATE, "sphmi_envelopes_read: single-device handles only");
+    }
+    // The per-bin maps (sphmi_maps.h) are accumulated where the rows are: a handle of one device overrides the three.  The slabs of a
+    // multi-device handle would each hold a part of every bin, and combining their records is not built.
+    virtual void maps_enable(const double*, const double*, const int64_t*, int32_t) {
+        require_uploaded("sphmi_maps_enable");
+        throw EngineError(SPHMI_ERR_STATE, "sphmi_maps_enable: single-device handles only (the slabs' parts of a bin are not combined)");
+    }
+    virtual void maps_disable() {
+        require_uploaded("sphmi_maps_disable");
+        throw EngineError(SPHMI_ERR_STATE, "sphmi_maps_disable: single-device handles only");
+    }
+    virtual void maps_read(int64_t*, double*, double* const*, int64_t*, double*, double*, double*) {
+        require_uploaded("sphmi_maps_read");
+        throw EngineError(SPHMI_ERR_STATE, "sphmi_maps_read: single-device handles only");
     }
     void group_forces_enable(int32_t n_groups, const uint64_t* markers, int64_t capacity_steps) {
         require_one_process("sphmi_group_forces_enable");
@@ -528,7 +543,7 @@ struct Engine final : EngineBase {
         for (auto& e : host_pinned) (void)hipHostUnregister(e.first);
         (void)hipFree(out_arena);
         (void)hipFree(col_arena); (void)hipFree(col_store); (void)hipFree(col_base[0]); (void)hipFree(col_base[1]);
-        gf_release(); pr_release(); bg_release(); fl_release(); en_release(); fg_arena.free(); pf_arena.free(); nl_free(); iso_free(); cc_free();
+        gf_release(); pr_release(); bg_release(); fl_release(); en_release(); mp_release(); fg_arena.free(); pf_arena.free(); nl_free(); iso_free(); cc_free();
         (void)hipFree(slot); (void)hipFree(tmp_idx); (void)hipFree(perm);
         for (int k = 0; k < 2; ++k) { (void)hipFree(tile_cost[k]); (void)hipFree(tile_order[k]); }
         (void)hipFree(kout_d); (void)hipFree(tile_work_d); (void)hipFree(tile_work1_d); (void)hipFree(xcd_clock_d); (void)hipHostFree(xcd_clock_h);
@@ -1207,6 +1222,7 @@ struct Engine final : EngineBase {
         if (bg_on) bg_sample(ctrl_cur(), obs_iteration0, obs_steps_base, iB);   // the budgets of the fluid, on the same set → the batch's log
         if (fl_on) fl_sample(ctrl_cur(), obs_iteration0, obs_steps_base, iB);   // the flow through the control boxes: that set against this step's marks
         if (en_mask) en_update(ctrl_cur(), iB);                                 // the per-particle envelopes: that set and the half step's density → the rows' records
+        if (mp_on) mp_update(ctrl_cur(), iB);                                   // the per-bin maps: the Fluid rows of that set → the step's map → the bins' records
         std::swap(iA, iB);
     }
 
@@ -1364,6 +1380,7 @@ struct Engine final : EngineBase {
         bg_disable();                              // … and the budgets
         fl_disable();                              // … and the control boxes
         en_disable();                              // … and the envelopes of the old rows
+        mp_disable();                              // … and the maps they drew
         iA = 0; iH = 1; iB = 2; cur = 0;
         ghost_given = ghost_points != nullptr;
         {
@@ -1428,6 +1445,7 @@ struct Engine final : EngineBase {
             bg_disable();
             fl_disable();
             en_disable();
+            mp_disable();
             iA = 0; iH = 1; iB = 2; cur = 0; ghost_given = false; mdbc_n_list = 0; mdbc_list_valid = false;
             int base = 0;
             const unsigned nbM = (unsigned)((M + 255) / 256);
@@ -2029,6 +2047,114 @@ struct Engine final : EngineBase {
         for (int c = 0; c < kEnValues; ++c) if (outs[c]) bounce.d2h(outs[c], t.out[c], n * 8, stream);
         deliver_envelope_window(header, steps_out, window_out);
         deliver_envelope_speed((int64_t)N, speed_max);
+    }
+
+    // ---- per-bin maps of crest, arrival and mean flow at every step (sphmi_maps.h) ------------------------------------------------------
+    // Two launches behind every corrector: the rows into the step's map (integer atomics), the step's map into the bins' records.
+    // Nothing is keyed by row, so rebuilds and permutations have no hook.  No series, no log: the records ARE the result.
+    bool mp_on = false;                        // off: no step launches anything for it
+    MapLattice mp_lat{};
+    DeviceBuf<double> mp_record;               // kMpValues · bins doubles, then the header (kMpHeaderDev doubles)
+    DeviceBuf<unsigned long long> mp_step64;   // 2 buffers × 5 arrays × bins
+    DeviceBuf<unsigned> mp_count;              // 2 buffers × bins
+    MapStore mp_store() const {
+        const size_t B = (size_t)mp_lat.bins;
+        MapStore m{};
+        m.record = mp_record.p; m.header = mp_record.p + (size_t)kMpValues * B;
+        for (int p = 0; p < 2; ++p) { m.step64[p] = mp_step64.p + (size_t)p * 5 * B; m.count[p] = mp_count.p + (size_t)p * B; }
+        return m;
+    }
+    void mp_release() { mp_record.free(); mp_step64.free(); mp_count.free(); mp_lat.bins = 0; }
+    void mp_disable() {
+        if (mp_on) {
+            mp_on = false;
+            HC(hipSetDevice(cfg.device)); HC(hipStreamSynchronize(stream));
+        }
+        mp_release();
+    }
+    void maps_disable() override {
+        require_uploaded("sphmi_maps_disable");
+        mp_disable();
+    }
+    void maps_enable(const double* origin, const double* spacing, const int64_t* counts, int32_t up_axis) override {
+        require_uploaded("sphmi_maps_enable");
+        if (dd_slab) throw EngineError(SPHMI_ERR_STATE, "sphmi_maps_enable: single-device handles only");
+        const int64_t bins = check_map_lattice(origin, spacing, counts, D, up_axis);
+        if ((int64_t)N > map_row_bound(cfg.c0))
+            throw EngineError(SPHMI_ERR_ARGUMENT, text("sphmi_maps_enable: %lld rows, and the fixed-point velocity sums hold at most 2^31 / (4 c0) = %lld", (long long)N,
+                                                       (long long)map_row_bound(cfg.c0)));
+        HC(hipSetDevice(cfg.device));
+        mp_disable();
+        const size_t B = (size_t)bins;
+        auto no_memory = [&](size_t) {
+            return text("sphmi_maps_enable: no device memory for %lld bins (%zu bytes, 184 per bin)", (long long)bins, B * (kMpValues * 8 + 2 * 44) + kMpHeaderDev * 8);
+        };
+        try {
+            mp_record.need(B * kMpValues + kMpHeaderDev, no_memory);
+            mp_step64.need(B * 10, no_memory);
+            mp_count.need(B * 2, no_memory);
+        } catch (...) { mp_release(); throw; }
+        for (int d = 0; d < 3; ++d) {
+            mp_lat.origin[d] = d < D ? origin[d] : 0.0;
+            mp_lat.spacing[d] = d < D ? spacing[d] : std::numeric_limits<double>::infinity();
+            mp_lat.counts[d] = d < D ? (int)counts[d] : 1;
+            mp_lat.countd[d] = (double)mp_lat.counts[d];
+        }
+        mp_lat.up = up_axis; mp_lat.bins = (int)bins;
+        hipLaunchKernelGGL(k_mp_fill, dim3(((int)bins + kMpBlock - 1) / kMpBlock), dim3(kMpBlock), 0, stream, mp_store(), (int)bins, total_time);
+        HC(hipGetLastError());
+        HC(hipStreamSynchronize(stream));
+        mp_on = true;
+    }
+    // queued behind the corrector of a step; `set`: the state set that corrector wrote
+    void mp_update(const StepCtrl* ctrl, int set) {
+        if (N <= 0) return;
+        MapArgs<T> A{};
+        A.ctrl = ctrl; A.pk0 = pk0[set]; A.pk1 = pk1[set]; A.comp = comp[cur]; A.type = nullptr;
+        A.m = mp_store(); A.lat = mp_lat; A.N = N; A.D = D;
+        hipLaunchKernelGGL(k_mp_bin<T>, dim3((N + kMpBlock - 1) / kMpBlock), dim3(kMpBlock), 0, stream, A);
+        hipLaunchKernelGGL(k_mp_fold, dim3((mp_lat.bins + kMpBlock - 1) / kMpBlock), dim3(kMpBlock), 0, stream, ctrl, A.m, mp_lat.bins);
+        HC(hipGetLastError());
+    }
+    // values[kMpValues − 2]: top_max, t_top_max, bottom_min, t_arrival, wet, fill, flux ([bins][3]), speed2_max, t_speed2_max, n_max
+    void maps_read(int64_t* steps_out, double* window_out, double* const* values, int64_t* last_n, double* last_top, double* last_bottom,
+                   double* last_sum) override {
+        require_uploaded("sphmi_maps_read");
+        if (!mp_on) throw EngineError(SPHMI_ERR_STATE, "sphmi_maps_read: maps are not enabled (sphmi_maps_enable)");
+        HC(hipSetDevice(cfg.device));
+        const size_t B = (size_t)mp_lat.bins;
+        const MapStore m = mp_store();
+        double header[kMpHeaderDev];
+        bounce.d2h(header, m.header, sizeof(header), stream);
+        deliver_envelope_window(header, steps_out, window_out);
+        static const int slot_of[kMpValues - 2] = {0, 1, 2, 3, 4, 5, 6, 9, 10, 11};
+        std::vector<double> c[3];
+        for (int k = 0; k < kMpValues - 2; ++k) {
+            if (!values[k]) continue;
+            if (slot_of[k] != 6) { bounce.d2h(values[k], m.record + (size_t)slot_of[k] * B, B * 8, stream); continue; }
+            for (int d = 0; d < 3; ++d) { c[d].resize(B); bounce.d2h(c[d].data(), m.record + (size_t)(6 + d) * B, B * 8, stream); }
+            deliver_map_vectors((int64_t)B, c[0].data(), c[1].data(), c[2].data(), values[k]);
+        }
+        // the map of the last executed step lies in the buffer that step chose: (steps − 1) & 1 (no step yet: both are at the identities)
+        int64_t steps = 0;
+        memcpy(&steps, header, 8);
+        const int p = steps > 0 ? (int)((steps - 1) & 1) : 0;
+        std::vector<unsigned> n(last_n || last_top || last_bottom ? B : 0);
+        if (!n.empty()) bounce.d2h(n.data(), m.count[p], B * 4, stream);
+        if (last_n) for (size_t b = 0; b < B; ++b) last_n[b] = (int64_t)n[b];
+        std::vector<uint64_t> w(B);
+        for (int side = 0; side < 2; ++side) {
+            double* out = side ? last_bottom : last_top;
+            if (!out) continue;
+            bounce.d2h(w.data(), m.step64[p] + (size_t)side * B, B * 8, stream);
+            for (size_t b = 0; b < B; ++b) out[b] = n[b] ? mp_value(w[b]) : mp_start(side ? 2 : 0);      // a dry bin: −inf / +inf, as the records start
+        }
+        if (last_sum) {
+            for (int d = 0; d < 3; ++d) {
+                bounce.d2h(w.data(), m.step64[p] + (size_t)(2 + d) * B, B * 8, stream);
+                for (size_t b = 0; b < B; ++b) last_sum[3 * b + d] = mp_unfixed((long long)w[b]);
+            }
+        }
     }
 
     // ---- kernel sums on a regular lattice, on demand (sphmi_field_grid.h) ------------------------------------------------------
@@ -2923,6 +3049,17 @@ int sphmi_envelopes_read(sphmi_handle* h, int64_t* steps_out, double* window_out
                          double* impulse_out, double* square_out, double* loaded_out, double* speed_max_out, double* t_arrival_out) {
     SPHMI_GUARD(h, h->e->envelopes_read(steps_out, window_out, p_max_out, t_p_max_out, p_min_out, impulse_out, square_out, loaded_out, speed_max_out,
                                         t_arrival_out));
+}
+int sphmi_maps_enable(sphmi_handle* h, const double* origin, const double* spacing, const int64_t* counts, int32_t up_axis) {
+    SPHMI_GUARD(h, h->e->maps_enable(origin, spacing, counts, up_axis));
+}
+int sphmi_maps_disable(sphmi_handle* h) { SPHMI_GUARD(h, h->e->maps_disable()); }
+int sphmi_maps_read(sphmi_handle* h, int64_t* steps_out, double* window_out, double* top_max_out, double* t_top_max_out, double* bottom_min_out,
+                    double* t_arrival_out, double* wet_out, double* fill_out, double* flux_out, double* speed2_max_out, double* t_speed2_max_out,
+                    double* n_max_out, int64_t* last_n_out, double* last_top_out, double* last_bottom_out, double* last_velocity_sum_out) {
+    double* const values[sphmi::kMpValues - 2] = {top_max_out, t_top_max_out, bottom_min_out, t_arrival_out, wet_out, fill_out, flux_out, speed2_max_out,
+                                                  t_speed2_max_out, n_max_out};
+    SPHMI_GUARD(h, h->e->maps_read(steps_out, window_out, values, last_n_out, last_top_out, last_bottom_out, last_velocity_sum_out));
 }
 int sphmi_set_motion(sphmi_handle* h, uint64_t group_marker, double velocity, double start_time, double duration,
                      const double* direction) {

@@ -78,8 +78,9 @@ template <class T> struct FlowRow {
     int counts;
 };
 // `full` = 0: the position alone (k_fl_mark)
-template <class T>
-__device__ __forceinline__ FlowRow<T> fl_load(const FlowArgs<T>& A, long long i, bool full) {
+// (`Args`: FlowArgs<T>, or whatever carries N, D, pk0, pk1, comp and type as it does — MapArgs<T>, sphmi_maps.h)
+template <class T, class Args>
+__device__ __forceinline__ FlowRow<T> fl_load(const Args& A, long long i, bool full) {
 #pragma clang fp contract(off)
     using V4 = typename Vec4<T>::type;
     FlowRow<T> r;

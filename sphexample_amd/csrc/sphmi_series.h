@@ -1,4 +1,4 @@
-// sphmi_series.h — the host side the observers share (group forces, probes, budgets, flow, envelopes, lattice, columns): the error type, the limits and
+// sphmi_series.h — the host side the observers share (group forces, probes, budgets, flow, envelopes, maps, lattice, columns): the error type, the limits and
 // record-layout constants host and device agree on, the argument checks every kind of handle reports alike, the per-step series
 // and the means of the kernel sums.  Plain C++17, no HIP: tests/host_series/series_main.cpp compiles it alone.
 #pragma once
@@ -37,6 +37,9 @@ constexpr int kMaxFlowBoxes = 16;                // SPHMI_MAX_FLOW_BOXES
 constexpr int kFlValues = 7;                     // per control box (sphmi_flow.h): n_after, Σ1/ρ, Σv[3], entered, left — every slot a sum
 constexpr int kEnValues = 8;                     // per row (sphmi_envelopes.h): p_max, t_p_max, p_min, impulse, square, loaded, speed2_max, t_arrival
 constexpr int kEnHeader = 4;                     // the window of the envelopes: steps (int64 bits), t_begin, t_end, duration
+constexpr long long kMaxMapBins = 1ll << 20;     // SPHMI_MAX_MAP_BINS
+constexpr int kMpValues = 12;                    // per bin (sphmi_maps.h): top_max, t_top_max, bottom_min, t_arrival, wet, fill, flux[3], speed2_max, t_speed2_max, n_max
+constexpr int kMpHeader = 4;                     // the window of the maps, as the envelopes keep it
 
 // sphmi_attach_columns: the argument errors every kind of handle reports alike
 inline void check_column_table(int32_t n_columns, const void* const* columns, const int32_t* row_bytes) {
@@ -87,6 +90,29 @@ inline void check_flow_table(int32_t n_boxes, const double* lo, const double* hi
 // sphmi_components_build; 0 disables; any other bit is an argument error
 inline void check_envelope_mask(uint32_t type_mask) {
     if (type_mask & ~0xEu) throw EngineError(SPHMI_ERR_ARGUMENT, "sphmi_envelopes_enable: type_mask has a bit other than 1 (Fluid), 2 (Fixed), 3 (Moving) set");
+}
+
+// sphmi_maps_enable: the argument errors; returns the number of bins.  An axis is collapsed by count 1 and spacing +inf; +inf with
+// a count above 1 could hold no row beyond the first bin and is refused.
+inline int64_t check_map_lattice(const double* origin, const double* spacing, const int64_t* counts, int dims, int32_t up_axis) {
+    if (!origin || !spacing || !counts) throw EngineError(SPHMI_ERR_ARGUMENT, "sphmi_maps_enable: null origin, spacing or counts");
+    if (up_axis < 0 || up_axis >= dims) throw EngineError(SPHMI_ERR_ARGUMENT, "sphmi_maps_enable: up_axis out of range [0, dims)");
+    int64_t bins = 1;
+    for (int d = 0; d < dims; ++d) {
+        if (!std::isfinite(origin[d])) throw EngineError(SPHMI_ERR_ARGUMENT, "sphmi_maps_enable: non-finite origin");
+        if (std::isnan(spacing[d]) || !(spacing[d] > 0.0)) throw EngineError(SPHMI_ERR_ARGUMENT, "sphmi_maps_enable: every spacing must be positive");
+        if (counts[d] < 1) throw EngineError(SPHMI_ERR_ARGUMENT, "sphmi_maps_enable: every count must be at least 1");
+        if (std::isinf(spacing[d]) && counts[d] > 1) throw EngineError(SPHMI_ERR_ARGUMENT, "sphmi_maps_enable: an infinite spacing collapses an axis and needs a count of 1");
+        if (counts[d] > kMaxMapBins || bins * counts[d] > kMaxMapBins) throw EngineError(SPHMI_ERR_ARGUMENT, "sphmi_maps_enable: more than SPHMI_MAX_MAP_BINS bins");
+        bins *= counts[d];
+    }
+    return bins;
+}
+// … and the rows a handle may have: Σ llrint(v·2³²) over the rows of a bin stays inside an int64 while rows · max|v| < 2³¹; with
+// |v| < 4·c₀ — a weakly compressible run keeps |v| near c₀ / 10 — that is rows <= 2³¹ / (4·c₀)
+inline int64_t map_row_bound(double c0) {
+    const double bound = 2147483648.0 / (4.0 * c0);
+    return !(bound < 9.0e18) ? INT64_MAX : (int64_t)bound;
 }
 
 // sphmi_sample_grid: the argument errors every kind of handle reports alike; returns the number of nodes
@@ -224,6 +250,11 @@ inline void deliver_envelope_window(const double* header, int64_t* steps_out, do
 // … and the largest speed of every row from max |v|² (slot 6), in place: the one sqrt, on the host (NaN stays NaN)
 inline void deliver_envelope_speed(int64_t n, double* speed) {
     if (speed) for (int64_t i = 0; i < n; ++i) speed[i] = std::sqrt(speed[i]);
+}
+
+// sphmi_maps_read: three arrays of one component each, as the device keeps them, → the caller's [bins][3]
+inline void deliver_map_vectors(int64_t bins, const double* c0, const double* c1, const double* c2, double* out) {
+    if (out) for (int64_t b = 0; b < bins; ++b) { out[3 * b] = c0[b]; out[3 * b + 1] = c1[b]; out[3 * b + 2] = c2[b]; }
 }
 
 // The host side of sphmi_sample_grid: the raw sums { S, SP, Sρ, Sv[3], n } of the lattice (sphmi_field_grid.h), the ones the

@@ -46,7 +46,7 @@ def RunSimulation(*, SimGeometry=None, SimMetaData: SimulationMetaData, SimConst
                   device_float_bytes: int = 0, device: int = 0, backend_factory=None,
                   async_output: bool = False, group_forces=None, probes=None, field_grid=None,
                   particle_fields=None, budgets: bool = False, neighbor_list: bool = False, isosurface=None, components=None,
-                  flow_boxes=None, envelopes=None) -> List[float]:
+                  flow_boxes=None, envelopes=None, maps=None) -> List[float]:
     """Same keyword signature as the reference (src/SPHCellList.jl:808-817); returns the list of
     time steps the reference collects in ``TimeSteps`` (:823,:884).  ``SimParticles`` is updated in
     place at every output time, in the engine's cell-sorted order, as the reference's is.
@@ -107,7 +107,13 @@ def RunSimulation(*, SimGeometry=None, SimMetaData: SimulationMetaData, SimConst
     time, impulse, time under load, largest speed, arrival time; ``sphexample_amd.envelopes`` forms means and an arrival map) and
     ``on_output`` receives the dict of ``Backend.envelopes_read`` as its last argument, the way ``particle_fields=`` hands over its
     fields (``None`` at the first call).  The envelopes keep growing over the whole run; row i is particle i of that output.
-    ``None`` or ``False`` (default): nothing is accumulated and the callback keeps its arguments."""
+    ``None`` or ``False`` (default): nothing is accumulated and the callback keeps its arguments.
+
+    ``maps=(origin, spacing, counts[, up_axis])``: what every bin of that lattice experiences is accumulated on the device at every
+    step (``Backend.maps_enable``: crest and its time, arrival time, wet duration, fill, flux, the largest bin-mean speed;
+    ``sphexample_amd.maps`` forms depths, mean velocities and an arrival map) and ``on_output`` receives the dict of
+    ``Backend.maps_read`` as its last argument, behind the envelopes (``None`` at the first call).  The maps keep growing over the
+    whole run.  ``None`` (default): nothing is accumulated and the callback keeps its arguments."""
     if SimMetaData.BMode.__name__ == "SimpleMDBC":
         LoadMDBCNormals(SimParticles, ParticleNormalsPath)                       # :827
     host_bytes = SimParticles.Position.dtype.itemsize
@@ -171,6 +177,9 @@ def RunSimulation(*, SimGeometry=None, SimMetaData: SimulationMetaData, SimConst
     if envelopes is not None and envelopes is not False:
         eng.envelopes_enable(("Fluid",) if envelopes is True else envelopes)
         extras.append((None, eng.envelopes_read))                                # (the rows of this output: no step lies between it and the download)
+    if maps is not None:
+        eng.maps_enable(*tuple(maps))
+        extras.append((None, eng.maps_read))
     none_yet = tuple(first for first, _ in extras)
     emit = lambda meta, samples: on_output(meta, SimParticles, *samples)         # noqa: E731
     if on_output:
