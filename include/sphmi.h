@@ -460,6 +460,43 @@ int sphmi_maps_read(sphmi_handle* h, int64_t* steps_out, double* window_out /* [
                     double* last_velocity_sum_out /* [bins][3] */);
 
 /*
+ * TRACERS: where the water goes, at STEP resolution, recorded on the device - pathlines, residence and transit times, the fate of the
+ * water that overtops an obstacle.  Probes sample at fixed points and the envelopes keep the extremes of a row but not its path; a
+ * trajectory needed a download after every step.  Two kinds of tracer share one per-step series; either kind may be absent.
+ *   TRACKED PARTICLES: up to SPHMI_MAX_TRACERS rows, named in the row order sphmi_download has at the moment of the enable.  After
+ *     every executed step each keeps 8 doubles { x[3], v[3], rho, P }: the values sphmi_download would deliver into Float64 host
+ *     arrays directly after that step, bit for bit (fp32 handles: record plus low word; P = Pressure!(rho_n+) of the half step; 2-D
+ *     handles: a zero third component).  The slots follow the PARTICLE through every sort, found the way the envelopes find their
+ *     records, with a map of their own composed in sphmi_download_permutation.  No atomics: a slot has one writer.
+ *   DRIFTERS: up to SPHMI_MAX_TRACERS massless points placed anywhere (`dims` doubles each).  Behind every executed step k, with
+ *     X the drifter's position before the step and the state after it: the raw sums S, SP, Srho, Sv[3], n of sphmi_probes_enable at X
+ *     (the same walk, the same bits a probe at X would record); then
+ *         if (S >= min_weight) X[d] = X[d] + (Sv[d] / S) * dt   for d < dims, dt the time step of step k
+ *     every operation fp64, rounded once, never contracted (sphexample_amd/tracers.py: step forms the same doubles); otherwise the
+ *     drifter is DRY and stays: in empty space, above the surface, outside the particles' bounding grid.  First order in dt, like the
+ *     tracer advection of comparable codes.  The record is 10 doubles { X[3] BEFORE the move, S, SP, Srho, Sv[3], n }: a complete
+ *     probe sample at a known point.  The move does not depend on the series: samples nobody reads are dropped, the drifter moves on.
+ *   enable: after sphmi_upload / sphmi_generate_dam_break_3d, at any later time too.  rows[n_particles], positions[n_drifters x dims],
+ *     min_weight finite and positive (0.5: "inside the fluid").  The handle keeps the newest capacity_steps (>= 1) samples that have
+ *     not been read.  A second call replaces both sets, drops the series and starts the drifters at the new positions; both counts 0
+ *     disables.  sphmi_upload and the generator disable.  Cancelled steps move and record nothing; sphmi_forces_once neither.  Off by
+ *     default; a handle that never enables it launches what it always did.
+ *   read: delivers and clears the oldest `capacity` samples recorded since the last read, oldest first: iteration_out / time_out /
+ *     dt_out [capacity] as sphmi_group_forces_read; particles_out [capacity x n_particles x 8]; drifters_out [capacity x n_drifters x
+ *     10]; and, whatever `capacity` is, drifter_positions_out [n_drifters x 3]: X NOW, after the last executed step - the series alone
+ *     ends one move short of it.  Any output pointer may be NULL.  *n_out, *n_dropped, capacity = 0: as sphmi_group_forces_read.
+ *   SPHMI_ERR_STATE: before the upload; read while disabled; rank-mode and multi-device handles (rows migrate between slabs; neither
+ *     their slots nor the drifters are carried along); drifters on handles with H < h.
+ *   SPHMI_ERR_ARGUMENT: a count outside [0, SPHMI_MAX_TRACERS], a null table, a row outside [0, n) or named twice, a non-finite
+ *     coordinate, a min_weight that is not finite and positive, capacity_steps < 1, negative capacity, null n_out.
+ */
+#define SPHMI_MAX_TRACERS 1024
+int sphmi_tracers_enable(sphmi_handle* h, int32_t n_particles, const int64_t* rows, int32_t n_drifters,
+                         const double* positions /* n_drifters x dims */, double min_weight, int64_t capacity_steps);
+int sphmi_tracers_read(sphmi_handle* h, int64_t capacity, int64_t* iteration_out, double* time_out, double* dt_out,
+                       double* particles_out, double* drifters_out, double* drifter_positions_out, int64_t* n_out, int64_t* n_dropped);
+
+/*
  * MotionDetails of the Geometry with this GroupMarker (src/SimulationGeometry.jl:17-22): particles of Type Moving
  * in that group get Velocity = velocity·direction while start_time <= TotalTime <= start_time + duration (0
  * otherwise) and are displaced by Velocity·dt/2 before each neighbour pass — ProgressMotion,

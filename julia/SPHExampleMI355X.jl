@@ -39,6 +39,9 @@
 # SPHMI_MAPS (unset by default; "origin:spacing:counts[:up_axis]", `dims` numbers per part, "Inf" allowed as a spacing next to a count of 1,
 # up_axis zero-based = accumulate per bin of that lattice, at every step on the device, crest, arrival time, wet duration, fill, flux and
 # the largest bin-mean speed — sphmi_maps_enable — and keep the newest read in SPHExampleMI355X.MAPS[SimParticles]).
+# SPHMI_TRACERS (unset by default; "rows:points[:min_weight]" = follow the particles in these zero-based rows of SimParticles, "0,17,512",
+# and advect massless drifters released at these points, "x,y,z;x,y,z", with the flow at every step on the device — either part may be
+# empty, min_weight defaults to 0.5 — sphmi_tracers_enable — and collect the series in SPHExampleMI355X.TRACERS[SimParticles]).
 #
 # EXPERIMENTAL: the build image has no Julia, so this file has never been executed.  struct layout and ABI version
 # are asserted against the library at first use (sphmi_create refuses a mismatching struct_size / abi_version).
@@ -228,6 +231,55 @@ function read_envelopes!(h, en::Envelopes, n::Integer)
     en.steps, w, a = envelopes_read(h, n)
     en.t_begin, en.t_end, en.duration = w
     en.p_max, en.t_p_max, en.p_min, en.impulse, en.square, en.loaded, en.speed_max, en.t_arrival = a
+    return nothing
+end
+# SPHMI_TRACERS: where the water goes, bound like PROBES — particles[:, s, k] = (x, y, z, vx, vy, vz, ρ, P) of tracked particle s after sample k,
+# drifters[:, p, k] = (X, Y, Z, S, SP, Sρ, Svx, Svy, Svz, n) of drifter p: the position the raw sums of sample k were taken at, BEFORE its move;
+# position[:, p] is where the drifters are now (a drifter moves by (Sv / S)·dt where S ≥ min_weight and stays where it is dry)
+mutable struct TracerSeries
+    rows::Vector{Int64}                  # zero-based rows at the enable
+    released::Matrix{Float64}            # dims × drifters
+    min_weight::Float64
+    iteration::Vector{Int64}; time::Vector{Float64}; dt::Vector{Float64}
+    particles::Array{Float64,3}          # 8 × tracked × samples
+    drifters::Array{Float64,3}           # 10 × drifters × samples
+    position::Matrix{Float64}            # 3 × drifters
+    dropped::Int64
+end
+const TRACERS = IdDict{Any,TracerSeries}()
+function tracer_spec(D)
+    spec = strip(get(ENV, "SPHMI_TRACERS", ""))
+    (isempty(spec) || spec == "0") && return nothing
+    parts = split(spec, ":")
+    2 <= length(parts) <= 3 || error("SPHMI_TRACERS: \"rows:points[:min_weight]\", either of the first two may be empty")
+    rows = Int64[parse(Int64, strip(r)) for r in split(parts[1], ",") if !isempty(strip(r))]
+    pts = [parse.(Float64, strip.(split(q, ","))) for q in split(parts[2], ";") if !isempty(strip(q))]
+    all(q -> length(q) == D, pts) || error("SPHMI_TRACERS: every point needs $D coordinates")
+    (isempty(rows) && isempty(pts)) && return nothing
+    weight = length(parts) == 3 ? parse(Float64, strip(parts[3])) : 0.5
+    return rows, (isempty(pts) ? zeros(Float64, D, 0) : reduce(hcat, pts)), weight
+end
+function tracers_enable(h, rows::Vector{Int64}, points::Matrix{Float64}, min_weight::Float64)
+    GC.@preserve rows points check(h, ccall((:sphmi_tracers_enable, LIB), Cint, (Ptr{Cvoid}, Int32, Ptr{Int64}, Int32, Ptr{Float64}, Float64, Int64),
+                                            h, Int32(length(rows)), isempty(rows) ? Ptr{Int64}(C_NULL) : pointer(rows), Int32(size(points, 2)),
+                                            isempty(points) ? Ptr{Float64}(C_NULL) : pointer(points), min_weight, 1 << 16))
+    return nothing
+end
+function read_tracers!(h, tr::TracerSeries)
+    np = length(tr.rows); nd = size(tr.released, 2); chunk = 256
+    n = Ref{Int64}(0); dropped = Ref{Int64}(0)
+    it = Vector{Int64}(undef, chunk); t = Vector{Float64}(undef, chunk); dt = Vector{Float64}(undef, chunk)
+    pv = Array{Float64,3}(undef, 8, np, chunk); dv = Array{Float64,3}(undef, 10, nd, chunk); x = zeros(Float64, 3, nd)
+    while true                           # the oldest `chunk` samples per call until none is left: one call site, no question first
+        GC.@preserve it t dt pv dv x check(h, ccall((:sphmi_tracers_read, LIB), Cint, (Ptr{Cvoid}, Int64, Ptr{Int64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ref{Int64}, Ref{Int64}),
+                                                   h, chunk, pointer(it), pointer(t), pointer(dt), pointer(pv), pointer(dv), pointer(x), n, dropped))
+        k = Int(n[])
+        append!(tr.iteration, it[1:k]); append!(tr.time, t[1:k]); append!(tr.dt, dt[1:k])
+        tr.particles = cat(tr.particles, pv[:, :, 1:k]; dims = 3); tr.drifters = cat(tr.drifters, dv[:, :, 1:k]; dims = 3)
+        tr.dropped += dropped[]
+        k < chunk && break
+    end
+    tr.position = x
     return nothing
 end
 # SPHMI_MAPS: what every bin of a lattice has experienced since the session opened, bound like ENVELOPES — a state, not a series: every
@@ -438,6 +490,12 @@ function open_session(SimDensityDiffusion, SimViscosity, SimKernel, SimMetaData:
         e = Float64[]
         MAPS[P] = Maps(lattice..., 0, 0.0, 0.0, 0.0, e, e, e, e, e, e, e, e, e, e, Int64[], e, e, e)
     end
+    traced = tracer_spec(D)                        # opt-in as well: SPHMI_TRACERS
+    if traced !== nothing
+        tracers_enable(h, traced...)
+        TRACERS[P] = TracerSeries(traced..., Int64[], Float64[], Float64[], Array{Float64,3}(undef, 8, length(traced[1]), 0),
+                                  Array{Float64,3}(undef, 10, size(traced[2], 2), 0), zeros(Float64, 3, size(traced[2], 2)), 0)
+    end
     return Session(h, Vector{Int64}(undef, N), zeros(8), zeros(Int64, 8), Vector{Int}(undef, N), Vector{Int64}(undef, SimMetaData.ExportGridCells ? N * D : 0),
                    columns, colptrs)
     catch
@@ -485,6 +543,7 @@ function SimulationLoop(SimDensityDiffusion::BuiltinDDT, SimViscosity::BuiltinVi
     haskey(FLOW, P) && read_flow!(h, FLOW[P])
     haskey(ENVELOPES, P) && read_envelopes!(h, ENVELOPES[P], length(P))
     haskey(MAPS, P) && read_maps!(h, MAPS[P])
+    haskey(TRACERS, P) && read_tracers!(h, TRACERS[P])
     GC.@preserve P s begin
         # the carried fields: snapshot on the device, copies on a second stream, straight into the StructArray's columns
         # (Cells: a Vector{CartesianIndex{D}} is N·D Int64; Type is a per-particle constant and follows the gather below)

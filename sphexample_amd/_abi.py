@@ -533,6 +533,55 @@ class Backend:
         self._check(f(self._h, C.byref(steps), _ptr(window), *[_ptr(a) for a in out.values()]))
         return {"steps": int(steps.value), "t_begin": float(window[0]), "t_end": float(window[1]), "duration": float(window[2]), **out}
 
+    # -- tracers: tracked particles and advected drifters at every step (sphmi_tracers_enable / sphmi_tracers_read) -------------
+    TRACER_PARTICLE_VALUES, TRACER_DRIFTER_VALUES = 8, 10
+
+    def has_tracers(self) -> bool:
+        return self._has("tracers_enable") and self._has("tracers_read")
+
+    def tracers_enable(self, particles=None, drifters=None, min_weight: float = 0.5, capacity: int = 4096) -> None:
+        """Follow, after every executed step and on the device, the rows `particles` (at most 1024 row numbers of what `download`
+        delivers NOW; they follow the particle through every sort) and advect the massless points `drifters` [m, dims] (at most
+        1024) with the Shepard-mean velocity of the fluid around them: ``X += (Sv / S) * dt`` where ``S >= min_weight``, else the
+        drifter is dry and stays.  The newest `capacity` unread samples are kept; the drifters move whether or not they are read.
+        A second call replaces both sets and restarts the drifters; neither set disables."""
+        rows = np.ascontiguousarray([] if particles is None else particles, dtype=np.int64).reshape(-1)
+        x = np.ascontiguousarray(np.zeros((0, self.D)) if drifters is None else drifters, dtype=np.float64).reshape(-1, self.D)
+        f = self._fn("tracers_enable")
+        f.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_double, C.c_int64]
+        self._check(f(self._h, len(rows), _ptr(rows) if len(rows) else None, len(x), _ptr(x) if len(x) else None, float(min_weight), int(capacity)))
+        self._tracers = (len(rows), len(x), float(min_weight))
+
+    def tracers_read(self) -> dict:
+        """The steps executed since the last read, oldest first, and clears them: iteration[K], time[K], dt[K];
+        ``particles``: ``values`` [K, n, 8] and its views ``position`` [K, n, 3], ``velocity`` [K, n, 3], ``density`` [K, n],
+        ``pressure`` [K, n] - what `download` would have delivered for those particles after each step;
+        ``drifters``: ``position`` [K, m, 3] (where the sums of that step were taken, BEFORE its move), ``sums`` [K, m, 7] (raw S, SP,
+        Srho, Sv[3], n) and, normalised as `probes_read` does, ``weight``, ``count``, ``pressure``, ``density``, ``velocity``;
+        ``drifter_position`` [m, 3]: where the drifters are NOW; ``min_weight``; ``dropped``: older samples the capacity pushed out."""
+        f = self._fn("tracers_read")
+        f.argtypes = [C.c_void_p, C.c_int64] + [C.c_void_p] * 6 + [C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+        n, dropped = C.c_int64(), C.c_int64()
+        self._check(f(self._h, 0, *[None] * 6, C.byref(n), C.byref(dropped)))                   # capacity 0: how many are waiting
+        np_, nd, min_weight = getattr(self, "_tracers", (0, 0, 0.5))
+        k = max(n.value, 1)
+        it, t, dt = np.zeros(k, dtype=np.int64), np.zeros(k), np.zeros(k)
+        pv, dv, x = np.zeros((k, np_, self.TRACER_PARTICLE_VALUES)), np.zeros((k, nd, self.TRACER_DRIFTER_VALUES)), np.zeros((nd, 3))
+        self._check(f(self._h, k, _ptr(it), _ptr(t), _ptr(dt), _ptr(pv), _ptr(dv), _ptr(x), C.byref(n), C.byref(dropped)))
+        self.tracers_dropped = dropped.value
+        K = n.value
+        it, t, dt, pv, dv = it[:K], t[:K], dt[:K], pv[:K], dv[:K]
+        sums = dv[:, :, 3:]
+        S, cnt = sums[:, :, 0], sums[:, :, 6]
+        some = (cnt > 0) & (S > 0)
+        safe = np.where(some, S, 1.0)
+        mean = lambda a: np.where(some if a.ndim == 2 else some[:, :, None], a / (safe if a.ndim == 2 else safe[:, :, None]), 0.0)    # noqa: E731
+        return {"iteration": it, "time": t, "dt": dt,
+                "particles": {"values": pv, "position": pv[:, :, 0:3], "velocity": pv[:, :, 3:6], "density": pv[:, :, 6], "pressure": pv[:, :, 7]},
+                "drifters": {"position": dv[:, :, 0:3], "sums": sums, "weight": S, "count": cnt.astype(np.int64), "pressure": mean(sums[:, :, 1]),
+                             "density": mean(sums[:, :, 2]), "velocity": mean(sums[:, :, 3:6])},
+                "drifter_position": x, "min_weight": min_weight, "dropped": int(dropped.value)}
+
     # -- kernel sums on a regular lattice, on demand (sphmi_sample_grid) -----------------------------------------------------
     GRID_FIELDS = ("weight", "count", "pressure", "density", "velocity")
 

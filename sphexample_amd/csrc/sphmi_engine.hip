@@ -24,6 +24,7 @@
 #include "sphmi_envelopes.h"
 #include "sphmi_maps.h"
 #include "sphmi_probes.h"
+#include "sphmi_tracers.h"
 #include "sphmi_field_grid.h"
 #include "sphmi_particle_fields.h"
 #include "sphmi_neighbor_list.h"
@@ -186,6 +187,16 @@ struct EngineBase {
     virtual void maps_read(int64_t*, double*, double* const*, int64_t*, double*, double*, double*) {
         require_uploaded("sphmi_maps_read");
         throw EngineError(SPHMI_ERR_STATE, "sphmi_maps_read: single-device handles only");
+    }
+    // The tracers (sphmi_tracers.h) follow rows and read the cell list of the rows' own device: a handle of one device overrides the
+    // pair.  Rows of a multi-device handle migrate between slabs, and a drifter would have to be handed from slab to slab with them.
+    virtual void tracers_enable(int32_t, const int64_t*, int32_t, const double*, double, int64_t) {
+        require_uploaded("sphmi_tracers_enable");
+        throw EngineError(SPHMI_ERR_STATE, "sphmi_tracers_enable: single-device handles only (rows migrate between slabs; neither their slots nor the drifters are carried along)");
+    }
+    virtual void tracers_read(int64_t, int64_t*, double*, double*, double*, double*, double*, int64_t*, int64_t*) {
+        require_uploaded("sphmi_tracers_read");
+        throw EngineError(SPHMI_ERR_STATE, "sphmi_tracers_read: single-device handles only");
     }
     void group_forces_enable(int32_t n_groups, const uint64_t* markers, int64_t capacity_steps) {
         require_one_process("sphmi_group_forces_enable");
@@ -543,7 +554,7 @@ struct Engine final : EngineBase {
         for (auto& e : host_pinned) (void)hipHostUnregister(e.first);
         (void)hipFree(out_arena);
         (void)hipFree(col_arena); (void)hipFree(col_store); (void)hipFree(col_base[0]); (void)hipFree(col_base[1]);
-        gf_release(); pr_release(); bg_release(); fl_release(); en_release(); mp_release(); fg_arena.free(); pf_arena.free(); nl_free(); iso_free(); cc_free();
+        gf_release(); pr_release(); bg_release(); fl_release(); en_release(); mp_release(); tr_release(); fg_arena.free(); pf_arena.free(); nl_free(); iso_free(); cc_free();
         (void)hipFree(slot); (void)hipFree(tmp_idx); (void)hipFree(perm);
         for (int k = 0; k < 2; ++k) { (void)hipFree(tile_cost[k]); (void)hipFree(tile_order[k]); }
         (void)hipFree(kout_d); (void)hipFree(tile_work_d); (void)hipFree(tile_work1_d); (void)hipFree(xcd_clock_d); (void)hipHostFree(xcd_clock_h);
@@ -1223,6 +1234,7 @@ struct Engine final : EngineBase {
         if (fl_on) fl_sample(ctrl_cur(), obs_iteration0, obs_steps_base, iB);   // the flow through the control boxes: that set against this step's marks
         if (en_mask) en_update(ctrl_cur(), iB);                                 // the per-particle envelopes: that set and the half step's density → the rows' records
         if (mp_on) mp_update(ctrl_cur(), iB);                                   // the per-bin maps: the Fluid rows of that set → the step's map → the bins' records
+        if (tr_on) tr_sample(ctrl_cur(), obs_iteration0, obs_steps_base, iB);   // the tracers: tracked rows of that set → the batch's log; the drifters sample it and move
         std::swap(iA, iB);
     }
 
@@ -1267,6 +1279,7 @@ struct Engine final : EngineBase {
                 if (pr_on) pr_log.fetch(batch, stream);                                      // … and the probe records
                 if (bg_on) bg_log.fetch(batch, stream);                                      // … and the budgets
                 if (fl_on) fl_log.fetch(batch, stream);                                      // … and the flow records
+                if (tr_on) tr_log.fetch(batch, stream);                                      // … and the tracers' records
                 // (the XCD finishing times of a sampled launch: the host-side rebuild reads them at its own synchronisation; handles that
                 // rebuild on the device have none — the shares of the next measured-work schedule would never move: 3 % on the 159 k-particle
                 // LaminarSPS case)
@@ -1283,6 +1296,7 @@ struct Engine final : EngineBase {
                 if (pr_on) push_records(pr_series, pr_log, kPrHeader, executed);
                 if (bg_on) push_records(bg_series, bg_log, kGfHeader, executed);
                 if (fl_on) push_records(fl_series, fl_log, kGfHeader, executed);
+                if (tr_on) push_records(tr_series, tr_log, kGfHeader, executed);
                 // (control inside the predictor: the slots flipped at queue time, once per queued step; what counts is where
                 // the last EXECUTED corrector left its maxima — cancelled steps consume nothing and zero nothing)
                 if (batch_fused) rpar = rpar0 ^ (int)(executed & 1);
@@ -1381,6 +1395,7 @@ struct Engine final : EngineBase {
         fl_disable();                              // … and the control boxes
         en_disable();                              // … and the envelopes of the old rows
         mp_disable();                              // … and the maps they drew
+        tr_disable();                              // … and the tracers: the tracked rows were rows of the old set
         iA = 0; iH = 1; iB = 2; cur = 0;
         ghost_given = ghost_points != nullptr;
         {
@@ -1446,6 +1461,7 @@ struct Engine final : EngineBase {
             fl_disable();
             en_disable();
             mp_disable();
+            tr_disable();
             iA = 0; iH = 1; iB = 2; cur = 0; ghost_given = false; mdbc_n_list = 0; mdbc_list_valid = false;
             int base = 0;
             const unsigned nbM = (unsigned)((M + 255) / 256);
@@ -1625,6 +1641,13 @@ struct Engine final : EngineBase {
         if (en_mask) {                                 // the envelopes' records are found the same way, through a map of their own
             hipLaunchKernelGGL(k_columns_base_compose, dim3((N + 255) / 256), dim3(256), 0, stream, (const int*)en_base[en_cur].p, (const int*)prow[cur], en_base[en_cur ^ 1].p, N);
             en_cur ^= 1;
+        }
+        if (tr_np) tr_map[tr_cur ^ 1].need((size_t)N, [&](size_t bytes) {
+            return text("sphmi_download_permutation: no device memory for the tracers' second row map (%zu bytes)", bytes);
+        });
+        if (tr_np) {                                   // the tracked particles' slots likewise: the map runs from the row of the epoch to the slot
+            hipLaunchKernelGGL(k_columns_base_compose, dim3((N + 255) / 256), dim3(256), 0, stream, (const int*)tr_map[tr_cur].p, (const int*)prow[cur], tr_map[tr_cur ^ 1].p, N);
+            tr_cur ^= 1;
         }
         if (col_store) {                               // attached columns: their records are found through the epoch that ends here
             hipLaunchKernelGGL(k_columns_base_compose, dim3((N + 255) / 256), dim3(256), 0, stream, (const int*)col_base[col_cur], (const int*)prow[cur], col_base[col_cur ^ 1], N);
@@ -2154,6 +2177,94 @@ struct Engine final : EngineBase {
                 bounce.d2h(w.data(), m.step64[p] + (size_t)(2 + d) * B, B * 8, stream);
                 for (size_t b = 0; b < B; ++b) last_sum[3 * b + d] = mp_unfixed((long long)w[b]);
             }
+        }
+    }
+
+    // ---- tracers: tracked particles and advected drifters at every step (sphmi_tracers.h) ------------------------------------------------
+    // One launch per kind behind every corrector; the records of a batch go where the probes' go.  The tracked rows are found through
+    // tr_map[tr_cur][prow[i]] (row of the last permutation epoch → slot, −1: not tracked), composed in sphmi_download_permutation like
+    // the envelopes' map; the drifters own their positions (tr_x), which move whether or not anybody reads the series.
+    bool tr_on = false;                        // off: no step launches anything for it
+    int tr_np = 0, tr_nd = 0;
+    double tr_min_weight = 0.0;
+    DeviceBuf<int> tr_rows;                    // enable: the tracked rows as the caller named them
+    DeviceBuf<int> tr_map[2];                  // [tr_cur] is live, the other one grows at the first permutation
+    int tr_cur = 0;
+    DeviceBuf<double> tr_x;                    // 3 doubles per drifter
+    StepLog tr_log;
+    StepSeries tr_series;                      // payload: kTrParticleValues per tracked particle, then kTrDrifterValues per drifter, as recorded
+    void tr_release() { tr_rows.free(); tr_map[0].free(); tr_map[1].free(); tr_x.free(); tr_log.release(); tr_np = tr_nd = 0; tr_cur = 0; }
+    void tr_disable() { observer_off(tr_on, tr_series, &Engine::tr_release); }
+    void tracers_enable(int32_t n_particles, const int64_t* rows, int32_t n_drifters, const double* positions, double min_weight, int64_t capacity_steps) override {
+        require_uploaded("sphmi_tracers_enable");
+        if (dd_slab) throw EngineError(SPHMI_ERR_STATE, "sphmi_tracers_enable: single-device handles only");
+        check_tracer_table(n_particles, rows, (int64_t)N, n_drifters, positions, D, min_weight, capacity_steps);
+        HC(hipSetDevice(cfg.device));
+        tr_disable();
+        if (n_particles == 0 && n_drifters == 0) return;
+        if (n_drifters > 0 && !(cfg.h <= cfg.H))
+            throw EngineError(SPHMI_ERR_STATE, "sphmi_tracers_enable: handles with H < h are not served (the candidate cells of a drifter are laid out for H + h <= 2H)");
+        auto no_memory = [&](size_t bytes) { return text("sphmi_tracers_enable: no device memory for the tracers of %lld rows (%zu bytes)", (long long)N, bytes); };
+        try {
+            const int record = kGfHeader + kTrParticleValues * n_particles + kTrDrifterValues * n_drifters;
+            tr_log.alloc(record, record);
+            if (n_particles > 0) {
+                std::vector<int> r32((size_t)n_particles);
+                for (int s = 0; s < n_particles; ++s) r32[(size_t)s] = (int)rows[s];
+                tr_rows.need((size_t)n_particles, no_memory);
+                tr_map[0].need((size_t)N, no_memory);
+                bounce.h2d(tr_rows.p, r32.data(), r32.size() * 4, stream);
+                HC(hipMemsetAsync(tr_map[0].p, 0xFF, (size_t)N * 4, stream));                 // −1: not tracked
+                // slot s belongs to row rows[s] of the present order: its row at the last epoch is prow[rows[s]]
+                hipLaunchKernelGGL(k_tr_map_init, dim3((n_particles + 255) / 256), dim3(256), 0, stream, (const int*)tr_rows.p, (const int*)prow[cur], tr_map[0].p,
+                                   n_particles, N);
+                HC(hipGetLastError());
+            }
+            if (n_drifters > 0) {
+                std::vector<double> xyz((size_t)3 * n_drifters, 0.0);
+                for (int p = 0; p < n_drifters; ++p) for (int d = 0; d < D; ++d) xyz[3 * (size_t)p + d] = positions[(size_t)p * D + d];
+                tr_x.need(xyz.size(), no_memory);
+                bounce.h2d(tr_x.p, xyz.data(), xyz.size() * 8, stream);
+            }
+            HC(hipStreamSynchronize(stream));
+        } catch (...) { tr_release(); throw; }
+        tr_np = n_particles; tr_nd = n_drifters; tr_min_weight = min_weight;
+        tr_series.reset(kTrParticleValues * n_particles + kTrDrifterValues * n_drifters, capacity_steps);
+        tr_on = true;
+    }
+    // queued behind the corrector of a step; `set`: the state set that corrector wrote
+    void tr_sample(const StepCtrl* ctrl, int64_t iteration0, int64_t steps_base, int set) {
+        if (tr_np > 0 && N > 0) {
+            TracerParticleArgs<T> A{};
+            A.ctrl = ctrl; A.pk0 = pk0[set]; A.pk1 = pk1[set]; A.half0 = pk0[iH]; A.comp = comp[cur];
+            A.prow = prow[cur]; A.slot_of_record = tr_map[tr_cur].p; A.log = tr_log.d.p;
+            A.iteration0 = iteration0; A.steps_base = steps_base;
+            A.rho0 = (T)cfg.rho0; A.inv_rho0 = (T)(1.0 / cfg.rho0); A.Cbe = cbe();
+            A.n_particles = tr_np; A.N = N; A.D = D; A.record = tr_log.record_doubles; A.slots = StepLog::slots;
+            hipLaunchKernelGGL(k_tr_particles<T>, dim3((N + kTrBlock - 1) / kTrBlock), dim3(kTrBlock), 0, stream, A);
+        }
+        if (tr_nd > 0) {
+            TracerDrifterArgs<T> A{};
+            A.s.ctrl = ctrl; A.s.pk0 = pk0[set]; A.s.pk1 = pk1[set]; A.s.half0 = pk0[iH]; A.s.comp = comp[cur];
+            A.s.type = nullptr; A.s.cstart = cstart; A.s.pos = tr_x.p; A.s.log = tr_log.d.p; A.s.g = grid;
+            A.s.iteration0 = iteration0; A.s.steps_base = steps_base;
+            fill_sample_consts(A.s);
+            A.s.n_probes = tr_nd; A.s.N = N; A.s.D = D; A.s.kernel = cfg.kernel; A.s.record = tr_log.record_doubles; A.s.slots = StepLog::slots;
+            A.X = tr_x.p; A.min_weight = tr_min_weight;
+            A.value0 = kGfHeader + kTrParticleValues * tr_np; A.write_header = tr_np > 0 && N > 0 ? 0 : 1;
+            hipLaunchKernelGGL(k_tr_drift<T>, dim3((tr_nd + 3) / 4), dim3(256), 0, stream, A);
+        }
+        HC(hipGetLastError());
+    }
+    void tracers_read(int64_t capacity, int64_t* iteration_out, double* time, double* dt, double* particles, double* drifters, double* drifter_positions,
+                      int64_t* n_out, int64_t* n_dropped) override {
+        require_uploaded("sphmi_tracers_read");
+        if (!tr_on) throw EngineError(SPHMI_ERR_STATE, "sphmi_tracers_read: tracers are not enabled (sphmi_tracers_enable)");
+        tr_series.read("sphmi_tracers_read", capacity, iteration_out, time, dt, n_out, n_dropped,
+                       [&](int64_t k, const double* v) { deliver_tracers(tr_np, tr_nd, k, v, particles, drifters); });
+        if (drifter_positions && tr_nd > 0) {          // X after the last executed step: the series alone ends one move short of it
+            HC(hipSetDevice(cfg.device));
+            bounce.d2h(drifter_positions, tr_x.p, (size_t)3 * tr_nd * 8, stream);
         }
     }
 
@@ -3060,6 +3171,15 @@ int sphmi_maps_read(sphmi_handle* h, int64_t* steps_out, double* window_out, dou
     double* const values[sphmi::kMpValues - 2] = {top_max_out, t_top_max_out, bottom_min_out, t_arrival_out, wet_out, fill_out, flux_out, speed2_max_out,
                                                   t_speed2_max_out, n_max_out};
     SPHMI_GUARD(h, h->e->maps_read(steps_out, window_out, values, last_n_out, last_top_out, last_bottom_out, last_velocity_sum_out));
+}
+static_assert(SPHMI_MAX_TRACERS == sphmi::kMaxTracers, "sphmi_series.h and sphmi.h disagree");
+int sphmi_tracers_enable(sphmi_handle* h, int32_t n_particles, const int64_t* rows, int32_t n_drifters, const double* positions, double min_weight,
+                         int64_t capacity_steps) {
+    SPHMI_GUARD(h, h->e->tracers_enable(n_particles, rows, n_drifters, positions, min_weight, capacity_steps));
+}
+int sphmi_tracers_read(sphmi_handle* h, int64_t capacity, int64_t* iteration_out, double* time_out, double* dt_out, double* particles_out, double* drifters_out,
+                       double* drifter_positions_out, int64_t* n_out, int64_t* n_dropped) {
+    SPHMI_GUARD(h, h->e->tracers_read(capacity, iteration_out, time_out, dt_out, particles_out, drifters_out, drifter_positions_out, n_out, n_dropped));
 }
 int sphmi_set_motion(sphmi_handle* h, uint64_t group_marker, double velocity, double start_time, double duration,
                      const double* direction) {

@@ -87,23 +87,13 @@ __device__ __forceinline__ double pr_kernel_w(int kernel, double alphaD, double 
     return alphaD * (t2 * t2) * (2.0 * q + 1.0);
 }
 
+// The walk of one wave over the candidate rows of the point xp (the header comment): the seven sums, complete in every lane.  `A` supplies
+// the record sets, the cell list and the constants; its point table and its log are not touched.  k_probe_sample and the drifters of
+// sphmi_tracers.h call it: a moving point is sampled with the arithmetic, and in the order, of a fixed one.
 template <class T>
-__global__ void __launch_bounds__(256) k_probe_sample(const ProbeSampleArgs<T> A) {
+__device__ __forceinline__ void pr_walk(const ProbeSampleArgs<T>& A, const double (&xp)[3], const int lane, double& n, double& S, double& SP, double& Sr,
+                                        double& Sx, double& Sy, double& Sz) {
     using V4 = typename Vec4<T>::type;
-    const StepCtrl c = *A.ctrl;
-    if (!c.active) return;
-    const long long slot = c.steps_done - 1 - A.steps_base;
-    if (slot < 0 || slot >= (long long)A.slots) return;
-    const int lane = (int)threadIdx.x & 63;
-    const int p = __builtin_amdgcn_readfirstlane((int)((blockIdx.x * blockDim.x + threadIdx.x) >> 6));
-    if (p >= A.n_probes) return;
-    double* rec = A.log + (size_t)slot * (size_t)A.record;
-    if (p == 0 && lane == 0) {
-        rec[0] = __longlong_as_double(A.iteration0 + c.steps_done);
-        rec[1] = c.total_time;
-        rec[2] = c.last_dt;
-    }
-    const double xp[3] = {A.pos[3 * p], A.pos[3 * p + 1], A.D == 3 ? A.pos[3 * p + 2] : 0.0};
     // padded cell range per axis, clamped to the grid (in fp64 before the conversion: a probe may be anywhere)
     int lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0};
     bool empty = false;
@@ -134,7 +124,7 @@ __global__ void __launch_bounds__(256) k_probe_sample(const ProbeSampleArgs<T> A
     for (int o = 1; o < 32; o <<= 1) { const int u = __shfl_up(jincl, o, 64); if (lane >= o) jincl += u; }
     const int jexcl = jincl - ((rc + 63) >> 6);
     const int njobs = nrow > 0 ? __shfl(jincl, nrow - 1, 64) : 0;
-    double n = 0.0, S = 0.0, SP = 0.0, Sr = 0.0, Sx = 0.0, Sy = 0.0, Sz = 0.0;
+    n = 0.0; S = 0.0; SP = 0.0; Sr = 0.0; Sx = 0.0; Sy = 0.0; Sz = 0.0;
     for (int jbase = 0; jbase < njobs; jbase += 64) {
         // lane l describes job jbase + l: its first row and the rows left in its range
         int job_first = 0, job_left = 0;
@@ -186,6 +176,26 @@ __global__ void __launch_bounds__(256) k_probe_sample(const ProbeSampleArgs<T> A
     }
     n = gf_wave_sum(n); S = gf_wave_sum(S); SP = gf_wave_sum(SP); Sr = gf_wave_sum(Sr);
     Sx = gf_wave_sum(Sx); Sy = gf_wave_sum(Sy); Sz = gf_wave_sum(Sz);
+}
+
+template <class T>
+__global__ void __launch_bounds__(256) k_probe_sample(const ProbeSampleArgs<T> A) {
+    const StepCtrl c = *A.ctrl;
+    if (!c.active) return;
+    const long long slot = c.steps_done - 1 - A.steps_base;
+    if (slot < 0 || slot >= (long long)A.slots) return;
+    const int lane = (int)threadIdx.x & 63;
+    const int p = __builtin_amdgcn_readfirstlane((int)((blockIdx.x * blockDim.x + threadIdx.x) >> 6));
+    if (p >= A.n_probes) return;
+    double* rec = A.log + (size_t)slot * (size_t)A.record;
+    if (p == 0 && lane == 0) {
+        rec[0] = __longlong_as_double(A.iteration0 + c.steps_done);
+        rec[1] = c.total_time;
+        rec[2] = c.last_dt;
+    }
+    const double xp[3] = {A.pos[3 * p], A.pos[3 * p + 1], A.D == 3 ? A.pos[3 * p + 2] : 0.0};
+    double n, S, SP, Sr, Sx, Sy, Sz;
+    pr_walk<T>(A, xp, lane, n, S, SP, Sr, Sx, Sy, Sz);
     if (lane == 0) {
         double* v = rec + kPrHeader + (size_t)kPrValues * p;
         v[0] = S; v[1] = SP; v[2] = Sr; v[3] = Sx; v[4] = Sy; v[5] = A.D == 3 ? Sz : 0.0; v[6] = n;

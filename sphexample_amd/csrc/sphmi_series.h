@@ -1,4 +1,4 @@
-// sphmi_series.h — the host side the observers share (group forces, probes, budgets, flow, envelopes, maps, lattice, columns): the error type, the limits and
+// sphmi_series.h — the host side the observers share (group forces, probes, budgets, flow, envelopes, maps, tracers, lattice, columns): the error type, the limits and
 // record-layout constants host and device agree on, the argument checks every kind of handle reports alike, the per-step series
 // and the means of the kernel sums.  Plain C++17, no HIP: tests/host_series/series_main.cpp compiles it alone.
 #pragma once
@@ -40,6 +40,9 @@ constexpr int kEnHeader = 4;                     // the window of the envelopes:
 constexpr long long kMaxMapBins = 1ll << 20;     // SPHMI_MAX_MAP_BINS
 constexpr int kMpValues = 12;                    // per bin (sphmi_maps.h): top_max, t_top_max, bottom_min, t_arrival, wet, fill, flux[3], speed2_max, t_speed2_max, n_max
 constexpr int kMpHeader = 4;                     // the window of the maps, as the envelopes keep it
+constexpr int kMaxTracers = 1024;                // SPHMI_MAX_TRACERS: of either kind
+constexpr int kTrParticleValues = 8;             // per tracked particle (sphmi_tracers.h): x[3], v[3], ρ, P
+constexpr int kTrDrifterValues = 3 + kPrValues;  // per drifter: X[3], the position the sums were taken at, then S, SP, Sρ, Sv[3], n
 
 // sphmi_attach_columns: the argument errors every kind of handle reports alike
 inline void check_column_table(int32_t n_columns, const void* const* columns, const int32_t* row_bytes) {
@@ -113,6 +116,36 @@ inline int64_t check_map_lattice(const double* origin, const double* spacing, co
 inline int64_t map_row_bound(double c0) {
     const double bound = 2147483648.0 / (4.0 * c0);
     return !(bound < 9.0e18) ? INT64_MAX : (int64_t)bound;
+}
+
+// sphmi_tracers_enable: the argument errors.  rows[] name the tracked particles in the row order of a download NOW (n_rows rows),
+// positions[] hold `dims` doubles per drifter; both counts zero disables and nothing else is looked at.
+inline void check_tracer_table(int32_t n_particles, const int64_t* rows, int64_t n_rows, int32_t n_drifters, const double* positions, int dims,
+                               double min_weight, int64_t capacity_steps) {
+    if (n_particles < 0 || n_particles > kMaxTracers) throw EngineError(SPHMI_ERR_ARGUMENT, "sphmi_tracers_enable: n_particles out of range [0, 1024]");
+    if (n_drifters < 0 || n_drifters > kMaxTracers) throw EngineError(SPHMI_ERR_ARGUMENT, "sphmi_tracers_enable: n_drifters out of range [0, 1024]");
+    if (n_particles == 0 && n_drifters == 0) return;
+    if (n_particles > 0 && !rows) throw EngineError(SPHMI_ERR_ARGUMENT, "sphmi_tracers_enable: null table of rows");
+    if (n_drifters > 0 && !positions) throw EngineError(SPHMI_ERR_ARGUMENT, "sphmi_tracers_enable: null table of positions");
+    if (capacity_steps < 1) throw EngineError(SPHMI_ERR_ARGUMENT, "sphmi_tracers_enable: capacity_steps must be positive");
+    if (!std::isfinite(min_weight) || !(min_weight > 0.0)) throw EngineError(SPHMI_ERR_ARGUMENT, "sphmi_tracers_enable: min_weight must be finite and positive");
+    std::vector<int64_t> sorted;
+    if (n_particles > 0) sorted.assign(rows, rows + n_particles);
+    std::sort(sorted.begin(), sorted.end());
+    for (int32_t k = 0; k < n_particles; ++k) {
+        if (sorted[k] < 0 || sorted[k] >= n_rows) throw EngineError(SPHMI_ERR_ARGUMENT, "sphmi_tracers_enable: row outside [0, n)");
+        if (k > 0 && sorted[k] == sorted[k - 1]) throw EngineError(SPHMI_ERR_ARGUMENT, "sphmi_tracers_enable: duplicate row");
+    }
+    for (int64_t k = 0; k < (int64_t)n_drifters * dims; ++k)
+        if (!std::isfinite(positions[k])) throw EngineError(SPHMI_ERR_ARGUMENT, "sphmi_tracers_enable: non-finite coordinate");
+}
+
+// sphmi_tracers_read: the payload { { x[3], v[3], ρ, P }[n_particles], { X[3], S, SP, Sρ, Sv[3], n }[n_drifters] } of the k-th
+// delivered step, as recorded — the raw sums stay raw (a caller normalises them as sphmi_probes_read does, or moves a drifter again)
+inline void deliver_tracers(int n_particles, int n_drifters, int64_t k, const double* v, double* particles, double* drifters) {
+    const size_t np = (size_t)kTrParticleValues * n_particles, nd = (size_t)kTrDrifterValues * n_drifters;
+    if (particles && np) memcpy(particles + (size_t)k * np, v, np * 8);
+    if (drifters && nd) memcpy(drifters + (size_t)k * nd, v + np, nd * 8);
 }
 
 // sphmi_sample_grid: the argument errors every kind of handle reports alike; returns the number of nodes

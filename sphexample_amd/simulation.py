@@ -46,7 +46,7 @@ def RunSimulation(*, SimGeometry=None, SimMetaData: SimulationMetaData, SimConst
                   device_float_bytes: int = 0, device: int = 0, backend_factory=None,
                   async_output: bool = False, group_forces=None, probes=None, field_grid=None,
                   particle_fields=None, budgets: bool = False, neighbor_list: bool = False, isosurface=None, components=None,
-                  flow_boxes=None, envelopes=None, maps=None) -> List[float]:
+                  flow_boxes=None, envelopes=None, maps=None, tracers=None) -> List[float]:
     """Same keyword signature as the reference (src/SPHCellList.jl:808-817); returns the list of
     time steps the reference collects in ``TimeSteps`` (:823,:884).  ``SimParticles`` is updated in
     place at every output time, in the engine's cell-sorted order, as the reference's is.
@@ -113,7 +113,13 @@ def RunSimulation(*, SimGeometry=None, SimMetaData: SimulationMetaData, SimConst
     step (``Backend.maps_enable``: crest and its time, arrival time, wet duration, fill, flux, the largest bin-mean speed;
     ``sphexample_amd.maps`` forms depths, mean velocities and an arrival map) and ``on_output`` receives the dict of
     ``Backend.maps_read`` as its last argument, behind the envelopes (``None`` at the first call).  The maps keep growing over the
-    whole run.  ``None`` (default): nothing is accumulated and the callback keeps its arguments."""
+    whole run.  ``None`` (default): nothing is accumulated and the callback keeps its arguments.
+
+    ``tracers=dict(particles=rows, drifters=points, min_weight=0.5)``: the rows `particles` of `SimParticles` are followed and
+    the massless points `drifters` advected with the flow on the device at every step (``Backend.tracers_enable``;
+    ``sphexample_amd.tracers.pathlines`` joins the intervals into one array of positions) and ``on_output`` receives the steps of
+    the interval, the dict of ``Backend.tracers_read``, as its last argument, behind the maps (``None`` at the first call).  Either
+    key may be missing.  ``None`` (default): nothing is followed and the callback keeps its arguments."""
     if SimMetaData.BMode.__name__ == "SimpleMDBC":
         LoadMDBCNormals(SimParticles, ParticleNormalsPath)                       # :827
     host_bytes = SimParticles.Position.dtype.itemsize
@@ -180,6 +186,9 @@ def RunSimulation(*, SimGeometry=None, SimMetaData: SimulationMetaData, SimConst
     if maps is not None:
         eng.maps_enable(*tuple(maps))
         extras.append((None, eng.maps_read))
+    if tracers is not None:
+        eng.tracers_enable(capacity=1 << 16, **dict(tracers))
+        extras.append((None, eng.tracers_read))                                  # (None at the first call: no step, no record)
     none_yet = tuple(first for first, _ in extras)
     emit = lambda meta, samples: on_output(meta, SimParticles, *samples)         # noqa: E731
     if on_output:
