@@ -213,6 +213,7 @@ def test_fuzzed_switches_match_the_oracle(seed):
             o.set_motions(p.geometries)
         return e, o
     eng, orc = both()
+    # (fp32 forces_once never reaches the fused window kernels, kWindow needs a predictor / corrector pass: tests/test_fused_pair_parity_gpu.py steps them on clouds like these)
     d1, a1 = eng.forces_once(apply_mdbc=mdbc); d2, a2 = orc.forces_once(apply_mdbc=mdbc)
     ie, io = np.argsort(eng.download(("ID",))["ID"], kind="stable"), np.argsort(orc.download(("ID",))["ID"], kind="stable")
     if fb == 8:
