@@ -2,10 +2,9 @@
 // potential and compressive energy, linear and angular momentum, centre of mass, the largest speed, the density extremes and the
 // bounding box (its maximum along x is the wave front of a dam break).
 //
-// For every EXECUTED step, over the rows i the handle owns with Type == Fluid — dead rows and ghost copies of a slab handle do not
-// count, recognised as in k_probe_sample (sphmi_probes.h) — on the state sphmi_download would deliver directly after that step,
-// formed exactly as k_pack_output forms the doubles of a download: x = Position (fp32 handles: record + low word), v = Velocity
-// widened, ρ = |ρ·s| (+ low word); 2-D handles have z = 0 and vz = 0.  The raw record, kBgValues doubles:
+// For every EXECUTED step, over the rows that count (owned_fluid, sphmi_step_record.h: the handle's own, Type == Fluid), on the row
+// a download would deliver directly after that step (the same header: delivered_coord, delivered_density; v = Velocity widened);
+// 2-D handles have z = 0 and vz = 0.  The raw record, kBgValues doubles:
 //     0        n                                    sum        10–12    Σ x                                 sum
 //     1        Σ ½·((vx·vx + vy·vy) + vz·vz)        sum        13       max ((vx·vx + vy·vy) + vz·vz)       max
 //     2        Σ x_last (the gravity axis)          sum        14, 15   min ρ, max ρ                        min, max
@@ -27,22 +26,21 @@
 //     k_bg_final     one wave: lane l takes the partials l, l + 64, … in order, then the same butterfly; the record of the step
 //     k_bg_small     both stages in one launch of one workgroup, the partials in LDS, adding in exactly the same order (handles of
 //                    at most kBgSmallRows rows, or $SPHMI_BUDGETS_SMALL_ROWS up to kBgSmallRowsMax)
-// All three return at once when the step was cancelled (StepCtrl::active == 0).  The record goes to slot steps_done − 1 − (steps
-// done when the batch was queued) of the batch's log, as gf_write_record writes it.
+// All three return at once when the step was cancelled (StepCtrl::active == 0).
 //
-// Record (kGfHeader + kBgValues doubles): { iteration (int64 bits), TotalTime at the end of the step, Δt, the 22 values above }.
+// Record (StepRecord, sphmi_step_record.h; kStepHeader + kBgValues doubles): the header, then the 22 values above.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "sphmi_kernels.h"
-#include "sphmi_rebuild.h"      // kTypeMask, kGhostMask
-#include "sphmi_series.h"       // kBgValues, bg_rule, kGfHeader
+#include "sphmi_series.h"       // kBgValues, bg_rule
+#include "sphmi_step_record.h"  // StepRecord, wave_butterfly, the delivered row
 
 namespace sphmi {
 
 constexpr int kBgBlock = 256;                    // rows of a partial = threads of the workgroup that forms it
-constexpr int kBgRecord = kGfHeader + kBgValues;
+constexpr int kBgRecord = kStepHeader + kBgValues;
 constexpr int kBgSmallBlocks = 32;               // k_bg_small keeps the partials in LDS: this many blocks at most
 constexpr int kBgSmallRowsMax = kBgSmallBlocks * kBgBlock;
 // One workgroup reduces its blocks one after the other, every butterfly a chain of cross-lane exchanges nothing hides: measured
@@ -52,16 +50,13 @@ constexpr int kBgFinalInFlight = 4;              // partials whose loads k_bg_fi
 
 template <class T> struct BudgetArgs {
     using V4 = typename Vec4<T>::type;
-    const StepCtrl* ctrl;                // the block this step's corrector read
+    StepRecord step;                     // records of kBgRecord doubles
     Half<const V4> pk0, pk1;             // the corrector's output set
     const V4* comp;                      // fp32 handles: low words of position and density (null: none)
     const uint8_t* type;                 // slab handles: the type byte (ghost copies, dead rows); null on plain handles
     double* partial;                     // kBgValues doubles per block of 256 rows
-    double* log;                         // `slots` records of kBgRecord doubles
-    long long iteration0;                // SimMetaData.Iteration when this sphmi_advance began
-    long long steps_base;                // steps done when the batch of this step was queued
     double rho0;
-    int N, D, nblk, slots;               // nblk = ⌈N / 256⌉
+    int N, D, nblk;                      // nblk = ⌈N / 256⌉
 };
 
 __device__ __forceinline__ double bg_identity(int slot) {
@@ -73,9 +68,7 @@ __device__ __forceinline__ double bg_op(int slot, double a, double b) {
 }
 // slot `slot` over the lanes of a wave, a fixed butterfly: every lane ends up with the same bits
 __device__ __forceinline__ double bg_wave(int slot, double v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v = bg_op(slot, v, __shfl_xor(v, d, 64));
-    return v;
+    return wave_butterfly(v, [slot](double a, double b) { return bg_op(slot, a, b); });
 }
 
 // what a lane reads of its row (a lane past N reads nothing: `has` = 0)
@@ -92,7 +85,7 @@ __device__ __forceinline__ BudgetRow<T> bg_load(const BudgetArgs<T>& A, long lon
     if (r.has) {
         r.q0 = A.pk0[i]; r.q1 = A.pk1[i];
         if (sizeof(T) == 4 && A.comp) r.lw = A.comp[i];
-        r.ty = A.type ? A.type[i] : (uint8_t)(r.q0.w > T(0) ? 1 : 2);       // plain handles: Fluid off the sign of the ρ·s slot
+        r.ty = row_type(A.type, i, r.q0.w);
     }
     return r;
 }
@@ -101,14 +94,14 @@ template <class T>
 __device__ __forceinline__ void bg_terms(const BudgetArgs<T>& A, const BudgetRow<T>& r, double v[kBgValues]) {
 #pragma unroll
     for (int k = 0; k < kBgValues; ++k) v[k] = bg_identity(k);
-    if (!r.has || (r.ty & kTypeMask) != 1 || (r.ty & kGhostMask)) return;       // SPHMI_FLUID, owned
+    if (!r.has || !owned_fluid(r.ty)) return;
     {
         // (no contraction: every product and sum is rounded on its own, the doubles a host forms from the download)
 #pragma clang fp contract(off)
         const bool three = A.D == 3;
-        const double x = (double)r.q0.x + (double)r.lw.x, y = (double)r.q0.y + (double)r.lw.y, z = three ? (double)r.q0.z + (double)r.lw.z : 0.0;
+        const double x = delivered_coord(r.q0.x, r.lw.x), y = delivered_coord(r.q0.y, r.lw.y), z = three ? delivered_coord(r.q0.z, r.lw.z) : 0.0;
         const double vx = (double)r.q1.x, vy = (double)r.q1.y, vz = three ? (double)r.q1.z : 0.0;
-        const double rho = (double)(r.q0.w < T(0) ? -r.q0.w : r.q0.w) + (double)r.lw.w;
+        const double rho = delivered_density(r.q0.w, r.lw.w);
         const double v2 = (vx * vx + vy * vy) + vz * vz;
         const double rr = rho / A.rho0, r2 = rr * rr, r6 = (r2 * r2) * r2;
         v[0] = 1.0;
@@ -148,8 +141,8 @@ __device__ __forceinline__ void bg_block_reduce(const BudgetArgs<T>& A, const Bu
 template <class T>
 __device__ __forceinline__ void bg_write_record(const BudgetArgs<T>& A, const StepCtrl& c, const double* partial, int nblk) {
     const int lane = (int)threadIdx.x & 63;
-    const long long slot = c.steps_done - 1 - A.steps_base;
-    if (slot < 0 || slot >= (long long)A.slots) return;
+    const long long slot = A.step.slot(c);
+    if (slot < 0) return;
     double v[kBgValues];
 #pragma unroll
     for (int k = 0; k < kBgValues; ++k) v[k] = bg_identity(k);
@@ -171,19 +164,17 @@ __device__ __forceinline__ void bg_write_record(const BudgetArgs<T>& A, const St
 #pragma unroll
     for (int k = 0; k < kBgValues; ++k) v[k] = bg_wave(k, v[k]);
     if (lane == 0) {
-        double* rec = A.log + (size_t)slot * (size_t)kBgRecord;
-        rec[0] = __longlong_as_double(A.iteration0 + c.steps_done);
-        rec[1] = c.total_time;
-        rec[2] = c.last_dt;
+        double* rec = A.step.at(slot);
+        A.step.write_header(rec, c);
 #pragma unroll
-        for (int k = 0; k < kBgValues; ++k) rec[kGfHeader + k] = v[k];
+        for (int k = 0; k < kBgValues; ++k) rec[kStepHeader + k] = v[k];
     }
 }
 
 // any grid: workgroup w takes blocks w, w + gridDim.x, …
 template <class T>
 __global__ void __launch_bounds__(kBgBlock) k_bg_partial(const BudgetArgs<T> A) {
-    if (!A.ctrl->active) return;
+    if (!A.step.ctrl->active) return;
     __shared__ double s_w[4][kBgValues];
     for (int b = (int)blockIdx.x; b < A.nblk; b += (int)gridDim.x) {
         const BudgetRow<T> r = bg_load<T>(A, (long long)b * kBgBlock + (int)threadIdx.x);
@@ -192,7 +183,7 @@ __global__ void __launch_bounds__(kBgBlock) k_bg_partial(const BudgetArgs<T> A) 
 }
 template <class T>
 __global__ void __launch_bounds__(64) k_bg_final(const BudgetArgs<T> A) {
-    const StepCtrl c = *A.ctrl;
+    const StepCtrl c = *A.step.ctrl;
     if (!c.active) return;
     bg_write_record<T>(A, c, A.partial, A.nblk);
 }
@@ -200,7 +191,7 @@ __global__ void __launch_bounds__(64) k_bg_final(const BudgetArgs<T> A) {
 // wave 0 writes the record
 template <class T>
 __global__ void __launch_bounds__(kBgBlock) k_bg_small(const BudgetArgs<T> A) {
-    const StepCtrl c = *A.ctrl;
+    const StepCtrl c = *A.step.ctrl;
     if (!c.active) return;
     __shared__ double s_w[4][kBgValues];
     __shared__ double s_partial[kBgSmallBlocks * kBgValues];

@@ -140,28 +140,34 @@ struct EngineBase {
         if (!(cfg.h <= cfg.H)) throw EngineError(SPHMI_ERR_STATE, std::string(fn) + ": handles with H < h are not served (the candidate cells are laid out for H + h <= 2H)");
         if (!cell_list) throw EngineError(SPHMI_ERR_STATE, std::string(fn) + ": the handle has not executed a step since the upload " + tail);
     }
-    // The observers' series (sphmi_series.h).  A multi-device handle keeps them itself; those of its slab engines stay empty.
-    bool gf_on = false, pr_on = false, bg_on = false, fl_on = false;
-    StepSeries gf_series, pr_series;           // payload: 3 forces per group / the RAW sums, kPrValues per probe (the read normalises)
-    StepSeries bg_series;                      // the RAW budgets of the fluid, kBgValues per step (the read forms energies, momenta, the centre)
+    // The observers that record once per executed step, in the order their samples are queued and their logs fetched.  `series`
+    // (sphmi_series.h) holds the payloads as recorded, RAW: the reads form what they deliver.  A multi-device handle keeps the series
+    // itself (those of its slab engines stay empty) and combines the slabs' records slot by slot with `rule` (null: every slot a sum).
+    enum Obs { OBS_GF = 0, OBS_PR, OBS_BG, OBS_FL, OBS_TR, OBS_COUNT };
+    struct SeriesObserver {
+        const char* what;                      // in error texts
+        int (*rule)(int);
+        bool on = false;
+        StepSeries series;
+    };
+    SeriesObserver obs[OBS_COUNT] = {{"group forces", nullptr}, {"probes", nullptr}, {"budgets", bg_rule}, {"flow", nullptr}, {"tracers", nullptr}};
     // the device side of an enable: the handle's own sampling, or that of every slab engine of a multi-device handle
     virtual void gf_enable_device(int32_t n_groups, const uint64_t* markers) = 0;
     virtual void pr_enable_device(int32_t n_probes, const double* positions) = 0;
     virtual void bg_enable_device(bool on) = 0;
-    StepSeries fl_series;                      // the RAW flow records, kFlValues per control box (the read multiplies by m₀)
     virtual void fl_enable_device(int32_t n_boxes, const double* lo, const double* hi) = 0;
     void flow_enable(int32_t n_boxes, const double* lo, const double* hi, int64_t capacity_steps) {
         require_one_process("sphmi_flow_enable");
         check_flow_table(n_boxes, lo, hi, cfg.dims, capacity_steps);
         fl_enable_device(n_boxes, lo, hi);
-        fl_series.reset(kFlValues * n_boxes, n_boxes > 0 ? capacity_steps : 0);
+        obs[OBS_FL].series.reset(kFlValues * n_boxes, n_boxes > 0 ? capacity_steps : 0);
     }
     void flow_read(int64_t capacity, int64_t* iteration_out, double* time, double* dt, int64_t* count, double* volume, double* momentum, int64_t* entered,
                    int64_t* left, int64_t* n_out, int64_t* n_dropped) {
         require_one_process("sphmi_flow_read");
-        if (!fl_on) throw EngineError(SPHMI_ERR_STATE, "sphmi_flow_read: sampling is not enabled (sphmi_flow_enable)");
-        fl_series.read("sphmi_flow_read", capacity, iteration_out, time, dt, n_out, n_dropped, [&](int64_t k, const double* v) {
-            deliver_flow(cfg.m0, fl_series.values / kFlValues, k, v, count, volume, momentum, entered, left);
+        if (!obs[OBS_FL].on) throw EngineError(SPHMI_ERR_STATE, "sphmi_flow_read: sampling is not enabled (sphmi_flow_enable)");
+        obs[OBS_FL].series.read("sphmi_flow_read", capacity, iteration_out, time, dt, n_out, n_dropped, [&](int64_t k, const double* v) {
+            deliver_flow(cfg.m0, obs[OBS_FL].series.values / kFlValues, k, v, count, volume, momentum, entered, left);
         });
     }
     // The per-particle envelopes (sphmi_envelopes.h) live in the rows' own device: a handle of one device overrides the pair.  Rows of
@@ -202,40 +208,40 @@ struct EngineBase {
         require_one_process("sphmi_group_forces_enable");
         check_group_table(n_groups, markers, capacity_steps);
         gf_enable_device(n_groups, markers);
-        gf_series.reset(3 * n_groups, capacity_steps);
+        obs[OBS_GF].series.reset(3 * n_groups, capacity_steps);
     }
     void probes_enable(int32_t n_probes, const double* positions, int64_t capacity_steps) {
         require_one_process("sphmi_probes_enable");
         check_probe_table(n_probes, positions, cfg.dims, capacity_steps);
         pr_enable_device(n_probes, positions);
-        pr_series.reset(kPrValues * n_probes, capacity_steps);
+        obs[OBS_PR].series.reset(kPrValues * n_probes, capacity_steps);
     }
     void budgets_enable(int64_t capacity_steps) {
         require_one_process("sphmi_budgets_enable");
         if (capacity_steps < 0) throw EngineError(SPHMI_ERR_ARGUMENT, "sphmi_budgets_enable: negative capacity_steps");
         bg_enable_device(capacity_steps > 0);
-        bg_series.reset(capacity_steps > 0 ? kBgValues : 0, capacity_steps);
+        obs[OBS_BG].series.reset(capacity_steps > 0 ? kBgValues : 0, capacity_steps);
     }
     void budgets_read(int64_t capacity, int64_t* iteration_out, double* time, double* dt, int64_t* count, double* energy, double* momentum, double* angular,
                       double* centre, double* extremes, double* box, int64_t* n_out, int64_t* n_dropped) {
         require_one_process("sphmi_budgets_read");
-        if (!bg_on) throw EngineError(SPHMI_ERR_STATE, "sphmi_budgets_read: sampling is not enabled (sphmi_budgets_enable)");
+        if (!obs[OBS_BG].on) throw EngineError(SPHMI_ERR_STATE, "sphmi_budgets_read: sampling is not enabled (sphmi_budgets_enable)");
         const BudgetFactors f(cfg.m0, cfg.g, cfg.c0, cfg.rho0);
-        bg_series.read("sphmi_budgets_read", capacity, iteration_out, time, dt, n_out, n_dropped,
-                       [&](int64_t k, const double* v) { deliver_budgets(f, k, v, count, energy, momentum, angular, centre, extremes, box); });
+        obs[OBS_BG].series.read("sphmi_budgets_read", capacity, iteration_out, time, dt, n_out, n_dropped,
+                                [&](int64_t k, const double* v) { deliver_budgets(f, k, v, count, energy, momentum, angular, centre, extremes, box); });
     }
     void group_forces_read(int64_t capacity, int64_t* iteration_out, double* time, double* dt, double* force, int64_t* n_out, int64_t* n_dropped) {
         require_one_process("sphmi_group_forces_read");
-        if (!gf_on) throw EngineError(SPHMI_ERR_STATE, "sphmi_group_forces_read: sampling is not enabled (sphmi_group_forces_enable)");
-        gf_series.read("sphmi_group_forces_read", capacity, iteration_out, time, dt, n_out, n_dropped,
-                       [&](int64_t k, const double* v) { deliver_forces(gf_series.values / 3, k, v, force); });
+        if (!obs[OBS_GF].on) throw EngineError(SPHMI_ERR_STATE, "sphmi_group_forces_read: sampling is not enabled (sphmi_group_forces_enable)");
+        obs[OBS_GF].series.read("sphmi_group_forces_read", capacity, iteration_out, time, dt, n_out, n_dropped,
+                                [&](int64_t k, const double* v) { deliver_forces(obs[OBS_GF].series.values / 3, k, v, force); });
     }
     void probes_read(int64_t capacity, int64_t* iteration_out, double* time, double* dt, double* weight, int64_t* count, double* pressure,
                      double* density, double* velocity, int64_t* n_out, int64_t* n_dropped) {
         require_one_process("sphmi_probes_read");
-        if (!pr_on) throw EngineError(SPHMI_ERR_STATE, "sphmi_probes_read: sampling is not enabled (sphmi_probes_enable)");
-        pr_series.read("sphmi_probes_read", capacity, iteration_out, time, dt, n_out, n_dropped, [&](int64_t k, const double* v) {
-            deliver_probe_means(pr_series.values / kPrValues, k, v, weight, count, pressure, density, velocity);
+        if (!obs[OBS_PR].on) throw EngineError(SPHMI_ERR_STATE, "sphmi_probes_read: sampling is not enabled (sphmi_probes_enable)");
+        obs[OBS_PR].series.read("sphmi_probes_read", capacity, iteration_out, time, dt, n_out, n_dropped, [&](int64_t k, const double* v) {
+            deliver_probe_means(obs[OBS_PR].series.values / kPrValues, k, v, weight, count, pressure, density, velocity);
         });
     }
     virtual ~EngineBase() {}
@@ -995,7 +1001,7 @@ struct Engine final : EngineBase {
         }
         have_grid = true;
         n_rebuilds += 1;
-        if (gf_on) gf_build_lists();
+        if (obs[OBS_GF].on) gf_build_lists();
         sched_state = 1; sched1_state = dd_slab ? 1 : 0; resched0_pending = false; resched1_pending = false; work_valid = false;
         end_phase(ev);
     }
@@ -1054,7 +1060,7 @@ struct Engine final : EngineBase {
         nonempty_pending = true;               // (misc_d[0] and the run table travel with the copy of the control block at the next batch boundary)
         hipLaunchKernelGGL(k_tile_schedule_small, dim3(8), dim3(1024), 0, stream, small_sched(nullptr, 0, ctrl_cur()));
         HC(hipGetLastError());
-        if (gf_on) gf_build_lists();
+        if (obs[OBS_GF].on) gf_build_lists();
         part_copy_queued = true;
         part_max[0] = part_bound(); part_max[1] = 0;
         list_tiles[0] = (N + kWave - 1) / kWave; list_tiles[1] = 0;
@@ -1194,7 +1200,7 @@ struct Engine final : EngineBase {
     }
     void enqueue_step() {
         serve_reschedules();
-        if (fl_on) fl_mark();                                                  // the boxes every row is inside of BEFORE the step (the corrector updates the low words in place)
+        fl_mark();                                                             // the boxes every row is inside of BEFORE the step (the corrector updates the low words in place)
         const bool fused = batch_fused;
         if (!fused) {
             Ev ev = begin_phase(PH_TIMESTEP);
@@ -1228,13 +1234,7 @@ struct Engine final : EngineBase {
         Ev e2 = begin_phase(PH_PASS2);
         launch_force<PASS_CORRECTOR>(P2);                                      // :789-798
         end_phase(e2);
-        if (gf_on) gf_sample(ctrl_cur(), obs_iteration0, obs_steps_base);       // Σ Acceleration of the selected groups → the batch's log
-        if (pr_on) pr_sample(ctrl_cur(), obs_iteration0, obs_steps_base, iB);   // the kernel sums at the probes, on the corrector's output set → the batch's log
-        if (bg_on) bg_sample(ctrl_cur(), obs_iteration0, obs_steps_base, iB);   // the budgets of the fluid, on the same set → the batch's log
-        if (fl_on) fl_sample(ctrl_cur(), obs_iteration0, obs_steps_base, iB);   // the flow through the control boxes: that set against this step's marks
-        if (en_mask) en_update(ctrl_cur(), iB);                                 // the per-particle envelopes: that set and the half step's density → the rows' records
-        if (mp_on) mp_update(ctrl_cur(), iB);                                   // the per-bin maps: the Fluid rows of that set → the step's map → the bins' records
-        if (tr_on) tr_sample(ctrl_cur(), obs_iteration0, obs_steps_base, iB);   // the tracers: tracked rows of that set → the batch's log; the drifters sample it and move
+        observe_step(ctrl_cur(), iB);
         std::swap(iA, iB);
     }
 
@@ -1243,7 +1243,7 @@ struct Engine final : EngineBase {
         HC(hipSetDevice(cfg.device));
         delta_x = 1.0 + cfg.h;                                                // :739
         int64_t steps = 0;
-        obs_iteration0 = iteration;
+        const int64_t iteration0 = iteration;
         StepCtrl c{};
         c.delta_x = delta_x; c.total_time = total_time; c.t_step_start = total_time; c.t_target = t_target;
         c.max_steps = max_steps; c.last_dt = last_dt;
@@ -1269,17 +1269,13 @@ struct Engine final : EngineBase {
                 if (dx0 >= cfg.h) batch = 1;
                 else if (dx_rate > 0.0) batch = (int)std::max(1.0, std::min((double)kBatch, std::ceil((cfg.h - dx0) / dx_rate) + (fresh ? 2.0 : 1.0)));
                 if (max_steps >= 0) batch = (int)std::min<int64_t>(batch, std::max<int64_t>(max_steps - steps, 1));
-                obs_steps_base = steps;
+                set_batch_clock(iteration0, steps);
                 for (int k = 0; k < batch; ++k) { batch_step = k; enqueue_step(); iteration += 1; }      // iteration: provisional (event sampling)
                 batch_step = -1;
                 // the block the last queued step wrote, both sets of slots (below: the bad-ρ flag), the counters and the run table of a
                 // device-side rebuild: one copy
                 HC(hipMemcpyAsync(ctl_m, ctl_d, kCtlBytes, hipMemcpyDeviceToHost, stream));
-                if (gf_on) gf_log.fetch(batch, stream);                                      // … and the group-force records of the batch with it
-                if (pr_on) pr_log.fetch(batch, stream);                                      // … and the probe records
-                if (bg_on) bg_log.fetch(batch, stream);                                      // … and the budgets
-                if (fl_on) fl_log.fetch(batch, stream);                                      // … and the flow records
-                if (tr_on) tr_log.fetch(batch, stream);                                      // … and the tracers' records
+                fetch_logs(batch);                                                           // … and the records of the batch with it
                 // (the XCD finishing times of a sampled launch: the host-side rebuild reads them at its own synchronisation; handles that
                 // rebuild on the device have none — the shares of the next measured-work schedule would never move: 3 % on the 159 k-particle
                 // LaminarSPS case)
@@ -1292,11 +1288,7 @@ struct Engine final : EngineBase {
                 c = *ctrl_h;
                 steps = c.steps_done;
                 const int64_t executed = steps - before;
-                if (gf_on) push_records(gf_series, gf_log, kGfHeader, executed);
-                if (pr_on) push_records(pr_series, pr_log, kPrHeader, executed);
-                if (bg_on) push_records(bg_series, bg_log, kGfHeader, executed);
-                if (fl_on) push_records(fl_series, fl_log, kGfHeader, executed);
-                if (tr_on) push_records(tr_series, tr_log, kGfHeader, executed);
+                push_records(executed);
                 // (control inside the predictor: the slots flipped at queue time, once per queued step; what counts is where
                 // the last EXECUTED corrector left its maxima — cancelled steps consume nothing and zero nothing)
                 if (batch_fused) rpar = rpar0 ^ (int)(executed & 1);
@@ -1389,13 +1381,7 @@ struct Engine final : EngineBase {
         for (int i = 0; i < N; ++i)
             if (!(std::fabs((double)h0[i].w) > 0.0)) throw EngineError(SPHMI_ERR_ARGUMENT, "sphmi_upload: density must be positive");
         detach_columns();                          // a new particle set: the attached columns described the old one
-        gf_disable();                              // … and so did the selected groups' row lists
-        pr_disable();                              // … and the probes go with them
-        bg_disable();                              // … and the budgets
-        fl_disable();                              // … and the control boxes
-        en_disable();                              // … and the envelopes of the old rows
-        mp_disable();                              // … and the maps they drew
-        tr_disable();                              // … and the tracers: the tracked rows were rows of the old set
+        observers_off();                           // … and so did every observer: row lists, tracked rows and records described the old set
         iA = 0; iH = 1; iB = 2; cur = 0;
         ghost_given = ghost_points != nullptr;
         {
@@ -1455,13 +1441,7 @@ struct Engine final : EngineBase {
         auto release = [&]() { (void)hipFree(flag); (void)hipFree(pos); (void)hipFree(tsum); (void)hipFree(tot_d); };
         try {
             detach_columns();
-            gf_disable();
-            pr_disable();
-            bg_disable();
-            fl_disable();
-            en_disable();
-            mp_disable();
-            tr_disable();
+            observers_off();
             iA = 0; iH = 1; iB = 2; cur = 0; ghost_given = false; mdbc_n_list = 0; mdbc_list_valid = false;
             int base = 0;
             const unsigned nbM = (unsigned)((M + 255) / 256);
@@ -1756,7 +1736,7 @@ struct Engine final : EngineBase {
     }
     // ---- what the observers share ---------------------------------------------------------------------------------------------
     // The device-side log of an observer that records once per executed step: kBatch slots of record_doubles doubles and their
-    // page-locked mirror, fetched with the control block of a batch.  obs_iteration0 / obs_steps_base: the clock of the batch.
+    // page-locked mirror, fetched with the control block of a batch; log[k] is that of obs[k].
     struct StepLog {
         static constexpr int slots = kBatch;
         DeviceBuf<double> d;
@@ -1770,17 +1750,44 @@ struct Engine final : EngineBase {
         void fetch(int batch, hipStream_t s) { HC(hipMemcpyAsync(m, d.p, (size_t)std::min(batch, slots) * (size_t)record_doubles * 8, hipMemcpyDeviceToHost, s)); }
         const double* record(int64_t k) const { return m + (size_t)k * (size_t)record_doubles; }      // of the k-th executed step of the fetched batch
     };
+    StepLog log[OBS_COUNT];
+    // the clock of the batch being queued; the driver — Engine::advance, or the multi-device handle for every slab engine — sets it
     int64_t obs_iteration0 = 0, obs_steps_base = 0;
-    // after the synchronisation of a batch: the records of its `executed` steps
-    static void push_records(StepSeries& series, const StepLog& log, int header, int64_t executed) {
-        for (int64_t k = 0; k < executed; ++k) series.push(StepSeries::decode(log.record(k), header, series.values));
+    void set_batch_clock(int64_t iteration0, int64_t steps_base) { obs_iteration0 = iteration0; obs_steps_base = steps_base; }
+    // where the step whose corrector read `ctrl` writes its record of observer k (sphmi_step_record.h)
+    StepRecord step_record(Obs k, const StepCtrl* ctrl) const {
+        return StepRecord{ctrl, log[k].d.p, obs_iteration0, obs_steps_base, log[k].record_doubles, StepLog::slots};
     }
-    // Switching an observer off, the part all four share: nothing is sampled from here on, the series is empty, and once the stream
-    // has drained the device side goes back (`release`, which also clears the observer's table).  Not on: only the release, so that
-    // an enable that failed half way leaves nothing behind for the next one.
-    void observer_off(bool& on, StepSeries& series, void (Engine::*release)()) {
-        if (on) {
-            on = false; series.reset(0, 0);
+    // Queued behind the corrector of a step, in this order; `ctrl`: the control block that corrector read, `set`: the state set it
+    // wrote.  An observer that is off touches none of its members.
+    void observe_step(const StepCtrl* ctrl, int set) {
+        if (obs[OBS_GF].on) gf_sample(ctrl, set);      // Σ Acceleration of the selected groups → the batch's log
+        if (obs[OBS_PR].on) pr_sample(ctrl, set);      // the kernel sums at the probes, on the corrector's output set → the batch's log
+        if (obs[OBS_BG].on) bg_sample(ctrl, set);      // the budgets of the fluid, on the same set → the batch's log
+        if (obs[OBS_FL].on) fl_sample(ctrl, set);      // the flow through the control boxes: that set against this step's marks
+        if (en_mask) en_update(ctrl, set);             // the per-particle envelopes: that set and the half step's density → the rows' records
+        if (mp_on) mp_update(ctrl, set);               // the per-bin maps: the Fluid rows of that set → the step's map → the bins' records
+        if (obs[OBS_TR].on) tr_sample(ctrl, set);      // the tracers: tracked rows of that set → the batch's log; the drifters sample it and move
+    }
+    // behind the last step of a batch: the logs travel with its control block
+    void fetch_logs(int batch) {
+        for (int k = 0; k < OBS_COUNT; ++k) if (obs[k].on) log[k].fetch(batch, stream);
+    }
+    // after the synchronisation of a batch: the records of its `executed` steps
+    void push_records(int64_t executed) {
+        for (int k = 0; k < OBS_COUNT; ++k) {
+            if (!obs[k].on) continue;
+            for (int64_t j = 0; j < executed; ++j) obs[k].series.push(StepSeries::decode(log[k].record(j), kStepHeader, obs[k].series.values));
+        }
+    }
+    // a new particle set: every observer described the old one
+    void observers_off() { gf_disable(); pr_disable(); bg_disable(); fl_disable(); en_disable(); mp_disable(); tr_disable(); }
+    // Switching a series observer off: nothing is sampled from here on, the series is empty, and once the stream has drained the
+    // device side goes back (`release`, which also clears the observer's table).  Not on: only the release, so that an enable that
+    // failed half way leaves nothing behind for the next one.
+    void observer_off(Obs k, void (Engine::*release)()) {
+        if (obs[k].on) {
+            obs[k].on = false; obs[k].series.reset(0, 0);
             HC(hipSetDevice(cfg.device)); HC(hipStreamSynchronize(stream));
         }
         (this->*release)();
@@ -1813,15 +1820,14 @@ struct Engine final : EngineBase {
     DeviceBuf<int> gf_list, gf_counts, gf_offsets;
     DeviceBuf<GroupListMeta> gf_meta;
     DeviceBuf<double> gf_partial;
-    StepLog gf_log;
     int gf_nblk_cap() const { return (cap + 255) / 256; }
     int gf_list_cap() const { return cap + kMaxForceGroups * kGfChunk; }
     int gf_chunk_cap() const { return cap / kGfChunk + kMaxForceGroups + 1; }
     void gf_release() {
-        gf_list.free(); gf_counts.free(); gf_offsets.free(); gf_meta.free(); gf_partial.free(); gf_log.release();
+        gf_list.free(); gf_counts.free(); gf_offsets.free(); gf_meta.free(); gf_partial.free(); log[OBS_GF].release();
         gf_table = GroupTable{};
     }
-    void gf_disable() { observer_off(gf_on, gf_series, &Engine::gf_release); }
+    void gf_disable() { observer_off(OBS_GF, &Engine::gf_release); }
     void gf_enable_device(int32_t n_groups, const uint64_t* markers) override {
         HC(hipSetDevice(cfg.device));
         gf_disable();
@@ -1830,10 +1836,10 @@ struct Engine final : EngineBase {
         gf_counts.need((size_t)kMaxForceGroups * gf_nblk_cap()); gf_offsets.need((size_t)kMaxForceGroups * gf_nblk_cap());
         gf_meta.need(1); HC(hipMemset(gf_meta.p, 0, sizeof(GroupListMeta)));
         gf_partial.need((size_t)gf_chunk_cap() * 3);
-        gf_log.alloc(kGfRecordMax, kGfHeader + 3 * n_groups);
+        log[OBS_GF].alloc(kGfRecordMax, kStepHeader + 3 * n_groups);
         gf_table.n = n_groups;
         for (int g = 0; g < n_groups; ++g) gf_table.marker[g] = markers[g];
-        gf_on = true;
+        obs[OBS_GF].on = true;
         gf_build_lists();                          // the rows as they lie now; every rebuild that permutes builds them again
         HC(hipStreamSynchronize(stream));
     }
@@ -1845,12 +1851,12 @@ struct Engine final : EngineBase {
                            (const int*)gf_offsets.p, gf_list.p, gf_list_cap());
         HC(hipGetLastError());
     }
-    // behind the corrector of a queued step; `ctrl`: the control block that corrector read
-    void gf_sample(const StepCtrl* ctrl, int64_t iteration0, int64_t steps_base) {
+    // (the Acceleration is the corrector's whichever set it wrote: `set` is not looked at)
+    void gf_sample(const StepCtrl* ctrl, int) {
         GroupSampleArgs A{};
-        A.ctrl = ctrl; A.list = gf_list.p; A.meta = gf_meta.p; A.partial = gf_partial.p; A.log = gf_log.d.p;
-        A.iteration0 = iteration0; A.steps_base = steps_base; A.m0 = cfg.m0;
-        A.n_groups = gf_table.n; A.N = N; A.D = D; A.record = gf_log.record_doubles; A.slots = StepLog::slots;
+        A.step = step_record(OBS_GF, ctrl); A.list = gf_list.p; A.meta = gf_meta.p; A.partial = gf_partial.p;
+        A.m0 = cfg.m0;
+        A.n_groups = gf_table.n; A.N = N; A.D = D;
         if (N <= kGfSmallRows) hipLaunchKernelGGL(k_gf_small<T>, dim3(1), dim3(kGfChunk), 0, stream, (const V4*)acc[cur], A);
         else {
             const int max_chunks = std::min(N / kGfChunk + gf_table.n + 1, gf_chunk_cap());
@@ -1864,9 +1870,8 @@ struct Engine final : EngineBase {
     // The records of a batch go where the group forces' go: a log of kBatch slots on the device, fetched with the control block.
     int pr_n = 0;
     DeviceBuf<double> pr_pos_d;
-    StepLog pr_log;
-    void pr_release() { pr_pos_d.free(); pr_log.release(); pr_n = 0; }
-    void pr_disable() { observer_off(pr_on, pr_series, &Engine::pr_release); }
+    void pr_release() { pr_pos_d.free(); log[OBS_PR].release(); pr_n = 0; }
+    void pr_disable() { observer_off(OBS_PR, &Engine::pr_release); }
     void pr_enable_device(int32_t n_probes, const double* positions) override {
         HC(hipSetDevice(cfg.device));
         pr_disable();
@@ -1875,19 +1880,17 @@ struct Engine final : EngineBase {
         std::vector<double> xyz((size_t)3 * n_probes, 0.0);
         for (int p = 0; p < n_probes; ++p) for (int d = 0; d < D; ++d) xyz[3 * (size_t)p + d] = positions[(size_t)p * D + d];
         pr_pos_d.need(xyz.size());
-        pr_log.alloc(kPrHeader + kPrValues * n_probes, kPrHeader + kPrValues * n_probes);
+        log[OBS_PR].alloc(kStepHeader + kPrValues * n_probes, kStepHeader + kPrValues * n_probes);
         bounce.h2d(pr_pos_d.p, xyz.data(), xyz.size() * 8, stream);
         pr_n = n_probes;
-        pr_on = true;
+        obs[OBS_PR].on = true;
     }
-    // queued behind the corrector of a step; `set`: the state set that corrector wrote
-    void pr_sample(const StepCtrl* ctrl, int64_t iteration0, int64_t steps_base, int set) {
+    void pr_sample(const StepCtrl* ctrl, int set) {
         ProbeSampleArgs<T> A{};
-        A.ctrl = ctrl; A.pk0 = pk0[set]; A.pk1 = pk1[set]; A.half0 = pk0[iH]; A.comp = comp[cur];
-        A.type = dd_slab ? type[cur] : nullptr; A.cstart = cstart; A.pos = pr_pos_d.p; A.log = pr_log.d.p; A.g = grid;
-        A.iteration0 = iteration0; A.steps_base = steps_base;
+        A.step = step_record(OBS_PR, ctrl); A.pk0 = pk0[set]; A.pk1 = pk1[set]; A.half0 = pk0[iH]; A.comp = comp[cur];
+        A.type = dd_slab ? type[cur] : nullptr; A.cstart = cstart; A.pos = pr_pos_d.p; A.g = grid;
         fill_sample_consts(A);
-        A.n_probes = pr_n; A.N = N; A.D = D; A.kernel = cfg.kernel; A.record = pr_log.record_doubles; A.slots = StepLog::slots;
+        A.n_probes = pr_n; A.N = N; A.D = D; A.kernel = cfg.kernel;
         hipLaunchKernelGGL(k_probe_sample<T>, dim3((pr_n + 3) / 4), dim3(256), 0, stream, A);
         HC(hipGetLastError());
     }
@@ -1896,11 +1899,10 @@ struct Engine final : EngineBase {
     // No row lists: every launch looks at every row, so rebuilds need no hook.  One launch behind every corrector on handles of at
     // most bg_small_rows rows, two above; the records of a batch go where the group forces' go.
     DeviceBuf<double> bg_partial;
-    StepLog bg_log;
     int bg_small_rows = kBgSmallRows;          // $SPHMI_BUDGETS_SMALL_ROWS, read at enable (0: always two stages)
     int bg_nblk_cap() const { return (cap + kBgBlock - 1) / kBgBlock; }
-    void bg_release() { bg_partial.free(); bg_log.release(); }
-    void bg_disable() { observer_off(bg_on, bg_series, &Engine::bg_release); }
+    void bg_release() { bg_partial.free(); log[OBS_BG].release(); }
+    void bg_disable() { observer_off(OBS_BG, &Engine::bg_release); }
     void bg_enable_device(bool on) override {
         HC(hipSetDevice(cfg.device));
         bg_disable();
@@ -1908,16 +1910,15 @@ struct Engine final : EngineBase {
         bg_small_rows = kBgSmallRows;
         if (const char* e = getenv("SPHMI_BUDGETS_SMALL_ROWS")) bg_small_rows = (int)std::min<long long>(std::max<long long>(atoll(e), 0), kBgSmallRowsMax);
         bg_partial.need((size_t)bg_nblk_cap() * kBgValues);
-        bg_log.alloc(kBgRecord, kBgRecord);
-        bg_on = true;
+        log[OBS_BG].alloc(kBgRecord, kBgRecord);
+        obs[OBS_BG].on = true;
     }
-    // queued behind the corrector of a step; `set`: the state set that corrector wrote
-    void bg_sample(const StepCtrl* ctrl, int64_t iteration0, int64_t steps_base, int set) {
+    void bg_sample(const StepCtrl* ctrl, int set) {
         BudgetArgs<T> A{};
-        A.ctrl = ctrl; A.pk0 = pk0[set]; A.pk1 = pk1[set]; A.comp = comp[cur];
-        A.type = dd_slab ? type[cur] : nullptr; A.partial = bg_partial.p; A.log = bg_log.d.p;
-        A.iteration0 = iteration0; A.steps_base = steps_base; A.rho0 = cfg.rho0;
-        A.N = N; A.D = D; A.nblk = std::min((N + kBgBlock - 1) / kBgBlock, bg_nblk_cap()); A.slots = StepLog::slots;
+        A.step = step_record(OBS_BG, ctrl); A.pk0 = pk0[set]; A.pk1 = pk1[set]; A.comp = comp[cur];
+        A.type = dd_slab ? type[cur] : nullptr; A.partial = bg_partial.p;
+        A.rho0 = cfg.rho0;
+        A.N = N; A.D = D; A.nblk = std::min((N + kBgBlock - 1) / kBgBlock, bg_nblk_cap());
         if (N <= bg_small_rows) hipLaunchKernelGGL(k_bg_small<T>, dim3(1), dim3(kBgBlock), 0, stream, A);
         else {
             hipLaunchKernelGGL(k_bg_partial<T>, dim3(std::min(A.nblk, 1 << 20)), dim3(kBgBlock), 0, stream, A);
@@ -1931,12 +1932,11 @@ struct Engine final : EngineBase {
     // handles of at most fl_small_rows rows, two above).  No row lists, so rebuilds have no hook: they run between steps.
     DeviceBuf<uint16_t> fl_mark_d;
     DeviceBuf<double> fl_partial;
-    StepLog fl_log;
     FlowBoxes fl_boxes{};
     int fl_small_rows = kFlSmallRows;          // $SPHMI_FLOW_SMALL_ROWS, read at enable (0: always two stages)
     int fl_nblk_cap() const { return (cap + kFlBlock - 1) / kFlBlock; }
-    void fl_release() { fl_mark_d.free(); fl_partial.free(); fl_log.release(); fl_boxes.n = 0; }
-    void fl_disable() { observer_off(fl_on, fl_series, &Engine::fl_release); }
+    void fl_release() { fl_mark_d.free(); fl_partial.free(); log[OBS_FL].release(); fl_boxes.n = 0; }
+    void fl_disable() { observer_off(OBS_FL, &Engine::fl_release); }
     void fl_enable_device(int32_t n_boxes, const double* lo, const double* hi) override {
         HC(hipSetDevice(cfg.device));
         fl_disable();
@@ -1949,32 +1949,31 @@ struct Engine final : EngineBase {
             }
         fl_small_rows = kFlSmallRows;
         if (const char* e = getenv("SPHMI_FLOW_SMALL_ROWS")) fl_small_rows = (int)std::min<long long>(std::max<long long>(atoll(e), 0), kFlSmallRowsMax);
-        const int record = kGfHeader + kFlValues * n_boxes;
+        const int record = kStepHeader + kFlValues * n_boxes;
         fl_mark_d.need((size_t)cap);
         fl_partial.need((size_t)fl_nblk_cap() * n_boxes * kFlValues);
-        fl_log.alloc(record, record);
+        log[OBS_FL].alloc(record, record);
         fl_boxes.n = n_boxes;
-        fl_on = true;
+        obs[OBS_FL].on = true;
     }
     template <class A> void fl_fill(A& a, int set) const {
         a.pk0 = pk0[set]; a.pk1 = pk1[set]; a.comp = comp[cur];
-        a.type = dd_slab ? type[cur] : nullptr; a.mark = fl_mark_d.p; a.partial = fl_partial.p; a.log = fl_log.d.p;
-        a.N = N; a.D = D; a.nblk = std::min((N + kFlBlock - 1) / kFlBlock, fl_nblk_cap()); a.slots = StepLog::slots;
+        a.type = dd_slab ? type[cur] : nullptr; a.mark = fl_mark_d.p; a.partial = fl_partial.p;
+        a.N = N; a.D = D; a.nblk = std::min((N + kFlBlock - 1) / kFlBlock, fl_nblk_cap());
         a.box = fl_boxes;
     }
-    // queued in front of everything else of a step: the current set + low words
+    // queued in front of everything else of a step: the current set + low words (off: nothing)
     void fl_mark() {
-        if (N <= 0) return;
+        if (!obs[OBS_FL].on || N <= 0) return;
         FlowArgs<T> A{};
         fl_fill(A, iA);
         hipLaunchKernelGGL(k_fl_mark<T>, dim3(A.nblk), dim3(kFlBlock), 0, stream, A);
         HC(hipGetLastError());
     }
-    // queued behind the corrector of a step; `set`: the state set that corrector wrote
-    void fl_sample(const StepCtrl* ctrl, int64_t iteration0, int64_t steps_base, int set) {
+    void fl_sample(const StepCtrl* ctrl, int set) {
         FlowArgs<T> A{};
         fl_fill(A, set);
-        A.ctrl = ctrl; A.iteration0 = iteration0; A.steps_base = steps_base;
+        A.step = step_record(OBS_FL, ctrl);
         // (a slab that holds no row still writes its record — zeros under the step's header — for the handle to add: one workgroup does)
         if (N <= fl_small_rows || N <= 0) hipLaunchKernelGGL(k_fl_small<T>, dim3(1), dim3(kFlBlock), 0, stream, A);
         else {
@@ -2026,7 +2025,6 @@ struct Engine final : EngineBase {
         HC(hipStreamSynchronize(stream));
         en_mask = type_mask;
     }
-    // queued behind the corrector of a step; `set`: the state set that corrector wrote
     void en_update(const StepCtrl* ctrl, int set) {
         if (N <= 0) return;
         EnvelopeArgs<T> A{};
@@ -2129,7 +2127,6 @@ struct Engine final : EngineBase {
         HC(hipStreamSynchronize(stream));
         mp_on = true;
     }
-    // queued behind the corrector of a step; `set`: the state set that corrector wrote
     void mp_update(const StepCtrl* ctrl, int set) {
         if (N <= 0) return;
         MapArgs<T> A{};
@@ -2184,17 +2181,14 @@ struct Engine final : EngineBase {
     // One launch per kind behind every corrector; the records of a batch go where the probes' go.  The tracked rows are found through
     // tr_map[tr_cur][prow[i]] (row of the last permutation epoch → slot, −1: not tracked), composed in sphmi_download_permutation like
     // the envelopes' map; the drifters own their positions (tr_x), which move whether or not anybody reads the series.
-    bool tr_on = false;                        // off: no step launches anything for it
     int tr_np = 0, tr_nd = 0;
     double tr_min_weight = 0.0;
     DeviceBuf<int> tr_rows;                    // enable: the tracked rows as the caller named them
     DeviceBuf<int> tr_map[2];                  // [tr_cur] is live, the other one grows at the first permutation
     int tr_cur = 0;
     DeviceBuf<double> tr_x;                    // 3 doubles per drifter
-    StepLog tr_log;
-    StepSeries tr_series;                      // payload: kTrParticleValues per tracked particle, then kTrDrifterValues per drifter, as recorded
-    void tr_release() { tr_rows.free(); tr_map[0].free(); tr_map[1].free(); tr_x.free(); tr_log.release(); tr_np = tr_nd = 0; tr_cur = 0; }
-    void tr_disable() { observer_off(tr_on, tr_series, &Engine::tr_release); }
+    void tr_release() { tr_rows.free(); tr_map[0].free(); tr_map[1].free(); tr_x.free(); log[OBS_TR].release(); tr_np = tr_nd = 0; tr_cur = 0; }
+    void tr_disable() { observer_off(OBS_TR, &Engine::tr_release); }
     void tracers_enable(int32_t n_particles, const int64_t* rows, int32_t n_drifters, const double* positions, double min_weight, int64_t capacity_steps) override {
         require_uploaded("sphmi_tracers_enable");
         if (dd_slab) throw EngineError(SPHMI_ERR_STATE, "sphmi_tracers_enable: single-device handles only");
@@ -2206,8 +2200,8 @@ struct Engine final : EngineBase {
             throw EngineError(SPHMI_ERR_STATE, "sphmi_tracers_enable: handles with H < h are not served (the candidate cells of a drifter are laid out for H + h <= 2H)");
         auto no_memory = [&](size_t bytes) { return text("sphmi_tracers_enable: no device memory for the tracers of %lld rows (%zu bytes)", (long long)N, bytes); };
         try {
-            const int record = kGfHeader + kTrParticleValues * n_particles + kTrDrifterValues * n_drifters;
-            tr_log.alloc(record, record);
+            const int record = kStepHeader + kTrParticleValues * n_particles + kTrDrifterValues * n_drifters;
+            log[OBS_TR].alloc(record, record);
             if (n_particles > 0) {
                 std::vector<int> r32((size_t)n_particles);
                 for (int s = 0; s < n_particles; ++s) r32[(size_t)s] = (int)rows[s];
@@ -2229,29 +2223,26 @@ struct Engine final : EngineBase {
             HC(hipStreamSynchronize(stream));
         } catch (...) { tr_release(); throw; }
         tr_np = n_particles; tr_nd = n_drifters; tr_min_weight = min_weight;
-        tr_series.reset(kTrParticleValues * n_particles + kTrDrifterValues * n_drifters, capacity_steps);
-        tr_on = true;
+        obs[OBS_TR].series.reset(kTrParticleValues * n_particles + kTrDrifterValues * n_drifters, capacity_steps);
+        obs[OBS_TR].on = true;
     }
-    // queued behind the corrector of a step; `set`: the state set that corrector wrote
-    void tr_sample(const StepCtrl* ctrl, int64_t iteration0, int64_t steps_base, int set) {
+    void tr_sample(const StepCtrl* ctrl, int set) {
         if (tr_np > 0 && N > 0) {
             TracerParticleArgs<T> A{};
-            A.ctrl = ctrl; A.pk0 = pk0[set]; A.pk1 = pk1[set]; A.half0 = pk0[iH]; A.comp = comp[cur];
-            A.prow = prow[cur]; A.slot_of_record = tr_map[tr_cur].p; A.log = tr_log.d.p;
-            A.iteration0 = iteration0; A.steps_base = steps_base;
+            A.step = step_record(OBS_TR, ctrl); A.pk0 = pk0[set]; A.pk1 = pk1[set]; A.half0 = pk0[iH]; A.comp = comp[cur];
+            A.prow = prow[cur]; A.slot_of_record = tr_map[tr_cur].p;
             A.rho0 = (T)cfg.rho0; A.inv_rho0 = (T)(1.0 / cfg.rho0); A.Cbe = cbe();
-            A.n_particles = tr_np; A.N = N; A.D = D; A.record = tr_log.record_doubles; A.slots = StepLog::slots;
+            A.n_particles = tr_np; A.N = N; A.D = D;
             hipLaunchKernelGGL(k_tr_particles<T>, dim3((N + kTrBlock - 1) / kTrBlock), dim3(kTrBlock), 0, stream, A);
         }
         if (tr_nd > 0) {
             TracerDrifterArgs<T> A{};
-            A.s.ctrl = ctrl; A.s.pk0 = pk0[set]; A.s.pk1 = pk1[set]; A.s.half0 = pk0[iH]; A.s.comp = comp[cur];
-            A.s.type = nullptr; A.s.cstart = cstart; A.s.pos = tr_x.p; A.s.log = tr_log.d.p; A.s.g = grid;
-            A.s.iteration0 = iteration0; A.s.steps_base = steps_base;
+            A.s.step = step_record(OBS_TR, ctrl); A.s.pk0 = pk0[set]; A.s.pk1 = pk1[set]; A.s.half0 = pk0[iH]; A.s.comp = comp[cur];
+            A.s.type = nullptr; A.s.cstart = cstart; A.s.pos = tr_x.p; A.s.g = grid;
             fill_sample_consts(A.s);
-            A.s.n_probes = tr_nd; A.s.N = N; A.s.D = D; A.s.kernel = cfg.kernel; A.s.record = tr_log.record_doubles; A.s.slots = StepLog::slots;
+            A.s.n_probes = tr_nd; A.s.N = N; A.s.D = D; A.s.kernel = cfg.kernel;
             A.X = tr_x.p; A.min_weight = tr_min_weight;
-            A.value0 = kGfHeader + kTrParticleValues * tr_np; A.write_header = tr_np > 0 && N > 0 ? 0 : 1;
+            A.value0 = kStepHeader + kTrParticleValues * tr_np; A.write_header = tr_np > 0 && N > 0 ? 0 : 1;
             hipLaunchKernelGGL(k_tr_drift<T>, dim3((tr_nd + 3) / 4), dim3(256), 0, stream, A);
         }
         HC(hipGetLastError());
@@ -2259,8 +2250,8 @@ struct Engine final : EngineBase {
     void tracers_read(int64_t capacity, int64_t* iteration_out, double* time, double* dt, double* particles, double* drifters, double* drifter_positions,
                       int64_t* n_out, int64_t* n_dropped) override {
         require_uploaded("sphmi_tracers_read");
-        if (!tr_on) throw EngineError(SPHMI_ERR_STATE, "sphmi_tracers_read: tracers are not enabled (sphmi_tracers_enable)");
-        tr_series.read("sphmi_tracers_read", capacity, iteration_out, time, dt, n_out, n_dropped,
+        if (!obs[OBS_TR].on) throw EngineError(SPHMI_ERR_STATE, "sphmi_tracers_read: tracers are not enabled (sphmi_tracers_enable)");
+        obs[OBS_TR].series.read("sphmi_tracers_read", capacity, iteration_out, time, dt, n_out, n_dropped,
                        [&](int64_t k, const double* v) { deliver_tracers(tr_np, tr_nd, k, v, particles, drifters); });
         if (drifter_positions && tr_nd > 0) {          // X after the last executed step: the series alone ends one move short of it
             HC(hipSetDevice(cfg.device));

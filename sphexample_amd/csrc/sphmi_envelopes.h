@@ -29,7 +29,7 @@
 //   k_en_fill     enable: the start record into every row's slot, the window header { 0 steps, t_begin, t_end = t_begin, 0 }
 //   k_en_update   behind the corrector of every queued step, one row per lane; returns at once when the step was cancelled
 //                 (StepCtrl::active == 0).  Two packets of the corrector's output set (the type off the sign of the ρ·s slot, as
-//                 fl_load reads it; v), the density slot of the half-step set (P), prow[i], base[…] — both indices range-tested, as
+//                 row_type of sphmi_step_record.h reads it; v), the density slot of the half-step set (P), prow[i], base[…] — both indices range-tested, as
 //                 the column kernels test them: a corrupted column must not become a wild store — then the record with four 16-byte
 //                 loads and at most four 16-byte stores (the pairs { p_max, t_p_max } and { speed2_max, t_arrival } only when they
 //                 changed: late in a run they rarely do).  A row whose Type is not selected is left alone and keeps the start
@@ -93,7 +93,7 @@ __global__ void __launch_bounds__(kEnBlock) k_en_update(const EnvelopeArgs<T> A)
     }
     if (i >= (long long)A.N) return;
     const V4 q0 = A.pk0[i];
-    // plain handles: Fluid off the sign of the ρ·s slot (fl_load, sphmi_flow.h); Fixed against Moving needs the type byte
+    // plain handles: Fluid off the sign of the ρ·s slot (row_type, sphmi_step_record.h); Fixed against Moving needs the type byte
     const unsigned ty = q0.w > T(0) ? 1u : (A.type ? (unsigned)A.type[i] & 3u : 2u);
     if (!((A.type_mask >> ty) & 1u)) return;
     const unsigned e = (unsigned)A.prow[i];

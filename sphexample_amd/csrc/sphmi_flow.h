@@ -2,10 +2,9 @@
 // a region holds and how much went in or out — the discharge through a section, overtopping, the filling curve of a compartment.
 //
 // A box is axis-aligned and half-open: row i is INSIDE box b iff lo[b][d] <= x_i[d] < hi[b][d] for every d < dims, compared in fp64
-// on the Position doubles sphmi_download would deliver (fp32 handles: record + low word, formed exactly as bg_terms forms x,
-// sphmi_budgets.h).  -inf and +inf are bounds like any other; a 2-D handle carries z = 0 and (-inf, +inf) on the third axis, so
-// the same three comparisons serve both.  Only rows the handle owns with Type == Fluid count — dead rows and ghost copies of a
-// slab handle do not, recognised as in bg_terms.
+// on the Position doubles sphmi_download would deliver (delivered_coord, sphmi_step_record.h).  -inf and +inf are bounds like any
+// other; a 2-D handle carries z = 0 and (-inf, +inf) on the third axis, so the same three comparisons serve both.  Only rows that
+// count do (owned_fluid, the same header: the handle's own, Type == Fluid).
 //
 // The raw record of an EXECUTED step, kFlValues doubles per box, every slot a sum over the counting rows:
 //     0        n_after    rows inside on the state a download delivers directly after the step
@@ -24,7 +23,7 @@
 //     k_fl_partial   behind the corrector, on its output set; block b = rows 256·b … 256·b + 255, one row per lane.  Per box (a run-
 //                    time loop, the bounds in the kernel arguments, nothing indexed per lane) a wave forms its three counts as
 //                    __popcll(__ballot(...)) of the after / entered / left predicates, and the four floating-point sums by the
-//                    budgets' __shfl_xor butterfly — only when the after-ballot is non-zero: a skipped box contributes +0.0, which
+//                    butterfly wave_sum — only when the after-ballot is non-zero: a skipped box contributes +0.0, which
 //                    is what the butterfly of sixty-four +0.0 identities yields, so skipping never changes a bit.  Then waves
 //                    0, 1, 2, 3 in that order → partial[b][box][kFlValues].
 //     k_fl_final     one workgroup of 64 per box: lane l takes the partials l, l + 64, … in order, then the same butterfly; box 0
@@ -34,15 +33,14 @@
 // The three samplers return at once when the step was cancelled (StepCtrl::active == 0).  No atomics; the order of every sum follows
 // from the row order alone.  Every term is formed with contraction off: a host forms the same doubles from a download.
 //
-// Record (kGfHeader + kFlValues · n_boxes doubles): { iteration (int64 bits), TotalTime at the end of the step, Δt, the boxes' values },
-// at slot steps_done − 1 − (steps done when the batch was queued) of the batch's log, as bg_write_record places it.
+// Record (StepRecord, sphmi_step_record.h; kStepHeader + kFlValues · n_boxes doubles): the header, then the boxes' values.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "sphmi_kernels.h"
-#include "sphmi_rebuild.h"      // kTypeMask, kGhostMask
-#include "sphmi_series.h"       // kMaxFlowBoxes, kFlValues, kGfHeader
+#include "sphmi_series.h"       // kMaxFlowBoxes, kFlValues
+#include "sphmi_step_record.h"  // StepRecord, wave_sum, the delivered row
 
 namespace sphmi {
 
@@ -59,16 +57,13 @@ struct FlowBoxes {
 
 template <class T> struct FlowArgs {
     using V4 = typename Vec4<T>::type;
-    const StepCtrl* ctrl;                // the block this step's corrector read (k_fl_mark: unused)
+    StepRecord step;                     // (k_fl_mark: unused)
     Half<const V4> pk0, pk1;             // k_fl_mark: the current set; the samplers: the corrector's output set
     const V4* comp;                      // fp32 handles: low words of position and density (null: none)
     const uint8_t* type;                 // slab handles: the type byte (ghost copies, dead rows); null on plain handles
     uint16_t* mark;                      // one per row: bit b = counted and inside box b at the start of the step
     double* partial;                     // n_boxes × kFlValues doubles per block of 256 rows
-    double* log;                         // `slots` records of kGfHeader + kFlValues · n_boxes doubles
-    long long iteration0;                // SimMetaData.Iteration when this sphmi_advance began
-    long long steps_base;                // steps done when the batch of this step was queued
-    int N, D, nblk, slots;               // nblk = ⌈N / 256⌉
+    int N, D, nblk;                      // nblk = ⌈N / 256⌉
     FlowBoxes box;
 };
 
@@ -88,19 +83,17 @@ __device__ __forceinline__ FlowRow<T> fl_load(const Args& A, long long i, bool f
     r.counts = 0;
     if (i >= (long long)A.N) return r;
     const V4 q0 = A.pk0[i];
-    const uint8_t ty = A.type ? A.type[i] : (uint8_t)(q0.w > T(0) ? 1 : 2);       // plain handles: Fluid off the sign of the ρ·s slot
-    if ((ty & kTypeMask) != 1 || (ty & kGhostMask)) return r;                     // SPHMI_FLUID, owned
+    if (!owned_fluid(row_type(A.type, i, q0.w))) return r;
     V4 lw;
     lw.x = lw.y = lw.z = lw.w = T(0);
     if (sizeof(T) == 4 && A.comp) lw = A.comp[i];
     const bool three = A.D == 3;
     r.counts = 1;
-    r.x = (double)q0.x + (double)lw.x; r.y = (double)q0.y + (double)lw.y; r.z = three ? (double)q0.z + (double)lw.z : 0.0;
+    r.x = delivered_coord(q0.x, lw.x); r.y = delivered_coord(q0.y, lw.y); r.z = three ? delivered_coord(q0.z, lw.z) : 0.0;
     if (full) {
         const V4 q1 = A.pk1[i];
-        const double rho = (double)(q0.w < T(0) ? -q0.w : q0.w) + (double)lw.w;
         r.vx = (double)q1.x; r.vy = (double)q1.y; r.vz = three ? (double)q1.z : 0.0;
-        r.inv_rho = 1.0 / rho;
+        r.inv_rho = 1.0 / delivered_density(q0.w, lw.w);
     }
     return r;
 }
@@ -109,13 +102,6 @@ template <class T>
 __device__ __forceinline__ bool fl_inside(const FlowArgs<T>& A, const FlowRow<T>& r, int b) {
     return r.counts && A.box.lo[b][0] <= r.x && r.x < A.box.hi[b][0] && A.box.lo[b][1] <= r.y && r.y < A.box.hi[b][1] &&
            A.box.lo[b][2] <= r.z && r.z < A.box.hi[b][2];
-}
-// a sum over the lanes of a wave, the budgets' fixed butterfly: every lane ends up with the same bits
-__device__ __forceinline__ double fl_wave(double v) {
-#pragma clang fp contract(off)
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v = v + __shfl_xor(v, d, 64);
-    return v;
 }
 
 // the first launch of a step: the boxes every counting row is inside of NOW
@@ -142,8 +128,8 @@ __device__ __forceinline__ void fl_block_reduce(const FlowArgs<T>& A, const Flow
         const double n_in = (double)__popcll(in), n_entered = (double)__popcll(__ballot(after && !was)), n_left = (double)__popcll(__ballot(was && !after));
         double s1 = 0.0, sx = 0.0, sy = 0.0, sz = 0.0;
         if (in != 0ull) {       // (wave-uniform; an empty wave would add sixty-four +0.0: the same +0.0)
-            s1 = fl_wave(after ? r.inv_rho : 0.0);
-            sx = fl_wave(after ? r.vx : 0.0); sy = fl_wave(after ? r.vy : 0.0); sz = fl_wave(after ? r.vz : 0.0);
+            s1 = wave_sum(after ? r.inv_rho : 0.0);
+            sx = wave_sum(after ? r.vx : 0.0); sy = wave_sum(after ? r.vy : 0.0); sz = wave_sum(after ? r.vz : 0.0);
         }
         if (lane == 0) {
             double* w = s_w[wave] + b * kFlValues;
@@ -160,8 +146,8 @@ template <class T>
 __device__ __forceinline__ void fl_write_box(const FlowArgs<T>& A, const StepCtrl& c, const double* partial, int nblk, int b) {
 #pragma clang fp contract(off)
     const int lane = (int)threadIdx.x & 63;
-    const long long slot = c.steps_done - 1 - A.steps_base;
-    if (slot < 0 || slot >= (long long)A.slots) return;
+    const long long slot = A.step.slot(c);
+    if (slot < 0) return;
     double v[kFlValues];
 #pragma unroll
     for (int k = 0; k < kFlValues; ++k) v[k] = 0.0;
@@ -171,23 +157,19 @@ __device__ __forceinline__ void fl_write_box(const FlowArgs<T>& A, const StepCtr
         for (int k = 0; k < kFlValues; ++k) v[k] = v[k] + p[k];
     }
 #pragma unroll
-    for (int k = 0; k < kFlValues; ++k) v[k] = fl_wave(v[k]);
+    for (int k = 0; k < kFlValues; ++k) v[k] = wave_sum(v[k]);
     if (lane == 0) {
-        double* rec = A.log + (size_t)slot * (size_t)(kGfHeader + kFlValues * A.box.n);
-        if (b == 0) {
-            rec[0] = __longlong_as_double(A.iteration0 + c.steps_done);
-            rec[1] = c.total_time;
-            rec[2] = c.last_dt;
-        }
+        double* rec = A.step.at(slot);
+        if (b == 0) A.step.write_header(rec, c);
 #pragma unroll
-        for (int k = 0; k < kFlValues; ++k) rec[kGfHeader + b * kFlValues + k] = v[k];
+        for (int k = 0; k < kFlValues; ++k) rec[kStepHeader + b * kFlValues + k] = v[k];
     }
 }
 
 // any grid: workgroup w takes blocks w, w + gridDim.x, …
 template <class T>
 __global__ void __launch_bounds__(kFlBlock) k_fl_partial(const FlowArgs<T> A) {
-    if (!A.ctrl->active) return;
+    if (!A.step.ctrl->active) return;
     __shared__ double s_w[4][kMaxFlowBoxes * kFlValues];
     for (int b = (int)blockIdx.x; b < A.nblk; b += (int)gridDim.x) {
         const long long i = (long long)b * kFlBlock + (int)threadIdx.x;
@@ -199,14 +181,14 @@ __global__ void __launch_bounds__(kFlBlock) k_fl_partial(const FlowArgs<T> A) {
 // grid = n_boxes workgroups of one wave
 template <class T>
 __global__ void __launch_bounds__(64) k_fl_final(const FlowArgs<T> A) {
-    const StepCtrl c = *A.ctrl;
+    const StepCtrl c = *A.step.ctrl;
     if (!c.active || (int)blockIdx.x >= A.box.n) return;
     fl_write_box<T>(A, c, A.partial, A.nblk, (int)blockIdx.x);
 }
 // one workgroup: the blocks one after the other, the partials in LDS; wave w writes boxes w, w + 4, …
 template <class T>
 __global__ void __launch_bounds__(kFlBlock) k_fl_small(const FlowArgs<T> A) {
-    const StepCtrl c = *A.ctrl;
+    const StepCtrl c = *A.step.ctrl;
     if (!c.active) return;
     __shared__ double s_w[4][kMaxFlowBoxes * kFlValues];
     __shared__ double s_partial[kFlSmallBlocks * kMaxFlowBoxes * kFlValues];

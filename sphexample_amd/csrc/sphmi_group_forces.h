@@ -16,23 +16,23 @@
 //
 // The order of every sum is a function of the row lists alone — no atomics on floating-point values, nothing depends on the grid
 // of the launch, on the tile schedule or on timing — and k_gf_small adds in exactly the order of the two-stage pair.
-// All three return at once when the step was cancelled (StepCtrl::active == 0), like the pass kernels.  The record goes to slot
-// steps_done − 1 − (steps done when the batch was queued): cancelled steps leave no holes, re-queued steps no duplicates.
+// All three return at once when the step was cancelled (StepCtrl::active == 0), like the pass kernels.
 //
-// Record (kGfHeader + 3·n_groups doubles): { iteration (int64 bits), TotalTime at the end of the step, Δt, F[g][0..2] }; 2-D handles
-// write a zero third component.
+// Record (StepRecord, sphmi_step_record.h; kStepHeader + 3·n_groups doubles): the header, then F[g][0..2]; 2-D handles write a zero
+// third component.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "sphmi_kernels.h"
 #include "sphmi_rebuild.h"
-#include "sphmi_series.h"       // kMaxForceGroups, kGfHeader
+#include "sphmi_series.h"       // kMaxForceGroups
+#include "sphmi_step_record.h"  // StepRecord, wave_sum
 
 namespace sphmi {
 
 constexpr int kGfChunk = 256;            // list entries per partial sum = threads of the workgroup that forms it
-constexpr int kGfRecordMax = kGfHeader + 3 * kMaxForceGroups;
+constexpr int kGfRecordMax = kStepHeader + 3 * kMaxForceGroups;
 constexpr int kGfSmallChunks = 96;       // k_gf_small keeps the partials in LDS: rows / kGfChunk + n_groups chunks at most
 constexpr int kGfSmallRows = (kGfSmallChunks - kMaxForceGroups) * kGfChunk;
 
@@ -126,13 +126,6 @@ __global__ void __launch_bounds__(256) k_gf_fill(const unsigned long long* __res
     if ((unsigned)at < (unsigned)list_cap) list[at] = i;
 }
 
-// Σ over the lanes of a wave, a fixed butterfly: every lane ends up with the same bits
-__device__ __forceinline__ double gf_wave_sum(double v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
-    return v;
-}
-
 // the workgroup's 256 threads form the sum of chunk c; thread 0 returns it (s_w: 4 × 3 doubles of LDS, free again on return)
 template <class T>
 __device__ __forceinline__ void gf_chunk_sum(const typename Vec4<T>::type* __restrict__ acc, const int* __restrict__ list,
@@ -146,7 +139,7 @@ __device__ __forceinline__ void gf_chunk_sum(const typename Vec4<T>::type* __res
         const unsigned row = (unsigned)list[(size_t)c * kGfChunk + tid];
         if (row < (unsigned)N) { const auto a = acc[row]; x = (double)a.x; y = (double)a.y; z = (double)a.z; }
     }
-    x = gf_wave_sum(x); y = gf_wave_sum(y); z = gf_wave_sum(z);
+    x = wave_sum(x); y = wave_sum(y); z = wave_sum(z);
     if (lane == 0) { s_w[wave][0] = x; s_w[wave][1] = y; s_w[wave][2] = z; }
     __syncthreads();
     if (tid == 0)
@@ -155,36 +148,29 @@ __device__ __forceinline__ void gf_chunk_sum(const typename Vec4<T>::type* __res
 }
 
 struct GroupSampleArgs {
-    const StepCtrl* ctrl;            // the block this step's corrector read
+    StepRecord step;
     const int* list;
     const GroupListMeta* meta;
     double* partial;                 // 3 doubles per chunk
-    double* log;                     // kGfBatch records of `record` doubles
-    long long iteration0;            // SimMetaData.Iteration when this sphmi_advance began (StepCtrl::steps_done counts from there)
-    long long steps_base;            // steps done when the batch of this step was queued
     double m0;
-    int n_groups, N, D, record, slots;
+    int n_groups, N, D;
 };
 
 // one wave: the record of this step from the partials (global memory or LDS)
 __device__ __forceinline__ void gf_write_record(const GroupSampleArgs& A, const StepCtrl& c, const double* partial, const GroupListMeta* meta) {
     const int lane = (int)threadIdx.x & 63;
-    const long long slot = c.steps_done - 1 - A.steps_base;
-    if (slot < 0 || slot >= (long long)A.slots) return;
-    double* rec = A.log + (size_t)slot * (size_t)A.record;
-    if (lane == 0) {
-        rec[0] = __longlong_as_double(A.iteration0 + c.steps_done);
-        rec[1] = c.total_time;
-        rec[2] = c.last_dt;
-    }
+    const long long slot = A.step.slot(c);
+    if (slot < 0) return;
+    double* rec = A.step.at(slot);
+    if (lane == 0) A.step.write_header(rec, c);
     for (int g = 0; g < A.n_groups; ++g) {
         double x = 0.0, y = 0.0, z = 0.0;
         for (int ch = meta->chunk0[g] + lane; ch < meta->chunk0[g + 1]; ch += 64) { x += partial[3 * ch]; y += partial[3 * ch + 1]; z += partial[3 * ch + 2]; }
-        x = gf_wave_sum(x); y = gf_wave_sum(y); z = gf_wave_sum(z);
+        x = wave_sum(x); y = wave_sum(y); z = wave_sum(z);
         if (lane == 0) {
-            rec[kGfHeader + 3 * g] = A.m0 * x;
-            rec[kGfHeader + 3 * g + 1] = A.m0 * y;
-            rec[kGfHeader + 3 * g + 2] = A.D == 3 ? A.m0 * z : 0.0;
+            rec[kStepHeader + 3 * g] = A.m0 * x;
+            rec[kStepHeader + 3 * g + 1] = A.m0 * y;
+            rec[kStepHeader + 3 * g + 2] = A.D == 3 ? A.m0 * z : 0.0;
         }
     }
 }
@@ -192,7 +178,7 @@ __device__ __forceinline__ void gf_write_record(const GroupSampleArgs& A, const 
 // any grid: workgroup b takes chunks b, b + gridDim.x, …
 template <class T>
 __global__ void __launch_bounds__(kGfChunk) k_gf_partial(const typename Vec4<T>::type* __restrict__ acc, GroupSampleArgs A, int max_chunks) {
-    if (!A.ctrl->active) return;
+    if (!A.step.ctrl->active) return;
     __shared__ double s_w[4][3];
     const int nchunk = min(A.meta->chunk0[A.n_groups], max_chunks);
     for (int c = (int)blockIdx.x; c < nchunk; c += (int)gridDim.x) {
@@ -202,14 +188,14 @@ __global__ void __launch_bounds__(kGfChunk) k_gf_partial(const typename Vec4<T>:
     }
 }
 __global__ void __launch_bounds__(64) k_gf_final(GroupSampleArgs A) {
-    const StepCtrl c = *A.ctrl;
+    const StepCtrl c = *A.step.ctrl;
     if (!c.active) return;
     gf_write_record(A, c, A.partial, A.meta);
 }
 // one workgroup: the chunks one after the other, the partials in LDS, wave 0 writes the record
 template <class T>
 __global__ void __launch_bounds__(kGfChunk) k_gf_small(const typename Vec4<T>::type* __restrict__ acc, GroupSampleArgs A) {
-    const StepCtrl c = *A.ctrl;
+    const StepCtrl c = *A.step.ctrl;
     if (!c.active) return;
     __shared__ double s_w[4][3];
     __shared__ double s_partial[3 * kGfSmallChunks];

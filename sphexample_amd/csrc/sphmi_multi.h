@@ -912,10 +912,7 @@ struct MultiEngine final : EngineBase {
         const int64_t N = cfg.n_particles;
         n_total = N;
         col_data.clear(); col_width.clear(); col_base.clear();     // a new particle set: the attached columns described the old one
-        gf_on = false; gf_series.reset(0, 0);                      // … and the selected groups (the slab engines are made anew below)
-        pr_on = false; pr_series.reset(0, 0);                      // … and the probes
-        bg_on = false; bg_series.reset(0, 0);                      // … and the budgets
-        fl_on = false; fl_series.reset(0, 0);                      // … and the control boxes
+        for (auto& o : obs) { o.on = false; o.series.reset(0, 0); }      // … and so did every observer (the slab engines are made anew below)
         SlabSetup S;
         plan_slabs(cfg, position, ghost_points, N, world, cfg.slab_axis - 1, given_plan.world() == world ? &given_plan : nullptr, 1.6, S);
         axis = S.axis; halo_width = S.halo_width; plan = S.plan;
@@ -1415,24 +1412,19 @@ struct MultiEngine final : EngineBase {
                 if (dx_rate > 0.0) batch = std::max(1, std::min(batch, (int)std::ceil((cfg.h - dxl) / dx_rate) + (fresh ? 1 : 0)));
                 if (max_steps >= 0) batch = (int)std::max<int64_t>(1, std::min<int64_t>(batch, max_steps - steps));
                 const double dx0 = dxl; const int64_t steps0 = steps;
+                for (auto& r : R) r.e->set_batch_clock(iteration, steps0);
                 for (int k = 0; k < batch; ++k) {
                     reductions_and_control();
                     if (have_halo) {                                     // before the first rebuild there is no ghost layer to exchange
                         // the boxes every owned row is inside of BEFORE the step: the corrector updates the low words in place (sphmi_flow.h)
-                        if (fl_on) for (auto& r : R) { HC(hipSetDevice(r.device)); r.e->fl_mark(); }
+                        for (auto& r : R) { HC(hipSetDevice(r.device)); r.e->fl_mark(); }
                         pass(1); pass(2);
-                        // every slab sums its OWNED rows behind its corrector (the edge tiles have joined `main`)
-                        if (gf_on) for (auto& r : R) { HC(hipSetDevice(r.device)); r.e->gf_sample(r.e->ctrl_d, iteration, steps0); }
-                        // … and the kernel sums at the probes (the corrector's output set is iA here: dd_pass has rotated the sets)
-                        if (pr_on) for (auto& r : R) { HC(hipSetDevice(r.device)); r.e->pr_sample(r.e->ctrl_d, iteration, steps0, r.e->iA); }
-                        if (bg_on) for (auto& r : R) { HC(hipSetDevice(r.device)); r.e->bg_sample(r.e->ctrl_d, iteration, steps0, r.e->iA); }
-                        if (fl_on) for (auto& r : R) { HC(hipSetDevice(r.device)); r.e->fl_sample(r.e->ctrl_d, iteration, steps0, r.e->iA); }
+                        // every slab samples its OWNED rows behind its corrector (the edge tiles have joined `main`; the corrector's output
+                        // set is iA here: dd_pass has rotated the sets)
+                        for (auto& r : R) { HC(hipSetDevice(r.device)); r.e->observe_step(r.e->ctrl_d, r.e->iA); }
                     }
                 }
-                if (gf_on) for (auto& r : R) { HC(hipSetDevice(r.device)); r.e->gf_log.fetch(batch, r.e->stream); }
-                if (pr_on) for (auto& r : R) { HC(hipSetDevice(r.device)); r.e->pr_log.fetch(batch, r.e->stream); }
-                if (bg_on) for (auto& r : R) { HC(hipSetDevice(r.device)); r.e->bg_log.fetch(batch, r.e->stream); }
-                if (fl_on) for (auto& r : R) { HC(hipSetDevice(r.device)); r.e->fl_log.fetch(batch, r.e->stream); }
+                for (auto& r : R) { HC(hipSetDevice(r.device)); r.e->fetch_logs(batch); }
                 for (auto& r : R) {
                     HC(hipSetDevice(r.device)); sphmi_dd_control s{}; r.e->dd_ctrl_sync(&s);
                     if (&r == &R[0]) st = s;
@@ -1447,10 +1439,7 @@ struct MultiEngine final : EngineBase {
                     }
                 }
                 steps = st.steps_done;
-                if (gf_on) collect_records(gf_series, &Engine<T>::gf_log, kGfHeader, "group forces", steps - steps0);
-                if (pr_on) collect_records(pr_series, &Engine<T>::pr_log, kPrHeader, "probes", steps - steps0);
-                if (bg_on) collect_records(bg_series, &Engine<T>::bg_log, kGfHeader, "budgets", steps - steps0, bg_rule);
-                if (fl_on) collect_records(fl_series, &Engine<T>::fl_log, kGfHeader, "flow", steps - steps0);
+                for (int k = 0; k < OBS_COUNT; ++k) if (obs[k].on) collect_records(obs[k], k, steps - steps0);
                 total_time = st.total_time; last_dt = st.last_dt; dxl = st.delta_x;
                 const int64_t grown = (steps - steps0) + (st.need_rebuild ? 1 : 0) - (fresh && steps > steps0 ? 1 : 0);
                 if (steps > steps0) fresh = false;
@@ -1732,41 +1721,38 @@ struct MultiEngine final : EngineBase {
     // every slab engine records the sums over the rows it owns — a row sits in exactly one slab, ghost copies do not count — and
     // the handle adds the slabs' records of a step in slab order, in fp64: the forces, and the RAW sums of the probes (the read
     // normalises).  The series are EngineBase's.
+    template <class F> void enable_on_slabs(Obs k, bool on, F&& enable) {
+        obs[k].on = false; obs[k].series.reset(0, 0);
+        for (auto& r : R) enable(*r.e);
+        obs[k].on = on;
+    }
     void gf_enable_device(int32_t n_groups, const uint64_t* markers) override {
-        gf_on = false; gf_series.reset(0, 0);
-        for (auto& r : R) r.e->gf_enable_device(n_groups, markers);
-        gf_on = n_groups > 0;
+        enable_on_slabs(OBS_GF, n_groups > 0, [&](Engine<T>& e) { e.gf_enable_device(n_groups, markers); });
     }
     void pr_enable_device(int32_t n_probes, const double* positions) override {
-        pr_on = false; pr_series.reset(0, 0);
-        for (auto& r : R) r.e->pr_enable_device(n_probes, positions);
-        pr_on = n_probes > 0;
+        enable_on_slabs(OBS_PR, n_probes > 0, [&](Engine<T>& e) { e.pr_enable_device(n_probes, positions); });
     }
     // The budgets of the fluid (sphmi_budgets.h): every slab reduces the rows it owns, the handle combines the slabs' raw records of a
     // step in slab order — sums add, extremes take min or max (bg_rule); the read forms the delivered values from the combined record.
     void bg_enable_device(bool on) override {
-        bg_on = false; bg_series.reset(0, 0);
-        for (auto& r : R) r.e->bg_enable_device(on);
-        bg_on = on;
+        enable_on_slabs(OBS_BG, on, [&](Engine<T>& e) { e.bg_enable_device(on); });
     }
     // The flow through control boxes (sphmi_flow.h): every slab marks and samples the rows it owns — migration happens in the collective
     // rebuild, between steps, so a row's start state and end state lie in the same slab — and the handle adds the slabs' records of a
     // step in slab order: every slot is a sum.
     void fl_enable_device(int32_t n_boxes, const double* lo, const double* hi) override {
-        fl_on = false; fl_series.reset(0, 0);
-        for (auto& r : R) r.e->fl_enable_device(n_boxes, lo, hi);
-        fl_on = n_boxes > 0;
+        enable_on_slabs(OBS_FL, n_boxes > 0, [&](Engine<T>& e) { e.fl_enable_device(n_boxes, lo, hi); });
     }
-    // after the synchronisation of a batch: the records of its `executed` steps, slab by slab (every slot a sum, or combined by `rule`)
-    void collect_records(StepSeries& series, typename Engine<T>::StepLog Engine<T>::*log, int header, const char* what, int64_t executed,
-                         int (*rule)(int) = nullptr) {
-        for (int64_t k = 0; k < executed; ++k) {
-            StepSeries::Sample s = StepSeries::decode((R[0].e.get()->*log).record(k), header, series.values);
+    // after the synchronisation of a batch: the records of its `executed` steps in the slabs' logs `k`, slab by slab (every slot a sum,
+    // or combined by the observer's rule)
+    void collect_records(SeriesObserver& o, int k, int64_t executed) {
+        for (int64_t j = 0; j < executed; ++j) {
+            StepSeries::Sample s = StepSeries::decode(R[0].e->log[k].record(j), kStepHeader, o.series.values);
             for (size_t q = 1; q < R.size(); ++q) {
-                const StepSeries::Sample o = StepSeries::decode((R[q].e.get()->*log).record(k), header, series.values);
-                if (rule) StepSeries::combine(s, o, what, rule); else StepSeries::add(s, o, what);
+                const StepSeries::Sample other = StepSeries::decode(R[q].e->log[k].record(j), kStepHeader, o.series.values);
+                if (o.rule) StepSeries::combine(s, other, o.what, o.rule); else StepSeries::add(s, other, o.what);
             }
-            series.push(std::move(s));
+            o.series.push(std::move(s));
         }
     }
     // Kernel sums on a lattice (sphmi_field_grid.h): every slab samples the WHOLE lattice over the rows it owns — the type byte keeps

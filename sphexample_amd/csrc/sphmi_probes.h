@@ -10,8 +10,7 @@
 // The RAW sums are recorded; the host normalises at read time (a multi-device handle adds the slabs' sums first).
 //
 // k_probe_sample — one wave per probe, queued behind every corrector (Engine::pr_sample), like k_gf_* (sphmi_group_forces.h):
-// returns at once when the step was cancelled, writes slot steps_done − 1 − (steps done when the batch was queued) of the
-// batch's log, which travels with the control block of the batch.
+// returns at once when the step was cancelled, writes this step's record of the batch's log (StepRecord, sphmi_step_record.h).
 //
 // EXACT, NOT STALE.  The pair loop reproduces the reference's stale cell lists (quirk Q1); a probe has no such quirk to keep.  The rows
 // are still found through `cstart`, i.e. through the cell every row was hashed into at the last rebuild, so the candidate cells
@@ -38,41 +37,37 @@
 // A probe outside the dense grid clamps to empty ranges: S = 0, n = 0.  Dead rows and ghost copies of a slab handle (type byte)
 // are skipped; plain handles read Fluid off the sign of the ρ·s slot.
 //
-// Record (kPrHeader + kPrValues · n_probes doubles): { iteration (int64 bits), TotalTime at the end of the step, Δt,
-// { S, SP, Sρ, Sv[0..2], n }[p] }; 2-D handles write a zero third velocity component.
+// Record (kStepHeader + kPrValues · n_probes doubles): the header, then { S, SP, Sρ, Sv[0..2], n }[p]; 2-D handles write a zero third
+// velocity component.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "sphmi_kernels.h"
 #include "sphmi_rebuild.h"
-#include "sphmi_group_forces.h"
 #include "sphmi_series.h"       // kMaxProbes, kPrValues
+#include "sphmi_step_record.h"  // StepRecord, wave_sum
 
 namespace sphmi {
 
-constexpr int kPrHeader = kGfHeader;     // the same three doubles in front of a record
-constexpr int kPrRecordMax = kPrHeader + kPrValues * kMaxProbes;
+constexpr int kPrRecordMax = kStepHeader + kPrValues * kMaxProbes;
 constexpr int kPrMaxRows = 25;           // (cy, cz) pairs of a probe: ≤ 5 × 5 — H + h ≤ 2H spans at most five cells per axis
 constexpr int kPrInFlight = 4;           // jobs whose loads are issued before the first is used
 
 template <class T> struct ProbeSampleArgs {
     using V4 = typename Vec4<T>::type;
-    const StepCtrl* ctrl;                // the block this step's corrector read
+    StepRecord step;
     Half<const V4> pk0, pk1;             // the corrector's output set
     Half<const V4> half0;                // the half-step set: Pressure!(ρₙ⁺), src/SPHCellList.jl:789
     const V4* comp;                      // fp32 handles: low words of position and density (null: none)
     const uint8_t* type;                 // slab handles: the type byte (ghost copies, dead rows); null on plain handles
     const int* cstart;
     const double* pos;                   // 3 doubles per probe
-    double* log;                         // `slots` records of `record` doubles
     GridDesc g;
-    long long iteration0;                // SimMetaData.Iteration when this sphmi_advance began
-    long long steps_base;                // steps done when the batch of this step was queued
     double H_inv, H2, h_inv, reach;      // reach = H + margin (above)
     double alphaD, m0;
     T rho0, inv_rho0, Cbe;
-    int n_probes, N, D, kernel, record, slots;
+    int n_probes, N, D, kernel;
 };
 
 // W(q) of src/SPHKernels.jl:75-78 (Wendland C2) and :89-92 (CubicSpline), fp64
@@ -174,30 +169,26 @@ __device__ __forceinline__ void pr_walk(const ProbeSampleArgs<T>& A, const doubl
             }
         }
     }
-    n = gf_wave_sum(n); S = gf_wave_sum(S); SP = gf_wave_sum(SP); Sr = gf_wave_sum(Sr);
-    Sx = gf_wave_sum(Sx); Sy = gf_wave_sum(Sy); Sz = gf_wave_sum(Sz);
+    n = wave_sum(n); S = wave_sum(S); SP = wave_sum(SP); Sr = wave_sum(Sr);
+    Sx = wave_sum(Sx); Sy = wave_sum(Sy); Sz = wave_sum(Sz);
 }
 
 template <class T>
 __global__ void __launch_bounds__(256) k_probe_sample(const ProbeSampleArgs<T> A) {
-    const StepCtrl c = *A.ctrl;
+    const StepCtrl c = *A.step.ctrl;
     if (!c.active) return;
-    const long long slot = c.steps_done - 1 - A.steps_base;
-    if (slot < 0 || slot >= (long long)A.slots) return;
+    const long long slot = A.step.slot(c);
+    if (slot < 0) return;
     const int lane = (int)threadIdx.x & 63;
     const int p = __builtin_amdgcn_readfirstlane((int)((blockIdx.x * blockDim.x + threadIdx.x) >> 6));
     if (p >= A.n_probes) return;
-    double* rec = A.log + (size_t)slot * (size_t)A.record;
-    if (p == 0 && lane == 0) {
-        rec[0] = __longlong_as_double(A.iteration0 + c.steps_done);
-        rec[1] = c.total_time;
-        rec[2] = c.last_dt;
-    }
+    double* rec = A.step.at(slot);
+    if (p == 0 && lane == 0) A.step.write_header(rec, c);
     const double xp[3] = {A.pos[3 * p], A.pos[3 * p + 1], A.D == 3 ? A.pos[3 * p + 2] : 0.0};
     double n, S, SP, Sr, Sx, Sy, Sz;
     pr_walk<T>(A, xp, lane, n, S, SP, Sr, Sx, Sy, Sz);
     if (lane == 0) {
-        double* v = rec + kPrHeader + (size_t)kPrValues * p;
+        double* v = rec + kStepHeader + (size_t)kPrValues * p;
         v[0] = S; v[1] = SP; v[2] = Sr; v[3] = Sx; v[4] = Sy; v[5] = A.D == 3 ? Sz : 0.0; v[6] = n;
     }
 }

@@ -23,7 +23,7 @@ struct EngineError : std::runtime_error {
 constexpr int kMaxColumns = 16;                  // SPHMI_MAX_COLUMNS
 constexpr int kMaxColumnRowBytes = 64;           // SPHMI_MAX_COLUMN_ROW_BYTES
 constexpr int kMaxForceGroups = 16;              // SPHMI_MAX_FORCE_GROUPS
-constexpr int kGfHeader = 3;                     // doubles in front of the payload of a record: iteration (int64 bits), time, Δt
+constexpr int kStepHeader = 3;                     // doubles in front of the payload of a record: iteration (int64 bits), time, Δt
 constexpr int kMaxProbes = 1024;                 // SPHMI_MAX_PROBES
 constexpr int kPrValues = 7;                     // S, SP, Sρ, Sv[3], n
 constexpr int kFgValues = kPrValues;             // S, SP, Sρ, Sv[3], n

@@ -2,16 +2,15 @@
 // every step (sphmi_tracers_enable / _read).  Probes sample at fixed points, the envelopes keep the extremes of a row but not its path;
 // a pathline, a residence time or the fate of the water that overtops an obstacle needs the position at step resolution.
 //
-// Two kinds of tracer share ONE per-step series; either kind may be absent.  The record of an executed step (kGfHeader +
-// kTrParticleValues · n_particles + kTrDrifterValues · n_drifters doubles, in the batch's log, which travels with the control block
-// like the probes'):
-//     { iteration (int64 bits), TotalTime at the end of the step, Δt,
+// Two kinds of tracer share ONE per-step series; either kind may be absent.  The record of an executed step (StepRecord,
+// sphmi_step_record.h; kStepHeader + kTrParticleValues · n_particles + kTrDrifterValues · n_drifters doubles):
+//     { the header,
 //       { x[3], v[3], ρ, P }[tracked particle s],                          — the state AFTER the step
 //       { X[3], S, SP, Sρ, Sv[3], n }[drifter p] }                         — X the position the sums were taken AT, before the move
 //
 // TRACKED PARTICLES — k_tr_particles, one row per lane over all rows.  The eight doubles are the values sphmi_download would deliver
-// into Float64 host arrays directly after that step, bit for bit: Position (fp32 handles: record + low word, as the probes read it),
-// Velocity, Density (|ρ·s| + low word), Pressure = Pressure!(ρₙ⁺) of the half-step set through eos7, as k_pack_output and the
+// into Float64 host arrays directly after that step, bit for bit: Position and Density (delivered_coord, delivered_density of
+// sphmi_step_record.h), Velocity, Pressure = Pressure!(ρₙ⁺) of the half-step set through eos7, as k_pack_output and the
 // envelopes form it; 2-D handles store a zero third component.  A tracked row is found again after every sort the way the envelopes
 // find their records (sphmi_envelopes.h, sphmi_columns.h), with a map of the tracers' own from the CURRENT row to the slot:
 //     slot of current row i  =  slot_of_record[prow[i]]        (−1: not tracked)
@@ -43,31 +42,30 @@
 #include "sphmi_kernels.h"      // StepCtrl, Half, Vec4, eos7
 #include "sphmi_probes.h"       // ProbeSampleArgs, pr_walk
 #include "sphmi_series.h"       // kMaxTracers, kTrParticleValues, kTrDrifterValues
+#include "sphmi_step_record.h"  // StepRecord, the delivered row
 
 namespace sphmi {
 
 constexpr int kTrBlock = 256;
-constexpr int kTrRecordMax = kGfHeader + (kTrParticleValues + kTrDrifterValues) * kMaxTracers;
+constexpr int kTrRecordMax = kStepHeader + (kTrParticleValues + kTrDrifterValues) * kMaxTracers;
 
 template <class T> struct TracerParticleArgs {
     using V4 = typename Vec4<T>::type;
-    const StepCtrl* ctrl;                // the block this step's corrector read
+    StepRecord step;
     Half<const V4> pk0, pk1;             // the corrector's output set
     Half<const V4> half0;                // the half-step set: Pressure is Pressure!(ρₙ⁺), as k_pack_output delivers it
     const V4* comp;                      // fp32 handles: low words of position and density (null: none)
     const int* prow;                     // row at the last sphmi_download_permutation
     const int* slot_of_record;           // row of that epoch → slot of the tracked particle, −1: not tracked
-    double* log;                         // `slots` records of `record` doubles
-    long long iteration0, steps_base;    // the clock of the batch, as the probes take it
     T rho0, inv_rho0, Cbe;
-    int n_particles, N, D, record, slots;
+    int n_particles, N, D;
 };
 
 template <class T> struct TracerDrifterArgs {
-    ProbeSampleArgs<T> s;                // the walk's arguments; pos: X (read and written), log: the tracers' log, n_probes: the drifters
+    ProbeSampleArgs<T> s;                // the walk's arguments; pos: X (read and written), step: the tracers' log, n_probes: the drifters
     double* X;                           // 3 doubles per drifter (s.pos, writable)
     double min_weight;
-    int value0;                          // first double of the drifters inside a record: kGfHeader + kTrParticleValues · n_particles
+    int value0;                          // first double of the drifters inside a record: kStepHeader + kTrParticleValues · n_particles
     int write_header;                    // no tracked particles: this kernel writes { iteration, time, Δt }
 };
 
@@ -84,17 +82,13 @@ __global__ void k_tr_map_init(const int* __restrict__ rows, const int* __restric
 template <class T>
 __global__ void __launch_bounds__(kTrBlock) k_tr_particles(const TracerParticleArgs<T> A) {
     using V4 = typename Vec4<T>::type;
-    const StepCtrl c = *A.ctrl;
+    const StepCtrl c = *A.step.ctrl;
     if (!c.active) return;
-    const long long slot = c.steps_done - 1 - A.steps_base;
-    if (slot < 0 || slot >= (long long)A.slots) return;
-    double* rec = A.log + (size_t)slot * (size_t)A.record;
+    const long long slot = A.step.slot(c);
+    if (slot < 0) return;
+    double* rec = A.step.at(slot);
     const long long i = (long long)blockIdx.x * kTrBlock + (int)threadIdx.x;
-    if (i == 0) {
-        rec[0] = __longlong_as_double(A.iteration0 + c.steps_done);
-        rec[1] = c.total_time;
-        rec[2] = c.last_dt;
-    }
+    if (i == 0) A.step.write_header(rec, c);
     if (i >= (long long)A.N) return;
     const unsigned e = (unsigned)A.prow[i];
     if (e >= (unsigned)A.N) return;
@@ -103,23 +97,23 @@ __global__ void __launch_bounds__(kTrBlock) k_tr_particles(const TracerParticleA
     const V4 q0 = A.pk0[i], q1 = A.pk1[i];
     V4 lw; lw.x = lw.y = lw.z = lw.w = T(0);
     if (sizeof(T) == 4 && A.comp) lw = A.comp[i];
-    double* v = rec + kGfHeader + (size_t)kTrParticleValues * s;
-    v[0] = (double)q0.x + (double)lw.x;
-    v[1] = (double)q0.y + (double)lw.y;
-    v[2] = A.D == 3 ? (double)q0.z + (double)lw.z : 0.0;
+    double* v = rec + kStepHeader + (size_t)kTrParticleValues * s;
+    v[0] = delivered_coord(q0.x, lw.x);
+    v[1] = delivered_coord(q0.y, lw.y);
+    v[2] = A.D == 3 ? delivered_coord(q0.z, lw.z) : 0.0;
     v[3] = (double)q1.x;
     v[4] = (double)q1.y;
     v[5] = A.D == 3 ? (double)q1.z : 0.0;
-    v[6] = (double)(q0.w < T(0) ? -q0.w : q0.w) + (double)lw.w;
+    v[6] = delivered_density(q0.w, lw.w);
     v[7] = (double)eos7<T>(A.half0[i].w, A.rho0, A.inv_rho0, A.Cbe);
 }
 
 template <class T>
 __global__ void __launch_bounds__(256) k_tr_drift(const TracerDrifterArgs<T> A) {
-    const StepCtrl c = *A.s.ctrl;
+    const StepCtrl c = *A.s.step.ctrl;
     if (!c.active) return;
-    const long long slot = c.steps_done - 1 - A.s.steps_base;
-    const bool keep = slot >= 0 && slot < (long long)A.s.slots;            // guards the record, not the walk: the move does not depend on the log
+    const long long slot = A.s.step.slot(c);
+    const bool keep = slot >= 0;                                           // guards the record, not the walk: the move does not depend on the log
     const int lane = (int)threadIdx.x & 63;
     const int p = __builtin_amdgcn_readfirstlane((int)((blockIdx.x * blockDim.x + threadIdx.x) >> 6));
     if (p >= A.s.n_probes) return;
@@ -135,12 +129,8 @@ __global__ void __launch_bounds__(256) k_tr_drift(const TracerDrifterArgs<T> A) 
         if (A.s.D == 3) A.X[3 * p + 2] = xp[2] + (Sz / S) * dt;
     }
     if (!keep) return;
-    double* rec = A.s.log + (size_t)slot * (size_t)A.s.record;
-    if (p == 0 && A.write_header) {
-        rec[0] = __longlong_as_double(A.s.iteration0 + c.steps_done);
-        rec[1] = c.total_time;
-        rec[2] = c.last_dt;
-    }
+    double* rec = A.s.step.at(slot);
+    if (p == 0 && A.write_header) A.s.step.write_header(rec, c);
     double* v = rec + A.value0 + (size_t)kTrDrifterValues * p;
     v[0] = xp[0]; v[1] = xp[1]; v[2] = xp[2];
     v[3] = S; v[4] = SP; v[5] = Sr; v[6] = Sx; v[7] = Sy; v[8] = A.s.D == 3 ? Sz : 0.0; v[9] = n;

@@ -82,11 +82,11 @@ static void test_table() {
 
 // a record of `n_boxes` boxes: slot c of box b holds base + 10 b + c, the three counts whole numbers
 static std::vector<double> record(int64_t it, int n_boxes, double base) {
-    std::vector<double> r((size_t)kGfHeader + (size_t)kFlValues * n_boxes, 0.0);
+    std::vector<double> r((size_t)kStepHeader + (size_t)kFlValues * n_boxes, 0.0);
     memcpy(&r[0], &it, 8);
     r[1] = 0.5 * (double)it; r[2] = 0.125;
     for (int b = 0; b < n_boxes; ++b)
-        for (int c = 0; c < kFlValues; ++c) r[(size_t)kGfHeader + (size_t)kFlValues * b + c] = base + 10.0 * b + c + (c >= 1 && c <= 4 ? 0.5 : 0.0);
+        for (int c = 0; c < kFlValues; ++c) r[(size_t)kStepHeader + (size_t)kFlValues * b + c] = base + 10.0 * b + c + (c >= 1 && c <= 4 ? 0.5 : 0.0);
     return r;
 }
 
@@ -113,13 +113,13 @@ static void test_delivery() {
     StepSeries s;
     s.reset(kFlValues * m, 4);
     const std::vector<double> r1 = record(3, m, 100.0), r2 = record(4, m, 200.0);
-    s.push(StepSeries::decode(r1.data(), kGfHeader, kFlValues * m));
-    s.push(StepSeries::decode(r2.data(), kGfHeader, kFlValues * m));
+    s.push(StepSeries::decode(r1.data(), kStepHeader, kFlValues * m));
+    s.push(StepSeries::decode(r2.data(), kStepHeader, kFlValues * m));
     Got got = read(s, m0, m, 2);
     CHECK(got.n == 2 && got.dropped == 0 && got.it[0] == 3 && got.it[1] == 4 && got.t[0] == 1.5 && got.dt[1] == 0.125);
     for (int k = 0; k < 2; ++k)
         for (int b = 0; b < m; ++b) {
-            const double* v = (k == 0 ? r1 : r2).data() + kGfHeader + kFlValues * b;
+            const double* v = (k == 0 ? r1 : r2).data() + kStepHeader + kFlValues * b;
             const size_t at = (size_t)k * m + b;
             CHECK(got.count[at] == (int64_t)v[0] && got.entered[at] == (int64_t)v[5] && got.left[at] == (int64_t)v[6]);
             CHECK(got.volume[at] == m0 * v[1]);                      // one multiplication each
@@ -127,16 +127,16 @@ static void test_delivery() {
         }
     CHECK(got.count[0] == 100 && got.entered[0] == 105 && got.left[0] == 106 && got.count[(size_t)m + 2] == 220);
     // every output null: the samples still leave the series
-    s.push(StepSeries::decode(r1.data(), kGfHeader, kFlValues * m));
+    s.push(StepSeries::decode(r1.data(), kStepHeader, kFlValues * m));
     int64_t n = -1;
     s.read(kFn, 1, nullptr, nullptr, nullptr, &n, nullptr, [&](int64_t k, const double* p) { deliver_flow(m0, m, k, p, nullptr, nullptr, nullptr, nullptr, nullptr); });
     CHECK(n == 1 && s.q.empty());
     // two slabs' records of a step add slot by slot; records of different steps do not
-    StepSeries::Sample a = StepSeries::decode(r1.data(), kGfHeader, kFlValues * m);
-    const StepSeries::Sample a0 = a, b = StepSeries::decode(record(3, m, 1.0).data(), kGfHeader, kFlValues * m);
+    StepSeries::Sample a = StepSeries::decode(r1.data(), kStepHeader, kFlValues * m);
+    const StepSeries::Sample a0 = a, b = StepSeries::decode(record(3, m, 1.0).data(), kStepHeader, kFlValues * m);
     StepSeries::add(a, b, "flow");
     for (size_t c = 0; c < a.v.size(); ++c) CHECK(a.v[c] == a0.v[c] + b.v[c]);
-    try { StepSeries::add(a, StepSeries::decode(r2.data(), kGfHeader, kFlValues * m), "flow"); CHECK(false); }
+    try { StepSeries::add(a, StepSeries::decode(r2.data(), kStepHeader, kFlValues * m), "flow"); CHECK(false); }
     catch (const EngineError& err) { CHECK(err.status == SPHMI_ERR_STATE && std::string(err.what()) == "flow: the slabs' records of a step do not belong together"); }
 }
 
@@ -145,7 +145,7 @@ static void test_capacity() {
     const int m = 16;
     StepSeries s;
     s.reset(kFlValues * m, 6);
-    for (int64_t it = 1; it <= 50; ++it) s.push(StepSeries::decode(record(it, m, (double)(1000 * it)).data(), kGfHeader, kFlValues * m));
+    for (int64_t it = 1; it <= 50; ++it) s.push(StepSeries::decode(record(it, m, (double)(1000 * it)).data(), kStepHeader, kFlValues * m));
     for (int rep = 0; rep < 2; ++rep) {
         int64_t n = -1, d = -1;
         s.read(kFn, 0, nullptr, nullptr, nullptr, &n, &d, [&](int64_t, const double*) { CHECK(false); });
@@ -161,7 +161,7 @@ static void test_capacity() {
     got = read(s, 1.0, m, 7);
     CHECK(got.n == 0 && got.dropped == 0);
     // a partial read leaves the rest, and the dropped count is handed out once
-    for (int64_t it = 1; it <= 8; ++it) s.push(StepSeries::decode(record(it, m, 0.0).data(), kGfHeader, kFlValues * m));
+    for (int64_t it = 1; it <= 8; ++it) s.push(StepSeries::decode(record(it, m, 0.0).data(), kStepHeader, kFlValues * m));
     got = read(s, 1.0, m, 4);
     CHECK(got.n == 4 && got.dropped == 2 && got.it[0] == 3 && got.it[3] == 6);
     got = read(s, 1.0, m, 4);

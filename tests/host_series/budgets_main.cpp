@@ -25,20 +25,20 @@ static const double kInf = std::numeric_limits<double>::infinity();
 
 // the record of a step without Fluid rows, as the kernels write it: 0 in the sum slots, +inf in the min slots, −inf in the max slots
 static std::vector<double> empty_record(int64_t it) {
-    std::vector<double> r((size_t)kGfHeader + kBgValues, 0.0);
+    std::vector<double> r((size_t)kStepHeader + kBgValues, 0.0);
     memcpy(&r[0], &it, 8);
     r[1] = 0.5 * (double)it; r[2] = 0.125;
-    for (int c = 0; c < kBgValues; ++c) r[(size_t)kGfHeader + c] = bg_rule(c) == 0 ? 0.0 : (bg_rule(c) == 1 ? kInf : -kInf);
+    for (int c = 0; c < kBgValues; ++c) r[(size_t)kStepHeader + c] = bg_rule(c) == 0 ? 0.0 : (bg_rule(c) == 1 ? kInf : -kInf);
     return r;
 }
 // … and one of `n` rows: slot c holds base + c (the min slots below, the max slots above what `other` holds when base differs)
 static std::vector<double> filled_record(int64_t it, double n, double base) {
     std::vector<double> r = empty_record(it);
-    for (int c = 0; c < kBgValues; ++c) r[(size_t)kGfHeader + c] = base + c;
-    r[kGfHeader] = n;
+    for (int c = 0; c < kBgValues; ++c) r[(size_t)kStepHeader + c] = base + c;
+    r[kStepHeader] = n;
     return r;
 }
-static StepSeries::Sample sample(const std::vector<double>& rec) { return StepSeries::decode(rec.data(), kGfHeader, kBgValues); }
+static StepSeries::Sample sample(const std::vector<double>& rec) { return StepSeries::decode(rec.data(), kStepHeader, kBgValues); }
 
 // the arrays of one read, exactly `cap` samples long (the sanitizer sees a write past them)
 struct Got {
@@ -73,12 +73,12 @@ static void test_factors_and_delivery() {
     StepSeries s;
     s.reset(kBgValues, 4);
     std::vector<double> rec = filled_record(3, 5.0, 0.5);
-    rec[kGfHeader + 13] = 6.25;
+    rec[kStepHeader + 13] = 6.25;
     s.push(sample(rec));
     s.push(sample(empty_record(4)));
     Got got = read(s, f, 2);
     CHECK(got.n == 2 && got.dropped == 0 && got.it[0] == 3 && got.it[1] == 4 && got.t[0] == 1.5 && got.dt[1] == 0.125);
-    const double* v = &rec[kGfHeader];
+    const double* v = &rec[kStepHeader];
     CHECK(got.count[0] == 5);
     CHECK(got.energy[0] == m0 * v[1] && got.energy[1] == (m0 * g) * v[2] && got.energy[2] == f.internal * v[3]);
     for (int d = 0; d < 3; ++d) {
@@ -104,7 +104,7 @@ static void test_factors_and_delivery() {
 static void test_combine() {
     // slab A holds the smallest values of slots 14, 16, 17 and the largest of 13, 19; slab B the others
     std::vector<double> ra = filled_record(9, 3.0, 1.0), rb = filled_record(9, 4.0, 2.0);
-    double* a = &ra[kGfHeader]; double* b = &rb[kGfHeader];
+    double* a = &ra[kStepHeader]; double* b = &rb[kStepHeader];
     a[13] = 50.0; b[13] = 40.0;     // max |v|²: in A
     a[18] = 7.5; b[18] = -7.5;      // min z: in B
     a[19] = 90.0; b[19] = 80.0;     // max x: in A

@@ -23,13 +23,13 @@ static const char* kFn = "sphmi_group_forces_read";
 
 // a device-side record of `values` payload doubles: { iteration (int64 bits), time, Δt, payload }, payload[c] = 100·it + c + ¼
 static std::vector<double> record(int64_t it, int values) {
-    std::vector<double> r((size_t)kGfHeader + values);
+    std::vector<double> r((size_t)kStepHeader + values);
     memcpy(&r[0], &it, 8);
     r[1] = 0.5 * (double)it; r[2] = 0.125 + (double)it;
-    for (int c = 0; c < values; ++c) r[(size_t)kGfHeader + c] = 100.0 * (double)it + c + 0.25;
+    for (int c = 0; c < values; ++c) r[(size_t)kStepHeader + c] = 100.0 * (double)it + c + 0.25;
     return r;
 }
-static void push(StepSeries& s, int64_t it) { s.push(StepSeries::decode(record(it, s.values).data(), kGfHeader, s.values)); }
+static void push(StepSeries& s, int64_t it) { s.push(StepSeries::decode(record(it, s.values).data(), kStepHeader, s.values)); }
 
 struct Got {
     std::vector<int64_t> it; std::vector<double> t, dt, v;
@@ -46,7 +46,7 @@ static void check_sample(const Got& g, int64_t k, int64_t it, int values) {
     const std::vector<double> r = record(it, values);
     CHECK(g.it[(size_t)k] == it);
     CHECK(g.t[(size_t)k] == r[1] && g.dt[(size_t)k] == r[2]);
-    CHECK(memcmp(&g.v[(size_t)k * values], &r[kGfHeader], (size_t)values * 8) == 0);
+    CHECK(memcmp(&g.v[(size_t)k * values], &r[kStepHeader], (size_t)values * 8) == 0);
 }
 
 // capacity 1 and 3, 0 / 1 / capacity / capacity + 2 pushes: the newest `capacity` samples wait, the others count as dropped
@@ -130,9 +130,9 @@ static void test_argument_errors() {
 
 static void test_add() {
     const int values = 6;
-    StepSeries::Sample a = StepSeries::decode(record(7, values).data(), kGfHeader, values);
-    const StepSeries::Sample b = StepSeries::decode(record(7, values).data(), kGfHeader, values);
-    StepSeries::Sample c = StepSeries::decode(record(8, values).data(), kGfHeader, values);
+    StepSeries::Sample a = StepSeries::decode(record(7, values).data(), kStepHeader, values);
+    const StepSeries::Sample b = StepSeries::decode(record(7, values).data(), kStepHeader, values);
+    StepSeries::Sample c = StepSeries::decode(record(8, values).data(), kStepHeader, values);
     c.v[2] = 0.1;
     const StepSeries::Sample a0 = a;
     StepSeries::add(a, b, "probes");
@@ -153,10 +153,10 @@ static void test_forces_bit_for_bit() {
     const int n_groups = 2, values = 3 * n_groups;
     const uint64_t bits[values] = {0x7ff8000000000abcull, 0x8000000000000000ull, 0x0000000000000001ull, 0xfff0000000000000ull, 0x3ff0000000000001ull, 0x7ff4000000000001ull};
     std::vector<double> rec = record(std::numeric_limits<int64_t>::min() + 5, values);
-    memcpy(&rec[kGfHeader], bits, sizeof bits);
+    memcpy(&rec[kStepHeader], bits, sizeof bits);
     StepSeries s;
     s.reset(values, 2);
-    s.push(StepSeries::decode(rec.data(), kGfHeader, values));
+    s.push(StepSeries::decode(rec.data(), kStepHeader, values));
     push(s, 2);
     Got g = read(s, 2);
     CHECK(g.n == 2 && g.it[0] == std::numeric_limits<int64_t>::min() + 5);
@@ -172,11 +172,11 @@ static void test_probe_means() {
         0.5, 9.0, 9.0, 9.0, 9.0, 9.0, 0.0,
         0.0, 9.0, 9.0, 9.0, 9.0, 9.0, 2.0};
     std::vector<double> rec = record(11, n_probes * kPrValues);
-    memcpy(&rec[kGfHeader], sums, sizeof sums);
+    memcpy(&rec[kStepHeader], sums, sizeof sums);
     StepSeries s;
     s.reset(n_probes * kPrValues, 4);
-    s.push(StepSeries::decode(rec.data(), kGfHeader, s.values));
-    s.push(StepSeries::decode(rec.data(), kGfHeader, s.values));
+    s.push(StepSeries::decode(rec.data(), kStepHeader, s.values));
+    s.push(StepSeries::decode(rec.data(), kStepHeader, s.values));
     const int64_t cap = 2;
     std::vector<double> w((size_t)cap * n_probes, -1.0), P(w), rho(w), vel((size_t)cap * n_probes * 3, -1.0);
     std::vector<int64_t> cnt((size_t)cap * n_probes, -1);

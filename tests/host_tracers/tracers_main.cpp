@@ -104,12 +104,12 @@ static void test_deliver() {
     // through a series: the record of the device-side log { iteration, time, dt, payload } is decoded and handed out in order
     StepSeries s;
     s.reset(per, 1);
-    std::vector<double> rec((size_t)(kGfHeader + per));
+    std::vector<double> rec((size_t)(kStepHeader + per));
     for (int it = 1; it <= 3; ++it) {
         const int64_t iteration = it;
         memcpy(&rec[0], &iteration, 8); rec[1] = 0.5 * it; rec[2] = 0.5;
-        for (int k = 0; k < per; ++k) rec[(size_t)(kGfHeader + k)] = 1000.0 * it + k;
-        s.push(StepSeries::decode(rec.data(), kGfHeader, per));
+        for (int k = 0; k < per; ++k) rec[(size_t)(kStepHeader + k)] = 1000.0 * it + k;
+        s.push(StepSeries::decode(rec.data(), kStepHeader, per));
     }
     int64_t iteration = 0, n = 0, dropped = 0;
     double time = 0, dt = 0;
