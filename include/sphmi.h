@@ -612,6 +612,37 @@ int sphmi_sample_grid(sphmi_handle* h, const double* origin, const double* spaci
                       double* weight_out, int64_t* count_out, double* pressure_out, double* density_out, double* velocity_out);
 
 /*
+ * Pressure, density, velocity and fill at ARBITRARY points, on demand: the sums of sphmi_sample_grid at every point of a cloud that is
+ * neither a lattice nor a handful of probes - the panel centroids of a hull, the nodes of another code's mesh, an oblique slice, a ring
+ * of sensors - by a kernel that first groups the points by blocks of cells so that up to 256 of them share the staged particle rows
+ * (csrc/sphmi_point_cloud.h).  Per point it is the contract of sphmi_sample_grid per node:
+ *   Synchronous, called between sphmi_advance calls like sphmi_sample_grid; it changes no state a later step, download, column download,
+ *   series read or other on-demand result reads, and leaves a download begun with sphmi_download_begin alone.
+ *   positions [n_points x dims], row p the coordinates of point p.  Per point: n Fluid rows the handle owns with
+ *   r^2 = ((dx^2 + dy^2) + dz^2) <= H^2 (inclusive, not fused, on the current positions, however stale the cell list), S = sum w_j, SP, Srho,
+ *   Sv with w_j = (m0 / rho_j) W(r), on the state sphmi_download would deliver now (Position and Density record + low word on fp32
+ *   handles, Pressure = Pressure!(rho_n+) of the half-step set), all in fp64, no self term, r = 0 legal.
+ *   weight_out [n_points] S, count_out [n_points] n, pressure_out / density_out [n_points] SP / S and Srho / S, velocity_out
+ *   [n_points x 3] Sv / S (2-D handles: a zero third component) - normalised on the host as for the lattice, 0 where n == 0.  Any output
+ *   pointer may be NULL.  Outputs are in the CALLER's order: entry p belongs to positions[p].
+ *   The result of a point depends on its own coordinates and the state of the handle alone - not on which other points are in the call,
+ *   how many there are, or their order: it is summed in ascending row order, without atomics.  A subset of a cloud, the cloud shuffled,
+ *   a point given twice in one call and a repeated call all deliver the same bits for that point.
+ *   A point in empty space, or outside the particles' cell grid on any side, reads zeros.  n_points == 0 is legal and does nothing.
+ *   SPHMI_ERR_STATE: as sphmi_sample_grid - before the upload; before the handle has executed its first step since the upload or
+ *     generator; rank-mode handles; handles with H < h.
+ *   SPHMI_ERR_ARGUMENT: null positions with n_points > 0; n_points < 0 or above SPHMI_MAX_SAMPLE_POINTS; a coordinate that is not finite
+ *     (the text names the index of the first such point).
+ *   SPHMI_ERR_DEVICE: the device cannot hold the positions, the plan and the result arena (7 doubles per point; the text names the
+ *     bytes of the allocation that failed); the handle stays usable.
+ * Multi-device handles of one process: every slab samples all points over the rows it owns (ghost copies do not count), the handle adds
+ * the slabs' raw sums in slab order and then normalises.
+ */
+#define SPHMI_MAX_SAMPLE_POINTS (1 << 24)
+int sphmi_sample_points(sphmi_handle* h, int64_t n_points, const double* positions /* n_points x dims */,
+                        double* weight_out, int64_t* count_out, double* pressure_out, double* density_out, double* velocity_out);
+
+/*
  * Differential fields AT THE PARTICLES, on demand: vorticity, velocity divergence, the free-surface indicator div r, the free-surface
  * normal, the Shepard sum and the neighbour count of every row - what a post-processor colours a breaking wave by or extracts a free
  * surface from - by a kernel that shares the staged rows among 256 consecutive target rows (csrc/sphmi_particle_fields.h).

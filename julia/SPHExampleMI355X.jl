@@ -338,6 +338,19 @@ function sample_grid(P, origin::Vector{Float64}, spacing::Vector{Float64}, count
                                                                        h, pointer(origin), pointer(spacing), pointer(counts), pointer(w), pointer(c), pointer(pp), pointer(rho), pointer(v)))
     return (weight = w, count = c, pressure = pp, density = rho, velocity = v)
 end
+# The same sums at ARBITRARY points, evaluated on the state the session holds NOW (sphmi_sample_points): positions is dims × n, column p
+# the coordinates of point p (column-major: the rows the library reads) — panel centroids, mesh nodes, a ring of sensors.  Returns vectors
+# of length n in the caller's order, velocity as 3 × n; a point's result does not depend on the other points of the call.  Call it from an
+# output callback, i.e. between two SimulationLoop calls, after the first step.
+function sample_points(P, positions::Matrix{Float64})
+    h = SESSIONS[P].h
+    n = size(positions, 2)
+    w = Vector{Float64}(undef, n); c = Vector{Int64}(undef, n); pp = Vector{Float64}(undef, n); rho = Vector{Float64}(undef, n)
+    v = Matrix{Float64}(undef, 3, n)
+    GC.@preserve positions w c pp rho v check(h, ccall((:sphmi_sample_points, LIB), Cint, (Ptr{Cvoid}, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Int64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+                                                      h, Int64(n), pointer(positions), pointer(w), pointer(c), pointer(pp), pointer(rho), pointer(v)))
+    return (weight = w, count = c, pressure = pp, density = rho, velocity = v)
+end
 # Differential fields at the particles, evaluated on the state the session holds NOW (sphmi_particle_fields): row i is row i of the next
 # download.  count[i] rows within H, shepard[i], div_r[i] (≈ D inside, lower at a free surface), div_v[i], normal[:, i] and vorticity[:, i]
 # (3 × n; 2-D: only vorticity[3, :] and normal[1:2, :] are non-zero).  Single-device sessions; call it from an output callback, after the first step.

@@ -20,6 +20,7 @@ MAX_COLUMN_ROW_BYTES = 64
 MAX_FORCE_GROUPS = 16
 MAX_PROBES = 1024
 MAX_GRID_NODES = 1 << 24
+MAX_SAMPLE_POINTS = 1 << 24
 NEIGHBORS_FULL, NEIGHBORS_HALF = 0, 1
 
 OK, ERR_ARGUMENT, ERR_DEVICE, ERR_NUMERIC, ERR_DOMAIN, ERR_STATE = range(6)
@@ -613,6 +614,31 @@ class Backend:
         out = {k: (np.zeros(shape + ((3,) if k == "velocity" else ()), dtype=np.int64 if k == "count" else np.float64) if k in fields else None)
                for k in self.GRID_FIELDS}
         self._check(f(self._h, _ptr(o), _ptr(s), _ptr(c), *[_ptr(out[k]) for k in self.GRID_FIELDS]))
+        return {k: v for k, v in out.items() if v is not None}
+
+    # -- kernel sums at arbitrary points, on demand (sphmi_sample_points) -----------------------------------------------------
+    def has_sample_points(self) -> bool:
+        return self._has("sample_points")
+
+    def sample_points(self, positions, fields=None) -> dict:
+        """The sums of `sample_grid` at every point of `positions` ([n, dims]: panel centroids, mesh nodes, a ring of sensors —
+        any cloud of up to 2**24 points), evaluated now.  Returns the dict of `sample_grid` with a leading axis of n instead of
+        the lattice's: `weight`, `count`, `pressure`, `density` [n] and `velocity` [n, 3], entry p belonging to
+        ``positions[p]``; `fields` names the ones wanted (default: all).  A point's result does not depend on the other points
+        of the call.  Call it between `advance` calls, after the first executed step."""
+        x = np.ascontiguousarray(positions, dtype=np.float64)
+        if x.ndim != 2 or x.shape[1] != self.D:
+            raise ValueError(f"sample_points: positions is shaped [n, {self.D}]")
+        fields = self.GRID_FIELDS if fields is None else tuple(fields)
+        unknown = [k for k in fields if k not in self.GRID_FIELDS]
+        if unknown:
+            raise ValueError(f"sample_points: unknown fields {unknown}")
+        n = len(x)
+        f = self._fn("sample_points")
+        f.argtypes = [C.c_void_p, C.c_int64] + [C.c_void_p] * 6
+        out = {k: (np.zeros((n, 3) if k == "velocity" else n, dtype=np.int64 if k == "count" else np.float64) if k in fields else None)
+               for k in self.GRID_FIELDS}
+        self._check(f(self._h, n, _ptr(x), *[_ptr(out[k]) for k in self.GRID_FIELDS]))
         return {k: v for k, v in out.items() if v is not None}
 
     # -- differential fields at the particles, on demand (sphmi_particle_fields) ------------------------------------------------

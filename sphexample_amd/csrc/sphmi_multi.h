@@ -1766,6 +1766,11 @@ struct MultiEngine final : EngineBase {
         const int64_t nodes = check_grid_lattice(origin, spacing, counts, D);
         for (auto& r : R) if (r.e->fg_ready()) r.e->fg_launch(origin, spacing, counts, nodes);        // all slabs at once, each on its device
         GridSums G(nodes, weight, count, pressure, density, velocity);
+        add_slab_sums(G, [&](Engine<T>& e, int f, double* dst) { e.fg_fetch(f, dst, nodes); });
+        G.deliver(count, pressure, density, velocity);
+    }
+    // the raw sums of a sampler the slabs have queued, added in slab order: fetch(engine, f, dst) brings sum f of one slab
+    template <class Fetch> void add_slab_sums(GridSums& G, Fetch&& fetch) {
         std::vector<double> part;
         bool first = true;
         for (auto& r : R) {
@@ -1774,14 +1779,27 @@ struct MultiEngine final : EngineBase {
             for (int f = 0; f < kFgValues; ++f) {
                 if (!G.want[f]) continue;
                 double* dst = G.dst(f);
-                if (first) { r.e->fg_fetch(f, dst, nodes); continue; }
-                part.resize((size_t)nodes);
-                r.e->fg_fetch(f, part.data(), nodes);
-                for (int64_t k = 0; k < nodes; ++k) dst[k] += part[(size_t)k];
+                if (first) { fetch(*r.e, f, dst); continue; }
+                part.resize((size_t)G.nodes);
+                fetch(*r.e, f, part.data());
+                for (int64_t k = 0; k < G.nodes; ++k) dst[k] += part[(size_t)k];
             }
             HC(hipStreamSynchronize(r.e->stream));
             first = false;
         }
+    }
+    // Kernel sums at arbitrary points (sphmi_point_cloud.h): every slab bins the WHOLE cloud on its own cell grid and samples it over the
+    // rows it owns; the sums are added like the lattice's, entry p staying the caller's point p.
+    void sample_points(int64_t n, const double* positions, double* weight, int64_t* count, double* pressure, double* density, double* velocity) override {
+        require_one_process("sphmi_sample_points");
+        bool any = false;
+        for (auto& r : R) any = any || r.e->fg_ready();
+        require_cell_list("sphmi_sample_points", any, "(no cell list, no half-step set)");
+        check_sample_points(n, positions, D);
+        if (n == 0) return;
+        for (auto& r : R) if (r.e->fg_ready()) r.e->pc_launch(positions, n);
+        GridSums G(n, weight, count, pressure, density, velocity);
+        add_slab_sums(G, [&](Engine<T>& e, int f, double* dst) { e.pc_fetch(f, dst, n); });
         G.deliver(count, pressure, density, velocity);
     }
     // Differential fields at the particles (sphmi_particle_fields.h): single-device handles only.  After the corrector a slab's ghost

@@ -28,6 +28,7 @@ constexpr int kMaxProbes = 1024;                 // SPHMI_MAX_PROBES
 constexpr int kPrValues = 7;                     // S, SP, Sρ, Sv[3], n
 constexpr int kFgValues = kPrValues;             // S, SP, Sρ, Sv[3], n
 constexpr long long kMaxGridNodes = 1ll << 24;   // SPHMI_MAX_GRID_NODES
+constexpr long long kMaxSamplePoints = 1ll << 24; // SPHMI_MAX_SAMPLE_POINTS
 constexpr int kBgValues = 22;                    // the raw budgets of the fluid (sphmi_budgets.h): thirteen sums, nine extremes
 
 // How two values of slot `slot` of a budget record combine: 0 sum (slots 0 … 12), 1 min, 2 max (13 max |v|², 14 / 15 min / max ρ,
@@ -162,6 +163,14 @@ inline int64_t check_grid_lattice(const double* origin, const double* spacing, c
     return nodes;
 }
 
+// sphmi_sample_points: the argument errors every kind of handle reports alike
+inline void check_sample_points(int64_t n_points, const double* positions, int dims) {
+    if (n_points < 0 || n_points > kMaxSamplePoints) throw EngineError(SPHMI_ERR_ARGUMENT, "sphmi_sample_points: n_points out of range [0, SPHMI_MAX_SAMPLE_POINTS]");
+    if (n_points > 0 && !positions) throw EngineError(SPHMI_ERR_ARGUMENT, "sphmi_sample_points: null positions");
+    for (int64_t k = 0; k < n_points * dims; ++k)
+        if (!std::isfinite(positions[k])) throw EngineError(SPHMI_ERR_ARGUMENT, "sphmi_sample_points: non-finite coordinate at point " + std::to_string(k / dims));
+}
+
 // The series of an observer that records once per executed step: what the batches delivered since the last read, the newest
 // `capacity` of it.  A sample carries the payload of a device-side record as it is (group forces: 3 per group; probes: the RAW
 // sums, kPrValues per probe); what a read hands out of it is the caller's `deliver`.
@@ -290,8 +299,8 @@ inline void deliver_map_vectors(int64_t bins, const double* c0, const double* c1
     if (out) for (int64_t b = 0; b < bins; ++b) { out[3 * b] = c0[b]; out[3 * b + 1] = c1[b]; out[3 * b + 2] = c2[b]; }
 }
 
-// The host side of sphmi_sample_grid: the raw sums { S, SP, Sρ, Sv[3], n } of the lattice (sphmi_field_grid.h), the ones the
-// requested outputs need.  S lands in weight_out itself when that is asked for; the means are formed here, 0 where n == 0.
+// The host side of sphmi_sample_grid and sphmi_sample_points: the raw sums { S, SP, Sρ, Sv[3], n } of the lattice
+// (sphmi_field_grid.h) or the cloud (sphmi_point_cloud.h), `nodes` of either, the ones the requested outputs need.  S lands in weight_out itself when that is asked for; the means are formed here, 0 where n == 0.
 struct GridSums {
     int64_t nodes = 0;
     double* S = nullptr;                       // weight_out, or s[0]

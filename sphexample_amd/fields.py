@@ -72,4 +72,65 @@ def free_surface_mask(div_r, dims: int, threshold: float = None) -> np.ndarray:
     return np.asarray(div_r, dtype=np.float64) < t
 
 
-__all__ = ["grid_axes", "grid_nodes", "surface_height", "free_surface_mask", "FREE_SURFACE_DIV_R"]
+# ---- clouds for ``Backend.sample_points``: a line of points, the panels of a surface mesh and the load on it ---------------------
+def segment(a, b, n: int) -> np.ndarray:
+    """`n` points from `a` to `b`, both included, evenly spaced: ``[n, dims]`` (n = 1: `a`)."""
+    a, b = np.asarray(a, dtype=np.float64).reshape(-1), np.asarray(b, dtype=np.float64).reshape(-1)
+    if len(a) != len(b) or len(a) not in (2, 3) or int(n) < 1:
+        raise ValueError("segment: two points of 2 or 3 coordinates each and n >= 1 are needed")
+    t = np.linspace(0.0, 1.0, int(n))[:, None] if int(n) > 1 else np.zeros((1, 1))
+    return a[None, :] + t * (b - a)[None, :]
+
+
+def _mesh(vertices, elements):
+    v = np.asarray(vertices, dtype=np.float64)
+    e = np.asarray(elements, dtype=np.int64)
+    if v.ndim != 2 or v.shape[1] not in (2, 3) or e.ndim != 2 or e.shape[1] != v.shape[1]:
+        raise ValueError("a mesh is vertices [nv, dims] and elements [ne, dims]: triangles in 3-D, segments in 2-D")
+    if e.size and (e.min() < 0 or e.max() >= len(v)):
+        raise ValueError("an element names a vertex the mesh does not have")
+    return v, e
+
+
+def triangle_centroids(vertices, triangles) -> np.ndarray:
+    """The centroid of every element of a surface mesh, ``[ne, dims]`` — the points to hand to ``Backend.sample_points``.
+    `triangles` is ``[ne, 3]`` vertex indices in 3-D; in 2-D the mesh is segments, ``[ne, 2]``, and the centroid the midpoint."""
+    v, e = _mesh(vertices, triangles)
+    return v[e].mean(axis=1)
+
+
+def _area_vectors(v, e):
+    """A_k n̂_k of every element: half the cross product of two edges (3-D, the normal the right-hand rule gives the vertex
+    order); the segment a → b turned a quarter to the right, (dy, −dx) (2-D: outward on a counter-clockwise polygon)."""
+    p = v[e]
+    if v.shape[1] == 3:
+        return 0.5 * np.cross(p[:, 1] - p[:, 0], p[:, 2] - p[:, 0])
+    d = p[:, 1] - p[:, 0]
+    return np.stack([d[:, 1], -d[:, 0]], axis=1)
+
+
+def surface_load(vertices, triangles, pressure, about=None):
+    """The pressure load on a surface mesh: the force ``−Σ p_k A_k n̂_k`` with `pressure` [ne] the pressure at the element
+    centroids (``Backend.sample_points(triangle_centroids(...))["pressure"]``), A_k the element's area and n̂_k its normal —
+    out of the body for triangles ordered counter-clockwise seen from outside.  In 2-D the mesh is segments, the normal lies
+    to the right of a → b (out of a counter-clockwise polygon) and the result is a force per unit width.  With `about`
+    (a point) returns ``(force, moment)``, the moment ``Σ (c_k − about) × f_k`` of the element forces applied at the centroids:
+    a vector in 3-D, the z component in 2-D.  One-point quadrature: exact for the force of a pressure that is linear over
+    each element."""
+    v, e = _mesh(vertices, triangles)
+    p = np.asarray(pressure, dtype=np.float64).reshape(-1)
+    if len(p) != len(e):
+        raise ValueError("surface_load: one pressure per element is needed")
+    f = -p[:, None] * _area_vectors(v, e)
+    force = f.sum(axis=0)
+    if about is None:
+        return force
+    r = v[e].mean(axis=1) - np.asarray(about, dtype=np.float64).reshape(1, -1)
+    if r.shape[1] != v.shape[1]:
+        raise ValueError("surface_load: `about` holds one coordinate per axis")
+    moment = np.cross(r, f).sum(axis=0) if v.shape[1] == 3 else float((r[:, 0] * f[:, 1] - r[:, 1] * f[:, 0]).sum())
+    return force, moment
+
+
+__all__ = ["grid_axes", "grid_nodes", "surface_height", "free_surface_mask", "FREE_SURFACE_DIV_R", "segment", "triangle_centroids",
+           "surface_load"]

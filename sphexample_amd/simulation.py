@@ -46,7 +46,7 @@ def RunSimulation(*, SimGeometry=None, SimMetaData: SimulationMetaData, SimConst
                   device_float_bytes: int = 0, device: int = 0, backend_factory=None,
                   async_output: bool = False, group_forces=None, probes=None, field_grid=None,
                   particle_fields=None, budgets: bool = False, neighbor_list: bool = False, isosurface=None, components=None,
-                  flow_boxes=None, envelopes=None, maps=None, tracers=None) -> List[float]:
+                  flow_boxes=None, envelopes=None, maps=None, tracers=None, sample_points=None) -> List[float]:
     """Same keyword signature as the reference (src/SPHCellList.jl:808-817); returns the list of
     time steps the reference collects in ``TimeSteps`` (:823,:884).  ``SimParticles`` is updated in
     place at every output time, in the engine's cell-sorted order, as the reference's is.
@@ -119,7 +119,13 @@ def RunSimulation(*, SimGeometry=None, SimMetaData: SimulationMetaData, SimConst
     the massless points `drifters` advected with the flow on the device at every step (``Backend.tracers_enable``;
     ``sphexample_amd.tracers.pathlines`` joins the intervals into one array of positions) and ``on_output`` receives the steps of
     the interval, the dict of ``Backend.tracers_read``, as its last argument, behind the maps (``None`` at the first call).  Either
-    key may be missing.  ``None`` (default): nothing is followed and the callback keeps its arguments."""
+    key may be missing.  ``None`` (default): nothing is followed and the callback keeps its arguments.
+
+    ``sample_points=positions`` ([n, dims]): at every output the sums of the field grid are sampled at those arbitrary points
+    (``Backend.sample_points``; ``sphexample_amd.fields`` forms panel centroids and integrates a surface load) and ``on_output``
+    receives the dict — ``weight``, ``count``, ``pressure``, ``density`` [n], ``velocity`` [n, 3] — as its last argument, behind the
+    tracers (``None`` at the first call, which precedes the first step).  ``None`` (default): nothing is sampled and the callback
+    keeps its arguments."""
     if SimMetaData.BMode.__name__ == "SimpleMDBC":
         LoadMDBCNormals(SimParticles, ParticleNormalsPath)                       # :827
     host_bytes = SimParticles.Position.dtype.itemsize
@@ -189,6 +195,9 @@ def RunSimulation(*, SimGeometry=None, SimMetaData: SimulationMetaData, SimConst
     if tracers is not None:
         eng.tracers_enable(capacity=1 << 16, **dict(tracers))
         extras.append((None, eng.tracers_read))                                  # (None at the first call: no step, no record)
+    if sample_points is not None:
+        cloud = np.ascontiguousarray(sample_points, dtype=np.float64).reshape(-1, SimMetaData.Dimensions)
+        extras.append((None, lambda: eng.sample_points(cloud)))                  # (the state of this output, like the field grid)
     none_yet = tuple(first for first, _ in extras)
     emit = lambda meta, samples: on_output(meta, SimParticles, *samples)         # noqa: E731
     if on_output:
