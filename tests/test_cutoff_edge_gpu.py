@@ -1,0 +1,203 @@
+"""The candidate mask of k_neighbor_force at the exact cut r = H of a kernel that has not vanished there (k = 1.5, √2).
+
+The layouts of tests/cutoff_edge_reference.py plant pairs at r²/H² = 1 ∓ δ, δ from 1e-12 up, on tiles that reach 4 H … 1 000 H; every other pair is
+clear of the cut.  A mask that is short of a superset loses a planted inside pair, a pair loop with a wrong cut takes a planted outside one, and either
+moves a compared quantity by at least ten tolerances (tests/test_cutoff_edge_host.py).  Every case runs for every launch shape ($SPHMI_WPT as in
+tests/test_fused_pair_parity_gpu.py) and for fp64 and fp32 handles.
+
+Tolerance per particle and quantity: fp64 handles 1e-10 × the field's maximum; fp32 handles FACTOR·Q·S_i with Q measured numpy.float32 against fp64 on
+these very layouts (the builders keep the corrector's positions x⁺ clear of the cut in fp32 as well).  Laminar viscosity and the kernel output
+(ΣW, Σ∇W) have no restatement in tests/bruteforce.py and therefore no S_i: fp64 handles only.  Figures: profiles/cutoff_edge.md."""
+import functools
+
+import numpy as np
+import pytest
+
+import bruteforce as bf
+import cutoff_edge_reference as ce
+import fused_pair_reference as fr
+from test_fused_pair_parity_gpu import WPT_2D, WPT_3D
+
+pytestmark = pytest.mark.gpu
+
+FIELDS = ("ID",) + fr.FIELDS
+CASES = [(n, w) for n in ce.LAYOUTS_3D for w in WPT_3D] + [(n, w) for n in ce.LAYOUTS_2D for w in WPT_2D]
+BOXES = [(n, w) for n, w in CASES if n in ("box", "box2d")]
+
+
+@pytest.fixture(autouse=True)
+def _launch_shape(monkeypatch):
+    for k in ("SPHMI_WPT", "SPHMI_WPT2_BELOW", "SPHMI_TPB", "SPHMI_TPB2"):
+        monkeypatch.delenv(k, raising=False)
+
+
+def _force(monkeypatch, wpt):
+    if wpt is not None:
+        monkeypatch.setenv("SPHMI_WPT", wpt)
+
+
+def _setup(L, **kw):
+    return ce.setup(L.dims, L.k, **kw) if kw else L.s
+
+
+@functools.lru_cache(maxsize=None)
+def _oracle_forces(name, width):
+    from oracle.oracle import make_oracle
+    L = ce.layout(name, width)
+    orc = make_oracle(L.p, L.s)
+    try:
+        d, a = orc.forces_once()
+        ids = orc.download(("ID",))["ID"]
+    finally:
+        orc.close()
+    o = np.argsort(ids, kind="stable")
+    return d[o], a[o]
+
+
+@functools.lru_cache(maxsize=None)
+def _oracle_step(name, width, viscosity=None, kernel_output=False):
+    from oracle.oracle import make_oracle
+    L = ce.layout(name, width)
+    orc = make_oracle(L.p, _setup(L, viscosity=viscosity, kernel_output=kernel_output))
+    try:
+        po = orc.advance(1e9, max_steps=1)
+        o = orc.download(FIELDS)
+        back = np.argsort(o["ID"], kind="stable")
+        out = {k: v[back] for k, v in o.items()}
+        half = orc.half_step_density()[back]
+        if kernel_output:
+            kw, kg = orc.kernel_output()
+            out["ΣW"], out["Σ∇W"] = kw[back], kg[back]
+    finally:
+        orc.close()
+    return (po.iteration, po.n_rebuilds, po.last_dt), out, half
+
+
+def _check(L, what, got, ref, tol, term=None):
+    """|got − ref| ≤ tol per particle (rows by ID); the message names the first offender and its planted pairs."""
+    err = np.abs(got - ref)
+    t = tol * np.ones_like(ref)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        frac = np.where(t > 0, err / t, np.where(err > 0, np.inf, 0.0))
+    worst = float(frac.max())
+    print(f"{what}: largest error {worst:.3f} of the tolerance")
+    if worst <= 1.0:
+        return worst
+    row = i = int(np.unravel_index(np.argmax(frac), frac.shape)[0])         # (rows are in ID order: ID = row + 1)
+    lines = ce.describe(L, row) or ["no planted pair on this particle"]
+    if term is not None:
+        for m, sgn, t_i in term(row):
+            diff = (got - ref)[i]
+            if np.allclose(diff, sgn * t_i, rtol=0.1, atol=0.1 * np.abs(t_i).max()):
+                lines.append(f"the difference {diff} matches the signed term of planted pair {m} ({'lost' if sgn < 0 else 'taken'})")
+    raise AssertionError(f"{what}: particle ID {i + 1} (row {row}) is {worst:.3g} tolerances off\n  " + "\n  ".join(lines))
+
+
+def _terms_of(L, f, quantity):
+    """row → [(planted pair, −1 if it would be LOST / +1 if TAKEN, its signed term for this row)]."""
+    def find(row):
+        s = f.st.rank[row]
+        out = []
+        for m in np.nonzero((f.terms.i == s) | (f.terms.j == s))[0]:
+            is_i = f.terms.i[m] == s
+            t = (f.terms.t_drho_i[m] if is_i else f.terms.t_drho_j[m]) if quantity == "drho" else (f.terms.t_acc[m] if is_i else -f.terms.t_acc[m])
+            out.append((int(m), -1.0 if L.planted.side[m] < 0 else 1.0, t))
+        return out
+    return find
+
+
+@pytest.mark.parametrize("width", [8, 4])
+@pytest.mark.parametrize("name,wpt", CASES)
+def test_forces_once(name, wpt, width, monkeypatch):
+    """dρ/dt and a of one force evaluation, per particle, against the numpy pair sums on the same state and against the oracle."""
+    from sphexample_amd.engine import make_engine
+    _force(monkeypatch, wpt)
+    L, f = ce.layout(name, width), ce.forces(name, width)
+    eng = make_engine(L.p, L.s, device_float_bytes=width)
+    try:
+        d, a = eng.forces_once()
+        ids = eng.download(("ID",))["ID"]
+    finally:
+        eng.close()
+    o = np.argsort(ids, kind="stable")
+    d, a = d[o].astype(float), a[o].astype(float)
+    tol_d, tol_a = f.tol_drho[f.back], f.tol_acc[f.back]
+    od, oa = _oracle_forces(name, width)
+    what = f"{name} fp{8 * width} wpt={wpt} forces_once"
+    _check(L, what + " dρ/dt against numpy", d, f.r64.drho[f.back], tol_d, _terms_of(L, f, "drho"))
+    _check(L, what + " a against numpy", a, f.r64.acc[f.back], tol_a, _terms_of(L, f, "acc"))
+    _check(L, what + " dρ/dt against the oracle", d, od, tol_d, _terms_of(L, f, "drho"))
+    _check(L, what + " a against the oracle", a, oa, tol_a, _terms_of(L, f, "acc"))
+
+
+def _step(name, wpt, width, monkeypatch, viscosity=None, kernel_output=False):
+    from sphexample_amd.engine import make_engine
+    _force(monkeypatch, wpt)
+    L = ce.layout(name, width)
+    (it, nreb, dt), o, half = _oracle_step(name, width, viscosity, kernel_output)
+    eng = make_engine(L.p, _setup(L, viscosity=viscosity, kernel_output=kernel_output), device_float_bytes=width)
+    try:
+        pe = eng.advance(1e9, max_steps=1)
+        e = fr.by_id(eng.download(FIELDS))
+        if kernel_output:
+            kw, kg = eng.kernel_output()
+            back = np.argsort(eng.download(("ID",))["ID"], kind="stable")
+            e["ΣW"], e["Σ∇W"] = kw[back].astype(float), kg[back].astype(float)
+    finally:
+        eng.close()
+    assert (pe.iteration, pe.n_rebuilds) == (it, nreb)
+    assert pe.last_dt == pytest.approx(dt, rel=1e-9 if width == 8 else 1e-6)
+    np.testing.assert_array_equal(e["ID"], o["ID"])
+    what = f"{name} fp{8 * width} wpt={wpt} step" + (" Laminar" if viscosity else "") + (" kernel output" if kernel_output else "")
+    if width == 8:
+        for k in fr.FIELDS + (("ΣW", "Σ∇W") if kernel_output else ()):
+            _check(L, f"{what} {k}", e[k], o[k], ce.FP64_BAR * np.abs(o[k]).max())
+    else:
+        cfg, r, S, q = ce.one_step(name, width)
+        assert np.isfinite(q)
+        o = dict(o); o["Pressure"] = bf.eos(cfg, half)                        # the oracle's Pressure IS Pressure!(ρₙ⁺) (tests/test_fused_pair_parity_gpu.py)
+        for k in fr.FIELDS:
+            _check(L, f"{what} {k} Q={q:.3f}", e[k], o[k], fr.FACTOR * q * S[k])
+
+
+@pytest.mark.parametrize("name,wpt", CASES)
+def test_one_fused_step_fp64(name, wpt, monkeypatch):
+    """The predictor and corrector instantiations and the compiled-in cut model: five fields per particle against the oracle."""
+    _step(name, wpt, 8, monkeypatch)
+
+
+@pytest.mark.parametrize("name,wpt", CASES)
+def test_one_fused_step_fp32(name, wpt, monkeypatch):
+    """The same on fp32 handles, within FACTOR·Q·S_i per particle and field."""
+    _step(name, wpt, 4, monkeypatch)
+
+
+@pytest.mark.parametrize("name,wpt", BOXES)
+def test_a_second_step_fp64(name, wpt, monkeypatch):
+    """Two calls of one step each: the second runs on positions that have left their cells' centres, with the Fixed–Fixed planted pairs still on
+    the cut and other pairs wherever the step put them (no classification: fp64 handles only, tests/test_cutoff_edge_host.py)."""
+    from oracle.oracle import make_oracle
+    from sphexample_amd.engine import make_engine
+    _force(monkeypatch, wpt)
+    L = ce.layout(name, 8)
+    eng, orc = make_engine(L.p, L.s, device_float_bytes=8), make_oracle(L.p, L.s)
+    try:
+        for _ in range(2):
+            pe, po = eng.advance(1e9, max_steps=1), orc.advance(1e9, max_steps=1)
+        assert (pe.iteration, pe.n_rebuilds) == (po.iteration, po.n_rebuilds)
+        e, o = fr.by_id(eng.download(FIELDS)), fr.by_id(orc.download(FIELDS))
+    finally:
+        eng.close(); orc.close()
+    for k in fr.FIELDS:
+        _check(L, f"{name} fp64 wpt={wpt} second step {k}", e[k], o[k], ce.FP64_BAR * np.abs(o[k]).max())
+
+
+@pytest.mark.parametrize("name,wpt", BOXES)
+def test_one_step_of_the_run_time_model_with_kernel_output(name, wpt, monkeypatch):
+    """StoreKernelOutput routes the handle to the run-time variant; ΣW at q = k is finite — the most direct count of pairs."""
+    _step(name, wpt, 8, monkeypatch, kernel_output=True)
+
+
+@pytest.mark.parametrize("name,wpt", BOXES)
+def test_one_step_with_laminar_viscosity(name, wpt, monkeypatch):
+    _step(name, wpt, 8, monkeypatch, viscosity="Laminar")

@@ -235,6 +235,7 @@ def test_fuzzed_switches_match_the_oracle(seed):
             # … and every one of them must HAVE such a reason (round-5 advice: a flat allowance is no check) — a partner within 2e-5 of r = H (the pair that
             # is in for one precision and out for the other), or, on mDBC handles, a boundary particle (whose density ApplyMDBCCorrection may have taken from
             # the other branch) as itself or among its neighbours; positions of the state the forces were evaluated on, by ID
+            # (this excuse is also what a candidate mask that is short of a superset would look like: tests/test_cutoff_edge_gpu.py plants pairs on r = H and excuses none)
             if bad.any():
                 from scipy.spatial import cKDTree
                 st = orc.download(("ID", "Position", "Type"))
