@@ -643,6 +643,38 @@ int sphmi_sample_points(sphmi_handle* h, int64_t n_points, const double* positio
                         double* weight_out, int64_t* count_out, double* pressure_out, double* density_out, double* velocity_out);
 
 /*
+ * The GRADIENTS of pressure, density, velocity and fill at arbitrary points, on demand: a vorticity slice through a breaking wave, the
+ * strain rate on the panels of a hull, the pressure gradient along a wall, the free-surface normal at the nodes of another code's mesh -
+ * without a download and a neighbour search on the host (csrc/sphmi_point_gradients.h; the cloud is binned as for sphmi_sample_points).
+ * Calling convention, limits, state and errors are those of sphmi_sample_points; what differs is what comes back.  Per point x, over the
+ * Fluid rows j the handle owns with r^2 = ((dx^2 + dy^2) + dz^2) <= H^2 (the cut of sphmi_sample_points), V_j = m0 / rho_j, W and W' the
+ * handle's kernel, g_j = W'(r) (x - x_j) / r, on the state sphmi_download would deliver now, all in fp64, no self term; a row at r = 0
+ * counts in n and the S sums and adds nothing to the G sums:
+ *   weight_out        [n_points]          S        = sum V_j W
+ *   count_out         [n_points]          n        = rows that pass the cut
+ *   sum_pressure_out  [n_points]          SP       = sum V_j P_j W
+ *   sum_density_out   [n_points]          Srho     = sum V_j rho_j W
+ *   sum_velocity_out  [n_points x 3]      Sv[a]    = sum V_j v_j[a] W
+ *   grad_weight_out   [n_points x 3]      G[b]     = sum V_j g_j[b]
+ *   grad_pressure_out [n_points x 3]      GP[b]    = sum V_j P_j g_j[b]
+ *   grad_density_out  [n_points x 3]      Grho[b]  = sum V_j rho_j g_j[b]
+ *   grad_velocity_out [n_points x 3 x 3]  Gv[a][b] = sum V_j v_j[a] g_j[b]      (entry 9 p + 3 a + b)
+ * Every sum is delivered RAW - nothing is divided by S here, unlike sphmi_sample_points: S, n, SP, Srho and Sv are the raw sums behind that
+ * call's outputs, bit for bit.  The caller normalises; the Shepard-corrected difference form grad A ~ (GA - (SA / S) G) / S is exact for a
+ * constant field whatever the particle disorder (sphexample_amd/fields.py: velocity_gradient, vorticity_at, divergence_at, strain_rate,
+ * pressure_gradient, surface_normal_at).  2-D handles write exact zeros to every z slot.  Any output pointer may be NULL.  Outputs are in
+ * the CALLER's order, and a point's result depends on its own coordinates and the state of the handle alone: rows are added in ascending
+ * row order, without atomics.  A point in empty space or outside the particles' cell grid reads zeros; n_points == 0 is legal.
+ *   SPHMI_ERR_STATE, SPHMI_ERR_ARGUMENT, SPHMI_ERR_DEVICE: as sphmi_sample_points (the arena holds 25 doubles per point).
+ * Multi-device handles of one process: every sum is linear in the rows, so every slab samples all points over the rows it owns and the
+ * handle adds the slabs' raw sums in slab order.  (sphmi_particle_fields, the same quantities AT the particles, stays single-device.)
+ */
+int sphmi_sample_point_gradients(sphmi_handle* h, int64_t n_points, const double* positions /* n_points x dims */,
+                                 double* weight_out, int64_t* count_out, double* sum_pressure_out, double* sum_density_out,
+                                 double* sum_velocity_out, double* grad_weight_out, double* grad_pressure_out, double* grad_density_out,
+                                 double* grad_velocity_out);
+
+/*
  * Differential fields AT THE PARTICLES, on demand: vorticity, velocity divergence, the free-surface indicator div r, the free-surface
  * normal, the Shepard sum and the neighbour count of every row - what a post-processor colours a breaking wave by or extracts a free
  * surface from - by a kernel that shares the staged rows among 256 consecutive target rows (csrc/sphmi_particle_fields.h).

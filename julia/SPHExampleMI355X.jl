@@ -351,6 +351,22 @@ function sample_points(P, positions::Matrix{Float64})
                                                       h, Int64(n), pointer(positions), pointer(w), pointer(c), pointer(pp), pointer(rho), pointer(v)))
     return (weight = w, count = c, pressure = pp, density = rho, velocity = v)
 end
+# The RAW kernel and gradient sums at arbitrary points, evaluated on the state the session holds NOW (sphmi_sample_point_gradients):
+# positions is dims × n as for sample_points.  weight S, count n, sum_pressure, sum_density (length n), sum_velocity, grad_weight,
+# grad_pressure, grad_density (3 × n) and grad_velocity (3 × 3 × n, entry [b, a, p] = Σ V_j v_j[a] ∂W/∂x_b: column-major, the derivative
+# axis first).  Nothing is divided by S: ∇A ≈ (GA − (SA / S) · G) / S is the caller's.  Multi-device sessions of one process deliver the
+# sums over all slabs.  Call it from an output callback, after the first step.
+function sample_point_gradients(P, positions::Matrix{Float64})
+    h = SESSIONS[P].h
+    n = size(positions, 2)
+    w = Vector{Float64}(undef, n); c = Vector{Int64}(undef, n); sp = Vector{Float64}(undef, n); sr = Vector{Float64}(undef, n)
+    sv = Matrix{Float64}(undef, 3, n); g = Matrix{Float64}(undef, 3, n); gp = Matrix{Float64}(undef, 3, n); gr = Matrix{Float64}(undef, 3, n)
+    gv = Array{Float64, 3}(undef, 3, 3, n)
+    GC.@preserve positions w c sp sr sv g gp gr gv check(h, ccall((:sphmi_sample_point_gradients, LIB), Cint,
+                                                             (Ptr{Cvoid}, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Int64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+                                                             h, Int64(n), pointer(positions), pointer(w), pointer(c), pointer(sp), pointer(sr), pointer(sv), pointer(g), pointer(gp), pointer(gr), pointer(gv)))
+    return (weight = w, count = c, sum_pressure = sp, sum_density = sr, sum_velocity = sv, grad_weight = g, grad_pressure = gp, grad_density = gr, grad_velocity = gv)
+end
 # Differential fields at the particles, evaluated on the state the session holds NOW (sphmi_particle_fields): row i is row i of the next
 # download.  count[i] rows within H, shepard[i], div_r[i] (≈ D inside, lower at a free surface), div_v[i], normal[:, i] and vorticity[:, i]
 # (3 × n; 2-D: only vorticity[3, :] and normal[1:2, :] are non-zero).  Single-device sessions; call it from an output callback, after the first step.

@@ -641,6 +641,38 @@ class Backend:
         self._check(f(self._h, n, _ptr(x), *[_ptr(out[k]) for k in self.GRID_FIELDS]))
         return {k: v for k, v in out.items() if v is not None}
 
+    # -- gradient sums at arbitrary points, on demand (sphmi_sample_point_gradients) ---------------------------------------------
+    # name → trailing shape, in the order of the C prototype; all float64 but `count`
+    GRADIENT_FIELDS = {"weight": (), "count": (), "sum_pressure": (), "sum_density": (), "sum_velocity": (3,), "grad_weight": (3,),
+                       "grad_pressure": (3,), "grad_density": (3,), "grad_velocity": (3, 3)}
+
+    def has_sample_point_gradients(self) -> bool:
+        return self._has("sample_point_gradients")
+
+    def sample_point_gradients(self, positions, fields=None) -> dict:
+        """The RAW kernel sums and gradient sums at every point of `positions` ([n, dims], up to 2**24 points), evaluated now:
+        `weight` S, `count` n, `sum_pressure`, `sum_density` [n], `sum_velocity` [n, 3], and with g_j = ∇W(x − x_j):
+        `grad_weight` Σ V_j g_j, `grad_pressure`, `grad_density` [n, 3], `grad_velocity` [n, 3, 3] with entry [a, b] =
+        Σ V_j v_j[a] g_j[b].  Nothing is divided by S; ``sphexample_amd.fields`` normalises (`velocity_gradient`,
+        `vorticity_at`, `divergence_at`, `strain_rate`, `pressure_gradient`, `surface_normal_at`).  `fields` names the sums
+        wanted (default: all).  Entry p belongs to ``positions[p]`` and does not depend on the other points of the call;
+        multi-device handles of one process deliver the sums over all slabs.  Call it between `advance` calls, after the
+        first executed step."""
+        x = np.ascontiguousarray(positions, dtype=np.float64)
+        if x.ndim != 2 or x.shape[1] != self.D:
+            raise ValueError(f"sample_point_gradients: positions is shaped [n, {self.D}]")
+        fields = tuple(self.GRADIENT_FIELDS) if fields is None else tuple(fields)
+        unknown = [k for k in fields if k not in self.GRADIENT_FIELDS]
+        if unknown:
+            raise ValueError(f"sample_point_gradients: unknown fields {unknown}")
+        n = len(x)
+        f = self._fn("sample_point_gradients")
+        f.argtypes = [C.c_void_p, C.c_int64] + [C.c_void_p] * 10
+        out = {k: (np.zeros((n,) + shape, dtype=np.int64 if k == "count" else np.float64) if k in fields else None)
+               for k, shape in self.GRADIENT_FIELDS.items()}
+        self._check(f(self._h, n, _ptr(x), *[_ptr(out[k]) for k in self.GRADIENT_FIELDS]))
+        return {k: v for k, v in out.items() if v is not None}
+
     # -- differential fields at the particles, on demand (sphmi_particle_fields) ------------------------------------------------
     PARTICLE_FIELDS = ("count", "shepard", "normal", "div_r", "div_v", "vorticity")
 

@@ -27,6 +27,7 @@
 #include "sphmi_tracers.h"
 #include "sphmi_field_grid.h"
 #include "sphmi_point_cloud.h"
+#include "sphmi_point_gradients.h"
 #include "sphmi_particle_fields.h"
 #include "sphmi_neighbor_list.h"
 #include "sphmi_components.h"
@@ -264,6 +265,7 @@ struct EngineBase {
                              double* density, double* velocity) = 0;
     virtual void sample_points(int64_t n_points, const double* positions, double* weight, int64_t* count, double* pressure, double* density,
                                double* velocity) = 0;
+    virtual void sample_point_gradients(int64_t n_points, const double* positions, const GradientOutputs& out) = 0;
     virtual void particle_fields(int64_t* count, double* shepard, double* normal, double* div_r, double* div_v, double* vorticity) = 0;
     // The results a handle holds between calls (HeldResult, sphmi_results.h): the neighbour list (sphmi_neighbor_list.h), the free
     // surface as a mesh (sphmi_isosurface.h) and the connected bodies of selected rows (sphmi_components.h).  sphmi_advance,
@@ -2305,28 +2307,32 @@ struct Engine final : EngineBase {
 
     // ---- kernel sums at arbitrary points, on demand (sphmi_point_cloud.h) -------------------------------------------------------------
     // Reads what the lattice reads; writes its own buffers and nothing else.  The positions, the plan (block of every point, counts,
-    // offsets, tiles, index) and the arena grow with the call and go back to the device where fg_arena does.
-    DeviceBuf<double> pc_arena, pc_pos;
+    // offsets, tiles, index) and the arena grow with the call and go back to the device where fg_arena does.  The gradients
+    // (sphmi_point_gradients.h) share the positions and the plan and keep an arena of their own, pg_arena.
+    DeviceBuf<double> pc_arena, pg_arena, pc_pos;
     DeviceBuf<int> pc_block, pc_index, pc_count, pc_tcount;
     DeviceBuf<long long> pc_poff, pc_toff, pc_tsum;
     DeviceBuf<PcTile> pc_tiles;
     long long pc_ntiles = 0;                   // of the last launch
     void pc_free() {
-        pc_arena.free(); pc_pos.free(); pc_block.free(); pc_index.free(); pc_count.free(); pc_tcount.free();
+        pc_arena.free(); pg_arena.free(); pc_pos.free(); pc_block.free(); pc_index.free(); pc_count.free(); pc_tcount.free();
         pc_poff.free(); pc_toff.free(); pc_tsum.free(); pc_tiles.free();
     }
     // upload the cloud, bin it and queue the kernel on the engine's stream (a multi-device handle calls it on every slab engine);
-    // n ≥ 1.  `clock` (may be null) gets a mark before the bin, behind it and behind the sampling kernel.
-    void pc_launch(const double* positions, int64_t n, PassClock* clock = nullptr) {
+    // n ≥ 1.  `clock` (may be null) gets a mark before the bin, behind it and behind the sampling kernel.  `gradients`: the same
+    // bin, then k_point_gradients into pg_arena instead of k_point_cloud into pc_arena.
+    void pc_launch(const double* positions, int64_t n, PassClock* clock = nullptr, bool gradients = false) {
+        const char* fn = gradients ? "sphmi_sample_point_gradients" : "sphmi_sample_points";
         HC(hipSetDevice(cfg.device));
         const PcTiling G = pc_tiling(grid.gmin, grid.np, D, cfg.H_inv);
         const long long nblocks = pc_blocks(G);
-        if (nblocks < 1 || nblocks > (long long)grid.ncell) throw EngineError(SPHMI_ERR_STATE, "sphmi_sample_points: the cell grid of the handle cannot be tiled");
+        if (nblocks < 1 || nblocks > (long long)grid.ncell) throw EngineError(SPHMI_ERR_STATE, std::string(fn) + ": the cell grid of the handle cannot be tiled");
         const size_t np = (size_t)n, nb = (size_t)nblocks;
         auto no_memory = [&](size_t bytes) {
-            return text("sphmi_sample_points: no device memory for the arena of %lld points (%zu bytes)", (long long)n, bytes);
+            return text("%s: no device memory for the arena of %lld points (%zu bytes)", fn, (long long)n, bytes);
         };
-        pc_arena.need((size_t)kFgValues * np, no_memory);
+        DeviceBuf<double>& arena = gradients ? pg_arena : pc_arena;
+        arena.need((size_t)(gradients ? kPgValues : kFgValues) * np, no_memory);
         pc_pos.need(np * (size_t)D, no_memory); pc_block.need(np, no_memory); pc_index.need(np, no_memory);
         pc_count.need(nb, no_memory); pc_tcount.need(nb, no_memory); pc_poff.need(nb + 1, no_memory); pc_toff.need(nb + 1, no_memory);
         bounce.h2d(pc_pos.p, positions, np * (size_t)D * 8, stream);
@@ -2339,7 +2345,7 @@ struct Engine final : EngineBase {
         const long long placed = scan64(pc_count.p, (int)nblocks, pc_tsum, pc_poff.p, bounce, stream, no_memory);
         pc_ntiles = scan64(pc_tcount.p, (int)nblocks, pc_tsum, pc_toff.p, bounce, stream, no_memory);
         if (placed != (long long)n || pc_ntiles < 1 || pc_ntiles > (long long)n)
-            throw EngineError(SPHMI_ERR_DEVICE, text("sphmi_sample_points: the plan of %lld points places %lld in %lld tiles", (long long)n, placed, pc_ntiles));
+            throw EngineError(SPHMI_ERR_DEVICE, text("%s: the plan of %lld points places %lld in %lld tiles", fn, (long long)n, placed, pc_ntiles));
         pc_tiles.need((size_t)pc_ntiles, no_memory);
         HC(hipMemsetAsync(pc_count.p, 0, nb * 4, stream));                            // the counts are in poff: the array serves as the cursors
         hipLaunchKernelGGL(k_pc_scatter, dim3(gp), dim3(256), 0, stream, (const int*)pc_block.p, (int)n, (const long long*)pc_poff.p, pc_count.p, pc_index.p);
@@ -2350,15 +2356,19 @@ struct Engine final : EngineBase {
         PointCloudArgs<T> A{};
         A.pk0 = pk0[iA]; A.pk1 = pk1[iA]; A.half0 = pk0[iH]; A.comp = comp[cur];
         A.type = dd_slab ? type[cur] : nullptr; A.cstart = cstart; A.pos = pc_pos.p; A.tiles = pc_tiles.p; A.index = pc_index.p;
-        A.out = pc_arena.p; A.g = grid; A.n_points = n;
+        A.out = arena.p; A.g = grid; A.n_points = n;
         fill_sample_consts(A);
         A.N = N; A.kernel = cfg.kernel;
-        by_dims([&](auto d) { hipLaunchKernelGGL((k_point_cloud<T, decltype(d)::value>), dim3((unsigned)pc_ntiles), dim3(kFgThreads), 0, stream, A); });
+        by_dims([&](auto d) {
+            if (gradients) hipLaunchKernelGGL((k_point_gradients<T, decltype(d)::value>), dim3((unsigned)pc_ntiles), dim3(kFgThreads), 0, stream, A);
+            else hipLaunchKernelGGL((k_point_cloud<T, decltype(d)::value>), dim3((unsigned)pc_ntiles), dim3(kFgThreads), 0, stream, A);
+        });
         HC(hipGetLastError());
         if (clock) clock->mark();
     }
     // one raw sum of the cloud → host, behind the kernel (as fg_fetch)
     void pc_fetch(int f, double* dst, int64_t n) { fetch_result(dst, pc_arena.p + (size_t)f * (size_t)n, (size_t)n * 8); }
+    void pg_fetch(int f, double* dst, int64_t n) { fetch_result(dst, pg_arena.p + (size_t)f * (size_t)n, (size_t)n * 8); }
     void sample_points(int64_t n, const double* positions, double* weight, int64_t* count, double* pressure, double* density, double* velocity) override {
         require_cell_list("sphmi_sample_points", fg_ready(), "(no cell list, no half-step set)");
         check_sample_points(n, positions, D);
@@ -2372,6 +2382,23 @@ struct Engine final : EngineBase {
         clock.report(text("sphmi_sample_points: %lld points, %lld tiles, %.1f lanes filled of %d:", (long long)n, pc_ntiles, (double)n / (double)pc_ntiles, kPcTile),
                      {"bin", "sample", "fetch"});
         G.deliver(count, pressure, density, velocity);
+    }
+    // … and their gradients (sphmi_point_gradients.h): the same checks, the same bin, the raw sums as they are
+    void sample_point_gradients(int64_t n, const double* positions, const GradientOutputs& out) override {
+        require_cell_list("sphmi_sample_point_gradients", fg_ready(), "(no cell list, no half-step set)");
+        check_sample_points(n, positions, D, "sphmi_sample_point_gradients");
+        if (n == 0) return;
+        PassClock clock("SPHMI_POINTS_CLOCK", stream);                     // (tools/point_gradients_cost.py)
+        pc_launch(positions, n, &clock, true);
+        bool wanted[kPgValues];
+        out.wanted(wanted);
+        GridSums G(n, out.weight, wanted);
+        for (int f = 0; f < kPgValues; ++f) if (G.want[f]) pg_fetch(f, G.dst(f), n);
+        clock.mark();
+        HC(hipStreamSynchronize(stream));
+        clock.report(text("sphmi_sample_point_gradients: %lld points, %lld tiles, %.1f lanes filled of %d:", (long long)n, pc_ntiles, (double)n / (double)pc_ntiles, kPcTile),
+                     {"bin", "sample", "fetch"});
+        out.deliver(G);
     }
 
     // ---- differential fields at the particles, on demand (sphmi_particle_fields.h) -------------------------------------------------
@@ -3182,6 +3209,13 @@ static_assert(SPHMI_MAX_SAMPLE_POINTS == sphmi::kMaxSamplePoints, "sphmi_series.
 int sphmi_sample_points(sphmi_handle* h, int64_t n_points, const double* positions, double* weight_out, int64_t* count_out, double* pressure_out,
                         double* density_out, double* velocity_out) {
     SPHMI_GUARD(h, h->e->sample_points(n_points, positions, weight_out, count_out, pressure_out, density_out, velocity_out));
+}
+int sphmi_sample_point_gradients(sphmi_handle* h, int64_t n_points, const double* positions, double* weight_out, int64_t* count_out,
+                                 double* sum_pressure_out, double* sum_density_out, double* sum_velocity_out, double* grad_weight_out,
+                                 double* grad_pressure_out, double* grad_density_out, double* grad_velocity_out) {
+    const sphmi::GradientOutputs out{weight_out, sum_pressure_out, sum_density_out, sum_velocity_out, grad_weight_out, grad_pressure_out,
+                                     grad_density_out, grad_velocity_out, count_out};
+    SPHMI_GUARD(h, h->e->sample_point_gradients(n_points, positions, out));
 }
 int sphmi_particle_fields(sphmi_handle* h, int64_t* count_out, double* shepard_out, double* normal_out, double* div_r_out, double* div_v_out,
                           double* vorticity_out) {

@@ -1776,7 +1776,7 @@ struct MultiEngine final : EngineBase {
         for (auto& r : R) {
             if (!r.e->fg_ready()) continue;                // (a slab that holds no rows has no cell list: it adds nothing)
             HC(hipSetDevice(r.device));
-            for (int f = 0; f < kFgValues; ++f) {
+            for (int f = 0; f < G.values; ++f) {
                 if (!G.want[f]) continue;
                 double* dst = G.dst(f);
                 if (first) { fetch(*r.e, f, dst); continue; }
@@ -1801,6 +1801,21 @@ struct MultiEngine final : EngineBase {
         GridSums G(n, weight, count, pressure, density, velocity);
         add_slab_sums(G, [&](Engine<T>& e, int f, double* dst) { e.pc_fetch(f, dst, n); });
         G.deliver(count, pressure, density, velocity);
+    }
+    // … and their gradients (sphmi_point_gradients.h): every sum is linear in the rows, so the slabs' raw sums add up like the cloud's
+    void sample_point_gradients(int64_t n, const double* positions, const GradientOutputs& out) override {
+        require_one_process("sphmi_sample_point_gradients");
+        bool any = false;
+        for (auto& r : R) any = any || r.e->fg_ready();
+        require_cell_list("sphmi_sample_point_gradients", any, "(no cell list, no half-step set)");
+        check_sample_points(n, positions, D, "sphmi_sample_point_gradients");
+        if (n == 0) return;
+        for (auto& r : R) if (r.e->fg_ready()) r.e->pc_launch(positions, n, nullptr, true);
+        bool wanted[kPgValues];
+        out.wanted(wanted);
+        GridSums G(n, out.weight, wanted);
+        add_slab_sums(G, [&](Engine<T>& e, int f, double* dst) { e.pg_fetch(f, dst, n); });
+        out.deliver(G);
     }
     // Differential fields at the particles (sphmi_particle_fields.h): single-device handles only.  After the corrector a slab's ghost
     // copies hold the half-step state, so a slab cannot see its neighbours' current rows without a halo exchange of its own.

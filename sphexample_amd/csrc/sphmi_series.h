@@ -29,6 +29,7 @@ constexpr int kPrValues = 7;                     // S, SP, Sρ, Sv[3], n
 constexpr int kFgValues = kPrValues;             // S, SP, Sρ, Sv[3], n
 constexpr long long kMaxGridNodes = 1ll << 24;   // SPHMI_MAX_GRID_NODES
 constexpr long long kMaxSamplePoints = 1ll << 24; // SPHMI_MAX_SAMPLE_POINTS
+constexpr int kPgValues = kFgValues + 18;        // the sums of the cloud, then G[3], GP[3], Gρ[3], Gv[3][3] (sphmi_point_gradients.h)
 constexpr int kBgValues = 22;                    // the raw budgets of the fluid (sphmi_budgets.h): thirteen sums, nine extremes
 
 // How two values of slot `slot` of a budget record combine: 0 sum (slots 0 … 12), 1 min, 2 max (13 max |v|², 14 / 15 min / max ρ,
@@ -163,12 +164,13 @@ inline int64_t check_grid_lattice(const double* origin, const double* spacing, c
     return nodes;
 }
 
-// sphmi_sample_points: the argument errors every kind of handle reports alike
-inline void check_sample_points(int64_t n_points, const double* positions, int dims) {
-    if (n_points < 0 || n_points > kMaxSamplePoints) throw EngineError(SPHMI_ERR_ARGUMENT, "sphmi_sample_points: n_points out of range [0, SPHMI_MAX_SAMPLE_POINTS]");
-    if (n_points > 0 && !positions) throw EngineError(SPHMI_ERR_ARGUMENT, "sphmi_sample_points: null positions");
+// sphmi_sample_points and sphmi_sample_point_gradients (`fn`): the argument errors every kind of handle reports alike
+inline void check_sample_points(int64_t n_points, const double* positions, int dims, const char* fn = "sphmi_sample_points") {
+    const std::string name(fn);
+    if (n_points < 0 || n_points > kMaxSamplePoints) throw EngineError(SPHMI_ERR_ARGUMENT, name + ": n_points out of range [0, SPHMI_MAX_SAMPLE_POINTS]");
+    if (n_points > 0 && !positions) throw EngineError(SPHMI_ERR_ARGUMENT, name + ": null positions");
     for (int64_t k = 0; k < n_points * dims; ++k)
-        if (!std::isfinite(positions[k])) throw EngineError(SPHMI_ERR_ARGUMENT, "sphmi_sample_points: non-finite coordinate at point " + std::to_string(k / dims));
+        if (!std::isfinite(positions[k])) throw EngineError(SPHMI_ERR_ARGUMENT, name + ": non-finite coordinate at point " + std::to_string(k / dims));
 }
 
 // The series of an observer that records once per executed step: what the batches delivered since the last read, the newest
@@ -301,11 +303,15 @@ inline void deliver_map_vectors(int64_t bins, const double* c0, const double* c1
 
 // The host side of sphmi_sample_grid and sphmi_sample_points: the raw sums { S, SP, Sρ, Sv[3], n } of the lattice
 // (sphmi_field_grid.h) or the cloud (sphmi_point_cloud.h), `nodes` of either, the ones the requested outputs need.  S lands in weight_out itself when that is asked for; the means are formed here, 0 where n == 0.
+// sphmi_sample_point_gradients (sphmi_point_gradients.h) carries `values` = kPgValues sums per point in the same arrays — the
+// first seven are the cloud's — and hands them out RAW (the second constructor, deliver_raw): a multi-device handle adds both kinds
+// with one loop.
 struct GridSums {
     int64_t nodes = 0;
+    int values = kFgValues;                    // sums per node
     double* S = nullptr;                       // weight_out, or s[0]
-    std::vector<double> s[kFgValues];
-    bool want[kFgValues] = {};
+    std::vector<double> s[kPgValues];
+    bool want[kPgValues] = {};
     double* dst(int f) { return f == 0 ? S : s[f].data(); }
     GridSums(int64_t n, double* weight, const int64_t* count, const double* pressure, const double* density, const double* velocity) : nodes(n) {
         const bool means = pressure || density || velocity;
@@ -324,6 +330,43 @@ struct GridSums {
             if (density) density[k] = kernel_mean(s[2][k], S[k], some);
             if (velocity) for (int d = 0; d < 3; ++d) velocity[3 * k + d] = kernel_mean(s[3 + d][k], S[k], some);
         }
+    }
+    // the raw sums of the gradients: slot f is wanted where wanted[f]; S goes straight into weight_out
+    GridSums(int64_t n, double* weight, const bool (&wanted)[kPgValues]) : nodes(n), values(kPgValues) {
+        for (int f = 0; f < kPgValues; ++f) {
+            want[f] = wanted[f];
+            if (want[f] && !(f == 0 && weight)) s[f].assign((size_t)n, 0.0);
+        }
+        S = weight ? weight : s[0].data();
+    }
+    // slots [first, first + width) → out [nodes × width], as they are; out may be null
+    void deliver_raw(int first, int width, double* out) const {
+        if (!out) return;
+        for (int c = 0; c < width; ++c) {
+            const double* v = s[first + c].data();
+            for (int64_t k = 0; k < nodes; ++k) out[(size_t)width * k + c] = v[k];
+        }
+    }
+    void deliver_count(int64_t* count) const {
+        if (count) for (int64_t k = 0; k < nodes; ++k) count[k] = (int64_t)s[6][k];
+    }
+};
+
+// sphmi_sample_point_gradients: the slots of kPgValues the caller's outputs need (any may be null)
+struct GradientOutputs {
+    double *weight, *sum_pressure, *sum_density, *sum_velocity, *grad_weight, *grad_pressure, *grad_density, *grad_velocity;
+    int64_t* count;
+    void wanted(bool (&w)[kPgValues]) const {
+        for (int f = 0; f < kPgValues; ++f) w[f] = false;
+        w[0] = weight != nullptr; w[1] = sum_pressure != nullptr; w[2] = sum_density != nullptr;
+        w[3] = w[4] = w[5] = sum_velocity != nullptr; w[6] = count != nullptr;
+        for (int b = 0; b < 3; ++b) { w[7 + b] = grad_weight != nullptr; w[10 + b] = grad_pressure != nullptr; w[13 + b] = grad_density != nullptr; }
+        for (int c = 0; c < 9; ++c) w[16 + c] = grad_velocity != nullptr;
+    }
+    void deliver(const GridSums& G) const {
+        G.deliver_count(count);
+        G.deliver_raw(1, 1, sum_pressure); G.deliver_raw(2, 1, sum_density); G.deliver_raw(3, 3, sum_velocity);
+        G.deliver_raw(7, 3, grad_weight); G.deliver_raw(10, 3, grad_pressure); G.deliver_raw(13, 3, grad_density); G.deliver_raw(16, 9, grad_velocity);
     }
 };
 

@@ -132,5 +132,79 @@ def surface_load(vertices, triangles, pressure, about=None):
     return force, moment
 
 
+# ---- gradients at arbitrary points, from the raw sums of ``Backend.sample_point_gradients`` ----------------------------------------
+# The device delivers, per point, S = Σ V_j W, SA = Σ V_j A_j W and GA[b] = Σ V_j A_j ∂W/∂x_b for A = 1 (G), the pressure, the density
+# and every velocity component.  GA alone is the gradient of the kernel interpolant of A — it carries the error of the particle
+# disorder and, at a free surface, the gradient of the fill itself.  The Shepard-corrected difference form
+#     ∇A ≈ (GA − (SA / S) · G) / S            (= Σ V_j (A_j − Ā) ∇W / S with Ā = SA / S the Shepard mean at the point)
+# is exact for a constant A whatever the disorder and the cut of the support; it is what every helper below forms, wherever
+# S ≥ `min_weight`, and NaN elsewhere (too little fluid within H to speak of a gradient).
+MIN_GRADIENT_WEIGHT = 0.1
+
+
+def _corrected_gradient(sums, ga: str, sa: str, min_weight: float) -> np.ndarray:
+    S = np.asarray(sums["weight"], dtype=np.float64)
+    G = np.asarray(sums["grad_weight"], dtype=np.float64)
+    GA = np.asarray(sums[ga], dtype=np.float64)
+    SA = np.asarray(sums[sa], dtype=np.float64)
+    n = len(S)
+    if G.shape != (n, 3) or GA.shape[:1] != (n,) or GA.shape[-1] != 3 or SA.shape != GA.shape[:-1]:
+        raise ValueError(f"the sums of sample_point_gradients are needed: weight [n], grad_weight [n, 3], {sa} and {ga} [.., 3]")
+    ok = S >= float(min_weight)
+    Ss = np.where(ok, S, 1.0)
+    lead = (n,) + (1,) * (GA.ndim - 1)
+    mean = SA / Ss.reshape((n,) + (1,) * (SA.ndim - 1))
+    out = (GA - mean[..., None] * G.reshape((n,) + (1,) * (GA.ndim - 2) + (3,))) / Ss.reshape(lead)
+    out[~ok] = np.nan
+    return out
+
+
+def velocity_gradient(sums, min_weight: float = MIN_GRADIENT_WEIGHT) -> np.ndarray:
+    """``L[p, a, b] = ∂v_a/∂x_b`` at every point, ``[n, 3, 3]``, from the dict of ``Backend.sample_point_gradients`` (the keys
+    `weight`, `grad_weight`, `sum_velocity`, `grad_velocity`): the Shepard-corrected difference form where
+    ``weight >= min_weight``, NaN elsewhere.  2-D: the z row and column are zero."""
+    return _corrected_gradient(sums, "grad_velocity", "sum_velocity", min_weight)
+
+
+def vorticity_at(sums, min_weight: float = MIN_GRADIENT_WEIGHT) -> np.ndarray:
+    """``ω = ∇ × v`` at every point, ``[n, 3]`` (2-D: only ω_z is non-zero); a rigid rotation v = Ω × x gives 2Ω, the sign of
+    ``Backend.particle_fields``."""
+    L = velocity_gradient(sums, min_weight)
+    return np.stack([L[:, 2, 1] - L[:, 1, 2], L[:, 0, 2] - L[:, 2, 0], L[:, 1, 0] - L[:, 0, 1]], axis=1)
+
+
+def divergence_at(sums, min_weight: float = MIN_GRADIENT_WEIGHT) -> np.ndarray:
+    """``∇·v`` at every point, ``[n]``: the trace of `velocity_gradient`."""
+    L = velocity_gradient(sums, min_weight)
+    return L[:, 0, 0] + L[:, 1, 1] + L[:, 2, 2]
+
+
+def strain_rate(sums, min_weight: float = MIN_GRADIENT_WEIGHT) -> np.ndarray:
+    """The rate-of-strain tensor ``½ (L + Lᵀ)`` at every point, ``[n, 3, 3]`` — times 2μ the viscous stress on a panel."""
+    L = velocity_gradient(sums, min_weight)
+    return 0.5 * (L + np.swapaxes(L, 1, 2))
+
+
+def pressure_gradient(sums, min_weight: float = MIN_GRADIENT_WEIGHT) -> np.ndarray:
+    """``∇P`` at every point, ``[n, 3]`` (the keys `weight`, `grad_weight`, `sum_pressure`, `grad_pressure`)."""
+    return _corrected_gradient(sums, "grad_pressure", "sum_pressure", min_weight)
+
+
+def surface_normal_at(sums, min_weight: float = MIN_GRADIENT_WEIGHT) -> np.ndarray:
+    """The unit normal OUT of the fluid at every point, ``[n, 3]``: ``−G / |G|`` with G the gradient of the colour function
+    Σ V_j W, which points into the fluid where the support is cut off.  NaN where ``weight < min_weight`` or G vanishes
+    (deep inside the fluid G is small and its direction noise: use it near the surface, say ``weight`` below 0.9)."""
+    S = np.asarray(sums["weight"], dtype=np.float64)
+    G = np.asarray(sums["grad_weight"], dtype=np.float64)
+    if G.shape != (len(S), 3):
+        raise ValueError("surface_normal_at: weight [n] and grad_weight [n, 3] are needed")
+    norm = np.sqrt((G * G).sum(axis=1))
+    ok = (S >= float(min_weight)) & (norm > 0.0)
+    out = -G / np.where(ok, norm, 1.0)[:, None]
+    out[~ok] = np.nan
+    return out
+
+
 __all__ = ["grid_axes", "grid_nodes", "surface_height", "free_surface_mask", "FREE_SURFACE_DIV_R", "segment", "triangle_centroids",
-           "surface_load"]
+           "surface_load", "MIN_GRADIENT_WEIGHT", "velocity_gradient", "vorticity_at", "divergence_at", "strain_rate",
+           "pressure_gradient", "surface_normal_at"]

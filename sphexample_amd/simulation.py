@@ -46,7 +46,8 @@ def RunSimulation(*, SimGeometry=None, SimMetaData: SimulationMetaData, SimConst
                   device_float_bytes: int = 0, device: int = 0, backend_factory=None,
                   async_output: bool = False, group_forces=None, probes=None, field_grid=None,
                   particle_fields=None, budgets: bool = False, neighbor_list: bool = False, isosurface=None, components=None,
-                  flow_boxes=None, envelopes=None, maps=None, tracers=None, sample_points=None) -> List[float]:
+                  flow_boxes=None, envelopes=None, maps=None, tracers=None, sample_points=None,
+                  sample_point_gradients=None) -> List[float]:
     """Same keyword signature as the reference (src/SPHCellList.jl:808-817); returns the list of
     time steps the reference collects in ``TimeSteps`` (:823,:884).  ``SimParticles`` is updated in
     place at every output time, in the engine's cell-sorted order, as the reference's is.
@@ -125,7 +126,12 @@ def RunSimulation(*, SimGeometry=None, SimMetaData: SimulationMetaData, SimConst
     (``Backend.sample_points``; ``sphexample_amd.fields`` forms panel centroids and integrates a surface load) and ``on_output``
     receives the dict — ``weight``, ``count``, ``pressure``, ``density`` [n], ``velocity`` [n, 3] — as its last argument, behind the
     tracers (``None`` at the first call, which precedes the first step).  ``None`` (default): nothing is sampled and the callback
-    keeps its arguments."""
+    keeps its arguments.
+
+    ``sample_point_gradients=positions`` ([n, dims]): at every output the raw kernel and gradient sums are sampled at those points
+    (``Backend.sample_point_gradients``; ``sphexample_amd.fields`` turns them into the velocity gradient, vorticity, divergence,
+    strain rate, pressure gradient and free-surface normal) and ``on_output`` receives the dict as its last argument, behind
+    ``sample_points`` (``None`` at the first call).  ``None`` (default): nothing is sampled and the callback keeps its arguments."""
     if SimMetaData.BMode.__name__ == "SimpleMDBC":
         LoadMDBCNormals(SimParticles, ParticleNormalsPath)                       # :827
     host_bytes = SimParticles.Position.dtype.itemsize
@@ -198,6 +204,9 @@ def RunSimulation(*, SimGeometry=None, SimMetaData: SimulationMetaData, SimConst
     if sample_points is not None:
         cloud = np.ascontiguousarray(sample_points, dtype=np.float64).reshape(-1, SimMetaData.Dimensions)
         extras.append((None, lambda: eng.sample_points(cloud)))                  # (the state of this output, like the field grid)
+    if sample_point_gradients is not None:
+        gradient_cloud = np.ascontiguousarray(sample_point_gradients, dtype=np.float64).reshape(-1, SimMetaData.Dimensions)
+        extras.append((None, lambda: eng.sample_point_gradients(gradient_cloud)))
     none_yet = tuple(first for first, _ in extras)
     emit = lambda meta, samples: on_output(meta, SimParticles, *samples)         # noqa: E731
     if on_output:
