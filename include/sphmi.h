@@ -675,6 +675,53 @@ int sphmi_sample_point_gradients(sphmi_handle* h, int64_t n_points, const double
                                  double* grad_velocity_out);
 
 /*
+ * WHERE ALONG A LINE DOES THE WATER BEGIN, on demand: the first crossing of S = level along rays - the water level at a gauge, the run-up
+ * along a slope, the wetted height on an obstacle, the depth image a viewer renders from - found on the device by a march and a
+ * subdivision instead of columns of fixed probes, a sample of every point of every line or a whole lattice (csrc/sphmi_rays.h).
+ *   Synchronous, called between sphmi_advance calls like sphmi_sample_points; it changes no state a later step, download, column
+ *   download, series read or other on-demand result reads, and leaves a download begun with sphmi_download_begin alone.
+ *   Ray r: origins / directions [n_rays x dims], t_begin / t_end [n_rays].  At the parameter t the point is x[a] = o[a] + t d[a], one
+ *   multiply then one add, not fused; d need not be a unit vector, t and step are in units of |d|.  At x the sums are those of
+ *   sphmi_sample_point_gradients, bit for bit: n, S, SP, Srho, Sv over the Fluid rows the handle owns with
+ *   r^2 = ((dx^2 + dy^2) + dz^2) <= H^2 on the state sphmi_download would deliver now, fp64, ascending row order, no self term.
+ *   inside(t) is S(t) >= level; a point outside the particles' cell grid reads zeros and is outside.
+ *   March: K = (int64) ceil((t_end - t_begin) / step) in fp64; t_k = t_begin + (double)k step for k < K, t_K = t_end exactly.  The
+ *   crossing is the smallest k in 1 .. K at which the two ends of the interval disagree the way `mode` asks - SPHMI_RAY_ENTER:
+ *   !inside(t_(k-1)) && inside(t_k); SPHMI_RAY_LEAVE: the reverse; SPHMI_RAY_ANY: either.
+ *   Refinement: from (a, b) = (t_(k-1), t_k), SPHMI_RAY_REFINE_ROUNDS rounds of: delta = (b - a) * 0.015625; u_m = a + (double)m delta
+ *   for m = 1 .. 63, u_0 = a, u_64 = b; the new bracket is (u_(m-1), u_m) for the smallest m in 1 .. 64 whose side differs from the side
+ *   of a.  A round with delta == 0 leaves the bracket as it is.  Four rounds narrow the interval by 2^24.
+ *   status_out   [n_rays]      bit 0: a crossing was found; bit 1: inside(t_0)
+ *   interval_out [n_rays]      k, or -1
+ *   bracket_out  [n_rays x 2]  the final (a, b)
+ *   point_out    [n_rays x 3]  x at the INSIDE end of the bracket - b for an entering crossing, a for a leaving one - and there
+ *   weight_out, count_out, sum_pressure_out, sum_density_out [n_rays], sum_velocity_out [n_rays x 3]: S, n, SP, Srho, Sv, RAW as
+ *   sphmi_sample_point_gradients delivers them at point_out; the record always describes fluid, S >= level.
+ *   A ray without a crossing delivers NaN brackets and points and zero sums.  2-D handles write exact zeros to every z slot.  Any output
+ *   pointer may be NULL.  Outputs are in the CALLER's order, and a ray's result depends on its own arguments and the state of the handle
+ *   alone.  n_rays == 0 is legal; t_end == t_begin is legal and finds no crossing.  A hit behind the first is the caller's: cast again
+ *   from bracket[1].
+ *   SPHMI_ERR_STATE: as sphmi_particle_fields - before the upload; before the first executed step since the upload or generator; handles
+ *     with H < h; rank-mode handles; multi-device handles (a crossing needs the slabs' COMBINED S at every evaluation of the search,
+ *     which is not built).
+ *   SPHMI_ERR_ARGUMENT: null origins, directions, t_begin or t_end with n_rays > 0; n_rays < 0 or above SPHMI_MAX_RAYS; a coordinate or
+ *     parameter that is not finite (the text names the first such ray); a zero direction; t_end < t_begin; step or level not finite
+ *     or <= 0; K above SPHMI_MAX_RAY_POINTS; an unknown mode.
+ *   SPHMI_ERR_DEVICE: the device cannot hold the arena (2 dims + 15 words of 8 bytes and 2 of 4 per ray); the handle stays usable.
+ */
+#define SPHMI_MAX_RAYS            (1 << 20)
+#define SPHMI_MAX_RAY_POINTS      (1 << 16)     /* march intervals per ray */
+#define SPHMI_RAY_REFINE_ROUNDS   4
+enum { SPHMI_RAY_ENTER = 0, SPHMI_RAY_LEAVE = 1, SPHMI_RAY_ANY = 2 };
+int sphmi_cast_rays(sphmi_handle* h, int64_t n_rays,
+                    const double* origins /* n x dims */, const double* directions /* n x dims */,
+                    const double* t_begin /* n */, const double* t_end /* n */,
+                    double step, double level, int32_t mode,
+                    int32_t* status_out /* n */, int64_t* interval_out /* n */, double* bracket_out /* n x 2 */,
+                    double* point_out /* n x 3 */, double* weight_out, int64_t* count_out,
+                    double* sum_pressure_out, double* sum_density_out, double* sum_velocity_out /* n x 3 */);
+
+/*
  * Differential fields AT THE PARTICLES, on demand: vorticity, velocity divergence, the free-surface indicator div r, the free-surface
  * normal, the Shepard sum and the neighbour count of every row - what a post-processor colours a breaking wave by or extracts a free
  * surface from - by a kernel that shares the staged rows among 256 consecutive target rows (csrc/sphmi_particle_fields.h).

@@ -367,6 +367,28 @@ function sample_point_gradients(P, positions::Matrix{Float64})
                                                              h, Int64(n), pointer(positions), pointer(w), pointer(c), pointer(sp), pointer(sr), pointer(sv), pointer(g), pointer(gp), pointer(gr), pointer(gv)))
     return (weight = w, count = c, sum_pressure = sp, sum_density = sr, sum_velocity = sv, grad_weight = g, grad_pressure = gp, grad_density = gr, grad_velocity = gv)
 end
+# The first crossing of S = level along rays, found on the state the session holds NOW (sphmi_cast_rays): origins and directions are
+# dims × n, t_end a number or a vector of length n; step is the march step in units of |d| (say h / 2); mode is :enter, :leave or :any.  status (bit 0: found, bit 1:
+# the ray starts inside), interval (k, or −1), bracket (2 × n), point (3 × n: the inside end), weight, count, sum_pressure, sum_density
+# (length n) and sum_velocity (3 × n) — the raw sums of sample_point_gradients at point.  NaN brackets and points where nothing was hit.
+# Single-device sessions; call it from an output callback, after the first step.
+function cast_rays(P, origins::Matrix{Float64}, directions::Matrix{Float64}, t_end; step, t_begin = 0.0, level = 0.5, mode = :enter)
+    h = SESSIONS[P].h
+    n = size(origins, 2)
+    size(directions) == size(origins) || error("cast_rays: origins and directions are both dims × n")
+    tb = t_begin isa Number ? fill(Float64(t_begin), n) : Vector{Float64}(t_begin)
+    te = t_end isa Number ? fill(Float64(t_end), n) : Vector{Float64}(t_end)
+    (length(tb) == n && length(te) == n) || error("cast_rays: t_begin and t_end are numbers or vectors of length n")
+    dt = Float64(step)
+    md = Int32(Dict(:enter => 0, :leave => 1, :any => 2)[mode])
+    st = Vector{Int32}(undef, n); iv = Vector{Int64}(undef, n); br = Matrix{Float64}(undef, 2, n); pt = Matrix{Float64}(undef, 3, n)
+    w = Vector{Float64}(undef, n); c = Vector{Int64}(undef, n); sp = Vector{Float64}(undef, n); sr = Vector{Float64}(undef, n)
+    sv = Matrix{Float64}(undef, 3, n)
+    GC.@preserve origins directions tb te st iv br pt w c sp sr sv check(h, ccall((:sphmi_cast_rays, LIB), Cint,
+                                                             (Ptr{Cvoid}, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Float64, Float64, Int32, Ptr{Int32}, Ptr{Int64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+                                                             h, Int64(n), pointer(origins), pointer(directions), pointer(tb), pointer(te), dt, Float64(level), md, pointer(st), pointer(iv), pointer(br), pointer(pt), pointer(w), pointer(c), pointer(sp), pointer(sr), pointer(sv)))
+    return (status = st, interval = iv, bracket = br, point = pt, weight = w, count = c, sum_pressure = sp, sum_density = sr, sum_velocity = sv)
+end
 # Differential fields at the particles, evaluated on the state the session holds NOW (sphmi_particle_fields): row i is row i of the next
 # download.  count[i] rows within H, shepard[i], div_r[i] (≈ D inside, lower at a free surface), div_v[i], normal[:, i] and vorticity[:, i]
 # (3 × n; 2-D: only vorticity[3, :] and normal[1:2, :] are non-zero).  Single-device sessions; call it from an output callback, after the first step.

@@ -21,6 +21,10 @@ MAX_FORCE_GROUPS = 16
 MAX_PROBES = 1024
 MAX_GRID_NODES = 1 << 24
 MAX_SAMPLE_POINTS = 1 << 24
+MAX_RAYS = 1 << 20
+MAX_RAY_POINTS = 1 << 16
+RAY_REFINE_ROUNDS = 4
+RAY_ENTER, RAY_LEAVE, RAY_ANY = 0, 1, 2
 NEIGHBORS_FULL, NEIGHBORS_HALF = 0, 1
 
 OK, ERR_ARGUMENT, ERR_DEVICE, ERR_NUMERIC, ERR_DOMAIN, ERR_STATE = range(6)
@@ -671,6 +675,46 @@ class Backend:
         out = {k: (np.zeros((n,) + shape, dtype=np.int64 if k == "count" else np.float64) if k in fields else None)
                for k, shape in self.GRADIENT_FIELDS.items()}
         self._check(f(self._h, n, _ptr(x), *[_ptr(out[k]) for k in self.GRADIENT_FIELDS]))
+        return {k: v for k, v in out.items() if v is not None}
+
+    # -- the first crossing of S = level along rays, on demand (sphmi_cast_rays) ---------------------------------------------------
+    # name → (dtype, trailing shape), in the order of the C prototype's outputs
+    RAY_FIELDS = {"status": (np.int32, ()), "interval": (np.int64, ()), "bracket": (np.float64, (2,)), "point": (np.float64, (3,)),
+                  "weight": (np.float64, ()), "count": (np.int64, ()), "sum_pressure": (np.float64, ()), "sum_density": (np.float64, ()),
+                  "sum_velocity": (np.float64, (3,))}
+    RAY_MODES = {"enter": RAY_ENTER, "leave": RAY_LEAVE, "any": RAY_ANY}
+
+    def has_cast_rays(self) -> bool:
+        return self._has("cast_rays")
+
+    def cast_rays(self, origins, directions, t_end, t_begin=0.0, step=None, level=0.5, mode="enter", fields=None) -> dict:
+        """Where along each ray ``origins[r] + t * directions[r]`` ([n, dims]; `t_begin`, `t_end` numbers or [n]; t and `step` in
+        units of |direction|) does ``S >= level`` begin (`mode` "enter"), end ("leave") or change ("any"): a march in steps of
+        `step` (default h / 2) to the first such interval, then four subdivisions by 64.  A dict: `status` (bit 0 found, bit 1
+        the ray starts inside), `interval` (k, or −1), `bracket` [n, 2], `point` [n, 3] (the inside end of the bracket) and the
+        raw sums of ``sample_point_gradients`` there: `weight`, `count`, `sum_pressure`, `sum_density` [n], `sum_velocity`
+        [n, 3].  NaN brackets and points and zero sums where nothing was hit.  `fields` names the outputs wanted (default: all).
+        A ray's result depends on its own arguments and the state alone.  Single-device handles; call it between `advance`
+        calls, after the first executed step.  ``sphexample_amd.rays`` builds gauges and depth images on it."""
+        o = np.ascontiguousarray(origins, dtype=np.float64)
+        d = np.ascontiguousarray(directions, dtype=np.float64)
+        if o.ndim != 2 or o.shape[1] != self.D or d.shape != o.shape:
+            raise ValueError(f"cast_rays: origins and directions are both shaped [n, {self.D}]")
+        n = len(o)
+        tb = np.ascontiguousarray(np.broadcast_to(np.asarray(t_begin, dtype=np.float64), (n,)))
+        te = np.ascontiguousarray(np.broadcast_to(np.asarray(t_end, dtype=np.float64), (n,)))
+        if mode not in self.RAY_MODES:
+            raise ValueError(f"cast_rays: mode is one of {sorted(self.RAY_MODES)}")
+        fields = tuple(self.RAY_FIELDS) if fields is None else tuple(fields)
+        unknown = [k for k in fields if k not in self.RAY_FIELDS]
+        if unknown:
+            raise ValueError(f"cast_rays: unknown fields {unknown}")
+        step = 0.5 * float(self.cfg.h) if step is None else float(step)
+        f = self._fn("cast_rays")
+        f.argtypes = [C.c_void_p, C.c_int64] + [C.c_void_p] * 4 + [C.c_double, C.c_double, C.c_int32] + [C.c_void_p] * 9
+        out = {k: (np.zeros((n,) + shape, dtype=dt) if k in fields else None) for k, (dt, shape) in self.RAY_FIELDS.items()}
+        self._check(f(self._h, n, _ptr(o), _ptr(d), _ptr(tb), _ptr(te), step, float(level), self.RAY_MODES[mode],
+                      *[_ptr(out[k]) for k in self.RAY_FIELDS]))
         return {k: v for k, v in out.items() if v is not None}
 
     # -- differential fields at the particles, on demand (sphmi_particle_fields) ------------------------------------------------

@@ -28,6 +28,7 @@
 #include "sphmi_field_grid.h"
 #include "sphmi_point_cloud.h"
 #include "sphmi_point_gradients.h"
+#include "sphmi_rays.h"
 #include "sphmi_particle_fields.h"
 #include "sphmi_neighbor_list.h"
 #include "sphmi_components.h"
@@ -266,6 +267,7 @@ struct EngineBase {
     virtual void sample_points(int64_t n_points, const double* positions, double* weight, int64_t* count, double* pressure, double* density,
                                double* velocity) = 0;
     virtual void sample_point_gradients(int64_t n_points, const double* positions, const GradientOutputs& out) = 0;
+    virtual void cast_rays(int64_t n_rays, const RayCall& c) = 0;
     virtual void particle_fields(int64_t* count, double* shepard, double* normal, double* div_r, double* div_v, double* vorticity) = 0;
     // The results a handle holds between calls (HeldResult, sphmi_results.h): the neighbour list (sphmi_neighbor_list.h), the free
     // surface as a mesh (sphmi_isosurface.h) and the connected bodies of selected rows (sphmi_components.h).  sphmi_advance,
@@ -565,7 +567,7 @@ struct Engine final : EngineBase {
         for (auto& e : host_pinned) (void)hipHostUnregister(e.first);
         (void)hipFree(out_arena);
         (void)hipFree(col_arena); (void)hipFree(col_store); (void)hipFree(col_base[0]); (void)hipFree(col_base[1]);
-        gf_release(); pr_release(); bg_release(); fl_release(); en_release(); mp_release(); tr_release(); fg_arena.free(); pc_free(); pf_arena.free(); nl_free(); iso_free(); cc_free();
+        gf_release(); pr_release(); bg_release(); fl_release(); en_release(); mp_release(); tr_release(); fg_arena.free(); pc_free(); ry_free(); pf_arena.free(); nl_free(); iso_free(); cc_free();
         (void)hipFree(slot); (void)hipFree(tmp_idx); (void)hipFree(perm);
         for (int k = 0; k < 2; ++k) { (void)hipFree(tile_cost[k]); (void)hipFree(tile_order[k]); }
         (void)hipFree(kout_d); (void)hipFree(tile_work_d); (void)hipFree(tile_work1_d); (void)hipFree(xcd_clock_d); (void)hipHostFree(xcd_clock_h);
@@ -2401,6 +2403,55 @@ struct Engine final : EngineBase {
         out.deliver(G);
     }
 
+    // ---- the first crossing of S = level along rays, on demand (sphmi_rays.h) ---------------------------------------------------------
+    // Reads what the cloud reads; writes its own two buffers and nothing else.  ry_arena holds, in 8-byte words per ray, the inputs
+    // { origin[D], direction[D], t_begin, t_end } and the outputs { interval, bracket[2], point[3], S, n, SP, Sρ, Sv[3] } laid out as
+    // the caller receives them; ry_words the march intervals and the status.
+    DeviceBuf<double> ry_arena;
+    DeviceBuf<int> ry_words;
+    void ry_free() { ry_arena.free(); ry_words.free(); }
+    void cast_rays(int64_t n, const RayCall& c) override {
+        require_cell_list("sphmi_cast_rays", fg_ready(), "(no cell list, no half-step set)");
+        char msg[200];
+        std::vector<int> K(n > 0 && n <= kMaxRays ? (size_t)n : 0);       // the march intervals of every ray, from the check (a count out of range is refused before one is written)
+        if (!ray_check(n, c.origins, c.directions, c.t_begin, c.t_end, c.step, c.level, c.mode, D, K.data(), msg, sizeof(msg)))
+            throw EngineError(SPHMI_ERR_ARGUMENT, msg);
+        if (n == 0) return;
+        HC(hipSetDevice(cfg.device));
+        const size_t nr = (size_t)n, d = (size_t)D;
+        auto no_memory = [&](size_t bytes) { return text("sphmi_cast_rays: no device memory for the arena of %lld rays (%zu bytes)", (long long)n, bytes); };
+        ry_arena.need((2 * d + 2 + 13) * nr, no_memory);
+        ry_words.need(2 * nr, no_memory);
+        PassClock clock("SPHMI_RAYS_CLOCK", stream);                       // (tools/rays_cost.py)
+        clock.mark();
+        double* const a = ry_arena.p;
+        RayArgs<T> A{};
+        A.org = a; A.dir = a + d * nr; A.t_begin = a + 2 * d * nr; A.t_end = A.t_begin + nr;
+        double* const o = a + (2 * d + 2) * nr;
+        A.interval = (long long*)o; A.bracket = o + nr; A.point = o + 3 * nr; A.S = o + 6 * nr; A.count = (long long*)(o + 7 * nr);
+        A.SP = o + 8 * nr; A.Sr = o + 9 * nr; A.Sv = o + 10 * nr;
+        A.K = ry_words.p; A.status = ry_words.p + nr;
+        bounce.h2d((void*)A.org, c.origins, d * nr * 8, stream); bounce.h2d((void*)A.dir, c.directions, d * nr * 8, stream);
+        bounce.h2d((void*)A.t_begin, c.t_begin, nr * 8, stream); bounce.h2d((void*)A.t_end, c.t_end, nr * 8, stream);
+        bounce.h2d(ry_words.p, K.data(), nr * 4, stream);
+        clock.mark();
+        A.pk0 = pk0[iA]; A.pk1 = pk1[iA]; A.half0 = pk0[iH]; A.comp = comp[cur];
+        A.type = dd_slab ? type[cur] : nullptr; A.cstart = cstart; A.g = grid; A.n_rays = n;
+        fill_sample_consts(A);
+        A.N = N; A.kernel = cfg.kernel; A.mode = c.mode; A.step = c.step; A.level = c.level;
+        const unsigned nb = (unsigned)((nr * 64 + kRayThreads - 1) / kRayThreads);
+        by_dims([&](auto dd) { hipLaunchKernelGGL((k_cast_rays<T, decltype(dd)::value>), dim3(nb), dim3(kRayThreads), 0, stream, A); });
+        HC(hipGetLastError());
+        clock.mark();
+        auto fetch = [&](void* dst, const void* src, size_t bytes) { if (dst) fetch_result(dst, src, bytes); };
+        fetch(c.status, A.status, nr * 4); fetch(c.interval, A.interval, nr * 8); fetch(c.bracket, A.bracket, 2 * nr * 8);
+        fetch(c.point, A.point, 3 * nr * 8); fetch(c.weight, A.S, nr * 8); fetch(c.count, A.count, nr * 8);
+        fetch(c.sum_pressure, A.SP, nr * 8); fetch(c.sum_density, A.Sr, nr * 8); fetch(c.sum_velocity, A.Sv, 3 * nr * 8);
+        clock.mark();
+        HC(hipStreamSynchronize(stream));
+        clock.report(text("sphmi_cast_rays: %lld rays:", (long long)n), {"upload", "cast", "fetch"});
+    }
+
     // ---- differential fields at the particles, on demand (sphmi_particle_fields.h) -------------------------------------------------
     // Reads the current set, the low words, `cstart` and the grid of the last rebuild; writes its own arena and nothing else.
     DeviceBuf<double> pf_arena;
@@ -3216,6 +3267,13 @@ int sphmi_sample_point_gradients(sphmi_handle* h, int64_t n_points, const double
     const sphmi::GradientOutputs out{weight_out, sum_pressure_out, sum_density_out, sum_velocity_out, grad_weight_out, grad_pressure_out,
                                      grad_density_out, grad_velocity_out, count_out};
     SPHMI_GUARD(h, h->e->sample_point_gradients(n_points, positions, out));
+}
+int sphmi_cast_rays(sphmi_handle* h, int64_t n_rays, const double* origins, const double* directions, const double* t_begin, const double* t_end,
+                    double step, double level, int32_t mode, int32_t* status_out, int64_t* interval_out, double* bracket_out, double* point_out,
+                    double* weight_out, int64_t* count_out, double* sum_pressure_out, double* sum_density_out, double* sum_velocity_out) {
+    const sphmi::RayCall c{origins, directions, t_begin, t_end, step, level, (int)mode, status_out, interval_out, bracket_out, point_out,
+                           weight_out, count_out, sum_pressure_out, sum_density_out, sum_velocity_out};
+    SPHMI_GUARD(h, h->e->cast_rays(n_rays, c));
 }
 int sphmi_particle_fields(sphmi_handle* h, int64_t* count_out, double* shepard_out, double* normal_out, double* div_r_out, double* div_v_out,
                           double* vorticity_out) {

@@ -1817,6 +1817,12 @@ struct MultiEngine final : EngineBase {
         add_slab_sums(G, [&](Engine<T>& e, int f, double* dst) { e.pg_fetch(f, dst, n); });
         out.deliver(G);
     }
+    // The first crossing along rays (sphmi_rays.h): single-device handles only.  Whether a march point is inside is decided by the slabs'
+    // COMBINED S at that point, at every evaluation of the search — a sum over slabs inside the march, which is not built.
+    void cast_rays(int64_t, const RayCall&) override {
+        if (rank_mode) throw EngineError(SPHMI_ERR_STATE, "sphmi_cast_rays: single-device handles only (a rank-mode process holds one slab of the rows)");
+        throw EngineError(SPHMI_ERR_STATE, "sphmi_cast_rays: single-device handles only (a crossing needs the slabs' combined S at every evaluation of the search, which is not built)");
+    }
     // Differential fields at the particles (sphmi_particle_fields.h): single-device handles only.  After the corrector a slab's ghost
     // copies hold the half-step state, so a slab cannot see its neighbours' current rows without a halo exchange of its own.
     void particle_fields(int64_t*, double*, double*, double*, double*, double*) override {

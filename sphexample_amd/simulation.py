@@ -47,7 +47,7 @@ def RunSimulation(*, SimGeometry=None, SimMetaData: SimulationMetaData, SimConst
                   async_output: bool = False, group_forces=None, probes=None, field_grid=None,
                   particle_fields=None, budgets: bool = False, neighbor_list: bool = False, isosurface=None, components=None,
                   flow_boxes=None, envelopes=None, maps=None, tracers=None, sample_points=None,
-                  sample_point_gradients=None) -> List[float]:
+                  sample_point_gradients=None, rays=None) -> List[float]:
     """Same keyword signature as the reference (src/SPHCellList.jl:808-817); returns the list of
     time steps the reference collects in ``TimeSteps`` (:823,:884).  ``SimParticles`` is updated in
     place at every output time, in the engine's cell-sorted order, as the reference's is.
@@ -131,7 +131,13 @@ def RunSimulation(*, SimGeometry=None, SimMetaData: SimulationMetaData, SimConst
     ``sample_point_gradients=positions`` ([n, dims]): at every output the raw kernel and gradient sums are sampled at those points
     (``Backend.sample_point_gradients``; ``sphexample_amd.fields`` turns them into the velocity gradient, vorticity, divergence,
     strain rate, pressure gradient and free-surface normal) and ``on_output`` receives the dict as its last argument, behind
-    ``sample_points`` (``None`` at the first call).  ``None`` (default): nothing is sampled and the callback keeps its arguments."""
+    ``sample_points`` (``None`` at the first call).  ``None`` (default): nothing is sampled and the callback keeps its arguments.
+
+    ``rays=dict(origins=…, directions=…, t_end=…, …)``: at every output those rays are cast through the fluid (the keywords of
+    ``Backend.cast_rays``; ``sphexample_amd.rays`` builds gauges and depth images on it) and ``on_output`` receives the dict —
+    ``status``, ``interval``, ``bracket``, ``point`` and the raw sums at the hit — as its last argument, behind
+    ``sample_point_gradients`` (``None`` at the first call).  ``None`` (default): nothing is cast and the callback keeps its
+    arguments."""
     if SimMetaData.BMode.__name__ == "SimpleMDBC":
         LoadMDBCNormals(SimParticles, ParticleNormalsPath)                       # :827
     host_bytes = SimParticles.Position.dtype.itemsize
@@ -207,6 +213,9 @@ def RunSimulation(*, SimGeometry=None, SimMetaData: SimulationMetaData, SimConst
     if sample_point_gradients is not None:
         gradient_cloud = np.ascontiguousarray(sample_point_gradients, dtype=np.float64).reshape(-1, SimMetaData.Dimensions)
         extras.append((None, lambda: eng.sample_point_gradients(gradient_cloud)))
+    if rays is not None:
+        ray_call = dict(rays)
+        extras.append((None, lambda: eng.cast_rays(**ray_call)))                 # (the state of this output, like the clouds above)
     none_yet = tuple(first for first, _ in extras)
     emit = lambda meta, samples: on_output(meta, SimParticles, *samples)         # noqa: E731
     if on_output:
