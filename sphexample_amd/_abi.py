@@ -1,7 +1,8 @@
-"""ctypes view of include/sphmi.h (structs + a thin call-marshalling base class).
+"""ctypes view of include/sphmi.h (structs, the prototype table + a thin call-marshalling base class).
 
 ``SphmiConfig`` / ``SphmiProgress`` must stay field-for-field identical to the C structs;
-``tests/test_abi.py`` cross-checks the sizes against the compiled library.
+``tests/test_abi.py`` cross-checks the sizes against the compiled library.  ``PROTOTYPES`` holds the
+ctypes prototype of every entry point Python calls; ``tests/test_prototype_table_host.py`` holds it to the headers.
 """
 from __future__ import annotations
 
@@ -55,10 +56,73 @@ class SphmiProgress(C.Structure):
     ]
 
 
+class SphmiMultiInfo(C.Structure):
+    _fields_ = [("world", C.c_int32), ("n_local", C.c_int32), ("axis", C.c_int32), ("halo_width", C.c_int32),
+                ("transport", C.c_int32), ("reserved", C.c_int32), ("n_recuts", C.c_int64),
+                ("cuts", C.c_int64 * MAX_DEVICES), ("n_live", C.c_int64 * MAX_DEVICES)]
+
+
 class SphmiError(RuntimeError):
     def __init__(self, status: int, text: str):
         super().__init__(f"sphmi status {status}: {text}")
         self.status = status
+
+
+# -- the prototype of every entry point of include/sphmi.h and include/sphmi_internal.h that Python calls ---------------------
+# unprefixed name → argtypes, or (argtypes, restype) where the function does not return int.  Array pointers travel as c_void_p,
+# POINTER(...) stands where a byref is passed.  `bind` is the one place that applies an entry.
+_P, _I32, _I64, _F = C.c_void_p, C.c_int32, C.c_int64, C.c_double
+_pI32, _pI64, _pF, _pCfg = C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_double), C.POINTER(SphmiConfig)
+_SERIES_TAIL = [_pI64, _pI64]              # n_out, n_dropped of every *_read of a step series
+PROTOTYPES = {
+    "backend_info": ([], C.c_char_p), "last_error": ([_P], C.c_char_p), "auto_device_float_bytes": ([_pCfg], C.c_int32),
+    "create": [_pCfg, C.POINTER(_P)], "create_rank": [_pCfg, _I32, _I32, C.c_char_p, C.POINTER(_P)], "destroy": [_P],
+    "device_float_bytes": [_P, _pI32], "owned_count": [_P, _pI64], "multi_info_get": [_P, C.POINTER(SphmiMultiInfo)],
+    "rccl_unique_id": [_P], "rccl_probe": [],
+    "dam_break_3d_count": [_F, _pI64, _pI64], "generate_dam_break_3d": [_P, _F],
+    "upload": [_P] * 9, "set_clock": [_P, _I64, _F], "set_motion": [_P, C.c_uint64, _F, _F, _F, _P],
+    "advance": [_P, _F, _I64, C.POINTER(SphmiProgress)],
+    "download": [_P] * 11, "download_begin": [_P] * 11, "download_end": [_P], "set_output_components": [_P, C.c_int],
+    "host_register": [_P, _P, _I64], "host_unregister": [_P, _P],
+    "download_kernel_output": [_P, _P, _P], "download_permutation": [_P, _P],
+    "attach_columns": [_P, _I32, _P, _P], "download_columns": [_P, _P], "download_columns_begin": [_P, _P],
+    "forces_once": [_P, C.c_int, _P, _P], "unique_cells": [_P, _P, _I64, _pI64],
+    "timers": [_P, _I32, C.POINTER(C.c_char_p), _pF, _pI64, _pI32], "force_kernel_stats": [_P, C.c_int, _pF, _pI64],
+    "device_ptrs": [_P, C.POINTER(_P), C.POINTER(_P), _pI64],
+    # the step series
+    "group_forces_enable": [_P, _I32, _P, _I64], "group_forces_read": [_P, _I64] + [_P] * 4 + _SERIES_TAIL,
+    "probes_enable": [_P, _I32, _P, _I64], "probes_read": [_P, _I64] + [_P] * 8 + _SERIES_TAIL,
+    "budgets_enable": [_P, _I64], "budgets_read": [_P, _I64] + [_P] * 10 + _SERIES_TAIL,
+    "flow_enable": [_P, _I32, _P, _P, _I64], "flow_read": [_P, _I64] + [_P] * 8 + _SERIES_TAIL,
+    "tracers_enable": [_P, _I32, _P, _I32, _P, _F, _I64], "tracers_read": [_P, _I64] + [_P] * 6 + _SERIES_TAIL,
+    # the accumulated records
+    "envelopes_enable": [_P, _I32], "envelopes_read": [_P, _pI64, _P] + [_P] * 8,
+    "maps_enable": [_P, _P, _P, _P, _I32], "maps_disable": [_P], "maps_read": [_P, _pI64, _P] + [_P] * 14,
+    # the results on demand
+    "sample_grid": [_P] * 9, "sample_points": [_P, _I64] + [_P] * 6, "sample_point_gradients": [_P, _I64] + [_P] * 10,
+    "cast_rays": [_P, _I64] + [_P] * 4 + [_F, _F, _I32] + [_P] * 9, "particle_fields": [_P] * 7,
+    "neighbors_build": [_P, _I32, _pI64, _pI64], "neighbors_read": [_P] * 3, "neighbors_release": [_P],
+    "isosurface_build": [_P] * 4 + [_F, _pI64, _pI64], "isosurface_read": [_P] * 5, "isosurface_release": [_P],
+    "components_build": [_P, _F, C.c_uint32, _pI64, _pI64], "components_read": [_P] * 5, "components_release": [_P],
+    # include/sphmi_internal.h: the hooks of tests and tools
+    "shm_selftest": [C.c_char_p, _I32, _I32, _I64], "plan_slabs": [_P, _P, _P, _I64, _I32] + [_P] * 5,
+    "multi_set_cuts": [_P, _P, _I32], "multi_column_cost": [_P, _I64, _I32, _P], "multi_halo_info": [_P, _pI64, _I32, _pI32],
+}
+
+
+def bind(lib, name: str, prefix: str = "sphmi_"):
+    """The entry point `prefix + name` of `lib` under its prototype of PROTOTYPES.  The prototype is assigned on every call:
+    whoever widened it on the (shared) function object to call it raw leaves the next caller unharmed."""
+    fn = getattr(lib, prefix + name)
+    proto = PROTOTYPES[name]
+    if isinstance(proto, tuple):
+        proto, fn.restype = proto
+    fn.argtypes = list(proto)
+    return fn
+
+
+def last_error(lib, handle=None, prefix: str = "sphmi_") -> str:
+    return (bind(lib, "last_error", prefix)(handle) or b"").decode()
 
 
 def make_config(n_particles: int, SimConstants: SimulationConstants, SimKernel: SPHKernelInstance,
@@ -104,41 +168,61 @@ def _ptr(a: Optional[np.ndarray]):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
 
 
+_F64, _INT64 = np.float64, np.int64
+
+# What sphmi_download delivers, in the order of its prototype: name, dtype (None: the host float), vector.  Host-float vectors
+# have `components` columns on request; Cells always has dims.
+DOWNLOAD_FIELDS = (("Position", None, True), ("Velocity", None, True), ("Acceleration", None, True), ("Density", None, False),
+                   ("Pressure", None, False), ("ID", np.int64, False), ("Type", np.uint8, False), ("GroupMarker", np.uint64, False),
+                   ("GhostPoints", None, True), ("Cells", np.int64, True))
+DOWNLOAD_NAMES = tuple(k for k, _, _ in DOWNLOAD_FIELDS)
+
+# has_<feature>() is true iff the library exports every one of these entry points
+FEATURES = {
+    "columns": ("attach_columns", "download_columns", "download_columns_begin"),
+    "neighbor_list": ("neighbors_build", "neighbors_read", "neighbors_release"),
+    "maps": ("maps_enable", "maps_read", "maps_disable"),
+    **{k: (k + "_enable", k + "_read") for k in ("group_forces", "probes", "budgets", "flow", "envelopes", "tracers")},
+    **{k: (k + "_build", k + "_read", k + "_release") for k in ("isosurface", "components")},
+    **{k: (k,) for k in ("sample_grid", "sample_points", "sample_point_gradients", "cast_rays", "particle_fields")},
+}
+
+
 class Backend:
     """Call marshalling shared by the HIP engine binding and (in tests) the oracle binding.
 
     A backend is `lib` + symbol `prefix`; every entry point has the signature declared in
     include/sphmi.h."""
 
+    # what this object enabled, attached, pinned and built (class-level: objects made with __new__ start from them too)
+    _column_widths = None
+    _force_groups = _probes = _flow_boxes = _map_bins = 0
+    _tracers = (0, 0, 0.5)
+    _pinned = ()
+    _neighbor_shape = _isosurface_shape = _components_shape = None
+
     def __init__(self, lib: C.CDLL, prefix: str, cfg: SphmiConfig, create=None):
         self._lib, self._p = lib, prefix
         self.cfg = cfg
         self.N, self.D = int(cfg.n_particles), int(cfg.dims)
         self._ft = np.float64 if cfg.host_float_bytes == 8 else np.float32
-        f = self._fn
-        f("last_error").restype = C.c_char_p
-        f("last_error").argtypes = [C.c_void_p]
         self._h = C.c_void_p()
-        f("create").argtypes = [C.POINTER(SphmiConfig), C.POINTER(C.c_void_p)]
-        rc = (create or f("create"))(C.byref(cfg), C.byref(self._h))
+        rc = (create or self._fn("create"))(C.byref(cfg), C.byref(self._h))
         if rc != OK:
-            raise SphmiError(rc, (f("last_error")(None) or b"").decode())
-        f("destroy").argtypes = [C.c_void_p]
-        f("upload").argtypes = [C.c_void_p] * 9
-        f("set_clock").argtypes = [C.c_void_p, C.c_int64, C.c_double]
-        f("download_kernel_output").argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
-        f("set_motion").argtypes = [C.c_void_p, C.c_uint64, C.c_double, C.c_double, C.c_double, C.c_void_p]
-        f("advance").argtypes = [C.c_void_p, C.c_double, C.c_int64, C.POINTER(SphmiProgress)]
-        f("download").argtypes = [C.c_void_p] * 11
-        f("forces_once").argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
-        f("unique_cells").argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]
+            raise SphmiError(rc, last_error(lib, None, prefix))
 
     def _fn(self, name):
-        return getattr(self._lib, self._p + name)
+        return bind(self._lib, name, self._p)
 
     def _check(self, rc: int):
         if rc != OK:
-            raise SphmiError(rc, (self._fn("last_error")(self._h) or b"").decode())
+            raise SphmiError(rc, last_error(self._lib, self._h, self._p))
+
+    def _has(self, name: str) -> bool:
+        return hasattr(self._lib, self._p + name)
+
+    def _has_all(self, names) -> bool:
+        return all(self._has(n) for n in names)
 
     def close(self):
         if self._h:
@@ -150,6 +234,94 @@ class Backend:
             self.close()
         except Exception:
             pass
+
+    # -- the call shapes --------------------------------------------------------------------
+    @staticmethod
+    def empty_series(schema, *lead, steps: int = 0) -> dict:
+        """The dict a series read delivers for `steps` steps, zeroed: iteration, time, dt and one [steps, *lead, *shape] array per
+        (key, shape, dtype) of `schema`."""
+        out = {"iteration": np.zeros(steps, dtype=np.int64), "time": np.zeros(steps), "dt": np.zeros(steps)}
+        out.update({key: np.zeros((steps, *lead, *shape), dtype=dtype) for key, shape, dtype in schema})
+        return out
+
+    def _read_series(self, name, columns, *lead, tail=()) -> dict:
+        """`<name>_read` of a step series: a call with capacity 0 learns how many steps wait, the second one fetches them.  `columns`
+        is the (key, trailing shape, dtype) list behind iteration, time, dt, `lead` what stands in front of every trailing shape
+        (the probes, boxes, groups); `tail` arrays that hold one state, not one row per step.  Returns the dict cut to the steps
+        delivered and sets `<name>_dropped`."""
+        f = self._fn(name + "_read")
+        n, dropped = C.c_int64(), C.c_int64()
+        self._check(f(self._h, 0, *[None] * (3 + len(columns) + len(tail)), C.byref(n), C.byref(dropped)))
+        k = max(n.value, 1)
+        out = self.empty_series(columns, *lead, steps=k)
+        self._check(f(self._h, k, *[_ptr(a) for a in (*out.values(), *tail)], C.byref(n), C.byref(dropped)))
+        setattr(self, name + "_dropped", dropped.value)
+        return {key: a[:n.value] for key, a in out.items()}
+
+    def _read_window(self, name, out) -> dict:
+        """`<name>_read` of records accumulated since the enable: the steps, the time window, and the arrays of `out` filled."""
+        steps, window = C.c_int64(), np.zeros(3)
+        self._check(self._fn(name + "_read")(self._h, C.byref(steps), _ptr(window), *[_ptr(a) for a in out.values()]))
+        return {"steps": int(steps.value), "t_begin": float(window[0]), "t_end": float(window[1]), "duration": float(window[2]), **out}
+
+    @staticmethod
+    def _wanted(who, table, fields):
+        fields = tuple(table) if fields is None else tuple(fields)
+        unknown = [k for k in fields if k not in table]
+        if unknown:
+            raise ValueError(f"{who}: unknown fields {unknown}")
+        return fields
+
+    def _sample(self, name, table, fields, lead, *inputs) -> dict:
+        """A result with selectable outputs: `table` maps name → (dtype, trailing shape) in the order of the C prototype, behind
+        `inputs`.  The outputs not in `fields` travel as NULL and are left out of the dict."""
+        fields = self._wanted(name, table, fields)
+        out = {k: (np.zeros((*lead, *shape), dtype=dtype) if k in fields else None) for k, (dtype, shape) in table.items()}
+        self._check(self._fn(name)(self._h, *inputs, *[_ptr(out[k]) for k in table]))
+        return {k: v for k, v in out.items() if v is not None}
+
+    def _lattice(self, who, origin, spacing, counts):
+        o = np.ascontiguousarray(origin, dtype=np.float64).reshape(-1)
+        s = np.ascontiguousarray(spacing, dtype=np.float64).reshape(-1)
+        c = np.ascontiguousarray(counts, dtype=np.int64).reshape(-1)
+        if not (len(o) == len(s) == len(c) == self.D):
+            raise ValueError(f"{who}: origin, spacing and counts hold {self.D} entries each")
+        return o, s, c
+
+    def _cloud(self, who, positions):
+        x = np.ascontiguousarray(positions, dtype=np.float64)
+        if x.ndim != 2 or x.shape[1] != self.D:
+            raise ValueError(f"{who}: positions is shaped [n, {self.D}]")
+        return x
+
+    # A result held on the device (<name>_build / _read / _release).  The reads take no capacities: the arrays are sized from the
+    # two counts THIS object's build reported, kept in the attribute named here; the second entry words the refusal.
+    _HELD = {"neighbors": ("_neighbor_shape", "a list"), "isosurface": ("_isosurface_shape", "a mesh"),
+             "components": ("_components_shape", "components")}
+
+    def _held_build(self, name, *args):
+        a, b = C.c_int64(), C.c_int64()
+        setattr(self, self._HELD[name][0], None)                                  # (a refused build leaves nothing this object may read)
+        self._check(self._fn(name + "_build")(self._h, *args, C.byref(a), C.byref(b)))
+        setattr(self, self._HELD[name][0], (a.value, b.value))
+        return a.value, b.value
+
+    def _held_read(self, name, arrays):
+        """`arrays(count, count)` makes the outputs (None skips one).  Without a build of its own the library is asked with every
+        pointer NULL — it words the refusal — and a result it then turns out to hold is refused here."""
+        f = self._fn(name + "_read")
+        attr, what = self._HELD[name]
+        shape = getattr(self, attr)
+        if shape is None:
+            self._check(f(self._h, *[None] * (len(PROTOTYPES[name + "_read"]) - 1)))
+            raise RuntimeError(f"{name}_read: the handle holds {what} this object did not build; call {name}_build first")
+        out = arrays(*shape)
+        self._check(f(self._h, *[_ptr(a) for a in out]))
+        return out
+
+    def _held_release(self, name) -> None:
+        self._check(self._fn(name + "_release")(self._h))
+        setattr(self, self._HELD[name][0], None)
 
     # -- data movement ----------------------------------------------------------------------
     def _f(self, a, shape):
@@ -197,55 +369,38 @@ class Backend:
         self._check(self._fn("advance")(self._h, t_target, max_steps, C.byref(prog)))
         return prog
 
-    def download(self, fields=("Position", "Velocity", "Acceleration", "Density", "Pressure", "ID",
-                               "Type", "GroupMarker", "GhostPoints", "Cells"), components: Optional[int] = None) -> dict:
+    def download(self, fields=DOWNLOAD_NAMES, components: Optional[int] = None) -> dict:
         """`components=3`: vector fields as n×3 (2-D vectors padded with a zero — the VTKHDF point layout the reference
         produces with to_3d!, src/ProduceHDFVTK.jl:251-325), packed that way on the device."""
         N, D = self.N, self.D
         Cv = D if components is None else int(components)
         native = Cv != D and self._has("set_output_components")
         Cd = Cv if native else D
-        spec = {
-            "Position": ((N, Cd), self._ft), "Velocity": ((N, Cd), self._ft),
-            "Acceleration": ((N, Cd), self._ft), "Density": ((N,), self._ft),
-            "Pressure": ((N,), self._ft), "ID": ((N,), np.int64), "Type": ((N,), np.uint8),
-            "GroupMarker": ((N,), np.uint64), "GhostPoints": ((N, Cd), self._ft),
-            "Cells": ((N, D), np.int64),
-        }
-        out = {k: (np.empty(*spec[k]) if k in fields else None) for k in spec}
+        out = {k: (np.empty((N, Cd if dtype is None else D) if vector else (N,), dtype=dtype or self._ft) if k in fields else None)
+               for k, dtype, vector in DOWNLOAD_FIELDS}
         if native:
-            self._fn("set_output_components").argtypes = [C.c_void_p, C.c_int]
             self._check(self._fn("set_output_components")(self._h, Cv))
         try:
-            self._check(self._fn("download")(self._h, *[_ptr(out[k]) for k in spec]))
+            self._check(self._fn("download")(self._h, *[_ptr(a) for a in out.values()]))
         finally:
             if native:
                 self._check(self._fn("set_output_components")(self._h, D))
         if Cv != D and not native:          # backends without the entry point (the oracle): pad on the host
             if Cv != 3:
                 raise ValueError("components must be dims or 3")
-            for k in ("Position", "Velocity", "Acceleration", "GhostPoints"):
-                if out[k] is not None:
+            for k, dtype, vector in DOWNLOAD_FIELDS:
+                if vector and dtype is None and out[k] is not None:
                     out[k] = np.concatenate([out[k], np.zeros((N, 3 - D), dtype=out[k].dtype)], axis=1)
         return {k: v for k, v in out.items() if v is not None}
 
     def download_into(self, p, begin_only: bool = False) -> None:
         """Write the engine state back into the arrays of a SimParticles IN PLACE (what the reference's loop leaves in
         its StructArray).  Call pin(p) once when the same arrays receive every output."""
-        order = ("Position", "Velocity", "Acceleration", "Density", "Pressure", "ID", "Type", "GroupMarker",
-                 "GhostPoints", "Cells")
-        want = {"Position": self._ft, "Velocity": self._ft, "Acceleration": self._ft, "Density": self._ft,
-                "Pressure": self._ft, "ID": np.int64, "Type": np.uint8, "GroupMarker": np.uint64,
-                "GhostPoints": self._ft, "Cells": np.int64}
-        args = []
-        for k in order:
-            a = getattr(p, k, None)
-            if not (isinstance(a, np.ndarray) and a.dtype == want[k] and a.flags.c_contiguous and len(a) == self.N):
-                a = None                       # field absent or in another layout: fall back to the copying path below
-            args.append(a)
-        if all(a is not None for a in args):
+        args = [getattr(p, k, None) for k in DOWNLOAD_NAMES]
+        # a field absent or in another layout: fall back to the copying path below
+        if all(isinstance(a, np.ndarray) and a.dtype == (dtype or self._ft) and a.flags.c_contiguous and len(a) == self.N
+               for a, (_, dtype, _) in zip(args, DOWNLOAD_FIELDS)):
             name = "download_begin" if begin_only and self._has("download_begin") else "download"
-            self._fn(name).argtypes = [C.c_void_p] * 11
             self._check(self._fn(name)(self._h, *[_ptr(a) for a in args]))
             return
         for k, v in self.download().items():
@@ -257,7 +412,6 @@ class Backend:
 
     def download_end(self) -> None:
         if self._has("download_end"):
-            self._fn("download_end").argtypes = [C.c_void_p]
             self._check(self._fn("download_end")(self._h))
 
     def pin(self, p) -> None:
@@ -265,27 +419,21 @@ class Backend:
         arrays must stay alive until unpin() / close()."""
         if not self._has("host_register"):
             return
-        self._fn("host_register").argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
-        self._pinned = getattr(self, "_pinned", [])
         if isinstance(p, np.ndarray) or isinstance(p, (list, tuple)):        # arbitrary arrays: the targets of download_columns
             arrays = [p] if isinstance(p, np.ndarray) else list(p)
         else:
-            arrays = [getattr(p, k, None) for k in ("Position", "Velocity", "Acceleration", "Density", "Pressure", "ID", "Type", "GroupMarker", "GhostPoints", "Cells")]
+            arrays = [getattr(p, k, None) for k in DOWNLOAD_NAMES]
         for a in arrays:
             if isinstance(a, np.ndarray) and a.flags.c_contiguous and a.nbytes and not any(a is b for b in self._pinned):
                 self._check(self._fn("host_register")(self._h, _ptr(a), a.nbytes))
-                self._pinned.append(a)
+                self._pinned = (*self._pinned, a)
 
     def unpin(self) -> None:
         if not self._has("host_unregister"):
             return
-        self._fn("host_unregister").argtypes = [C.c_void_p, C.c_void_p]
-        for a in getattr(self, "_pinned", []):
+        for a in self._pinned:
             self._fn("host_unregister")(self._h, _ptr(a))
-        self._pinned = []
-
-    def _has(self, name: str) -> bool:
-        return hasattr(self._lib, self._p + name)
+        self._pinned = ()
 
     def kernel_output(self):
         """(Kernel, KernelGradient) of StoreKernelOutput runs, current order."""
@@ -298,15 +446,11 @@ class Backend:
         """prev_row: row i of what download() returns now was row prev_row[i] at the previous call (at the upload for the
         first).  The reference's sort! permutes all 17 fields of the StructArray (src/SPHCellList.jl:142); this is what lets
         the caller bring along the fields the engine does not carry (`permute_passive_fields`)."""
-        self._fn("download_permutation").argtypes = [C.c_void_p, C.c_void_p]
         out = np.empty(self.N, dtype=np.int64)
         self._check(self._fn("download_permutation")(self._h, _ptr(out)))
         return out
 
     # -- the caller's passive columns on the device (sphmi_attach_columns / sphmi_download_columns*) --------------------
-    def has_columns(self) -> bool:
-        return all(self._has(n) for n in ("attach_columns", "download_columns", "download_columns_begin"))
-
     def _column_table(self, arrays, what):
         arrays = list(arrays)
         for a in arrays:
@@ -324,16 +468,14 @@ class Backend:
         if any(a is None for a in arrays):
             raise ValueError("attach_columns: a column is None")
         widths = (C.c_int32 * max(len(arrays), 1))(*[a.nbytes // self.N for a in arrays])
-        self._fn("attach_columns").argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
         self._check(self._fn("attach_columns")(self._h, len(arrays), table, widths))
         self._column_widths = [a.nbytes // self.N for a in arrays]
 
     def _download_columns(self, name, outs) -> None:
         outs, table = self._column_table(outs, name)
-        widths = getattr(self, "_column_widths", None)
+        widths = self._column_widths
         if widths is not None and (len(outs) != len(widths) or any(a is not None and a.nbytes // self.N != w for a, w in zip(outs, widths))):
             raise ValueError(f"{name}: the arrays do not match the attached columns")
-        self._fn(name).argtypes = [C.c_void_p, C.c_void_p]
         self._check(self._fn(name)(self._h, table))
 
     def download_columns(self, outs) -> None:
@@ -346,42 +488,29 @@ class Backend:
         self._download_columns("download_columns_begin", outs)
 
     # -- the per-step force on particle groups (sphmi_group_forces_enable / sphmi_group_forces_read) ---------------------
-    def has_group_forces(self) -> bool:
-        return self._has("group_forces_enable") and self._has("group_forces_read")
+    GROUP_FORCE_FIELDS = (("force", (3,), np.float64),)
 
     def group_forces_enable(self, markers, capacity: int = 4096) -> None:
         """Record F_g = m0 * sum(Acceleration[GroupMarker == g]) of every executed step on the device, for the listed
         GroupMarkers (at most 16, distinct); the newest `capacity` unread samples are kept.  An empty list disables."""
         m = np.ascontiguousarray(list(markers), dtype=np.uint64)
-        self._fn("group_forces_enable").argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64]
         self._check(self._fn("group_forces_enable")(self._h, len(m), _ptr(m) if len(m) else None, int(capacity)))
         self._force_groups = len(m)
 
     def group_forces_read(self):
         """(iteration[n], time[n], dt[n], F[n, groups, 3]) of the steps executed since the last read, oldest first, and clears
         them; `group_forces_dropped` holds how many older samples the capacity pushed out."""
-        f = self._fn("group_forces_read")
-        f.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
-        n, dropped = C.c_int64(), C.c_int64()
-        self._check(f(self._h, 0, None, None, None, None, C.byref(n), C.byref(dropped)))        # capacity 0: how many are waiting
-        g = int(getattr(self, "_force_groups", 0))
-        k = max(n.value, 1)
-        it, t, dt = np.zeros(k, dtype=np.int64), np.zeros(k), np.zeros(k)
-        F = np.zeros((k, g, 3))
-        self._check(f(self._h, k, _ptr(it), _ptr(t), _ptr(dt), _ptr(F), C.byref(n), C.byref(dropped)))
-        self.group_forces_dropped = dropped.value
-        return it[:n.value], t[:n.value], dt[:n.value], F[:n.value]
+        return tuple(self._read_series("group_forces", self.GROUP_FORCE_FIELDS, int(self._force_groups)).values())
 
     # -- kernel sums at fixed probe points (sphmi_probes_enable / sphmi_probes_read) ---------------------------------------
-    def has_probes(self) -> bool:
-        return self._has("probes_enable") and self._has("probes_read")
+    PROBE_FIELDS = (("weight", (), np.float64), ("count", (), np.int64), ("pressure", (), np.float64), ("density", (), np.float64),
+                    ("velocity", (3,), np.float64))
 
     def probes_enable(self, positions, capacity: int = 4096) -> None:
         """Sample S = sum w_j, and the w-weighted means of Pressure, Density and Velocity over the Fluid rows within H, at the
         fixed points `positions` [n, dims] (at most 1024) after every executed step, on the device; the newest `capacity`
         unread samples are kept.  An empty array disables."""
         x = np.ascontiguousarray(positions, dtype=np.float64).reshape(-1, self.D)
-        self._fn("probes_enable").argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64]
         self._check(self._fn("probes_enable")(self._h, len(x), _ptr(x) if len(x) else None, int(capacity)))
         self._probes = len(x)
 
@@ -389,30 +518,15 @@ class Backend:
         """The steps executed since the last read, oldest first, and clears them: a dict of iteration[n], time[n], dt[n],
         weight[n, probes] (S), count[n, probes], pressure[n, probes], density[n, probes], velocity[n, probes, 3];
         `probes_dropped` holds how many older samples the capacity pushed out."""
-        f = self._fn("probes_read")
-        f.argtypes = [C.c_void_p, C.c_int64] + [C.c_void_p] * 8 + [C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
-        n, dropped = C.c_int64(), C.c_int64()
-        self._check(f(self._h, 0, *[None] * 8, C.byref(n), C.byref(dropped)))                   # capacity 0: how many are waiting
-        m = int(getattr(self, "_probes", 0))
-        k = max(n.value, 1)
-        out = {"iteration": np.zeros(k, dtype=np.int64), "time": np.zeros(k), "dt": np.zeros(k), "weight": np.zeros((k, m)),
-               "count": np.zeros((k, m), dtype=np.int64), "pressure": np.zeros((k, m)), "density": np.zeros((k, m)),
-               "velocity": np.zeros((k, m, 3))}
-        self._check(f(self._h, k, *[_ptr(a) for a in out.values()], C.byref(n), C.byref(dropped)))
-        self.probes_dropped = dropped.value
-        return {key: a[:n.value] for key, a in out.items()}
+        return self._read_series("probes", self.PROBE_FIELDS, int(self._probes))
 
     # -- the budgets of the fluid at every step (sphmi_budgets_enable / sphmi_budgets_read) ---------------------------------
     BUDGET_FIELDS = (("count", (), np.int64), ("energy", (3,), np.float64), ("momentum", (3,), np.float64), ("angular", (3,), np.float64),
                      ("centre", (3,), np.float64), ("extremes", (3,), np.float64), ("box", (6,), np.float64))
 
-    def has_budgets(self) -> bool:
-        return self._has("budgets_enable") and self._has("budgets_read")
-
     def budgets_enable(self, capacity: int = 4096) -> None:
         """Record the energy, momentum and extent budgets of the Fluid rows after every executed step, on the device; the newest
         `capacity` unread samples are kept.  `capacity = 0` disables."""
-        self._fn("budgets_enable").argtypes = [C.c_void_p, C.c_int64]
         self._check(self._fn("budgets_enable")(self._h, int(capacity)))
 
     def budgets_read(self) -> dict:
@@ -420,23 +534,11 @@ class Backend:
         (Fluid rows), energy[n, 3] (kinetic, potential, compressive), momentum[n, 3], angular[n, 3] (about the origin), centre[n, 3]
         (of mass), extremes[n, 3] (largest speed, smallest and largest density) and box[n, 6] (min x, max x);
         `budgets_dropped` holds how many older samples the capacity pushed out."""
-        f = self._fn("budgets_read")
-        f.argtypes = [C.c_void_p, C.c_int64] + [C.c_void_p] * 10 + [C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
-        n, dropped = C.c_int64(), C.c_int64()
-        self._check(f(self._h, 0, *[None] * 10, C.byref(n), C.byref(dropped)))                  # capacity 0: how many are waiting
-        k = max(n.value, 1)
-        out = {"iteration": np.zeros(k, dtype=np.int64), "time": np.zeros(k), "dt": np.zeros(k)}
-        out.update({name: np.zeros((k,) + shape, dtype=dtype) for name, shape, dtype in self.BUDGET_FIELDS})
-        self._check(f(self._h, k, *[_ptr(a) for a in out.values()], C.byref(n), C.byref(dropped)))
-        self.budgets_dropped = dropped.value
-        return {key: a[:n.value] for key, a in out.items()}
+        return self._read_series("budgets", self.BUDGET_FIELDS)
 
     # -- the flow through control boxes at every step (sphmi_flow_enable / sphmi_flow_read) ----------------------------------
     FLOW_FIELDS = (("count", (), np.int64), ("volume", (), np.float64), ("momentum", (3,), np.float64), ("entered", (), np.int64),
                    ("left", (), np.int64))
-
-    def has_flow(self) -> bool:
-        return self._has("flow_enable") and self._has("flow_read")
 
     def flow_enable(self, lo, hi, capacity: int = 4096) -> None:
         """Record, after every executed step and on the device, how many Fluid rows lie in each of the half-open boxes
@@ -446,7 +548,6 @@ class Backend:
         b = np.ascontiguousarray(hi, dtype=np.float64).reshape(-1, self.D)
         if a.shape != b.shape:
             raise ValueError("flow_enable: lo and hi hold one row of `dims` bounds per box each")
-        self._fn("flow_enable").argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64]
         self._check(self._fn("flow_enable")(self._h, len(a), _ptr(a) if len(a) else None, _ptr(b) if len(b) else None, int(capacity)))
         self._flow_boxes = len(a)
 
@@ -455,73 +556,41 @@ class Backend:
         count[n, boxes] (Fluid rows inside after the step), volume[n, boxes] (m0 * sum 1/rho), momentum[n, boxes, 3],
         entered[n, boxes] and left[n, boxes] (rows that crossed into / out of the box during the step);
         `flow_dropped` holds how many older samples the capacity pushed out."""
-        f = self._fn("flow_read")
-        f.argtypes = [C.c_void_p, C.c_int64] + [C.c_void_p] * 8 + [C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
-        n, dropped = C.c_int64(), C.c_int64()
-        self._check(f(self._h, 0, *[None] * 8, C.byref(n), C.byref(dropped)))                   # capacity 0: how many are waiting
-        m = int(getattr(self, "_flow_boxes", 0))
-        k = max(n.value, 1)
-        out = {"iteration": np.zeros(k, dtype=np.int64), "time": np.zeros(k), "dt": np.zeros(k)}
-        out.update({name: np.zeros((k, m) + shape, dtype=dtype) for name, shape, dtype in self.FLOW_FIELDS})
-        self._check(f(self._h, k, *[_ptr(a) for a in out.values()], C.byref(n), C.byref(dropped)))
-        self.flow_dropped = dropped.value
-        return {key: a[:n.value] for key, a in out.items()}
+        return self._read_series("flow", self.FLOW_FIELDS, int(self._flow_boxes))
 
     # -- per-particle pressure and speed envelopes at every step (sphmi_envelopes_enable / sphmi_envelopes_read) ---------------
     ENVELOPE_FIELDS = ("p_max", "t_p_max", "p_min", "impulse", "square", "loaded", "speed_max", "t_arrival")
-
-    def has_envelopes(self) -> bool:
-        return self._has("envelopes_enable") and self._has("envelopes_read")
 
     def envelopes_enable(self, types=("Fluid",)) -> None:
         """Accumulate, after every executed step and on the device, what each row of `types` ("Fluid", "Fixed", "Moving", or their
         Type numbers) experiences: the largest and smallest pressure, when the largest occurred, the pressure impulse, the time
         under load, the largest speed and the arrival time of the first positive pressure.  The records follow the particle
         through every sort.  A second call replaces the selection and restarts the window; an empty `types` disables."""
-        f = self._fn("envelopes_enable")
-        f.argtypes = [C.c_void_p, C.c_int32]
-        self._check(f(self._h, self._type_mask(types)))
+        self._check(self._fn("envelopes_enable")(self._h, self._type_mask(types)))
 
     def envelopes_read(self) -> dict:
         """The envelopes as they stand, without clearing them: `steps` (executed steps since the enable), `t_begin`, `t_end`,
         `duration` (sum of dt) and float64 [n] arrays `p_max`, `t_p_max`, `p_min`, `impulse` (sum P dt), `square` (sum P^2 dt),
         `loaded` (sum dt over steps with P > 0), `speed_max` and `t_arrival` (+inf: never loaded); row i is row i of what `download`
         delivers now.  Rows of a type that is not selected hold the start record (-inf, 0, +inf, 0, 0, 0, 0, +inf)."""
-        f = self._fn("envelopes_read")
-        f.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.c_void_p] + [C.c_void_p] * 8
-        steps, window = C.c_int64(), np.zeros(3)
-        out = {name: np.zeros(self.N) for name in self.ENVELOPE_FIELDS}
-        self._check(f(self._h, C.byref(steps), _ptr(window), *[_ptr(a) for a in out.values()]))
-        return {"steps": int(steps.value), "t_begin": float(window[0]), "t_end": float(window[1]), "duration": float(window[2]), **out}
+        return self._read_window("envelopes", {name: np.zeros(self.N) for name in self.ENVELOPE_FIELDS})
 
     # -- per-bin maps of crest, arrival and mean flow at every step (sphmi_maps_enable / _read / _disable) ----------------------
     MAP_FIELDS = ("top_max", "t_top_max", "bottom_min", "t_arrival", "wet", "fill", "flux", "speed2_max", "t_speed2_max", "n_max")
     MAP_LAST = ("last_n", "last_top", "last_bottom", "last_velocity_sum")
-
-    def has_maps(self) -> bool:
-        return self._has("maps_enable") and self._has("maps_read") and self._has("maps_disable")
 
     def maps_enable(self, origin, spacing, counts, up_axis: int = None) -> None:
         """Accumulate, after every executed step and on the device, what every bin of a lattice experiences: bin (k0, k1[, k2]) holds
         the Fluid rows with ``k = floor((x - origin) / spacing)``, ``0 <= k < counts`` per axis; ``counts[d] = 1`` with
         ``spacing[d] = inf`` collapses axis d (a column map over the floor of a 3-D tank: ``counts = (nx, ny, 1)``).  `up_axis`
         (default: the last axis) names the coordinate whose extremes are kept.  A second call restarts the records."""
-        D = self.D
-        o = np.ascontiguousarray(origin, dtype=np.float64).reshape(-1)
-        s = np.ascontiguousarray(spacing, dtype=np.float64).reshape(-1)
-        c = np.ascontiguousarray(counts, dtype=np.int64).reshape(-1)
-        if not (len(o) == len(s) == len(c) == D):
-            raise ValueError(f"maps_enable: origin, spacing and counts hold {D} entries each")
-        f = self._fn("maps_enable")
-        f.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]
-        self._check(f(self._h, _ptr(o), _ptr(s), _ptr(c), D - 1 if up_axis is None else int(up_axis)))
+        o, s, c = self._lattice("maps_enable", origin, spacing, counts)
+        self._check(self._fn("maps_enable")(self._h, _ptr(o), _ptr(s), _ptr(c), self.D - 1 if up_axis is None else int(up_axis)))
         self._map_bins = int(np.prod(c))
 
     def maps_disable(self) -> None:
         """Stop accumulating and free the device memory of the maps."""
-        f = self._fn("maps_disable")
-        f.argtypes = [C.c_void_p]
-        self._check(f(self._h))
+        self._check(self._fn("maps_disable")(self._h))
         self._map_bins = 0
 
     def maps_read(self) -> dict:
@@ -529,20 +598,13 @@ class Backend:
         (bin ``k0 + counts[0] * (k1 + counts[1] * k2)``): `top_max`, `t_top_max`, `bottom_min`, `t_arrival` (+inf: never wet), `wet`,
         `fill`, `flux` [bins, 3], `speed2_max` (the square; `sphexample_amd.maps.max_speed` takes the root), `t_speed2_max`, `n_max`;
         then the map of the last executed step: `last_n` (int64), `last_top`, `last_bottom`, `last_velocity_sum` [bins, 3]."""
-        f = self._fn("maps_read")
-        f.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.c_void_p] + [C.c_void_p] * 14
-        B = int(getattr(self, "_map_bins", 0))
-        steps, window = C.c_int64(), np.zeros(3)
+        B = int(self._map_bins)
         shape = lambda k: (B, 3) if k in ("flux", "last_velocity_sum") else (B,)       # noqa: E731
-        out = {k: np.zeros(shape(k), dtype=np.int64 if k == "last_n" else np.float64) for k in self.MAP_FIELDS + self.MAP_LAST}
-        self._check(f(self._h, C.byref(steps), _ptr(window), *[_ptr(a) for a in out.values()]))
-        return {"steps": int(steps.value), "t_begin": float(window[0]), "t_end": float(window[1]), "duration": float(window[2]), **out}
+        return self._read_window("maps", {k: np.zeros(shape(k), dtype=np.int64 if k == "last_n" else np.float64)
+                                          for k in self.MAP_FIELDS + self.MAP_LAST})
 
     # -- tracers: tracked particles and advected drifters at every step (sphmi_tracers_enable / sphmi_tracers_read) -------------
     TRACER_PARTICLE_VALUES, TRACER_DRIFTER_VALUES = 8, 10
-
-    def has_tracers(self) -> bool:
-        return self._has("tracers_enable") and self._has("tracers_read")
 
     def tracers_enable(self, particles=None, drifters=None, min_weight: float = 0.5, capacity: int = 4096) -> None:
         """Follow, after every executed step and on the device, the rows `particles` (at most 1024 row numbers of what `download`
@@ -552,9 +614,8 @@ class Backend:
         A second call replaces both sets and restarts the drifters; neither set disables."""
         rows = np.ascontiguousarray([] if particles is None else particles, dtype=np.int64).reshape(-1)
         x = np.ascontiguousarray(np.zeros((0, self.D)) if drifters is None else drifters, dtype=np.float64).reshape(-1, self.D)
-        f = self._fn("tracers_enable")
-        f.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_double, C.c_int64]
-        self._check(f(self._h, len(rows), _ptr(rows) if len(rows) else None, len(x), _ptr(x) if len(x) else None, float(min_weight), int(capacity)))
+        self._check(self._fn("tracers_enable")(self._h, len(rows), _ptr(rows) if len(rows) else None, len(x), _ptr(x) if len(x) else None,
+                                               float(min_weight), int(capacity)))
         self._tracers = (len(rows), len(x), float(min_weight))
 
     def tracers_read(self) -> dict:
@@ -564,34 +625,26 @@ class Backend:
         ``drifters``: ``position`` [K, m, 3] (where the sums of that step were taken, BEFORE its move), ``sums`` [K, m, 7] (raw S, SP,
         Srho, Sv[3], n) and, normalised as `probes_read` does, ``weight``, ``count``, ``pressure``, ``density``, ``velocity``;
         ``drifter_position`` [m, 3]: where the drifters are NOW; ``min_weight``; ``dropped``: older samples the capacity pushed out."""
-        f = self._fn("tracers_read")
-        f.argtypes = [C.c_void_p, C.c_int64] + [C.c_void_p] * 6 + [C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
-        n, dropped = C.c_int64(), C.c_int64()
-        self._check(f(self._h, 0, *[None] * 6, C.byref(n), C.byref(dropped)))                   # capacity 0: how many are waiting
-        np_, nd, min_weight = getattr(self, "_tracers", (0, 0, 0.5))
-        k = max(n.value, 1)
-        it, t, dt = np.zeros(k, dtype=np.int64), np.zeros(k), np.zeros(k)
-        pv, dv, x = np.zeros((k, np_, self.TRACER_PARTICLE_VALUES)), np.zeros((k, nd, self.TRACER_DRIFTER_VALUES)), np.zeros((nd, 3))
-        self._check(f(self._h, k, _ptr(it), _ptr(t), _ptr(dt), _ptr(pv), _ptr(dv), _ptr(x), C.byref(n), C.byref(dropped)))
-        self.tracers_dropped = dropped.value
-        K = n.value
-        it, t, dt, pv, dv = it[:K], t[:K], dt[:K], pv[:K], dv[:K]
+        np_, nd, min_weight = self._tracers
+        x = np.zeros((nd, 3))
+        got = self._read_series("tracers", (("particles", (np_, self.TRACER_PARTICLE_VALUES), np.float64),
+                                            ("drifters", (nd, self.TRACER_DRIFTER_VALUES), np.float64)), tail=(x,))
+        pv, dv = got["particles"], got["drifters"]
         sums = dv[:, :, 3:]
         S, cnt = sums[:, :, 0], sums[:, :, 6]
         some = (cnt > 0) & (S > 0)
         safe = np.where(some, S, 1.0)
         mean = lambda a: np.where(some if a.ndim == 2 else some[:, :, None], a / (safe if a.ndim == 2 else safe[:, :, None]), 0.0)    # noqa: E731
-        return {"iteration": it, "time": t, "dt": dt,
+        return {"iteration": got["iteration"], "time": got["time"], "dt": got["dt"],
                 "particles": {"values": pv, "position": pv[:, :, 0:3], "velocity": pv[:, :, 3:6], "density": pv[:, :, 6], "pressure": pv[:, :, 7]},
                 "drifters": {"position": dv[:, :, 0:3], "sums": sums, "weight": S, "count": cnt.astype(np.int64), "pressure": mean(sums[:, :, 1]),
                              "density": mean(sums[:, :, 2]), "velocity": mean(sums[:, :, 3:6])},
-                "drifter_position": x, "min_weight": min_weight, "dropped": int(dropped.value)}
+                "drifter_position": x, "min_weight": min_weight, "dropped": int(self.tracers_dropped)}
 
     # -- kernel sums on a regular lattice, on demand (sphmi_sample_grid) -----------------------------------------------------
-    GRID_FIELDS = ("weight", "count", "pressure", "density", "velocity")
-
-    def has_sample_grid(self) -> bool:
-        return self._has("sample_grid")
+    # the selectable outputs: name → (dtype, trailing shape), in the order of the C prototype
+    _GRID = {"weight": (_F64, ()), "count": (_INT64, ()), "pressure": (_F64, ()), "density": (_F64, ()), "velocity": (_F64, (3,))}
+    GRID_FIELDS = tuple(_GRID)
 
     def sample_grid(self, origin, spacing, counts, fields=None) -> dict:
         """The probes' sums at every node of a regular lattice, evaluated now: node (i, j, k) lies at
@@ -599,59 +652,27 @@ class Backend:
         nodes per axis, at most 2**24 in all.  Returns a dict of `weight` (S), `count`, `pressure`, `density`, each shaped
         ``counts[::-1]`` — x fastest, the order of VTK image data — and `velocity` shaped ``counts[::-1] + (3,)``; `fields`
         names the ones wanted (default: all).  Call it between `advance` calls, after the first executed step."""
-        D = self.D
-        o = np.ascontiguousarray(origin, dtype=np.float64).reshape(-1)
-        s = np.ascontiguousarray(spacing, dtype=np.float64).reshape(-1)
-        c = np.ascontiguousarray(counts, dtype=np.int64).reshape(-1)
-        if not (len(o) == len(s) == len(c) == D):
-            raise ValueError(f"sample_grid: origin, spacing and counts hold {D} entries each")
-        fields = self.GRID_FIELDS if fields is None else tuple(fields)
-        unknown = [k for k in fields if k not in self.GRID_FIELDS]
-        if unknown:
-            raise ValueError(f"sample_grid: unknown fields {unknown}")
-        f = self._fn("sample_grid")
-        f.argtypes = [C.c_void_p] * 9
+        o, s, c = self._lattice("sample_grid", origin, spacing, counts)
+        fields = self._wanted("sample_grid", self._GRID, fields)
         if (c < 1).any() or int(np.prod(c, dtype=object)) > MAX_GRID_NODES:
-            self._check(f(self._h, _ptr(o), _ptr(s), _ptr(c), *[None] * 5))     # the library words the refusal (state errors come first)
+            self._sample("sample_grid", self._GRID, (), (), _ptr(o), _ptr(s), _ptr(c))     # the library words the refusal (state errors come first)
             raise ValueError("sample_grid: counts out of range")
-        shape = tuple(int(v) for v in c[::-1])
-        out = {k: (np.zeros(shape + ((3,) if k == "velocity" else ()), dtype=np.int64 if k == "count" else np.float64) if k in fields else None)
-               for k in self.GRID_FIELDS}
-        self._check(f(self._h, _ptr(o), _ptr(s), _ptr(c), *[_ptr(out[k]) for k in self.GRID_FIELDS]))
-        return {k: v for k, v in out.items() if v is not None}
+        return self._sample("sample_grid", self._GRID, fields, tuple(int(v) for v in c[::-1]), _ptr(o), _ptr(s), _ptr(c))
 
     # -- kernel sums at arbitrary points, on demand (sphmi_sample_points) -----------------------------------------------------
-    def has_sample_points(self) -> bool:
-        return self._has("sample_points")
-
     def sample_points(self, positions, fields=None) -> dict:
         """The sums of `sample_grid` at every point of `positions` ([n, dims]: panel centroids, mesh nodes, a ring of sensors —
         any cloud of up to 2**24 points), evaluated now.  Returns the dict of `sample_grid` with a leading axis of n instead of
         the lattice's: `weight`, `count`, `pressure`, `density` [n] and `velocity` [n, 3], entry p belonging to
         ``positions[p]``; `fields` names the ones wanted (default: all).  A point's result does not depend on the other points
         of the call.  Call it between `advance` calls, after the first executed step."""
-        x = np.ascontiguousarray(positions, dtype=np.float64)
-        if x.ndim != 2 or x.shape[1] != self.D:
-            raise ValueError(f"sample_points: positions is shaped [n, {self.D}]")
-        fields = self.GRID_FIELDS if fields is None else tuple(fields)
-        unknown = [k for k in fields if k not in self.GRID_FIELDS]
-        if unknown:
-            raise ValueError(f"sample_points: unknown fields {unknown}")
-        n = len(x)
-        f = self._fn("sample_points")
-        f.argtypes = [C.c_void_p, C.c_int64] + [C.c_void_p] * 6
-        out = {k: (np.zeros((n, 3) if k == "velocity" else n, dtype=np.int64 if k == "count" else np.float64) if k in fields else None)
-               for k in self.GRID_FIELDS}
-        self._check(f(self._h, n, _ptr(x), *[_ptr(out[k]) for k in self.GRID_FIELDS]))
-        return {k: v for k, v in out.items() if v is not None}
+        x = self._cloud("sample_points", positions)
+        return self._sample("sample_points", self._GRID, fields, (len(x),), len(x), _ptr(x))
 
     # -- gradient sums at arbitrary points, on demand (sphmi_sample_point_gradients) ---------------------------------------------
-    # name → trailing shape, in the order of the C prototype; all float64 but `count`
-    GRADIENT_FIELDS = {"weight": (), "count": (), "sum_pressure": (), "sum_density": (), "sum_velocity": (3,), "grad_weight": (3,),
-                       "grad_pressure": (3,), "grad_density": (3,), "grad_velocity": (3, 3)}
-
-    def has_sample_point_gradients(self) -> bool:
-        return self._has("sample_point_gradients")
+    GRADIENT_FIELDS = {"weight": (_F64, ()), "count": (_INT64, ()), "sum_pressure": (_F64, ()), "sum_density": (_F64, ()),
+                       "sum_velocity": (_F64, (3,)), "grad_weight": (_F64, (3,)), "grad_pressure": (_F64, (3,)),
+                       "grad_density": (_F64, (3,)), "grad_velocity": (_F64, (3, 3))}
 
     def sample_point_gradients(self, positions, fields=None) -> dict:
         """The RAW kernel sums and gradient sums at every point of `positions` ([n, dims], up to 2**24 points), evaluated now:
@@ -662,30 +683,14 @@ class Backend:
         wanted (default: all).  Entry p belongs to ``positions[p]`` and does not depend on the other points of the call;
         multi-device handles of one process deliver the sums over all slabs.  Call it between `advance` calls, after the
         first executed step."""
-        x = np.ascontiguousarray(positions, dtype=np.float64)
-        if x.ndim != 2 or x.shape[1] != self.D:
-            raise ValueError(f"sample_point_gradients: positions is shaped [n, {self.D}]")
-        fields = tuple(self.GRADIENT_FIELDS) if fields is None else tuple(fields)
-        unknown = [k for k in fields if k not in self.GRADIENT_FIELDS]
-        if unknown:
-            raise ValueError(f"sample_point_gradients: unknown fields {unknown}")
-        n = len(x)
-        f = self._fn("sample_point_gradients")
-        f.argtypes = [C.c_void_p, C.c_int64] + [C.c_void_p] * 10
-        out = {k: (np.zeros((n,) + shape, dtype=np.int64 if k == "count" else np.float64) if k in fields else None)
-               for k, shape in self.GRADIENT_FIELDS.items()}
-        self._check(f(self._h, n, _ptr(x), *[_ptr(out[k]) for k in self.GRADIENT_FIELDS]))
-        return {k: v for k, v in out.items() if v is not None}
+        x = self._cloud("sample_point_gradients", positions)
+        return self._sample("sample_point_gradients", self.GRADIENT_FIELDS, fields, (len(x),), len(x), _ptr(x))
 
     # -- the first crossing of S = level along rays, on demand (sphmi_cast_rays) ---------------------------------------------------
-    # name → (dtype, trailing shape), in the order of the C prototype's outputs
-    RAY_FIELDS = {"status": (np.int32, ()), "interval": (np.int64, ()), "bracket": (np.float64, (2,)), "point": (np.float64, (3,)),
-                  "weight": (np.float64, ()), "count": (np.int64, ()), "sum_pressure": (np.float64, ()), "sum_density": (np.float64, ()),
-                  "sum_velocity": (np.float64, (3,))}
+    RAY_FIELDS = {"status": (np.int32, ()), "interval": (_INT64, ()), "bracket": (_F64, (2,)), "point": (_F64, (3,)),
+                  "weight": (_F64, ()), "count": (_INT64, ()), "sum_pressure": (_F64, ()), "sum_density": (_F64, ()),
+                  "sum_velocity": (_F64, (3,))}
     RAY_MODES = {"enter": RAY_ENTER, "leave": RAY_LEAVE, "any": RAY_ANY}
-
-    def has_cast_rays(self) -> bool:
-        return self._has("cast_rays")
 
     def cast_rays(self, origins, directions, t_end, t_begin=0.0, step=None, level=0.5, mode="enter", fields=None) -> dict:
         """Where along each ray ``origins[r] + t * directions[r]`` ([n, dims]; `t_begin`, `t_end` numbers or [n]; t and `step` in
@@ -705,23 +710,15 @@ class Backend:
         te = np.ascontiguousarray(np.broadcast_to(np.asarray(t_end, dtype=np.float64), (n,)))
         if mode not in self.RAY_MODES:
             raise ValueError(f"cast_rays: mode is one of {sorted(self.RAY_MODES)}")
-        fields = tuple(self.RAY_FIELDS) if fields is None else tuple(fields)
-        unknown = [k for k in fields if k not in self.RAY_FIELDS]
-        if unknown:
-            raise ValueError(f"cast_rays: unknown fields {unknown}")
+        fields = self._wanted("cast_rays", self.RAY_FIELDS, fields)
         step = 0.5 * float(self.cfg.h) if step is None else float(step)
-        f = self._fn("cast_rays")
-        f.argtypes = [C.c_void_p, C.c_int64] + [C.c_void_p] * 4 + [C.c_double, C.c_double, C.c_int32] + [C.c_void_p] * 9
-        out = {k: (np.zeros((n,) + shape, dtype=dt) if k in fields else None) for k, (dt, shape) in self.RAY_FIELDS.items()}
-        self._check(f(self._h, n, _ptr(o), _ptr(d), _ptr(tb), _ptr(te), step, float(level), self.RAY_MODES[mode],
-                      *[_ptr(out[k]) for k in self.RAY_FIELDS]))
-        return {k: v for k, v in out.items() if v is not None}
+        return self._sample("cast_rays", self.RAY_FIELDS, fields, (n,), n, _ptr(o), _ptr(d), _ptr(tb), _ptr(te), step, float(level),
+                            self.RAY_MODES[mode])
 
     # -- differential fields at the particles, on demand (sphmi_particle_fields) ------------------------------------------------
-    PARTICLE_FIELDS = ("count", "shepard", "normal", "div_r", "div_v", "vorticity")
-
-    def has_particle_fields(self) -> bool:
-        return self._has("particle_fields")
+    _PARTICLE = {"count": (_INT64, ()), "shepard": (_F64, ()), "normal": (_F64, (3,)), "div_r": (_F64, ()), "div_v": (_F64, ()),
+                 "vorticity": (_F64, (3,))}
+    PARTICLE_FIELDS = tuple(_PARTICLE)
 
     def particle_fields(self, fields=PARTICLE_FIELDS) -> dict:
         """Vorticity, velocity divergence, the free-surface indicator div r, the free-surface normal, the Shepard sum and the
@@ -729,56 +726,25 @@ class Backend:
         (int64), `shepard`, `div_r`, `div_v` [n] and `normal`, `vorticity` [n, 3] (2-D: only the z component of the vorticity
         and the x, y of the normal are non-zero), row i being row i of what `download` delivers now.  Only the fields named are
         computed into host arrays.  Single-device handles; call it between `advance` calls, after the first executed step."""
-        fields = tuple(fields)
-        unknown = [k for k in fields if k not in self.PARTICLE_FIELDS]
-        if unknown:
-            raise ValueError(f"particle_fields: unknown fields {unknown}")
-        f = self._fn("particle_fields")
-        f.argtypes = [C.c_void_p] * 7
-        n = self.N
-        out = {k: (np.zeros((n, 3) if k in ("normal", "vorticity") else n, dtype=np.int64 if k == "count" else np.float64) if k in fields else None)
-               for k in self.PARTICLE_FIELDS}
-        self._check(f(self._h, *[_ptr(out[k]) for k in self.PARTICLE_FIELDS]))
-        return {k: v for k, v in out.items() if v is not None}
+        return self._sample("particle_fields", self._PARTICLE, fields, (self.N,))
 
     # -- the neighbour list of every row, on demand (sphmi_neighbors_build / _read / _release) ----------------------------------
-    def has_neighbor_list(self) -> bool:
-        return all(self._has(n) for n in ("neighbors_build", "neighbors_read", "neighbors_release"))
-
     def neighbors_build(self, half: bool = False):
         """Build the CSR neighbour list of every row on the device and keep it there: (n_rows, n_pairs).  `half`: only j > i,
         every pair once.  It stays until the next build, `neighbors_release` or `close`; a step, an upload or `forces_once`
         marks it stale."""
-        f = self._fn("neighbors_build")
-        f.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
-        rows, pairs = C.c_int64(), C.c_int64()
-        self._neighbor_shape = None                                               # (a refused build leaves nothing this object may read)
-        self._check(f(self._h, NEIGHBORS_HALF if half else NEIGHBORS_FULL, C.byref(rows), C.byref(pairs)))
-        self._neighbor_shape = (rows.value, pairs.value)
-        return self._neighbor_shape
+        return self._held_build("neighbors", NEIGHBORS_HALF if half else NEIGHBORS_FULL)
 
     def neighbors_read(self, offsets: bool = True, neighbors: bool = True):
         """(offsets int64 [n_rows + 1], neighbors int32 [n_pairs]) of the list built last; False skips one (None in its place).
         sphmi_neighbors_read takes no capacities: the arrays are sized from what THIS object's `neighbors_build` reported, so a
         list built through the raw entry point behind its back must not be read here.  Without a build of its own the library
         is asked with both pointers NULL — it words the refusal — and a list it then turns out to hold is refused here."""
-        f = self._fn("neighbors_read")
-        f.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
-        shape = getattr(self, "_neighbor_shape", None)
-        if shape is None:
-            self._check(f(self._h, None, None))
-            raise RuntimeError("neighbors_read: the handle holds a list this object did not build; call neighbors_build first")
-        rows, pairs = shape
-        off = np.zeros(rows + 1, dtype=np.int64) if offsets else None
-        nbr = np.zeros(pairs, dtype=np.int32) if neighbors else None
-        self._check(f(self._h, _ptr(off), _ptr(nbr)))
-        return off, nbr
+        return self._held_read("neighbors", lambda rows, pairs: (np.zeros(rows + 1, dtype=np.int64) if offsets else None,
+                                                                 np.zeros(pairs, dtype=np.int32) if neighbors else None))
 
     def neighbors_release(self) -> None:
-        f = self._fn("neighbors_release")
-        f.argtypes = [C.c_void_p]
-        self._check(f(self._h))
-        self._neighbor_shape = None
+        self._held_release("neighbors")
 
     def neighbor_list(self, half: bool = False):
         """The neighbour list of every row, evaluated now: (offsets int64 [n + 1], neighbors int32 [total]); row i — row i of what
@@ -792,48 +758,23 @@ class Backend:
             self.neighbors_release()
 
     # -- the free surface as a mesh, on demand (sphmi_isosurface_build / _read / _release) ---------------------------------------
-    def has_isosurface(self) -> bool:
-        return all(self._has(n) for n in ("isosurface_build", "isosurface_read", "isosurface_release"))
-
     def isosurface_build(self, origin, spacing, counts, level: float = 0.5):
         """Sample the Shepard sum on the lattice of `sample_grid` and extract the surface ``S == level`` on the device, where it
         stays: (n_vertices, n_elements).  It is held until the next build, `isosurface_release` or `close`; a step, an upload or
         `forces_once` marks it stale."""
-        D = self.D
-        o = np.ascontiguousarray(origin, dtype=np.float64).reshape(-1)
-        s = np.ascontiguousarray(spacing, dtype=np.float64).reshape(-1)
-        c = np.ascontiguousarray(counts, dtype=np.int64).reshape(-1)
-        if not (len(o) == len(s) == len(c) == D):
-            raise ValueError(f"isosurface_build: origin, spacing and counts hold {D} entries each")
-        f = self._fn("isosurface_build")
-        f.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
-        nv, ne = C.c_int64(), C.c_int64()
-        self._isosurface_shape = None                                             # (a refused build leaves nothing this object may read)
-        self._check(f(self._h, _ptr(o), _ptr(s), _ptr(c), float(level), C.byref(nv), C.byref(ne)))
-        self._isosurface_shape = (nv.value, ne.value)
-        return self._isosurface_shape
+        o, s, c = self._lattice("isosurface_build", origin, spacing, counts)
+        return self._held_build("isosurface", _ptr(o), _ptr(s), _ptr(c), float(level))
 
     def isosurface_read(self, vertices: bool = True, elements: bool = True, pressure: bool = False, velocity: bool = False):
         """(vertices float64 [nv, 3], elements int32 [ne, D], pressure [nv], velocity [nv, 3]) of the mesh built last; False skips
         one (None in its place).  sphmi_isosurface_read takes no capacities: the arrays are sized from what THIS object's
         `isosurface_build` reported, so a mesh built through the raw entry point behind its back must not be read here."""
-        f = self._fn("isosurface_read")
-        f.argtypes = [C.c_void_p] * 5
-        shape = getattr(self, "_isosurface_shape", None)
-        if shape is None:
-            self._check(f(self._h, None, None, None, None))                        # the library words the refusal
-            raise RuntimeError("isosurface_read: the handle holds a mesh this object did not build; call isosurface_build first")
-        nv, ne = shape
-        out = (np.zeros((nv, 3)) if vertices else None, np.zeros((ne, self.D), dtype=np.int32) if elements else None,
-               np.zeros(nv) if pressure else None, np.zeros((nv, 3)) if velocity else None)
-        self._check(f(self._h, *[_ptr(a) for a in out]))
-        return out
+        return self._held_read("isosurface", lambda nv, ne: (np.zeros((nv, 3)) if vertices else None,
+                                                             np.zeros((ne, self.D), dtype=np.int32) if elements else None,
+                                                             np.zeros(nv) if pressure else None, np.zeros((nv, 3)) if velocity else None))
 
     def isosurface_release(self) -> None:
-        f = self._fn("isosurface_release")
-        f.argtypes = [C.c_void_p]
-        self._check(f(self._h))
-        self._isosurface_shape = None
+        self._held_release("isosurface")
 
     def isosurface(self, origin, spacing, counts, level: float = 0.5, attributes: bool = False):
         """The free surface as a mesh, evaluated now: ``(vertices [nv, 3], elements [ne, D] int32)`` — triangles on 3-D handles,
@@ -852,9 +793,6 @@ class Backend:
     # -- the connected bodies of selected rows, on demand (sphmi_components_build / _read / _release) ----------------------------
     COMPONENT_TYPES = {"Fluid": 1, "Fixed": 2, "Moving": 3}
 
-    def has_components(self) -> bool:
-        return all(self._has(n) for n in ("components_build", "components_read", "components_release"))
-
     def _type_mask(self, types) -> int:
         if isinstance(types, (str, int, np.integer)):
             types = (types,)
@@ -870,35 +808,19 @@ class Backend:
         keep the result there: (n_rows, n_components).  Two selected rows are linked iff r^2 <= link^2 on the current positions;
         `link=None` means H, the longest the library serves.  It stays until the next build, `components_release` or `close`; a
         step, an upload or `forces_once` marks it stale."""
-        f = self._fn("components_build")
-        f.argtypes = [C.c_void_p, C.c_double, C.c_uint32, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
-        rows, comps = C.c_int64(), C.c_int64()
-        self._components_shape = None                                             # (a refused build leaves nothing this object may read)
-        self._check(f(self._h, float(self.cfg.H if link is None else link), self._type_mask(types), C.byref(rows), C.byref(comps)))
-        self._components_shape = (rows.value, comps.value)
-        return self._components_shape
+        return self._held_build("components", float(self.cfg.H if link is None else link), self._type_mask(types))
 
     def components_read(self, label: bool = True, first_row: bool = True, count: bool = True, box: bool = True):
         """(label int32 [n_rows], first_row int32 [C], count int32 [C], box float64 [C, 6]) of the components built last; False
         skips one (None in its place).  sphmi_components_read takes no capacities: the arrays are sized from what THIS object's
         `components_build` reported, so a result built through the raw entry point behind its back must not be read here."""
-        f = self._fn("components_read")
-        f.argtypes = [C.c_void_p] * 5
-        shape = getattr(self, "_components_shape", None)
-        if shape is None:
-            self._check(f(self._h, None, None, None, None))                        # the library words the refusal
-            raise RuntimeError("components_read: the handle holds components this object did not build; call components_build first")
-        rows, comps = shape
-        out = (np.zeros(rows, dtype=np.int32) if label else None, np.zeros(comps, dtype=np.int32) if first_row else None,
-               np.zeros(comps, dtype=np.int32) if count else None, np.zeros((comps, 6)) if box else None)
-        self._check(f(self._h, *[_ptr(a) for a in out]))
-        return out
+        return self._held_read("components", lambda rows, comps: (np.zeros(rows, dtype=np.int32) if label else None,
+                                                                  np.zeros(comps, dtype=np.int32) if first_row else None,
+                                                                  np.zeros(comps, dtype=np.int32) if count else None,
+                                                                  np.zeros((comps, 6)) if box else None))
 
     def components_release(self) -> None:
-        f = self._fn("components_release")
-        f.argtypes = [C.c_void_p]
-        self._check(f(self._h))
-        self._components_shape = None
+        self._held_release("components")
 
     def components(self, link=None, types=("Fluid",)) -> dict:
         """The connected bodies of the rows of `types`, evaluated now: a dict of `label` int32 [n] (the component of row i — row i of
@@ -924,3 +846,7 @@ class Backend:
         out = np.empty((n.value, self.D), dtype=np.int64)
         self._check(self._fn("unique_cells")(self._h, _ptr(out), n.value, C.byref(n)))
         return out
+
+
+for _feature, _symbols in FEATURES.items():       # has_columns(), has_group_forces(), … has_components()
+    setattr(Backend, "has_" + _feature, lambda self, _symbols=_symbols: self._has_all(_symbols))

@@ -14,9 +14,7 @@ from ._abi import Backend
 
 def empty_budgets() -> dict:
     """A series of no steps, shaped like ``Backend.budgets_read``'s."""
-    out = {"iteration": np.zeros(0, dtype=np.int64), "time": np.zeros(0), "dt": np.zeros(0)}
-    out.update({name: np.zeros((0,) + shape, dtype=dtype) for name, shape, dtype in Backend.BUDGET_FIELDS})
-    return out
+    return Backend.empty_series(Backend.BUDGET_FIELDS)
 
 
 def total_energy(samples) -> np.ndarray:

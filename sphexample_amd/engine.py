@@ -10,7 +10,7 @@ import os
 import numpy as np
 
 from . import build as _build
-from ._abi import MAX_DEVICES, OK, Backend, SphmiConfig, SphmiError, make_config
+from ._abi import MAX_DEVICES, OK, Backend, SphmiConfig, SphmiError, SphmiMultiInfo, bind, last_error, make_config
 
 _lib = None
 
@@ -29,14 +29,8 @@ def load_library(rebuild_if_stale: bool = True) -> C.CDLL:
                 raise RuntimeError(f"libsphmi.so is missing and cannot be built: {exc}") from exc
     if not os.path.exists(path):
         raise RuntimeError("libsphmi.so is missing: run `python -m sphexample_amd.build` (needs hipcc)")
-    lib = C.CDLL(path)
-    lib.sphmi_backend_info.restype = C.c_char_p
-    lib.sphmi_timers.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_char_p), C.POINTER(C.c_double),
-                                 C.POINTER(C.c_int64), C.POINTER(C.c_int32)]
-    lib.sphmi_force_kernel_stats.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_int64)]
-    lib.sphmi_device_ptrs.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]
-    _lib = lib
-    return lib
+    _lib = C.CDLL(path)
+    return _lib
 
 
 def _reset_library_cache() -> None:
@@ -46,30 +40,27 @@ def _reset_library_cache() -> None:
 
 
 def backend_info() -> str:
-    return load_library().sphmi_backend_info().decode()
+    return bind(load_library(), "backend_info")().decode()
 
 
-class SphmiMultiInfo(C.Structure):
-    _fields_ = [("world", C.c_int32), ("n_local", C.c_int32), ("axis", C.c_int32), ("halo_width", C.c_int32),
-                ("transport", C.c_int32), ("reserved", C.c_int32), ("n_recuts", C.c_int64),
-                ("cuts", C.c_int64 * MAX_DEVICES), ("n_live", C.c_int64 * MAX_DEVICES)]
+def _call(name, *args) -> None:
+    """An entry point that takes no handle: a refusal carries the library's text."""
+    lib = load_library()
+    rc = bind(lib, name)(*args)
+    if rc != OK:
+        raise SphmiError(rc, last_error(lib))
 
 
 def rccl_unique_id() -> bytes:
     """128 bytes for sphmi_create_rank: made on rank 0, handed to the other ranks by the launcher."""
     buf = C.create_string_buffer(128)
-    rc = load_library().sphmi_rccl_unique_id(buf)
-    if rc != OK:
-        raise SphmiError(rc, (load_library().sphmi_last_error(None) or b"").decode())
+    _call("rccl_unique_id", buf)
     return buf.raw
 
 
 def rccl_probe() -> None:
     """RCCL binds in this process (no id is made: `ncclGetUniqueId` starts a bootstrap root — a socket and a thread — per call)."""
-    lib = load_library()
-    rc = lib.sphmi_rccl_probe()
-    if rc != OK:
-        raise SphmiError(rc, (lib.sphmi_last_error(None) or b"").decode())
+    _call("rccl_probe")
 
 
 class Engine(Backend):
@@ -81,36 +72,31 @@ class Engine(Backend):
         if rank is None:
             super().__init__(lib, "sphmi_", cfg)
         else:
-            lib.sphmi_create_rank.argtypes = [C.POINTER(SphmiConfig), C.c_int32, C.c_int32, C.c_char_p, C.POINTER(C.c_void_p)]
-            create = lambda c, h: lib.sphmi_create_rank(c, rank, world, unique_id, h)  # noqa: E731
+            create = lambda c, h: bind(lib, "create_rank")(c, rank, world, unique_id, h)  # noqa: E731
             super().__init__(lib, "sphmi_", cfg, create=create)
         self.rank_mode = rank is not None
 
     def multi_info(self) -> SphmiMultiInfo:
         info = SphmiMultiInfo()
-        self._lib.sphmi_multi_info_get.argtypes = [C.c_void_p, C.POINTER(SphmiMultiInfo)]
-        self._check(self._lib.sphmi_multi_info_get(self._h, C.byref(info)))
+        self._check(self._fn("multi_info_get")(self._h, C.byref(info)))
         return info
 
     @property
     def device_float_bytes(self) -> int:
         """The arithmetic this handle runs (the resolution of `device_float_bytes = 0`)."""
         n = C.c_int32()
-        self._lib.sphmi_device_float_bytes.argtypes = [C.c_void_p, C.POINTER(C.c_int32)]
-        self._check(self._lib.sphmi_device_float_bytes(self._h, C.byref(n)))
+        self._check(self._fn("device_float_bytes")(self._h, C.byref(n)))
         return n.value
 
     def owned_count(self) -> int:
         n = C.c_int64()
-        self._lib.sphmi_owned_count.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
-        self._check(self._lib.sphmi_owned_count(self._h, C.byref(n)))
+        self._check(self._fn("owned_count")(self._h, C.byref(n)))
         return n.value
 
     def set_cuts(self, cuts) -> None:
         """Test hook: initial slab cuts (first cell column of slabs 1 … world-1) instead of the balanced ones."""
         a = np.ascontiguousarray(cuts, dtype=np.int64)
-        self._lib.sphmi_multi_set_cuts.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
-        self._check(self._lib.sphmi_multi_set_cuts(self._h, a.ctypes.data_as(C.c_void_p), len(a)))
+        self._check(self._fn("multi_set_cuts")(self._h, a.ctypes.data_as(C.c_void_p), len(a)))
 
     def download(self, *args, **kw) -> dict:
         out = super().download(*args, **kw)
@@ -124,13 +110,13 @@ class Engine(Backend):
         secs = (C.c_double * 16)()
         calls = (C.c_int64 * 16)()
         n = C.c_int32()
-        self._check(self._lib.sphmi_timers(self._h, 16, names, secs, calls, C.byref(n)))
+        self._check(self._fn("timers")(self._h, 16, names, secs, calls, C.byref(n)))
         return {names[i].decode(): (secs[i], calls[i]) for i in range(n.value)}
 
     def force_kernel_stats(self, reset: bool = False):
         ms = C.c_double()
         n = C.c_int64()
-        self._check(self._lib.sphmi_force_kernel_stats(self._h, int(reset), C.byref(ms), C.byref(n)))
+        self._check(self._fn("force_kernel_stats")(self._h, int(reset), C.byref(ms), C.byref(n)))
         return ms.value, n.value
 
 
@@ -166,11 +152,9 @@ def make_engine(particles, setup, device_float_bytes: int = 0, device: int = 0, 
 def dam_break_3d_count(dp: float):
     """(boundary, fluid) particles of the 3-D dam-break lattice at spacing dp (host formula of the library)."""
     nb, nf = C.c_int64(), C.c_int64()
-    lib = load_library()
-    lib.sphmi_dam_break_3d_count.argtypes = [C.c_double, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
-    rc = lib.sphmi_dam_break_3d_count(dp, C.byref(nb), C.byref(nf))
+    rc = bind(load_library(), "dam_break_3d_count")(dp, C.byref(nb), C.byref(nf))
     if rc != OK:
-        raise SphmiError(rc, "sphmi_dam_break_3d_count")
+        raise SphmiError(rc, "sphmi_dam_break_3d_count")          # (a host formula: the library leaves no text)
     return nb.value, nf.value
 
 
@@ -181,8 +165,7 @@ def make_generated_dam_break_engine(dp: float, setup, device_float_bytes: int = 
     cfg = make_config(nb + nf, setup.SimConstants, setup.SimKernel, setup.SimMetaData, setup.SimViscosity,
                       setup.SimDensityDiffusion, device_float_bytes=device_float_bytes, host_float_bytes=8, device=device)
     e = Engine(cfg)
-    e._lib.sphmi_generate_dam_break_3d.argtypes = [C.c_void_p, C.c_double]
-    e._check(e._lib.sphmi_generate_dam_break_3d(e._h, dp))
+    e._check(e._fn("generate_dam_break_3d")(e._h, dp))
     return e
 
 

@@ -17,9 +17,7 @@ FLUID = 1
 
 def empty_flow(n_boxes: int) -> dict:
     """A series of no steps, shaped like ``Backend.flow_read``'s for `n_boxes` boxes."""
-    out = {"iteration": np.zeros(0, dtype=np.int64), "time": np.zeros(0), "dt": np.zeros(0)}
-    out.update({name: np.zeros((0, int(n_boxes)) + shape, dtype=dtype) for name, shape, dtype in Backend.FLOW_FIELDS})
-    return out
+    return Backend.empty_series(Backend.FLOW_FIELDS, int(n_boxes))
 
 
 def strips(axis: int, edges, dims: int):

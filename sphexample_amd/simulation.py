@@ -14,7 +14,7 @@ from typing import Callable, List, Optional
 
 import numpy as np
 
-from ._abi import make_config
+from ._abi import Backend, make_config
 from .config import (SimulationConstants, SimulationMetaData, SPHDensityDiffusion, SPHKernelInstance,
                      SPHViscosity, next_output_time)
 from .budgets import empty_budgets
@@ -163,59 +163,49 @@ def RunSimulation(*, SimGeometry=None, SimMetaData: SimulationMetaData, SimConst
     eng.set_clock(SimMetaData.Iteration, SimMetaData.TotalTime)
     time_steps: List[float] = []
     SimMetaData.OutputIterationCounter = 1                                       # :849
-    extras = []          # per output: what the callback receives behind the particles — a list of (first value, reader)
-    if group_forces is not None:
-        markers = [int(m) for m in group_forces]
-        eng.group_forces_enable(markers, capacity=1 << 20)
-        extras.append(((np.zeros(0, dtype=np.int64), np.zeros(0), np.zeros(0), np.zeros((0, len(markers), 3))), eng.group_forces_read))
-    if probes is not None:
-        points = np.ascontiguousarray(probes, dtype=np.float64).reshape(-1, SimMetaData.Dimensions)
-        eng.probes_enable(points, capacity=1 << 16)
-        m = len(points)
-        extras.append(({"iteration": np.zeros(0, dtype=np.int64), "time": np.zeros(0), "dt": np.zeros(0), "weight": np.zeros((0, m)),
-                        "count": np.zeros((0, m), dtype=np.int64), "pressure": np.zeros((0, m)), "density": np.zeros((0, m)),
-                        "velocity": np.zeros((0, m, 3))}, eng.probes_read))
-    if field_grid is not None:
-        lattice = tuple(field_grid)
-        extras.append((None, lambda: eng.sample_grid(*lattice)))                 # (the state of this output: sampled before the next advance)
-    if particle_fields is not None:
-        names = tuple(particle_fields)
-        extras.append((None, lambda: eng.particle_fields(names)))                # (the rows of this output: no step lies between it and the download)
-    if neighbor_list:
-        extras.append((None, lambda: eng.neighbor_list()))                       # (the rows of this output, like the fields above)
-    if isosurface is not None:
-        surface = tuple(isosurface)
-        extras.append((None, lambda: eng.isosurface(*surface)))                  # (the state of this output, like the field grid)
-    if components is not None and components is not False:
-        asked = () if components is True else tuple(components) if isinstance(components, (tuple, list)) else (components,)
-        extras.append((None, lambda: eng.components(*asked)))                    # (the rows of this output, like the neighbour list)
-    if budgets:
-        eng.budgets_enable(capacity=1 << 20)
-        extras.append((empty_budgets(), eng.budgets_read))
-    if flow_boxes is not None:
-        if len(flow_boxes) == 0:
+    dims = SimMetaData.Dimensions
+    cloud = lambda v: np.ascontiguousarray(v, dtype=np.float64).reshape(-1, dims)            # noqa: E731
+    chosen = lambda v: None if v is False else v                                             # noqa: E731
+    series = Backend.empty_series
+
+    def boxes(v):
+        if len(v) == 0:
             raise ValueError("RunSimulation: flow_boxes holds no box (pass None to record nothing)")
-        boxes = [(np.asarray(lo, dtype=np.float64), np.asarray(hi, dtype=np.float64)) for lo, hi in flow_boxes]
-        eng.flow_enable([lo for lo, _ in boxes], [hi for _, hi in boxes], capacity=1 << 20)
-        extras.append((empty_flow(len(boxes)), eng.flow_read))
-    if envelopes is not None and envelopes is not False:
-        eng.envelopes_enable(("Fluid",) if envelopes is True else envelopes)
-        extras.append((None, eng.envelopes_read))                                # (the rows of this output: no step lies between it and the download)
-    if maps is not None:
-        eng.maps_enable(*tuple(maps))
-        extras.append((None, eng.maps_read))
-    if tracers is not None:
-        eng.tracers_enable(capacity=1 << 16, **dict(tracers))
-        extras.append((None, eng.tracers_read))                                  # (None at the first call: no step, no record)
-    if sample_points is not None:
-        cloud = np.ascontiguousarray(sample_points, dtype=np.float64).reshape(-1, SimMetaData.Dimensions)
-        extras.append((None, lambda: eng.sample_points(cloud)))                  # (the state of this output, like the field grid)
-    if sample_point_gradients is not None:
-        gradient_cloud = np.ascontiguousarray(sample_point_gradients, dtype=np.float64).reshape(-1, SimMetaData.Dimensions)
-        extras.append((None, lambda: eng.sample_point_gradients(gradient_cloud)))
-    if rays is not None:
-        ray_call = dict(rays)
-        extras.append((None, lambda: eng.cast_rays(**ray_call)))                 # (the state of this output, like the clouds above)
+        return [(np.asarray(lo, dtype=np.float64), np.asarray(hi, dtype=np.float64)) for lo, hi in v]
+
+    # What the callback receives behind the particles, in this order.  Per row: the keyword's value (None: off), what makes its
+    # normal form `a` of it, the enable call, the first value — handed over before the first step — and the reader of every later
+    # output.  No enable: nothing is recorded between the outputs, the reader evaluates the state of its output (no step lies
+    # between it and the download).  No first value: None at the first call.
+    table = (
+        (group_forces, lambda v: [int(m) for m in v], lambda a: eng.group_forces_enable(a, capacity=1 << 20),
+         lambda a: tuple(series(Backend.GROUP_FORCE_FIELDS, len(a)).values()), lambda a: eng.group_forces_read()),
+        (probes, cloud, lambda a: eng.probes_enable(a, capacity=1 << 16),
+         lambda a: series(Backend.PROBE_FIELDS, len(a)), lambda a: eng.probes_read()),
+        (field_grid, tuple, None, None, lambda a: eng.sample_grid(*a)),
+        (particle_fields, tuple, None, None, lambda a: eng.particle_fields(a)),
+        (neighbor_list or None, bool, None, None, lambda a: eng.neighbor_list()),
+        (isosurface, tuple, None, None, lambda a: eng.isosurface(*a)),
+        (chosen(components), lambda v: () if v is True else tuple(v) if isinstance(v, (tuple, list)) else (v,), None, None,
+         lambda a: eng.components(*a)),
+        (budgets or None, bool, lambda a: eng.budgets_enable(capacity=1 << 20), lambda a: empty_budgets(), lambda a: eng.budgets_read()),
+        (flow_boxes, boxes, lambda a: eng.flow_enable([lo for lo, _ in a], [hi for _, hi in a], capacity=1 << 20),
+         lambda a: empty_flow(len(a)), lambda a: eng.flow_read()),
+        (chosen(envelopes), lambda v: ("Fluid",) if v is True else v, lambda a: eng.envelopes_enable(a), None, lambda a: eng.envelopes_read()),
+        (maps, tuple, lambda a: eng.maps_enable(*a), None, lambda a: eng.maps_read()),
+        (tracers, dict, lambda a: eng.tracers_enable(capacity=1 << 16, **a), None, lambda a: eng.tracers_read()),
+        (sample_points, cloud, None, None, lambda a: eng.sample_points(a)),
+        (sample_point_gradients, cloud, None, None, lambda a: eng.sample_point_gradients(a)),
+        (rays, dict, None, None, lambda a: eng.cast_rays(**a)),
+    )
+    extras = []          # per output: what the callback receives behind the particles — a list of (first value, reader)
+    for value, normal, enable, first, read in table:
+        if value is None:
+            continue
+        a = normal(value)
+        if enable:
+            enable(a)
+        extras.append((first(a) if first else None, lambda read=read, a=a: read(a)))
     none_yet = tuple(first for first, _ in extras)
     emit = lambda meta, samples: on_output(meta, SimParticles, *samples)         # noqa: E731
     if on_output:

@@ -55,12 +55,12 @@ def main():
     med, lo, hi = timed(lambda: eng.download(), args.reps)
     print(f"[dam break 3-D, N={eng.N}, fp32, {args.steps} steps in] full sphmi_download into fresh arrays: {med:.2f} ms (min {lo:.2f}, max {hi:.2f})", flush=True)
     into = {k: np.empty_like(v) for k, v in d.items()}
-    f = eng._fn("download"); f.argtypes = [C.c_void_p] * 11
+    f = eng._fn("download")
     order = ("Position", "Velocity", "Acceleration", "Density", "Pressure", "ID", "Type", "GroupMarker", "GhostPoints", "Cells")
     ptrs = [into[k].ctypes.data_as(C.c_void_p) for k in order]
     med, lo, hi = timed(lambda: eng._check(f(eng._h, *ptrs)), args.reps)
     print(f"[dam break 3-D, N={eng.N}] full sphmi_download into the same arrays: {med:.2f} ms (min {lo:.2f}, max {hi:.2f})", flush=True)
-    g = eng._fn("sample_grid"); g.argtypes = [C.c_void_p] * 9
+    g = eng._fn("sample_grid")
     for n in [float(x) for x in args.nodes.split(",")]:
         o, s, c = lattice(n)
         nodes = int(c.prod())

@@ -41,7 +41,7 @@ def main():
     eng.advance(1e9, max_steps=args.steps)
     o, s, c = lattice(args.nodes)
     nodes = int(c.prod())
-    g = eng._fn("sample_grid"); g.argtypes = [C.c_void_p] * 9
+    g = eng._fn("sample_grid")
     po, ps, pc = [a.ctypes.data_as(C.c_void_p) for a in (o, s, c)]
     print(f"[dam break 3-D, N={eng.N}, fp32, {args.steps} steps in] lattice {tuple(int(v) for v in c)} = {nodes} nodes, spacing {s[0] / eng.cfg.H:.3f} H", flush=True)
     for rep in range(3):

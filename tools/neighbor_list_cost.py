@@ -45,7 +45,7 @@ def main():
     args = ap.parse_args()
     eng = make_generated_dam_break_engine(DP, setup_dam_break_3d(DP), device_float_bytes=4)
     eng.advance(1e9, max_steps=args.steps)
-    g = eng._fn("particle_fields"); g.argtypes = [C.c_void_p] * 7
+    g = eng._fn("particle_fields")
     for rep in range(3):
         k = timed(lambda: eng._check(g(eng._h, *[None] * 6)), args.reps)
         print(f"[dam break 3-D, N={eng.N}, fp32, {args.steps} steps in] yardstick {rep + 1}/3: sphmi_particle_fields kernel {k[0]:.2f} ms (min {k[1]:.2f}, max {k[2]:.2f})", flush=True)

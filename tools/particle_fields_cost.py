@@ -68,11 +68,11 @@ def main():
     eng.advance(1e9, max_steps=args.steps)
     d = eng.download()
     order = ("Position", "Velocity", "Acceleration", "Density", "Pressure", "ID", "Type", "GroupMarker", "GhostPoints", "Cells")
-    f = eng._fn("download"); f.argtypes = [C.c_void_p] * 11
+    f = eng._fn("download")
     ptrs = [d[k].ctypes.data_as(C.c_void_p) for k in order]
     dl = timed(lambda: eng._check(f(eng._h, *ptrs)), args.reps)
     print(f"[dam break 3-D, N={eng.N}, fp32, {args.steps} steps in] full sphmi_download into the same arrays: {dl[0]:.2f} ms (min {dl[1]:.2f}, max {dl[2]:.2f})", flush=True)
-    g = eng._fn("particle_fields"); g.argtypes = [C.c_void_p] * 7
+    g = eng._fn("particle_fields")
     k = timed(lambda: eng._check(g(eng._h, *[None] * 6)), args.reps)
     w = np.empty((eng.N, 3))
     v = timed(lambda: eng._check(g(eng._h, None, None, None, None, None, w.ctypes.data_as(C.c_void_p))), args.reps)

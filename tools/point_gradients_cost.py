@@ -26,8 +26,8 @@ from sphexample_amd.fields import grid_nodes  # noqa: E402
 
 
 def measure(eng, label, reps):
-    f = eng._fn("sample_points"); f.argtypes = [C.c_void_p, C.c_int64] + [C.c_void_p] * 6
-    g = eng._fn("sample_point_gradients"); g.argtypes = [C.c_void_p, C.c_int64] + [C.c_void_p] * 10
+    f = eng._fn("sample_points")
+    g = eng._fn("sample_point_gradients")
     x = np.ascontiguousarray(grid_nodes(*lattice(1e6)))
     px = x.ctypes.data_as(C.c_void_p)
     os.environ.pop("SPHMI_POINTS_CLOCK", None)

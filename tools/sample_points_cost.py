@@ -37,8 +37,8 @@ def sphere(n, rng):
 
 
 def measure(eng, label, reps):
-    f = eng._fn("sample_points"); f.argtypes = [C.c_void_p, C.c_int64] + [C.c_void_p] * 6
-    g = eng._fn("sample_grid"); g.argtypes = [C.c_void_p] * 9
+    f = eng._fn("sample_points")
+    g = eng._fn("sample_grid")
     rng = np.random.default_rng(5)
     o, s, c = lattice(1e6)
     nodes = grid_nodes(o, s, c)

@@ -40,8 +40,7 @@ def child(world, steps):
     else:
         out = (C.c_int64 * (12 * world))()
         n = C.c_int32()
-        e._lib.sphmi_multi_halo_info.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.c_int32, C.POINTER(C.c_int32)]
-        e._check(e._lib.sphmi_multi_halo_info(e._h, out, 12 * world, C.byref(n)))
+        e._check(e._fn("multi_halo_info")(e._h, out, 12 * world, C.byref(n)))
         res["per_slab"] = [dict(zip(KEYS, out[12 * k:12 * k + 12])) for k in range(n.value // 12)]
         res["owned"] = e.owned_count()
     print(json.dumps(res), flush=True)
