@@ -865,6 +865,72 @@ int sphmi_components_read(sphmi_handle* h, int32_t* label_out /* [n_rows] */, in
                           int32_t* count_out /* [C] */, double* box_out /* [C x 6] */);
 int sphmi_components_release(sphmi_handle* h);
 
+/*
+ * A selected subset of the rows, compacted on the device on demand: the slice a viewer draws, the Fluid rows, every 8th particle of a
+ * movie, the rows a mask flagged, the rows with P above a level - only those cross the bus, in the layout of sphmi_download, instead
+ * of every row followed by a mask on the host (csrc/sphmi_select.h).
+ *   sphmi_select_build is synchronous and called between sphmi_advance calls; it needs an upload and nothing more - no cell list, no
+ *   first step.  It changes no state a later step, download, column download, series read or on-demand result reads, and leaves a
+ *   download begun with sphmi_download_begin alone: it stages in buffers of its own, not in those of the pending snapshot.
+ *   n_rows = sphmi_owned_count rows; row i is row i of what sphmi_download delivers now.
+ *   Selection rule: a row is selected iff EVERY enabled clause holds - the clauses are ANDed; the boxes inside the spatial clause are ORed.
+ *     type_mask  bit (Type - 1) is set: 1 Fluid, 2 Fixed, 4 Moving; always on, 7 keeps every row.
+ *     boxes      n_boxes > 0: for SOME box b, box_lo[b][d] <= x[d] < box_hi[b][d] for every d < dims (n_boxes x dims doubles each, the
+ *                half-open test of sphmi_flow_enable; -inf / +inf allowed; a box with lo >= hi on an axis holds nothing).
+ *     markers    n_markers > 0: GroupMarker is one of markers[].
+ *     id         id_stride > 1: (uint64)ID % id_stride == id_phase.  Keyed on ID, not on the row: a decimated movie follows the same
+ *                particles through every sort.
+ *     field      field != SPHMI_SELECT_FIELD_NONE: field_lo <= value <= field_hi, both ends inclusive; a NaN value is never kept.
+ *     row_mask   not NULL: n_rows bytes in the CURRENT row order, a non-zero byte keeps the row (copied at the build).
+ *   Values the clauses read: the doubles a handle with Float64 host arrays would deliver for that row at this moment - Position is
+ *   record + low word on fp32 handles; Density has its sign stripped (and its low word added); Pressure is Pressure!(rho_n+) of the last
+ *   step's half-step set, or before the first step the value the upload left, the branch sphmi_download takes;
+ *   SPEED2 = (vx * vx + vy * vy) + vz * vz of the Velocity doubles (2-D handles: vz = 0), one rounding per operation, never contracted.
+ *   The host float type and sphmi_set_output_components change what is DELIVERED, never what is SELECTED: a host reproduces the selection
+ *   bit for bit from a Float64 download (sphexample_amd/selection.py: restate).
+ *   Row order: the selected rows come back ascending.  A flag per row, an exclusive scan and rows[offsets[i]] = i: no atomic decides a
+ *   place, repeated builds give the same bytes.
+ *   The result stays in a device arena of the handle until the next build, sphmi_select_release (which gives the memory back) or
+ *   sphmi_destroy.  sphmi_advance, sphmi_upload, sphmi_generate_dam_break_3d and sphmi_forces_once mark it stale: rows may have moved.
+ *   sphmi_select_read copies the n_selected row numbers, ascending, 0-based, to rows_out (NULL: nothing is copied).
+ *   sphmi_select_download has the signature and the per-field meaning of sphmi_download with n_selected rows per array, slot s holding
+ *   row rows[s]: a NULL pointer skips that field, floats in the host float type, vectors padded to 3 components after
+ *   sphmi_set_output_components(h, 3) as sphmi_download pads them, cells always n_selected x dims.  Every array equals the rows rows[]
+ *   of what sphmi_download delivers now, byte for byte.  sphmi_select_download_columns delivers the attached columns
+ *   (sphmi_attach_columns) for the same rows, n_selected x row_bytes[c] each; a NULL entry skips a column.  Both are synchronous -
+ *   a selection is small by construction; there is no begin / end pair.
+ *   SPHMI_ERR_ARGUMENT: a null sel or a null n_selected_out (n_rows_out may be NULL); a type_mask of 0 or above 7; n_boxes or n_markers
+ *     negative or above its maximum, or positive with a null table; id_stride < 1 or id_phase outside [0, id_stride); an unknown field;
+ *     a NaN box bound, or a NaN field bound with a field clause; a null table of sphmi_select_download_columns.
+ *   SPHMI_ERR_STATE: before the upload; rank-mode handles; multi-device handles (single-device handles only, as for the neighbour list);
+ *     sphmi_select_read / _download / _download_columns without a build, or of a stale or released result;
+ *     sphmi_select_download_columns with nothing attached.
+ *   SPHMI_ERR_DEVICE: the device cannot hold the arena (17 bytes per row: flag, row, offset, mask) or the staging of a download; the
+ *     message gives the bytes, and the handle stays usable.
+ */
+enum { SPHMI_SELECT_FIELD_NONE = 0, SPHMI_SELECT_FIELD_DENSITY, SPHMI_SELECT_FIELD_PRESSURE, SPHMI_SELECT_FIELD_SPEED2 };
+#define SPHMI_MAX_SELECT_BOXES   16
+#define SPHMI_MAX_SELECT_MARKERS 16
+typedef struct sphmi_selection {
+    uint32_t        type_mask;            /* bit (Type-1): 1 Fluid, 2 Fixed, 4 Moving; 1..7                        */
+    int32_t         n_boxes;              /* 0 = no spatial clause; else the UNION of the boxes                    */
+    const double*   box_lo;               /* n_boxes x dims, lo <= x < hi per axis, +-inf allowed (sphmi_flow's test) */
+    const double*   box_hi;
+    int32_t         n_markers;            /* 0 = no clause; else GroupMarker is one of markers[]                   */
+    const uint64_t* markers;
+    int64_t         id_stride, id_phase;  /* keep (uint64)ID % id_stride == id_phase; stride 1 = no clause          */
+    int32_t         field;                /* SPHMI_SELECT_FIELD_*                                                  */
+    double          field_lo, field_hi;   /* keep field_lo <= value <= field_hi; a NaN value is never kept          */
+    const uint8_t*  row_mask;             /* NULL, or n_rows bytes in the CURRENT row order; non-zero keeps         */
+} sphmi_selection;
+
+int sphmi_select_build(sphmi_handle* h, const sphmi_selection* sel, int64_t* n_rows_out, int64_t* n_selected_out);
+int sphmi_select_read(sphmi_handle* h, int32_t* rows_out /* [n_selected], ascending */);
+int sphmi_select_download(sphmi_handle* h, void* position, void* velocity, void* acceleration, void* density, void* pressure,
+                          int64_t* id, uint8_t* type, uint64_t* group_marker, void* ghost_points, int64_t* cells);
+int sphmi_select_download_columns(sphmi_handle* h, void* const* columns_out);
+int sphmi_select_release(sphmi_handle* h);
+
 #ifdef __cplusplus
 }
 #endif

@@ -447,6 +447,47 @@ function components(P, link::Float64; types = (1,))
     check(h, ccall((:sphmi_components_release, LIB), Cint, (Ptr{Cvoid},), h))
     return (label = label, first_row = first_row, count = count, box = box)
 end
+# A selected subset of the rows of the state the session holds NOW, compacted on the device (sphmi_select_build / _read / _download /
+# _release): only the selected rows cross the bus.  Every clause that is given must hold: `types` (Fluid = 1, Fixed = 2, Moving = 3),
+# `lo` / `hi` (D × n_boxes, half-open lo <= x < hi per axis, ±Inf allowed; the row lies in SOME box), `markers`, ID % stride == phase
+# (the same particles through every sort), `field` (0 none, 1 Density, 2 Pressure, 3 the squared speed) within [field_lo, field_hi],
+# `mask` (one byte per row of the next download, non-zero keeps).  rows are the library's RAW 0-BASED row numbers, ascending; position
+# and velocity are D × n, in the float type of the StructArray.  Single-device sessions; from an output callback, any time after the upload.
+struct SphmiSelection
+    type_mask::UInt32; n_boxes::Int32
+    box_lo::Ptr{Float64}; box_hi::Ptr{Float64}
+    n_markers::Int32
+    markers::Ptr{UInt64}
+    id_stride::Int64; id_phase::Int64
+    field::Int32
+    field_lo::Float64; field_hi::Float64
+    row_mask::Ptr{UInt8}
+end
+function select_rows(P; types = (1, 2, 3), lo::Matrix{Float64} = zeros(0, 0), hi::Matrix{Float64} = zeros(0, 0), markers::Vector{UInt64} = UInt64[],
+                     stride::Integer = 1, phase::Integer = 0, field::Integer = 0, field_lo::Float64 = -Inf, field_hi::Float64 = Inf,
+                     mask::Vector{UInt8} = UInt8[])
+    h = SESSIONS[P].h
+    F = eltype(P.Density)
+    size(lo) == size(hi) || error("select_rows: lo and hi are both dims × n_boxes")
+    isempty(mask) || length(mask) == length(P) || error("select_rows: the mask holds one byte per row")
+    tmask = reduce(|, (UInt32(1) << (t - 1) for t in types); init = UInt32(0))
+    nrows = Ref{Int64}(0); kept = Ref{Int64}(0)
+    GC.@preserve lo hi markers mask begin
+        sel = Ref(SphmiSelection(tmask, size(lo, 2), size(lo, 2) > 0 ? pointer(lo) : C_NULL, size(hi, 2) > 0 ? pointer(hi) : C_NULL,
+                                 length(markers), isempty(markers) ? C_NULL : pointer(markers), stride, phase, field, field_lo, field_hi,
+                                 isempty(mask) ? C_NULL : pointer(mask)))
+        check(h, ccall((:sphmi_select_build, LIB), Cint, (Ptr{Cvoid}, Ref{SphmiSelection}, Ref{Int64}, Ref{Int64}), h, sel, nrows, kept))
+    end
+    n = kept[]; D = length(first(P.Position))
+    rows = Vector{Int32}(undef, n); x = Matrix{F}(undef, D, n); v = Matrix{F}(undef, D, n); rho = Vector{F}(undef, n); pp = Vector{F}(undef, n)
+    id = Vector{Int64}(undef, n); ty = Vector{UInt8}(undef, n); grp = Vector{UInt64}(undef, n)
+    GC.@preserve rows check(h, ccall((:sphmi_select_read, LIB), Cint, (Ptr{Cvoid}, Ptr{Int32}), h, pointer(rows)))
+    GC.@preserve x v rho pp id ty grp check(h, ccall((:sphmi_select_download, LIB), Cint,
+        (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Int64}, Ptr{UInt8}, Ptr{UInt64}, Ptr{Cvoid}, Ptr{Int64}),
+        h, pointer(x), pointer(v), C_NULL, pointer(rho), pointer(pp), pointer(id), pointer(ty), pointer(grp), C_NULL, C_NULL))
+    check(h, ccall((:sphmi_select_release, LIB), Cint, (Ptr{Cvoid},), h))
+    return (rows = rows, position = x, velocity = v, density = rho, pressure = pp, id = id, type = ty, group_marker = grp)
+end
 atexit(() -> foreach(s -> ccall((:sphmi_destroy, LIB), Cint, (Ptr{Cvoid},), s.h), values(SESSIONS)))
 
 function check(h, rc)

@@ -27,6 +27,8 @@ MAX_RAY_POINTS = 1 << 16
 RAY_REFINE_ROUNDS = 4
 RAY_ENTER, RAY_LEAVE, RAY_ANY = 0, 1, 2
 NEIGHBORS_FULL, NEIGHBORS_HALF = 0, 1
+MAX_SELECT_BOXES = MAX_SELECT_MARKERS = 16
+SELECT_FIELD_NONE, SELECT_FIELD_DENSITY, SELECT_FIELD_PRESSURE, SELECT_FIELD_SPEED2 = range(4)
 
 OK, ERR_ARGUMENT, ERR_DEVICE, ERR_NUMERIC, ERR_DOMAIN, ERR_STATE = range(6)
 
@@ -60,6 +62,12 @@ class SphmiMultiInfo(C.Structure):
     _fields_ = [("world", C.c_int32), ("n_local", C.c_int32), ("axis", C.c_int32), ("halo_width", C.c_int32),
                 ("transport", C.c_int32), ("reserved", C.c_int32), ("n_recuts", C.c_int64),
                 ("cuts", C.c_int64 * MAX_DEVICES), ("n_live", C.c_int64 * MAX_DEVICES)]
+
+
+class SphmiSelection(C.Structure):
+    _fields_ = [("type_mask", C.c_uint32), ("n_boxes", C.c_int32), ("box_lo", C.c_void_p), ("box_hi", C.c_void_p),
+                ("n_markers", C.c_int32), ("markers", C.c_void_p), ("id_stride", C.c_int64), ("id_phase", C.c_int64),
+                ("field", C.c_int32), ("field_lo", C.c_double), ("field_hi", C.c_double), ("row_mask", C.c_void_p)]
 
 
 class SphmiError(RuntimeError):
@@ -104,6 +112,8 @@ PROTOTYPES = {
     "neighbors_build": [_P, _I32, _pI64, _pI64], "neighbors_read": [_P] * 3, "neighbors_release": [_P],
     "isosurface_build": [_P] * 4 + [_F, _pI64, _pI64], "isosurface_read": [_P] * 5, "isosurface_release": [_P],
     "components_build": [_P, _F, C.c_uint32, _pI64, _pI64], "components_read": [_P] * 5, "components_release": [_P],
+    "select_build": [_P, _P, _pI64, _pI64], "select_read": [_P, _P], "select_download": [_P] * 11, "select_download_columns": [_P, _P],
+    "select_release": [_P],
     # include/sphmi_internal.h: the hooks of tests and tools
     "shm_selftest": [C.c_char_p, _I32, _I32, _I64], "plan_slabs": [_P, _P, _P, _I64, _I32] + [_P] * 5,
     "multi_set_cuts": [_P, _P, _I32], "multi_column_cost": [_P, _I64, _I32, _P], "multi_halo_info": [_P, _pI64, _I32, _pI32],
@@ -184,6 +194,7 @@ FEATURES = {
     "maps": ("maps_enable", "maps_read", "maps_disable"),
     **{k: (k + "_enable", k + "_read") for k in ("group_forces", "probes", "budgets", "flow", "envelopes", "tracers")},
     **{k: (k + "_build", k + "_read", k + "_release") for k in ("isosurface", "components")},
+    "select": ("select_build", "select_read", "select_download", "select_download_columns", "select_release"),
     **{k: (k,) for k in ("sample_grid", "sample_points", "sample_point_gradients", "cast_rays", "particle_fields")},
 }
 
@@ -199,7 +210,7 @@ class Backend:
     _force_groups = _probes = _flow_boxes = _map_bins = 0
     _tracers = (0, 0, 0.5)
     _pinned = ()
-    _neighbor_shape = _isosurface_shape = _components_shape = None
+    _neighbor_shape = _isosurface_shape = _components_shape = _select_shape = None
 
     def __init__(self, lib: C.CDLL, prefix: str, cfg: SphmiConfig, create=None):
         self._lib, self._p = lib, prefix
@@ -297,7 +308,7 @@ class Backend:
     # A result held on the device (<name>_build / _read / _release).  The reads take no capacities: the arrays are sized from the
     # two counts THIS object's build reported, kept in the attribute named here; the second entry words the refusal.
     _HELD = {"neighbors": ("_neighbor_shape", "a list"), "isosurface": ("_isosurface_shape", "a mesh"),
-             "components": ("_components_shape", "components")}
+             "components": ("_components_shape", "components"), "select": ("_select_shape", "a selection")}
 
     def _held_build(self, name, *args):
         a, b = C.c_int64(), C.c_int64()
@@ -833,6 +844,81 @@ class Backend:
             return dict(zip(("label", "first_row", "count", "box"), self.components_read()))
         finally:
             self.components_release()
+
+    # -- a selected subset of the rows, compacted on the device (sphmi_select_build / _read / _download* / _release) -----------------
+    def select_build(self, spec):
+        """Flag, scan and list the rows `spec` (a ``sphexample_amd.selection.Selection``) selects, on the device, and keep the list
+        there: (n_rows, n_selected).  It needs an upload and nothing more.  It stays until the next build, `select_release` or
+        `close`; a step, an upload or `forces_once` marks it stale."""
+        lo, hi = spec.box_tables(self.D)
+        markers = np.ascontiguousarray(list(spec.markers), dtype=np.uint64)
+        mask = spec.mask_bytes(self.N)
+        sel = SphmiSelection(spec.type_mask(), len(lo), lo.ctypes.data if len(lo) else None, hi.ctypes.data if len(hi) else None,
+                             len(markers), markers.ctypes.data if len(markers) else None, int(spec.id_stride), int(spec.id_phase),
+                             spec.field_code(), float(spec.field_lo), float(spec.field_hi), None if mask is None else mask.ctypes.data)
+        return self._held_build("select", C.byref(sel))                           # (lo, hi, markers, mask live until the call returns)
+
+    def select_read(self) -> np.ndarray:
+        """The selected rows, int32 ascending: row numbers of what `download` delivers now."""
+        return self._held_read("select", lambda rows, kept: (np.zeros(kept, dtype=np.int32),))[0]
+
+    def _select_shape_or_refusal(self, name):
+        if self._select_shape is None:                                             # the library words the refusal
+            self._check(self._fn(name)(self._h, *[None] * (len(PROTOTYPES[name]) - 1)))
+            raise RuntimeError(f"{name}: the handle holds a selection this object did not build; call select_build first")
+        return self._select_shape
+
+    def select_download(self, fields=DOWNLOAD_NAMES, components: Optional[int] = None) -> dict:
+        """`download` for the selected rows only: every array holds n_selected rows, slot s being row ``select_read()[s]``, and equals
+        ``download(fields, components)[name][rows]`` byte for byte."""
+        _, kept = self._select_shape_or_refusal("select_download")
+        D = self.D
+        Cv = D if components is None else int(components)
+        if Cv not in (D, 3):
+            raise ValueError("components must be dims or 3")
+        out = {k: (np.empty((kept, Cv if dtype is None else D) if vector else (kept,), dtype=dtype or self._ft) if k in fields else None)
+               for k, dtype, vector in DOWNLOAD_FIELDS}
+        if Cv != D:
+            self._check(self._fn("set_output_components")(self._h, Cv))
+        try:
+            self._check(self._fn("select_download")(self._h, *[_ptr(a) for a in out.values()]))
+        finally:
+            if Cv != D:
+                self._check(self._fn("set_output_components")(self._h, D))
+        return {k: v for k, v in out.items() if v is not None}
+
+    def select_download_columns(self, which=None) -> list:
+        """The attached columns of the selected rows: one uint8 array [n_selected, row_bytes] per attached column, opaque bytes as
+        `attach_columns` took them (``.view(dtype)`` restores the type); `which`: one bool per column, False skips it (None in its
+        place)."""
+        _, kept = self._select_shape_or_refusal("select_download_columns")
+        widths = self._column_widths
+        if widths is None:
+            self._check(self._fn("select_download_columns")(self._h, (C.c_void_p * 1)(None)))      # (nothing attached: the library words the refusal)
+            raise RuntimeError("select_download_columns: this object attached no columns")
+        which = [True] * len(widths) if which is None else [bool(w) for w in which]
+        if len(which) != len(widths):
+            raise ValueError("select_download_columns: one entry per attached column")
+        outs = [np.zeros((kept, w), dtype=np.uint8) if on else None for w, on in zip(widths, which)]
+        table = (C.c_void_p * max(len(outs), 1))(*[None if a is None else a.ctypes.data for a in outs])
+        self._check(self._fn("select_download_columns")(self._h, table))
+        return outs
+
+    def select_release(self) -> None:
+        self._held_release("select")
+
+    def select(self, spec, fields=DOWNLOAD_NAMES, columns: bool = False, components: Optional[int] = None):
+        """The rows `spec` selects and their fields, evaluated now: ``(rows, dict of arrays)``, or ``(rows, dict, columns)`` with
+        `columns` — rows int32 ascending, every array ``download()[name][rows]`` byte for byte, only the selected rows crossing the
+        bus.  ``sphexample_amd.selection`` builds selections (`slab`, `every`, `where`) and restates the rule in numpy.
+        Single-device handles; call it between `advance` calls, any time after the upload.  The device memory is given back
+        before it returns."""
+        self.select_build(spec)
+        try:
+            got = (self.select_read(), self.select_download(fields, components))
+            return (*got, self.select_download_columns()) if columns else got
+        finally:
+            self.select_release()
 
     def forces_once(self, apply_mdbc: bool = False):
         drho = np.empty(self.N, dtype=self._ft)

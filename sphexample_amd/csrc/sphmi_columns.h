@@ -11,6 +11,7 @@
 //   k_columns_base_init     attach:                       base[prow[i]] = i          (the identity on a fresh epoch)
 //   k_columns_base_compose  sphmi_download_permutation:   base'[i] = base[prow[i]]   (before prow becomes the identity again)
 //   k_gather_columns        download:                     record → one contiguous array per column, current order
+//   k_gather_selected_columns  sphmi_select_download_columns: the same for the rows of a selection, record of base[prow[rows[s]]]
 //
 // Record layout: the columns of a row side by side, the wider-aligned first (a width divisible by 16, then by 8, 4, 2, then
 // the odd ones), so every column whose width is a multiple of 4 starts on a 4-byte boundary without padding; the stride is
@@ -65,8 +66,11 @@ __global__ void k_columns_base_compose(const int* __restrict__ base_in, const in
 // the block's rows are ONE contiguous byte range of the output: it is written in dwords by consecutive lanes — a column whose
 // width and offset are multiples of 4 reads one LDS dword per store, any other (1-, 2-, 3-, 7-, 33-byte rows) assembles a
 // dword from four LDS bytes, which may belong to four rows: a 1-byte column costs a quarter store per row, not one.
-__global__ void __launch_bounds__(kGatherThreads)
-k_gather_columns(const uint4* __restrict__ store, const int* __restrict__ base, const int* __restrict__ prow, int n, ColumnTable t) {
+// `kRows`: the block delivers the rows sel[row0 …] of a selection (k_gather_selected_columns) instead of the rows row0 … themselves;
+// `n` is then the number of selected rows and `n_src` the number of rows of the handle.
+template <bool kRows>
+__device__ __forceinline__ void gather_columns_block(const uint4* __restrict__ store, const int* __restrict__ base, const int* __restrict__ prow,
+                                                     const int* __restrict__ sel, int n, int n_src, const ColumnTable& t) {
     extern __shared__ uint4 gather_lds[];
     const int R = t.rows_per_block, S = t.stride, L = S >> 4;
     int* src = (int*)gather_lds;                       // R ints (R is a multiple of 16: the records behind them stay 16-byte aligned)
@@ -75,9 +79,11 @@ k_gather_columns(const uint4* __restrict__ store, const int* __restrict__ base, 
     const int row0 = (int)blockIdx.x * R;
     const int rows = min(R, n - row0);
     for (int r = tid; r < rows; r += kGatherThreads) {
-        const unsigned e = (unsigned)prow[row0 + r];
-        const int s = e < (unsigned)n ? base[e] : -1;
-        src[r] = (unsigned)s < (unsigned)n ? s : -1;
+        unsigned i = (unsigned)(row0 + r);
+        if (kRows) i = (unsigned)sel[row0 + r];
+        const unsigned e = i < (unsigned)n_src ? (unsigned)prow[i] : ~0u;
+        const int s = e < (unsigned)n_src ? base[e] : -1;
+        src[r] = (unsigned)s < (unsigned)n_src ? s : -1;
     }
     __syncthreads();
     for (int g = tid; g < rows * L; g += kGatherThreads) {
@@ -116,6 +122,18 @@ k_gather_columns(const uint4* __restrict__ store, const int* __restrict__ base, 
             }
         }
     }
+}
+
+__global__ void __launch_bounds__(kGatherThreads)
+k_gather_columns(const uint4* __restrict__ store, const int* __restrict__ base, const int* __restrict__ prow, int n, ColumnTable t) {
+    gather_columns_block<false>(store, base, prow, nullptr, n, n, t);
+}
+
+// the columns of the selected rows sel[0 … n_sel) (sphmi_select.h), n_sel × width[c] bytes per column
+__global__ void __launch_bounds__(kGatherThreads)
+k_gather_selected_columns(const uint4* __restrict__ store, const int* __restrict__ base, const int* __restrict__ prow, const int* __restrict__ sel,
+                          int n_sel, int n, ColumnTable t) {
+    gather_columns_block<true>(store, base, prow, sel, n_sel, n, t);
 }
 
 }  // namespace sphmi

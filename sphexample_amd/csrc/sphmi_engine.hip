@@ -33,6 +33,7 @@
 #include "sphmi_neighbor_list.h"
 #include "sphmi_components.h"
 #include "sphmi_isosurface.h"
+#include "sphmi_select.h"
 
 namespace sphmi {
 
@@ -273,8 +274,8 @@ struct EngineBase {
     // surface as a mesh (sphmi_isosurface.h) and the connected bodies of selected rows (sphmi_components.h).  sphmi_advance,
     // sphmi_upload, the generator and sphmi_forces_once call results_stale() at the C boundary.  A read checks the state here and
     // then asks the engine for the arrays; only an engine that built a result is ever asked.
-    HeldResult nl_held, iso_held, cc_held;
-    void results_stale() { for (HeldResult* r : {&nl_held, &iso_held, &cc_held}) r->stale(); }
+    HeldResult nl_held, iso_held, cc_held, sel_held;
+    void results_stale() { for (HeldResult* r : {&nl_held, &iso_held, &cc_held, &sel_held}) r->stale(); }
     virtual void neighbors_build(int32_t mode, int64_t* n_rows_out, int64_t* n_pairs_out) = 0;
     virtual void neighbors_fetch(int64_t*, int32_t*) {}
     virtual void neighbors_release() {}
@@ -296,6 +297,27 @@ struct EngineBase {
         cc_held.require_readable("sphmi_components_read", "no components are held (sphmi_components_build)", "the components are stale (rows may have moved since sphmi_components_build)");
         components_fetch(label_out, first_row_out, count_out, box_out);
     }
+    // A selected subset of the rows (sphmi_select.h) is compacted where the rows are: a handle of one device overrides the build and
+    // the fetches.  The slabs of a multi-device handle each hold a part of the rows in an order of their own.
+    virtual void select_build(const sphmi_selection*, int64_t*, int64_t*) {
+        require_uploaded("sphmi_select_build");
+        throw EngineError(SPHMI_ERR_STATE, "sphmi_select_build: single-device handles only (a slab holds a part of the rows, in an order of its own)");
+    }
+    virtual void select_fetch_rows(int32_t*) {}
+    virtual void select_fetch_fields(void*, void*, void*, void*, void*, int64_t*, uint8_t*, uint64_t*, void*, int64_t*) {}
+    virtual void select_fetch_columns(void* const*) {}
+    virtual void select_release() { require_uploaded("sphmi_select_release"); }
+    void select_require(const char* fn) const {
+        require_uploaded(fn);
+        sel_held.require_readable(fn, "no selection is held (sphmi_select_build)", "the selection is stale (rows may have moved since sphmi_select_build)");
+    }
+    void select_read(int32_t* rows_out) { select_require("sphmi_select_read"); select_fetch_rows(rows_out); }
+    void select_download(void* position, void* velocity, void* acceleration, void* density, void* pressure, int64_t* ids, uint8_t* ty, uint64_t* groups,
+                         void* ghost_points, int64_t* cells) {
+        select_require("sphmi_select_download");
+        select_fetch_fields(position, velocity, acceleration, density, pressure, ids, ty, groups, ghost_points, cells);
+    }
+    void select_download_columns(void* const* columns_out) { select_require("sphmi_select_download_columns"); select_fetch_columns(columns_out); }
     virtual void unique_cells(int64_t* out, int64_t cap, int64_t* n) = 0;
     virtual void timers(int32_t cap, const char** names, double* secs, int64_t* calls, int32_t* n) = 0;
     virtual void force_stats(int reset, double* avg_ms, int64_t* launches) = 0;
@@ -567,7 +589,7 @@ struct Engine final : EngineBase {
         for (auto& e : host_pinned) (void)hipHostUnregister(e.first);
         (void)hipFree(out_arena);
         (void)hipFree(col_arena); (void)hipFree(col_store); (void)hipFree(col_base[0]); (void)hipFree(col_base[1]);
-        gf_release(); pr_release(); bg_release(); fl_release(); en_release(); mp_release(); tr_release(); fg_arena.free(); pc_free(); ry_free(); pf_arena.free(); nl_free(); iso_free(); cc_free();
+        gf_release(); pr_release(); bg_release(); fl_release(); en_release(); mp_release(); tr_release(); fg_arena.free(); pc_free(); ry_free(); pf_arena.free(); nl_free(); iso_free(); cc_free(); sel_free();
         (void)hipFree(slot); (void)hipFree(tmp_idx); (void)hipFree(perm);
         for (int k = 0; k < 2; ++k) { (void)hipFree(tile_cost[k]); (void)hipFree(tile_order[k]); }
         (void)hipFree(kout_d); (void)hipFree(tile_work_d); (void)hipFree(tile_work1_d); (void)hipFree(xcd_clock_d); (void)hipHostFree(xcd_clock_h);
@@ -2539,6 +2561,158 @@ struct Engine final : EngineBase {
         nl_free();
     }
 
+    // ---- a selected subset of the rows, compacted on demand (sphmi_select.h) ------------------------------------------------------------
+    // Reads the current set, the low words, the half-step set, type, id and grp; writes its own buffers and nothing else: flags and rows
+    // [N] int32, offsets [N + 1] int64, the scan's tile sums, the caller's mask bytes, and the staging of a download — its own, so that
+    // a download begun with sphmi_download_begin keeps its arena.  All go back to the device at sphmi_select_release.
+    DeviceBuf<int> sel_flags, sel_rows;
+    DeviceBuf<long long> sel_offsets, sel_tsum;
+    DeviceBuf<uint8_t> sel_mask;
+    DeviceBuf<char> sel_stage;
+    int64_t sel_n = 0, sel_count = 0;
+    void sel_free() {
+        sel_flags.free(); sel_rows.free(); sel_offsets.free(); sel_tsum.free(); sel_mask.free(); sel_stage.free();
+        sel_n = sel_count = 0;
+        sel_held.drop();
+    }
+    void select_build(const sphmi_selection* sel, int64_t* n_rows_out, int64_t* n_selected_out) override {
+        const char* fn = "sphmi_select_build";
+        require_uploaded(fn);
+        auto bad = [&](const char* what) { throw EngineError(SPHMI_ERR_ARGUMENT, std::string(fn) + ": " + what); };
+        if (!sel) bad("null selection");
+        if (!n_selected_out) bad("null n_selected_out");
+        if (sel->type_mask < 1 || sel->type_mask > 7) bad("type_mask outside 1 .. 7 (bit Type - 1: 1 Fluid, 2 Fixed, 4 Moving)");
+        if (sel->n_boxes < 0 || sel->n_boxes > SPHMI_MAX_SELECT_BOXES) bad("n_boxes outside 0 .. SPHMI_MAX_SELECT_BOXES");
+        if (sel->n_boxes > 0 && (!sel->box_lo || !sel->box_hi)) bad("boxes without box_lo or box_hi");
+        if (sel->n_markers < 0 || sel->n_markers > SPHMI_MAX_SELECT_MARKERS) bad("n_markers outside 0 .. SPHMI_MAX_SELECT_MARKERS");
+        if (sel->n_markers > 0 && !sel->markers) bad("markers without a table");
+        if (sel->id_stride < 1) bad("id_stride below 1");
+        if (sel->id_phase < 0 || sel->id_phase >= sel->id_stride) bad("id_phase outside [0, id_stride)");
+        if (sel->field < SPHMI_SELECT_FIELD_NONE || sel->field > SPHMI_SELECT_FIELD_SPEED2) bad("unknown field");
+        if (sel->field != SPHMI_SELECT_FIELD_NONE && (std::isnan(sel->field_lo) || std::isnan(sel->field_hi))) bad("a NaN field bound");
+        SelSpec S{};
+        S.type_mask = sel->type_mask; S.n_boxes = sel->n_boxes; S.n_markers = sel->n_markers; S.field = sel->field; S.dims = D;
+        S.has_mask = sel->row_mask ? 1 : 0; S.id_stride = sel->id_stride; S.id_phase = sel->id_phase;
+        S.field_lo = sel->field_lo; S.field_hi = sel->field_hi;
+        for (int b = 0; b < S.n_boxes; ++b)
+            for (int d = 0; d < 3; ++d) {
+                S.lo[b][d] = d < D ? sel->box_lo[b * D + d] : 0.0; S.hi[b][d] = d < D ? sel->box_hi[b * D + d] : 0.0;
+                if (std::isnan(S.lo[b][d]) || std::isnan(S.hi[b][d])) bad("a NaN box bound");
+            }
+        for (int k = 0; k < S.n_markers; ++k) S.markers[k] = sel->markers[k];
+        HC(hipSetDevice(cfg.device));
+        sel_held.drop(); sel_n = sel_count = 0;                            // the result of the build before is gone, whatever happens below
+        const size_t n = (size_t)N;
+        auto no_memory = [&](size_t bytes) { return text("sphmi_select_build: no device memory for the arena over %d rows (%zu bytes)", N, bytes); };
+        sel_flags.need(n, no_memory); sel_offsets.need(n + 1, no_memory); sel_rows.need(n, no_memory);
+        if (S.has_mask) { sel_mask.need(n, no_memory); bounce.h2d(sel_mask.p, sel->row_mask, n, stream); }
+        SelFlagArgs<T> A{};
+        A.pk0 = pk0[iA]; A.pk1 = pk1[iA]; A.half0 = stepped ? Half<const V4>(pk0[iH]) : Half<const V4>(); A.comp = comp[cur];
+        A.type = type[cur]; A.id = id[cur]; A.grp = grp[cur]; A.mask = S.has_mask ? sel_mask.p : nullptr;
+        A.flags = sel_flags.p; A.N = N;
+        A.rho0 = (T)cfg.rho0; A.inv_rho0 = (T)(1.0 / cfg.rho0); A.Cbe = cbe();
+        PassClock clock("SPHMI_SELECT_TIMES", stream);                     // the device time of every pass → stderr (tools/bench_select.py)
+        const unsigned nb = (unsigned)((N + kSelThreads - 1) / kSelThreads);
+        clock.mark();
+        hipLaunchKernelGGL(k_sel_flag<T>, dim3(nb), dim3(kSelThreads), 0, stream, A, S);
+        HC(hipGetLastError());
+        clock.mark();
+        const long long kept = scan64(sel_flags.p, N, sel_tsum, sel_offsets.p, bounce, stream, no_memory);
+        clock.mark();
+        if (kept < 0 || kept > (long long)N) throw EngineError(SPHMI_ERR_DEVICE, "sphmi_select_build: the scan left the row count (a defect)");
+        if (kept > 0) {
+            hipLaunchKernelGGL(k_sel_fill, dim3(nb), dim3(kSelThreads), 0, stream, (const int*)sel_flags.p, (const long long*)sel_offsets.p, N, kept, sel_rows.p);
+            HC(hipGetLastError());
+        }
+        clock.mark();
+        HC(hipStreamSynchronize(stream));
+        clock.report(text("sphmi_select_build: %d rows, %lld selected:", N, kept), {"flag", "scan", "fill"});
+        sel_n = N; sel_count = kept; sel_held.set_valid();
+        if (n_rows_out) *n_rows_out = sel_n;
+        *n_selected_out = sel_count;
+    }
+    void select_fetch_rows(int32_t* rows_out) override {
+        HC(hipSetDevice(cfg.device));
+        if (rows_out && sel_count > 0) fetch_result(rows_out, sel_rows.p, (size_t)sel_count * 4);
+        HC(hipStreamSynchronize(stream));
+    }
+    template <class H>
+    void select_fetch_fields_as(void* position, void* velocity, void* acceleration, void* density, void* pressure, int64_t* ids, uint8_t* ty,
+                                uint64_t* groups, void* ghost_points, int64_t* cells) {
+        if (sel_count == 0) return;
+        const size_t n = (size_t)sel_count, nd = n * (size_t)out_comp, ncell_d = n * (size_t)D;
+        const size_t need = (4 * nd + 2 * n) * sizeof(H) + ncell_d * 8 + n * 17 + 256 * 12;
+        sel_stage.need(need, [&](size_t bytes) { return text("sphmi_select_download: no device memory for the staging of %lld rows (%zu bytes)", (long long)sel_count, bytes); });
+        char* cursor = sel_stage.p;
+        auto take = [&](bool wanted, size_t bytes) -> char* {
+            if (!wanted) return nullptr;
+            char* r = cursor; cursor += (bytes + 255) & ~size_t(255); return r;
+        };
+        OutFields<H> o{};
+        o.pos = (H*)take(position, nd * sizeof(H)); o.vel = (H*)take(velocity, nd * sizeof(H));
+        o.acc = (H*)take(acceleration, nd * sizeof(H)); o.rho = (H*)take(density, n * sizeof(H));
+        o.press = (H*)take(pressure, n * sizeof(H)); o.ghost = (H*)take(ghost_points, nd * sizeof(H));
+        o.cells = (long long*)take(cells, ncell_d * 8);
+        SelTags t{};
+        t.id = id[cur]; t.type = type[cur]; t.grp = grp[cur];
+        t.id_out = (long long*)take(ids, n * 8); t.grp_out = (unsigned long long*)take(groups, n * 8); t.type_out = (uint8_t*)take(ty, n);
+        PassClock clock("SPHMI_SELECT_TIMES", stream);
+        clock.mark();
+        hipLaunchKernelGGL((k_pack_selected<T, H>), dim3((unsigned)((n + kSelThreads - 1) / kSelThreads)), dim3(kSelThreads), 0, stream,
+                           (const int*)sel_rows.p, (int)sel_count, pk0[iA], pk1[iA], stepped ? Half<const V4>(pk0[iH]) : Half<const V4>(), acc[cur], ghost[cur],
+                           comp[cur], key[cur], N, D, out_comp, grid, have_grid ? 1 : 0, (T)cfg.rho0, (T)(1.0 / cfg.rho0), cbe(), o, t);
+        HC(hipGetLastError());
+        clock.mark();
+        auto fetch = [&](void* dst, const void* src, size_t bytes) { if (dst) fetch_result(dst, src, bytes); };
+        fetch(position, o.pos, nd * sizeof(H)); fetch(velocity, o.vel, nd * sizeof(H)); fetch(acceleration, o.acc, nd * sizeof(H));
+        fetch(density, o.rho, n * sizeof(H)); fetch(pressure, o.press, n * sizeof(H)); fetch(ghost_points, o.ghost, nd * sizeof(H));
+        fetch(cells, o.cells, ncell_d * 8); fetch(ids, t.id_out, n * 8); fetch(ty, t.type_out, n); fetch(groups, t.grp_out, n * 8);
+        clock.mark();
+        HC(hipStreamSynchronize(stream));
+        clock.report(text("sphmi_select_download: %lld rows:", (long long)sel_count), {"pack", "copy"});
+    }
+    void select_fetch_fields(void* position, void* velocity, void* acceleration, void* density, void* pressure, int64_t* ids, uint8_t* ty, uint64_t* groups,
+                             void* ghost_points, int64_t* cells) override {
+        HC(hipSetDevice(cfg.device));
+        if (cfg.host_float_bytes == 8) select_fetch_fields_as<double>(position, velocity, acceleration, density, pressure, ids, ty, groups, ghost_points, cells);
+        else select_fetch_fields_as<float>(position, velocity, acceleration, density, pressure, ids, ty, groups, ghost_points, cells);
+    }
+    void select_fetch_columns(void* const* columns_out) override {
+        if (!col_store) throw EngineError(SPHMI_ERR_STATE, "sphmi_select_download_columns: no columns attached (sphmi_attach_columns)");
+        if (!columns_out) throw EngineError(SPHMI_ERR_ARGUMENT, "sphmi_select_download_columns: null table");
+        if (sel_count == 0) return;
+        HC(hipSetDevice(cfg.device));
+        const size_t n = (size_t)sel_count;
+        ColumnTable t = col_table;
+        size_t need = 0;
+        for (int c = 0; c < t.n_columns; ++c) need += (n * (size_t)t.width[c] + 255) & ~size_t(255);
+        sel_stage.need(need, [&](size_t bytes) { return text("sphmi_select_download_columns: no device memory for the staging of %lld rows (%zu bytes)", (long long)sel_count, bytes); });
+        char* cursor = sel_stage.p;
+        bool any = false;
+        for (int c = 0; c < t.n_columns; ++c) {
+            t.out[c] = columns_out[c] ? cursor : nullptr;
+            if (columns_out[c]) { cursor += (n * (size_t)t.width[c] + 255) & ~size_t(255); any = true; }
+        }
+        if (!any) return;
+        PassClock clock("SPHMI_SELECT_TIMES", stream);
+        clock.mark();
+        const int blocks = (int)((n + (size_t)t.rows_per_block - 1) / (size_t)t.rows_per_block);
+        hipLaunchKernelGGL(k_gather_selected_columns, dim3(blocks), dim3(kGatherThreads), gather_lds_bytes(t), stream, (const uint4*)col_store,
+                           (const int*)col_base[col_cur], (const int*)prow[cur], (const int*)sel_rows.p, (int)sel_count, N, t);
+        HC(hipGetLastError());
+        clock.mark();
+        for (int c = 0; c < t.n_columns; ++c)
+            if (columns_out[c]) fetch_result(columns_out[c], t.out[c], n * (size_t)t.width[c]);
+        clock.mark();
+        HC(hipStreamSynchronize(stream));
+        clock.report(text("sphmi_select_download_columns: %lld rows:", (long long)sel_count), {"pack", "copy"});
+    }
+    void select_release() override {
+        require_uploaded("sphmi_select_release");
+        HC(hipSetDevice(cfg.device));
+        sel_free();
+    }
+
     // ---- the connected bodies of selected rows, on demand (sphmi_components.h) ----------------------------------------------------------
     // Reads the current set's positions, the low words, the types, `cstart` and the grid of the last rebuild; writes its own buffers and
     // nothing else: parent, root, flag, label [N] int32, the scan's tile sums and dense [N + 1] int64, the error word — they grow with
@@ -3284,6 +3458,16 @@ int sphmi_neighbors_build(sphmi_handle* h, int32_t mode, int64_t* n_rows_out, in
 }
 int sphmi_neighbors_read(sphmi_handle* h, int64_t* offsets_out, int32_t* neighbors_out) { SPHMI_GUARD(h, h->e->neighbors_read(offsets_out, neighbors_out)); }
 int sphmi_neighbors_release(sphmi_handle* h) { SPHMI_GUARD(h, h->e->neighbors_release()); }
+int sphmi_select_build(sphmi_handle* h, const sphmi_selection* sel, int64_t* n_rows_out, int64_t* n_selected_out) {
+    SPHMI_GUARD(h, h->e->select_build(sel, n_rows_out, n_selected_out));
+}
+int sphmi_select_read(sphmi_handle* h, int32_t* rows_out) { SPHMI_GUARD(h, h->e->select_read(rows_out)); }
+int sphmi_select_download(sphmi_handle* h, void* position, void* velocity, void* acceleration, void* density, void* pressure, int64_t* id, uint8_t* type,
+                          uint64_t* group_marker, void* ghost_points, int64_t* cells) {
+    SPHMI_GUARD(h, h->e->select_download(position, velocity, acceleration, density, pressure, id, type, group_marker, ghost_points, cells));
+}
+int sphmi_select_download_columns(sphmi_handle* h, void* const* columns_out) { SPHMI_GUARD(h, h->e->select_download_columns(columns_out)); }
+int sphmi_select_release(sphmi_handle* h) { SPHMI_GUARD(h, h->e->select_release()); }
 int sphmi_isosurface_build(sphmi_handle* h, const double* origin, const double* spacing, const int64_t* counts, double level, int64_t* n_vertices_out,
                            int64_t* n_elements_out) {
     SPHMI_GUARD(h, h->e->isosurface_build(origin, spacing, counts, level, n_vertices_out, n_elements_out));

@@ -1198,41 +1198,42 @@ template <class H> struct OutFields {
     H *pos, *vel, *acc, *rho, *press, *ghost;      // N×D, N×D, N×D, N, N, N×D  (null = not requested)
     long long* cells;                              // N×D
 };
+// The per-row body of k_pack_output(…): row i of the state into slot s of the arrays.  The kernel below packs every row into its
+// own slot (s = i); k_pack_selected (sphmi_select.h) packs the rows of a selection into consecutive slots.  (tests/test_envelopes_host.py
+// reads the Pressure line below as that of k_pack_output: it is the one both kernels run.)
 template <class T, class H>
-__global__ void __launch_bounds__(256) k_pack_output(Half<const typename Vec4<T>::type> pk0, Half<const typename Vec4<T>::type> pk1,
-                                                     Half<const typename Vec4<T>::type> half0, const typename Vec4<T>::type* accv,
-                                                     const typename Vec4<T>::type* ghostv, const typename Vec4<T>::type* comp,
-                                                     const int* key, int N, int D, int C,
-                                                     GridDesc g, int have_grid, T rho0, T inv_rho0, T Cbe, OutFields<H> o) {
+__device__ __forceinline__ void pack_output_row(const int i, const size_t s, Half<const typename Vec4<T>::type> pk0, Half<const typename Vec4<T>::type> pk1,
+                                                Half<const typename Vec4<T>::type> half0, const typename Vec4<T>::type* accv,
+                                                const typename Vec4<T>::type* ghostv, const typename Vec4<T>::type* comp,
+                                                const int* key, int D, int C,
+                                                const GridDesc& g, int have_grid, T rho0, T inv_rho0, T Cbe, const OutFields<H>& o) {
     // C: components per vector in the output (D, or 3 for the VTKHDF point layout: 2-D handles keep z = 0)
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= N) return;
-    const size_t b = (size_t)i * C;
+    const size_t b = s * C;
     if (o.pos || o.rho) {
         const auto q = pk0[i];
         if (sizeof(T) == 4 && comp) {
             // fp32 handles: the state is the record + its low word (ForceParams::comp) — a Float64 caller gets both
             const auto c = comp[i];
             if (o.pos) { o.pos[b] = (H)((double)q.x + (double)c.x); o.pos[b + 1] = (H)((double)q.y + (double)c.y); if (C == 3) o.pos[b + 2] = (H)((double)q.z + (double)c.z); }
-            if (o.rho) o.rho[i] = (H)((double)(q.w < T(0) ? -q.w : q.w) + (double)c.w);
+            if (o.rho) o.rho[s] = (H)((double)(q.w < T(0) ? -q.w : q.w) + (double)c.w);
         } else {
             if (o.pos) { o.pos[b] = (H)q.x; o.pos[b + 1] = (H)q.y; if (C == 3) o.pos[b + 2] = (H)q.z; }
-            if (o.rho) o.rho[i] = (H)(q.w < T(0) ? -q.w : q.w);
+            if (o.rho) o.rho[s] = (H)(q.w < T(0) ? -q.w : q.w);
         }
     }
     if (o.vel || (o.press && !half0)) {
         const auto q = pk1[i];
         if (o.vel) { o.vel[b] = (H)q.x; o.vel[b + 1] = (H)q.y; if (C == 3) o.vel[b + 2] = (H)q.z; }
-        if (o.press && !half0) o.press[i] = (H)q.w;                 // before any step: Pressure!(ρ) of :835
+        if (o.press && !half0) o.press[s] = (H)q.w;                 // before any step: Pressure!(ρ) of :835
     }
     if (o.press && half0) {
         // SimParticles.Pressure holds Pressure!(ρₙ⁺) of the last step (src/SPHCellList.jl:789)
-        o.press[i] = (H)eos7<T>(half0[i].w, rho0, inv_rho0, Cbe);     // (k_en_update forms the same value: sphmi_envelopes.h)
+        o.press[s] = (H)eos7<T>(half0[i].w, rho0, inv_rho0, Cbe);     // (k_en_update forms the same value: sphmi_envelopes.h)
     }
     if (o.acc) { const auto q = accv[i]; o.acc[b] = (H)q.x; o.acc[b + 1] = (H)q.y; if (C == 3) o.acc[b + 2] = (H)q.z; }
     if (o.ghost) { const auto q = ghostv[i]; o.ghost[b] = (H)q.x; o.ghost[b + 1] = (H)q.y; if (C == 3) o.ghost[b + 2] = (H)q.z; }
     if (o.cells) {
-        const size_t bc = (size_t)i * D;          // CartesianIndex{D}: never padded
+        const size_t bc = s * D;                  // CartesianIndex{D}: never padded
         if (!have_grid) { o.cells[bc] = 0; o.cells[bc + 1] = 0; if (D == 3) o.cells[bc + 2] = 0; }
         else {
             int kk = key[i];
@@ -1243,6 +1244,16 @@ __global__ void __launch_bounds__(256) k_pack_output(Half<const typename Vec4<T>
             if (D == 3) o.cells[bc + 2] = (long long)cz - 1 + g.gmin[2];
         }
     }
+}
+template <class T, class H>
+__global__ void __launch_bounds__(256) k_pack_output(Half<const typename Vec4<T>::type> pk0, Half<const typename Vec4<T>::type> pk1,
+                                                     Half<const typename Vec4<T>::type> half0, const typename Vec4<T>::type* accv,
+                                                     const typename Vec4<T>::type* ghostv, const typename Vec4<T>::type* comp,
+                                                     const int* key, int N, int D, int C,
+                                                     GridDesc g, int have_grid, T rho0, T inv_rho0, T Cbe, OutFields<H> o) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= N) return;
+    pack_output_row<T, H>(i, (size_t)i, pk0, pk1, half0, accv, ghostv, comp, key, D, C, g, have_grid, rho0, inv_rho0, Cbe, o);
 }
 
 // ---- pre-processing on the device: the 3-D dam-break lattice of SURVEY §8d generated where it is used ----

@@ -103,7 +103,7 @@ struct PassClock {
     }
 };
 
-// Whether a result the handle holds between calls (the neighbour list, the components, the mesh) matches the rows: a build sets it
+// Whether a result the handle holds between calls (the neighbour list, the components, the mesh, a selection) matches the rows: a build sets it
 // valid, whatever moves rows — sphmi_advance, sphmi_upload, the generator, sphmi_forces_once — turns valid into stale, a release or
 // a failed build leaves none.
 struct HeldResult {
