@@ -675,6 +675,41 @@ int sphmi_sample_point_gradients(sphmi_handle* h, int64_t n_points, const double
                                  double* grad_velocity_out);
 
 /*
+ * The MOMENTS of the kernel weights at arbitrary points, on demand: what a linear (first-order moving-least-squares) fit of pressure,
+ * density and velocity AT a point needs - a pressure sensor on a wall or on the bed, a probe within H of the free surface, wherever the
+ * support is one-sided and the Shepard mean of sphmi_sample_points reads the field at the centroid of the neighbours instead of at the
+ * point (csrc/sphmi_point_moments.h; the cloud is binned as for sphmi_sample_points).  Calling convention, limits, state and errors are
+ * those of sphmi_sample_points; what differs is what comes back.  Per point x, over the Fluid rows j the handle owns with
+ * r^2 = ((dx^2 + dy^2) + dz^2) <= H^2 (the cut of sphmi_sample_points: inclusive, not fused, on the current positions),
+ * w_j = (m0 / rho_j) W(r), e_j = x_j - x, on the state sphmi_download would deliver now, all in fp64, no self term; a row at r = 0
+ * counts in n and the zeroth sums and adds nothing to the others:
+ *   weight_out          [n_points]          S        = sum w
+ *   count_out           [n_points]          n        = rows that pass the cut
+ *   sum_pressure_out    [n_points]          SP       = sum w P
+ *   sum_density_out     [n_points]          Srho     = sum w rho
+ *   sum_velocity_out    [n_points x 3]      Sv[a]    = sum w v[a]
+ *   moment1_out         [n_points x 3]      M1[b]    = sum w e[b]
+ *   moment2_out         [n_points x 6]      M2[bc]   = sum w e[b] e[c]      (xx, xy, xz, yy, yz, zz)
+ *   moment_pressure_out [n_points x 3]      P1[b]    = sum w P e[b]
+ *   moment_density_out  [n_points x 3]      R1[b]    = sum w rho e[b]
+ *   moment_velocity_out [n_points x 3 x 3]  V1[a][b] = sum w v[a] e[b]      (entry 9 p + 3 a + b)
+ * Every sum is delivered RAW: S, n, SP, Srho and Sv are the sums sphmi_sample_point_gradients delivers, bit for bit.  The caller solves
+ * [[S, M1^T], [M1, M2]] [a; b] = [sum w f; sum w f e] per point and field: a is the field AT the point, b its gradient, exact for a
+ * linear field whatever the particle disorder and however one-sided the support (sphexample_amd/fields.py: linear_fit, which falls back
+ * to the Shepard mean where the support cannot carry a plane).  2-D handles write exact zeros to every slot of the third axis.  Any
+ * output pointer may be NULL.  Outputs are in the CALLER's order, and a point's result depends on its own coordinates and the state of
+ * the handle alone: rows are added in ascending row order, without atomics.  A point in empty space or outside the particles' cell
+ * grid reads zeros; n_points == 0 is legal.
+ *   SPHMI_ERR_STATE, SPHMI_ERR_ARGUMENT, SPHMI_ERR_DEVICE: as sphmi_sample_points (the arena holds 31 doubles per point).
+ * Multi-device handles of one process: every sum is linear in the rows, so every slab samples all points over the rows it owns and the
+ * handle adds the slabs' raw sums in slab order.
+ */
+int sphmi_sample_point_moments(sphmi_handle* h, int64_t n_points, const double* positions /* n_points x dims */,
+                               double* weight_out, int64_t* count_out, double* sum_pressure_out, double* sum_density_out,
+                               double* sum_velocity_out, double* moment1_out, double* moment2_out, double* moment_pressure_out,
+                               double* moment_density_out, double* moment_velocity_out);
+
+/*
  * WHERE ALONG A LINE DOES THE WATER BEGIN, on demand: the first crossing of S = level along rays - the water level at a gauge, the run-up
  * along a slope, the wetted height on an obstacle, the depth image a viewer renders from - found on the device by a march and a
  * subdivision instead of columns of fixed probes, a sample of every point of every line or a whole lattice (csrc/sphmi_rays.h).

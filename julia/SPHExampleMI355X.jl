@@ -367,6 +367,23 @@ function sample_point_gradients(P, positions::Matrix{Float64})
                                                              h, Int64(n), pointer(positions), pointer(w), pointer(c), pointer(sp), pointer(sr), pointer(sv), pointer(g), pointer(gp), pointer(gr), pointer(gv)))
     return (weight = w, count = c, sum_pressure = sp, sum_density = sr, sum_velocity = sv, grad_weight = g, grad_pressure = gp, grad_density = gr, grad_velocity = gv)
 end
+# The RAW kernel sums and their first and second moments at arbitrary points, evaluated on the state the session holds NOW
+# (sphmi_sample_point_moments): positions is dims × n as for sample_points.  With w_j = (m0 / ρ_j) W(r) and e_j = x_j − x: weight S,
+# count n, sum_pressure, sum_density (length n), sum_velocity, moment1 Σ w e, moment_pressure Σ w P e, moment_density Σ w ρ e (3 × n),
+# moment2 (6 × n: xx, xy, xz, yy, yz, zz of Σ w e ⊗ e) and moment_velocity (3 × 3 × n, entry [b, a, p] = Σ w v[a] e[b]: column-major, the
+# offset axis first).  Nothing is divided by S: the linear fit [[S, M1ᵀ], [M1, M2]] · [a; b] = [Σ w f; Σ w f e] is the caller's.
+# Multi-device sessions of one process deliver the sums over all slabs.  Call it from an output callback, after the first step.
+function sample_point_moments(P, positions::Matrix{Float64})
+    h = SESSIONS[P].h
+    n = size(positions, 2)
+    w = Vector{Float64}(undef, n); c = Vector{Int64}(undef, n); sp = Vector{Float64}(undef, n); sr = Vector{Float64}(undef, n)
+    sv = Matrix{Float64}(undef, 3, n); m1 = Matrix{Float64}(undef, 3, n); m2 = Matrix{Float64}(undef, 6, n); p1 = Matrix{Float64}(undef, 3, n)
+    r1 = Matrix{Float64}(undef, 3, n); v1 = Array{Float64, 3}(undef, 3, 3, n)
+    GC.@preserve positions w c sp sr sv m1 m2 p1 r1 v1 check(h, ccall((:sphmi_sample_point_moments, LIB), Cint,
+                                                             (Ptr{Cvoid}, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Int64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+                                                             h, Int64(n), pointer(positions), pointer(w), pointer(c), pointer(sp), pointer(sr), pointer(sv), pointer(m1), pointer(m2), pointer(p1), pointer(r1), pointer(v1)))
+    return (weight = w, count = c, sum_pressure = sp, sum_density = sr, sum_velocity = sv, moment1 = m1, moment2 = m2, moment_pressure = p1, moment_density = r1, moment_velocity = v1)
+end
 # The first crossing of S = level along rays, found on the state the session holds NOW (sphmi_cast_rays): origins and directions are
 # dims × n, t_end a number or a vector of length n; step is the march step in units of |d| (say h / 2); mode is :enter, :leave or :any.  status (bit 0: found, bit 1:
 # the ray starts inside), interval (k, or −1), bracket (2 × n), point (3 × n: the inside end), weight, count, sum_pressure, sum_density

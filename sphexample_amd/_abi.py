@@ -108,6 +108,7 @@ PROTOTYPES = {
     "maps_enable": [_P, _P, _P, _P, _I32], "maps_disable": [_P], "maps_read": [_P, _pI64, _P] + [_P] * 14,
     # the results on demand
     "sample_grid": [_P] * 9, "sample_points": [_P, _I64] + [_P] * 6, "sample_point_gradients": [_P, _I64] + [_P] * 10,
+    "sample_point_moments": [_P, _I64] + [_P] * 11,
     "cast_rays": [_P, _I64] + [_P] * 4 + [_F, _F, _I32] + [_P] * 9, "particle_fields": [_P] * 7,
     "neighbors_build": [_P, _I32, _pI64, _pI64], "neighbors_read": [_P] * 3, "neighbors_release": [_P],
     "isosurface_build": [_P] * 4 + [_F, _pI64, _pI64], "isosurface_read": [_P] * 5, "isosurface_release": [_P],
@@ -195,7 +196,7 @@ FEATURES = {
     **{k: (k + "_enable", k + "_read") for k in ("group_forces", "probes", "budgets", "flow", "envelopes", "tracers")},
     **{k: (k + "_build", k + "_read", k + "_release") for k in ("isosurface", "components")},
     "select": ("select_build", "select_read", "select_download", "select_download_columns", "select_release"),
-    **{k: (k,) for k in ("sample_grid", "sample_points", "sample_point_gradients", "cast_rays", "particle_fields")},
+    **{k: (k,) for k in ("sample_grid", "sample_points", "sample_point_gradients", "sample_point_moments", "cast_rays", "particle_fields")},
 }
 
 
@@ -696,6 +697,31 @@ class Backend:
         first executed step."""
         x = self._cloud("sample_point_gradients", positions)
         return self._sample("sample_point_gradients", self.GRADIENT_FIELDS, fields, (len(x),), len(x), _ptr(x))
+
+    # -- moment sums at arbitrary points, on demand (sphmi_sample_point_moments) --------------------------------------------------
+    # (moment2 travels as the six entries xx, xy, xz, yy, yz, zz and is handed out as the symmetric [n, 3, 3])
+    MOMENT_FIELDS = {"weight": (_F64, ()), "count": (_INT64, ()), "sum_pressure": (_F64, ()), "sum_density": (_F64, ()),
+                     "sum_velocity": (_F64, (3,)), "moment1": (_F64, (3,)), "moment2": (_F64, (6,)), "moment_pressure": (_F64, (3,)),
+                     "moment_density": (_F64, (3,)), "moment_velocity": (_F64, (3, 3))}
+    _SYMMETRIC = np.array([[0, 1, 2], [1, 3, 4], [2, 4, 5]])
+
+    def sample_point_moments(self, positions, fields=None) -> dict:
+        """The RAW kernel sums and their moments at every point of `positions` ([n, dims], up to 2**24 points), evaluated now, with
+        w_j = (m0 / ρ_j) W(r) and e_j = x_j − x: `weight` S, `count` n, `sum_pressure`, `sum_density` [n], `sum_velocity` [n, 3],
+        `moment1` Σ w e [n, 3], `moment2` Σ w e ⊗ e [n, 3, 3] (symmetric), `moment_pressure` Σ w P e, `moment_density` Σ w ρ e
+        [n, 3] and `moment_velocity` [n, 3, 3] with entry [a, b] = Σ w v[a] e[b].  Nothing is divided by S;
+        ``sphexample_amd.fields.linear_fit`` solves the per-point system for the values AT the points and their gradients, exact
+        for a linear field however one-sided the support (`vorticity_linear`, `divergence_linear`, `strain_rate_linear`,
+        `surface_load_linear` build on it).  `fields` names the sums wanted (default: all); the dict also carries the handle's `h`
+        and `dims`, which `linear_fit` scales its system with.  Entry p belongs to ``positions[p]``
+        and does not depend on the other points of the call; multi-device handles of one process deliver the sums over all
+        slabs.  Call it between `advance` calls, after the first executed step."""
+        x = self._cloud("sample_point_moments", positions)
+        out = self._sample("sample_point_moments", self.MOMENT_FIELDS, fields, (len(x),), len(x), _ptr(x))
+        if "moment2" in out:
+            out["moment2"] = np.ascontiguousarray(out["moment2"][:, self._SYMMETRIC])
+        out["h"], out["dims"] = float(self.cfg.h), int(self.D)                 # what `fields.linear_fit` scales the system with
+        return out
 
     # -- the first crossing of S = level along rays, on demand (sphmi_cast_rays) ---------------------------------------------------
     RAY_FIELDS = {"status": (np.int32, ()), "interval": (_INT64, ()), "bracket": (_F64, (2,)), "point": (_F64, (3,)),

@@ -28,6 +28,7 @@
 #include "sphmi_field_grid.h"
 #include "sphmi_point_cloud.h"
 #include "sphmi_point_gradients.h"
+#include "sphmi_point_moments.h"
 #include "sphmi_rays.h"
 #include "sphmi_particle_fields.h"
 #include "sphmi_neighbor_list.h"
@@ -268,6 +269,7 @@ struct EngineBase {
     virtual void sample_points(int64_t n_points, const double* positions, double* weight, int64_t* count, double* pressure, double* density,
                                double* velocity) = 0;
     virtual void sample_point_gradients(int64_t n_points, const double* positions, const GradientOutputs& out) = 0;
+    virtual void sample_point_moments(int64_t n_points, const double* positions, const MomentOutputs& out) = 0;
     virtual void cast_rays(int64_t n_rays, const RayCall& c) = 0;
     virtual void particle_fields(int64_t* count, double* shepard, double* normal, double* div_r, double* div_v, double* vorticity) = 0;
     // The results a handle holds between calls (HeldResult, sphmi_results.h): the neighbour list (sphmi_neighbor_list.h), the free
@@ -2332,21 +2334,23 @@ struct Engine final : EngineBase {
     // ---- kernel sums at arbitrary points, on demand (sphmi_point_cloud.h) -------------------------------------------------------------
     // Reads what the lattice reads; writes its own buffers and nothing else.  The positions, the plan (block of every point, counts,
     // offsets, tiles, index) and the arena grow with the call and go back to the device where fg_arena does.  The gradients
-    // (sphmi_point_gradients.h) share the positions and the plan and keep an arena of their own, pg_arena.
-    DeviceBuf<double> pc_arena, pg_arena, pc_pos;
+    // (sphmi_point_gradients.h) and the moments (sphmi_point_moments.h) share the positions and the plan and keep an arena of their
+    // own each, pg_arena and pm_arena.
+    DeviceBuf<double> pc_arena, pg_arena, pm_arena, pc_pos;
     DeviceBuf<int> pc_block, pc_index, pc_count, pc_tcount;
     DeviceBuf<long long> pc_poff, pc_toff, pc_tsum;
     DeviceBuf<PcTile> pc_tiles;
     long long pc_ntiles = 0;                   // of the last launch
     void pc_free() {
-        pc_arena.free(); pg_arena.free(); pc_pos.free(); pc_block.free(); pc_index.free(); pc_count.free(); pc_tcount.free();
+        pc_arena.free(); pg_arena.free(); pm_arena.free(); pc_pos.free(); pc_block.free(); pc_index.free(); pc_count.free(); pc_tcount.free();
         pc_poff.free(); pc_toff.free(); pc_tsum.free(); pc_tiles.free();
     }
     // upload the cloud, bin it and queue the kernel on the engine's stream (a multi-device handle calls it on every slab engine);
-    // n ≥ 1.  `clock` (may be null) gets a mark before the bin, behind it and behind the sampling kernel.  `gradients`: the same
-    // bin, then k_point_gradients into pg_arena instead of k_point_cloud into pc_arena.
-    void pc_launch(const double* positions, int64_t n, PassClock* clock = nullptr, bool gradients = false) {
-        const char* fn = gradients ? "sphmi_sample_point_gradients" : "sphmi_sample_points";
+    // n ≥ 1.  `clock` (may be null) gets a mark before the bin, behind it and behind the sampling kernel.  `what`: the same bin,
+    // then k_point_cloud into pc_arena, k_point_gradients into pg_arena or k_point_moments into pm_arena.
+    enum PcWhat { PC_CLOUD, PC_GRADIENTS, PC_MOMENTS };
+    void pc_launch(const double* positions, int64_t n, PassClock* clock = nullptr, PcWhat what = PC_CLOUD) {
+        const char* fn = what == PC_MOMENTS ? "sphmi_sample_point_moments" : what == PC_GRADIENTS ? "sphmi_sample_point_gradients" : "sphmi_sample_points";
         HC(hipSetDevice(cfg.device));
         const PcTiling G = pc_tiling(grid.gmin, grid.np, D, cfg.H_inv);
         const long long nblocks = pc_blocks(G);
@@ -2355,8 +2359,8 @@ struct Engine final : EngineBase {
         auto no_memory = [&](size_t bytes) {
             return text("%s: no device memory for the arena of %lld points (%zu bytes)", fn, (long long)n, bytes);
         };
-        DeviceBuf<double>& arena = gradients ? pg_arena : pc_arena;
-        arena.need((size_t)(gradients ? kPgValues : kFgValues) * np, no_memory);
+        DeviceBuf<double>& arena = what == PC_MOMENTS ? pm_arena : what == PC_GRADIENTS ? pg_arena : pc_arena;
+        arena.need((size_t)(what == PC_MOMENTS ? kPmValues : what == PC_GRADIENTS ? kPgValues : kFgValues) * np, no_memory);
         pc_pos.need(np * (size_t)D, no_memory); pc_block.need(np, no_memory); pc_index.need(np, no_memory);
         pc_count.need(nb, no_memory); pc_tcount.need(nb, no_memory); pc_poff.need(nb + 1, no_memory); pc_toff.need(nb + 1, no_memory);
         bounce.h2d(pc_pos.p, positions, np * (size_t)D * 8, stream);
@@ -2384,7 +2388,9 @@ struct Engine final : EngineBase {
         fill_sample_consts(A);
         A.N = N; A.kernel = cfg.kernel;
         by_dims([&](auto d) {
-            if (gradients) hipLaunchKernelGGL((k_point_gradients<T, decltype(d)::value>), dim3((unsigned)pc_ntiles), dim3(kFgThreads), 0, stream, A);
+            constexpr int Dd = decltype(d)::value;
+            if (what == PC_MOMENTS) hipLaunchKernelGGL((k_point_moments<T, Dd>), dim3((unsigned)pc_ntiles), dim3(kFgThreads), 0, stream, A);
+            else if (what == PC_GRADIENTS) hipLaunchKernelGGL((k_point_gradients<T, Dd>), dim3((unsigned)pc_ntiles), dim3(kFgThreads), 0, stream, A);
             else hipLaunchKernelGGL((k_point_cloud<T, decltype(d)::value>), dim3((unsigned)pc_ntiles), dim3(kFgThreads), 0, stream, A);
         });
         HC(hipGetLastError());
@@ -2393,6 +2399,7 @@ struct Engine final : EngineBase {
     // one raw sum of the cloud → host, behind the kernel (as fg_fetch)
     void pc_fetch(int f, double* dst, int64_t n) { fetch_result(dst, pc_arena.p + (size_t)f * (size_t)n, (size_t)n * 8); }
     void pg_fetch(int f, double* dst, int64_t n) { fetch_result(dst, pg_arena.p + (size_t)f * (size_t)n, (size_t)n * 8); }
+    void pm_fetch(int f, double* dst, int64_t n) { fetch_result(dst, pm_arena.p + (size_t)f * (size_t)n, (size_t)n * 8); }
     void sample_points(int64_t n, const double* positions, double* weight, int64_t* count, double* pressure, double* density, double* velocity) override {
         require_cell_list("sphmi_sample_points", fg_ready(), "(no cell list, no half-step set)");
         check_sample_points(n, positions, D);
@@ -2413,7 +2420,7 @@ struct Engine final : EngineBase {
         check_sample_points(n, positions, D, "sphmi_sample_point_gradients");
         if (n == 0) return;
         PassClock clock("SPHMI_POINTS_CLOCK", stream);                     // (tools/point_gradients_cost.py)
-        pc_launch(positions, n, &clock, true);
+        pc_launch(positions, n, &clock, PC_GRADIENTS);
         bool wanted[kPgValues];
         out.wanted(wanted);
         GridSums G(n, out.weight, wanted);
@@ -2421,6 +2428,23 @@ struct Engine final : EngineBase {
         clock.mark();
         HC(hipStreamSynchronize(stream));
         clock.report(text("sphmi_sample_point_gradients: %lld points, %lld tiles, %.1f lanes filled of %d:", (long long)n, pc_ntiles, (double)n / (double)pc_ntiles, kPcTile),
+                     {"bin", "sample", "fetch"});
+        out.deliver(G);
+    }
+    // … and the moments of the weights (sphmi_point_moments.h): the same checks, the same bin, the raw sums as they are
+    void sample_point_moments(int64_t n, const double* positions, const MomentOutputs& out) override {
+        require_cell_list("sphmi_sample_point_moments", fg_ready(), "(no cell list, no half-step set)");
+        check_sample_points(n, positions, D, "sphmi_sample_point_moments");
+        if (n == 0) return;
+        PassClock clock("SPHMI_POINTS_CLOCK", stream);                     // (tools/point_moments_cost.py)
+        pc_launch(positions, n, &clock, PC_MOMENTS);
+        bool wanted[kPmValues];
+        out.wanted(wanted);
+        GridSums G(n, out.weight, wanted);
+        for (int f = 0; f < kPmValues; ++f) if (G.want[f]) pm_fetch(f, G.dst(f), n);
+        clock.mark();
+        HC(hipStreamSynchronize(stream));
+        clock.report(text("sphmi_sample_point_moments: %lld points, %lld tiles, %.1f lanes filled of %d:", (long long)n, pc_ntiles, (double)n / (double)pc_ntiles, kPcTile),
                      {"bin", "sample", "fetch"});
         out.deliver(G);
     }
@@ -3441,6 +3465,13 @@ int sphmi_sample_point_gradients(sphmi_handle* h, int64_t n_points, const double
     const sphmi::GradientOutputs out{weight_out, sum_pressure_out, sum_density_out, sum_velocity_out, grad_weight_out, grad_pressure_out,
                                      grad_density_out, grad_velocity_out, count_out};
     SPHMI_GUARD(h, h->e->sample_point_gradients(n_points, positions, out));
+}
+int sphmi_sample_point_moments(sphmi_handle* h, int64_t n_points, const double* positions, double* weight_out, int64_t* count_out,
+                               double* sum_pressure_out, double* sum_density_out, double* sum_velocity_out, double* moment1_out,
+                               double* moment2_out, double* moment_pressure_out, double* moment_density_out, double* moment_velocity_out) {
+    const sphmi::MomentOutputs out{weight_out, sum_pressure_out, sum_density_out, sum_velocity_out, moment1_out, moment2_out,
+                                   moment_pressure_out, moment_density_out, moment_velocity_out, count_out};
+    SPHMI_GUARD(h, h->e->sample_point_moments(n_points, positions, out));
 }
 int sphmi_cast_rays(sphmi_handle* h, int64_t n_rays, const double* origins, const double* directions, const double* t_begin, const double* t_end,
                     double step, double level, int32_t mode, int32_t* status_out, int64_t* interval_out, double* bracket_out, double* point_out,

@@ -1810,11 +1810,26 @@ struct MultiEngine final : EngineBase {
         require_cell_list("sphmi_sample_point_gradients", any, "(no cell list, no half-step set)");
         check_sample_points(n, positions, D, "sphmi_sample_point_gradients");
         if (n == 0) return;
-        for (auto& r : R) if (r.e->fg_ready()) r.e->pc_launch(positions, n, nullptr, true);
+        for (auto& r : R) if (r.e->fg_ready()) r.e->pc_launch(positions, n, nullptr, Engine<T>::PC_GRADIENTS);
         bool wanted[kPgValues];
         out.wanted(wanted);
         GridSums G(n, out.weight, wanted);
         add_slab_sums(G, [&](Engine<T>& e, int f, double* dst) { e.pg_fetch(f, dst, n); });
+        out.deliver(G);
+    }
+    // … and the moments of the weights (sphmi_point_moments.h): linear in the rows as well, added in slab order
+    void sample_point_moments(int64_t n, const double* positions, const MomentOutputs& out) override {
+        require_one_process("sphmi_sample_point_moments");
+        bool any = false;
+        for (auto& r : R) any = any || r.e->fg_ready();
+        require_cell_list("sphmi_sample_point_moments", any, "(no cell list, no half-step set)");
+        check_sample_points(n, positions, D, "sphmi_sample_point_moments");
+        if (n == 0) return;
+        for (auto& r : R) if (r.e->fg_ready()) r.e->pc_launch(positions, n, nullptr, Engine<T>::PC_MOMENTS);
+        bool wanted[kPmValues];
+        out.wanted(wanted);
+        GridSums G(n, out.weight, wanted);
+        add_slab_sums(G, [&](Engine<T>& e, int f, double* dst) { e.pm_fetch(f, dst, n); });
         out.deliver(G);
     }
     // The first crossing along rays (sphmi_rays.h): single-device handles only.  Whether a march point is inside is decided by the slabs'

@@ -30,6 +30,8 @@ constexpr int kFgValues = kPrValues;             // S, SP, Sρ, Sv[3], n
 constexpr long long kMaxGridNodes = 1ll << 24;   // SPHMI_MAX_GRID_NODES
 constexpr long long kMaxSamplePoints = 1ll << 24; // SPHMI_MAX_SAMPLE_POINTS
 constexpr int kPgValues = kFgValues + 18;        // the sums of the cloud, then G[3], GP[3], Gρ[3], Gv[3][3] (sphmi_point_gradients.h)
+constexpr int kPmValues = kFgValues + 24;        // the sums of the cloud, then M1[3], M2[6], P1[3], R1[3], V1[3][3] (sphmi_point_moments.h)
+constexpr int kSampleValuesMax = kPmValues;      // the most sums per node any sampler delivers through GridSums
 constexpr int kBgValues = 22;                    // the raw budgets of the fluid (sphmi_budgets.h): thirteen sums, nine extremes
 
 // How two values of slot `slot` of a budget record combine: 0 sum (slots 0 … 12), 1 min, 2 max (13 max |v|², 14 / 15 min / max ρ,
@@ -164,7 +166,7 @@ inline int64_t check_grid_lattice(const double* origin, const double* spacing, c
     return nodes;
 }
 
-// sphmi_sample_points and sphmi_sample_point_gradients (`fn`): the argument errors every kind of handle reports alike
+// sphmi_sample_points, sphmi_sample_point_gradients and sphmi_sample_point_moments (`fn`): the argument errors every kind of handle reports alike
 inline void check_sample_points(int64_t n_points, const double* positions, int dims, const char* fn = "sphmi_sample_points") {
     const std::string name(fn);
     if (n_points < 0 || n_points > kMaxSamplePoints) throw EngineError(SPHMI_ERR_ARGUMENT, name + ": n_points out of range [0, SPHMI_MAX_SAMPLE_POINTS]");
@@ -305,13 +307,13 @@ inline void deliver_map_vectors(int64_t bins, const double* c0, const double* c1
 // (sphmi_field_grid.h) or the cloud (sphmi_point_cloud.h), `nodes` of either, the ones the requested outputs need.  S lands in weight_out itself when that is asked for; the means are formed here, 0 where n == 0.
 // sphmi_sample_point_gradients (sphmi_point_gradients.h) carries `values` = kPgValues sums per point in the same arrays — the
 // first seven are the cloud's — and hands them out RAW (the second constructor, deliver_raw): a multi-device handle adds both kinds
-// with one loop.
+// with one loop.  sphmi_sample_point_moments (sphmi_point_moments.h) does the same with kPmValues sums.
 struct GridSums {
     int64_t nodes = 0;
     int values = kFgValues;                    // sums per node
     double* S = nullptr;                       // weight_out, or s[0]
-    std::vector<double> s[kPgValues];
-    bool want[kPgValues] = {};
+    std::vector<double> s[kSampleValuesMax];
+    bool want[kSampleValuesMax] = {};
     double* dst(int f) { return f == 0 ? S : s[f].data(); }
     GridSums(int64_t n, double* weight, const int64_t* count, const double* pressure, const double* density, const double* velocity) : nodes(n) {
         const bool means = pressure || density || velocity;
@@ -331,9 +333,10 @@ struct GridSums {
             if (velocity) for (int d = 0; d < 3; ++d) velocity[3 * k + d] = kernel_mean(s[3 + d][k], S[k], some);
         }
     }
-    // the raw sums of the gradients: slot f is wanted where wanted[f]; S goes straight into weight_out
-    GridSums(int64_t n, double* weight, const bool (&wanted)[kPgValues]) : nodes(n), values(kPgValues) {
-        for (int f = 0; f < kPgValues; ++f) {
+    // the raw sums of the gradients (V = kPgValues) or the moments (kPmValues): slot f is wanted where wanted[f]; S goes straight into weight_out
+    template <int V> GridSums(int64_t n, double* weight, const bool (&wanted)[V]) : nodes(n), values(V) {
+        static_assert(V <= kSampleValuesMax, "GridSums holds at most kSampleValuesMax sums per node");
+        for (int f = 0; f < V; ++f) {
             want[f] = wanted[f];
             if (want[f] && !(f == 0 && weight)) s[f].assign((size_t)n, 0.0);
         }
@@ -367,6 +370,26 @@ struct GradientOutputs {
         G.deliver_count(count);
         G.deliver_raw(1, 1, sum_pressure); G.deliver_raw(2, 1, sum_density); G.deliver_raw(3, 3, sum_velocity);
         G.deliver_raw(7, 3, grad_weight); G.deliver_raw(10, 3, grad_pressure); G.deliver_raw(13, 3, grad_density); G.deliver_raw(16, 9, grad_velocity);
+    }
+};
+
+// sphmi_sample_point_moments: the slots of kPmValues the caller's outputs need (any may be null)
+struct MomentOutputs {
+    double *weight, *sum_pressure, *sum_density, *sum_velocity, *moment1, *moment2, *moment_pressure, *moment_density, *moment_velocity;
+    int64_t* count;
+    void wanted(bool (&w)[kPmValues]) const {
+        for (int f = 0; f < kPmValues; ++f) w[f] = false;
+        w[0] = weight != nullptr; w[1] = sum_pressure != nullptr; w[2] = sum_density != nullptr;
+        w[3] = w[4] = w[5] = sum_velocity != nullptr; w[6] = count != nullptr;
+        for (int b = 0; b < 3; ++b) { w[7 + b] = moment1 != nullptr; w[16 + b] = moment_pressure != nullptr; w[19 + b] = moment_density != nullptr; }
+        for (int c = 0; c < 6; ++c) w[10 + c] = moment2 != nullptr;
+        for (int c = 0; c < 9; ++c) w[22 + c] = moment_velocity != nullptr;
+    }
+    void deliver(const GridSums& G) const {
+        G.deliver_count(count);
+        G.deliver_raw(1, 1, sum_pressure); G.deliver_raw(2, 1, sum_density); G.deliver_raw(3, 3, sum_velocity);
+        G.deliver_raw(7, 3, moment1); G.deliver_raw(10, 6, moment2); G.deliver_raw(16, 3, moment_pressure); G.deliver_raw(19, 3, moment_density);
+        G.deliver_raw(22, 9, moment_velocity);
     }
 };
 

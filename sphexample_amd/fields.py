@@ -205,6 +205,129 @@ def surface_normal_at(sums, min_weight: float = MIN_GRADIENT_WEIGHT) -> np.ndarr
     return out
 
 
+# ---- the linear fit at arbitrary points, from the raw sums of ``Backend.sample_point_moments`` --------------------------------------
+# A Shepard mean SA / S returns the field at the kernel-weighted centroid of the neighbours, not at the point: on a wall, on the bed
+# and within H of the free surface, where the support is one-sided, that is a fraction of h inside the fluid.  With the moments
+#     S = Σ w    M1 = Σ w e    M2 = Σ w e ⊗ e    SA = Σ w A    A1 = Σ w A e        (e = x_j − x)
+# the weighted least-squares plane a + b·e through the neighbours' values solves, per point and field,
+#     [[S, M1ᵀ], [M1, M2]] · [a; b] = [SA; A1]
+# — the linear reconstruction mDBC makes at its ghost nodes.  a is the field AT the point, b its gradient, both exact for a linear
+# field whatever the disorder and the cut of the support.  The system is solved with the offsets in units of h and divided by S:
+# its matrix is then dimensionless — 1 in the corner, the centroid offset / h beside it, the second moments / h² — and its
+# reciprocal condition number λ_min / λ_max means the same at every resolution.  Where the support cannot carry a plane the
+# point keeps the Shepard mean.  LINEAR_FIT_MIN_RCOND: supports on one line (2-D) or in one plane (3-D) reach 1.6e-16 at the most
+# (rounding); the most one-sided full-rank supports of the 700-point clouds on the shipped dam-break fixtures — D + 1 rows or more,
+# S ≥ MIN_GRADIENT_WEIGHT — reach 5.4e-3 (2-D) and 3.5e-3 (3-D) at the least (profiles/point_moments.md, "The threshold").  The
+# constant is the geometric middle of that gap, 7e-10, in a round figure.  A fit amplifies the error of the sums by 1 / rcond at
+# the worst: callers who feed it the sums of an fp32 handle (2e-4) may want a higher floor.
+LINEAR_FIT_MIN_RCOND = 1e-9
+
+
+def _moment_system(sums, h, dims):
+    """S [n], the scaled matrices [n, D + 1, D + 1] and their reciprocal condition numbers [n] (0 where S is not positive)."""
+    h = float(sums["h"] if h is None else h)
+    D = int(sums["dims"] if dims is None else dims)
+    if D not in (2, 3) or not h > 0.0:
+        raise ValueError("linear_fit: dims is 2 or 3 and h positive (the dict of Backend.sample_point_moments carries both)")
+    S = np.asarray(sums["weight"], dtype=np.float64)
+    M1 = np.asarray(sums["moment1"], dtype=np.float64)
+    M2 = np.asarray(sums["moment2"], dtype=np.float64)
+    n = len(S)
+    if S.ndim != 1 or M1.shape != (n, 3) or M2.shape != (n, 3, 3):
+        raise ValueError("the sums of sample_point_moments are needed: weight [n], moment1 [n, 3], moment2 [n, 3, 3]")
+    some = S > 0.0
+    Ss = np.where(some, S, 1.0)
+    A = np.zeros((n, D + 1, D + 1))
+    A[:, 0, 0] = 1.0
+    A[:, 0, 1:] = A[:, 1:, 0] = M1[:, :D] / (Ss * h)[:, None]
+    A[:, 1:, 1:] = M2[:, :D, :D] / (Ss * h * h)[:, None, None]
+    A[~some] = 0.0
+    lam = np.linalg.eigvalsh(A) if n else np.zeros((0, D + 1))                     # ascending; A is a Gram matrix: λ ≥ 0 up to rounding
+    top = lam[:, -1]
+    rcond = np.where(some & (top > 0.0), np.maximum(lam[:, 0], 0.0) / np.where(top > 0.0, top, 1.0), 0.0)
+    return h, D, S, A, rcond
+
+
+def linear_fit_rcond(sums, h: float = None, dims: int = None) -> np.ndarray:
+    """The reciprocal condition number λ_min / λ_max of every point's scaled moment matrix, ``[n]`` — what `linear_fit` holds
+    against `min_rcond`; 0 where ``weight`` is not positive."""
+    return _moment_system(sums, h, dims)[4]
+
+
+def linear_fit(sums, min_count: int = None, min_rcond: float = LINEAR_FIT_MIN_RCOND, h: float = None, dims: int = None) -> dict:
+    """Pressure, density and velocity AT the points and their gradients, from the dict of ``Backend.sample_point_moments``: the
+    weighted least-squares plane through the neighbours' values, exact for a linear field however one-sided the support.
+    Returns `pressure`, `density` [n], `velocity` [n, 3], `pressure_gradient`, `density_gradient` [n, 3], `velocity_gradient`
+    [n, 3, 3] (entry [a, b] = ∂v_a/∂x_b), `linear` [n] bool — the points that were fitted — and `rcond` [n], the reciprocal
+    condition number of every point's system.  A point with fewer than `min_count` rows (default dims + 1), with ``weight`` below
+    `MIN_GRADIENT_WEIGHT` or with ``rcond < min_rcond`` keeps the Shepard means SA / S, gets zero gradients and
+    ``linear == False``; a point without rows reads zeros.  2-D: the z entries are zero.  `h` and `dims` default to the entries
+    of those names the backend puts into the dict."""
+    h, D, S, A, rcond = _moment_system(sums, h, dims)
+    n = len(S)
+    cnt = np.asarray(sums["count"])
+    SA = np.concatenate([np.asarray(sums["sum_pressure"], dtype=np.float64).reshape(n, 1), np.asarray(sums["sum_density"], dtype=np.float64).reshape(n, 1),
+                         np.asarray(sums["sum_velocity"], dtype=np.float64).reshape(n, 3)], axis=1)                       # [n, 5]
+    A1 = np.concatenate([np.asarray(sums["moment_pressure"], dtype=np.float64).reshape(n, 1, 3), np.asarray(sums["moment_density"], dtype=np.float64).reshape(n, 1, 3),
+                         np.asarray(sums["moment_velocity"], dtype=np.float64).reshape(n, 3, 3)], axis=1)                 # [n, 5, 3]
+    need = D + 1 if min_count is None else int(min_count)
+    some = (cnt > 0) & (S > 0.0)
+    fit = some & (cnt >= need) & (S >= MIN_GRADIENT_WEIGHT) & (rcond >= float(min_rcond))
+    Ss = np.where(some, S, 1.0)
+    value = np.where(some[:, None], SA / Ss[:, None], 0.0)                         # the Shepard means: what a point keeps without a fit
+    grad = np.zeros((n, 5, 3))
+    if fit.any():
+        rhs = np.concatenate([SA[fit][:, None, :] / S[fit][:, None, None], np.swapaxes(A1[fit][:, :, :D], 1, 2) / (S[fit] * h)[:, None, None]], axis=1)
+        sol = np.linalg.solve(A[fit], rhs)                                         # [m, D + 1, 5]: a, then b · h
+        value[fit] = sol[:, 0, :]
+        g = np.zeros((int(fit.sum()), 5, 3))
+        g[:, :, :D] = np.swapaxes(sol[:, 1:, :], 1, 2) / h
+        grad[fit] = g
+    if D == 2:
+        value[:, 4] = 0.0
+    return {"pressure": value[:, 0].copy(), "density": value[:, 1].copy(), "velocity": value[:, 2:5].copy(),
+            "pressure_gradient": grad[:, 0].copy(), "density_gradient": grad[:, 1].copy(), "velocity_gradient": grad[:, 2:5].copy(),
+            "linear": fit, "rcond": rcond}
+
+
+def _fitted_velocity_gradient(sums, **kw):
+    """∂v_a/∂x_b of `linear_fit`, NaN where the point was not fitted — the convention of `velocity_gradient`."""
+    f = sums if "velocity_gradient" in sums and "linear" in sums else linear_fit(sums, **kw)
+    L = np.array(f["velocity_gradient"], dtype=np.float64)
+    L[~np.asarray(f["linear"], dtype=bool)] = np.nan
+    return L
+
+
+def vorticity_linear(sums, **kw) -> np.ndarray:
+    """``ω = ∇ × v`` at every point, ``[n, 3]``, from the velocity gradient of `linear_fit` (`sums`: the dict of
+    ``Backend.sample_point_moments``, or the result of `linear_fit` itself; keywords go to `linear_fit`): shaped and signed
+    like `vorticity_at`, NaN where the point was not fitted."""
+    L = _fitted_velocity_gradient(sums, **kw)
+    return np.stack([L[:, 2, 1] - L[:, 1, 2], L[:, 0, 2] - L[:, 2, 0], L[:, 1, 0] - L[:, 0, 1]], axis=1)
+
+
+def divergence_linear(sums, **kw) -> np.ndarray:
+    """``∇·v`` at every point, ``[n]``: the trace of the velocity gradient of `linear_fit`; NaN where the point was not fitted."""
+    L = _fitted_velocity_gradient(sums, **kw)
+    return L[:, 0, 0] + L[:, 1, 1] + L[:, 2, 2]
+
+
+def strain_rate_linear(sums, **kw) -> np.ndarray:
+    """The rate-of-strain tensor ``½ (L + Lᵀ)`` at every point, ``[n, 3, 3]``, of the velocity gradient of `linear_fit`; NaN
+    where the point was not fitted."""
+    L = _fitted_velocity_gradient(sums, **kw)
+    return 0.5 * (L + np.swapaxes(L, 1, 2))
+
+
+def surface_load_linear(vertices, triangles, backend, about=None, **kw):
+    """`surface_load` with the FITTED pressure at the element centroids: the centroids are sampled with
+    ``backend.sample_point_moments`` and `linear_fit` (keywords go to it) gives the pressure at the panels themselves, not a
+    fraction of h inside the fluid; panels that could not be fitted keep the Shepard mean, dry ones read zero."""
+    sums = backend.sample_point_moments(triangle_centroids(vertices, triangles))
+    return surface_load(vertices, triangles, linear_fit(sums, **kw)["pressure"], about=about)
+
+
 __all__ = ["grid_axes", "grid_nodes", "surface_height", "free_surface_mask", "FREE_SURFACE_DIV_R", "segment", "triangle_centroids",
            "surface_load", "MIN_GRADIENT_WEIGHT", "velocity_gradient", "vorticity_at", "divergence_at", "strain_rate",
-           "pressure_gradient", "surface_normal_at"]
+           "pressure_gradient", "surface_normal_at", "LINEAR_FIT_MIN_RCOND", "linear_fit", "linear_fit_rcond", "vorticity_linear",
+           "divergence_linear", "strain_rate_linear", "surface_load_linear"]

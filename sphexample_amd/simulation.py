@@ -47,7 +47,7 @@ def RunSimulation(*, SimGeometry=None, SimMetaData: SimulationMetaData, SimConst
                   async_output: bool = False, group_forces=None, probes=None, field_grid=None,
                   particle_fields=None, budgets: bool = False, neighbor_list: bool = False, isosurface=None, components=None,
                   flow_boxes=None, envelopes=None, maps=None, tracers=None, sample_points=None,
-                  sample_point_gradients=None, rays=None, output_select=None) -> List[float]:
+                  sample_point_gradients=None, rays=None, output_select=None, sample_point_moments=None) -> List[float]:
     """Same keyword signature as the reference (src/SPHCellList.jl:808-817); returns the list of
     time steps the reference collects in ``TimeSteps`` (:823,:884).  ``SimParticles`` is updated in
     place at every output time, in the engine's cell-sorted order, as the reference's is.
@@ -144,7 +144,13 @@ def RunSimulation(*, SimGeometry=None, SimMetaData: SimulationMetaData, SimConst
     decimations and masks) and ``on_output`` receives ``(rows, dict of arrays)`` as its last argument, behind the rays.  It is taken
     at the same point as the snapshot, with no step between it and the download: ``rows`` index the particles of that output and
     every array equals that field's ``[rows]``.  A selection needs no executed step, so the first call receives one too, of the
-    particles as uploaded.  ``None`` (default): nothing is selected and the callback keeps its arguments."""
+    particles as uploaded.  ``None`` (default): nothing is selected and the callback keeps its arguments.
+
+    ``sample_point_moments=positions`` ([n, dims]): at every output the raw kernel sums and their first and second moments are
+    sampled at those points (``Backend.sample_point_moments``; ``sphexample_amd.fields.linear_fit`` turns them into values and
+    gradients that are exact for a linear field however one-sided the support — sensors on a wall, on the bed, at the free surface)
+    and ``on_output`` receives the dict as its last argument, behind ``output_select`` (``None`` at the first call).  ``None``
+    (default): nothing is sampled and the callback keeps its arguments."""
     if SimMetaData.BMode.__name__ == "SimpleMDBC":
         LoadMDBCNormals(SimParticles, ParticleNormalsPath)                       # :827
     host_bytes = SimParticles.Position.dtype.itemsize
@@ -205,6 +211,7 @@ def RunSimulation(*, SimGeometry=None, SimMetaData: SimulationMetaData, SimConst
         (sample_point_gradients, cloud, None, None, lambda a: eng.sample_point_gradients(a)),
         (rays, dict, None, None, lambda a: eng.cast_rays(**a)),
         (output_select, lambda v: tuple(v) if isinstance(v, (tuple, list)) else (v,), None, lambda a: eng.select(*a), lambda a: eng.select(*a)),
+        (sample_point_moments, cloud, None, None, lambda a: eng.sample_point_moments(a)),
     )
     extras = []          # per output: what the callback receives behind the particles — a list of (first value, reader)
     for value, normal, enable, first, read in table:
