@@ -264,12 +264,24 @@ struct EngineBase {
     virtual void download_permutation(int64_t* prev_row) = 0;
     virtual void attach_columns(int32_t n_columns, const void* const* columns, const int32_t* row_bytes) = 0;
     virtual void download_columns_begin(void* const* columns_out) = 0;
-    virtual void sample_grid(const double* origin, const double* spacing, const int64_t* counts, double* weight, int64_t* count, double* pressure,
-                             double* density, double* velocity) = 0;
-    virtual void sample_points(int64_t n_points, const double* positions, double* weight, int64_t* count, double* pressure, double* density,
-                               double* velocity) = 0;
-    virtual void sample_point_gradients(int64_t n_points, const double* positions, const GradientOutputs& out) = 0;
-    virtual void sample_point_moments(int64_t n_points, const double* positions, const MomentOutputs& out) = 0;
+    // The on-demand samplers (lattice, cloud, gradients, moments).  One call of any of them, on every kind of handle: the state
+    // errors, then the argument errors — `check` returns the number of nodes — and nothing more for no node; `launch(n)` queues the
+    // kernels, the sums `out` needs are allocated behind it, `gather(G)` brings exactly those — complete on return — and `out`
+    // (MeanOutputs or RawOutputs, sphmi_series.h) delivers.  A handle supplies `ready`, `launch` and `gather`.
+    template <class Out, class Check, class Launch, class Gather>
+    void sample(const char* fn, bool ready, const Out& out, Check&& check, Launch&& launch, Gather&& gather) {
+        require_cell_list(fn, ready, "(no cell list, no half-step set)");
+        const int64_t n = check();
+        if (n == 0) return;
+        launch(n);
+        GridSums G(n, out);
+        gather(G);
+        out.deliver(G);
+    }
+    enum PcKind { PC_CLOUD = 0, PC_GRADIENTS, PC_MOMENTS, PC_KINDS };          // the samplers at arbitrary points (Engine::pc_sampler)
+    virtual void sample_grid(const double* origin, const double* spacing, const int64_t* counts, const MeanOutputs& out) = 0;
+    virtual void sample_points(int64_t n_points, const double* positions, const MeanOutputs& out) = 0;
+    virtual void sample_point_sums(PcKind kind, int64_t n_points, const double* positions, const RawOutputs& out) = 0;
     virtual void cast_rays(int64_t n_rays, const RayCall& c) = 0;
     virtual void particle_fields(int64_t* count, double* shepard, double* normal, double* div_r, double* div_v, double* vorticity) = 0;
     // The results a handle holds between calls (HeldResult, sphmi_results.h): the neighbour list (sphmi_neighbor_list.h), the free
@@ -2315,42 +2327,53 @@ struct Engine final : EngineBase {
         by_dims([&](auto d) { hipLaunchKernelGGL((k_field_grid<T, decltype(d)::value>), dim3((unsigned)nb), dim3(kFgThreads), 0, stream, A); });
         HC(hipGetLastError());
     }
-    // One raw sum of the lattice → host, behind the kernel.  No synchronisation of its own: sample_grid synchronises once before
-    // it forms the means, and the slab engines of a multi-device handle — whose `dst` that handle adds to as soon as this returns —
-    // never hold registered memory (MultiEngine::host_register registers nothing), so there the copy is the bounce buffer's,
-    // which is complete on return.
-    void fg_fetch(int f, double* dst, int64_t nodes) { fetch_result(dst, fg_arena.p + (size_t)f * (size_t)nodes, (size_t)nodes * 8); }
-    void sample_grid(const double* origin, const double* spacing, const int64_t* counts, double* weight, int64_t* count, double* pressure,
-                     double* density, double* velocity) override {
-        require_cell_list("sphmi_sample_grid", fg_ready(), "(no cell list, no half-step set)");
-        const int64_t nodes = check_grid_lattice(origin, spacing, counts, D);
-        fg_launch(origin, spacing, counts, nodes);
-        GridSums G(nodes, weight, count, pressure, density, velocity);
-        for (int f = 0; f < kFgValues; ++f) if (G.want[f]) fg_fetch(f, G.dst(f), nodes);
+    // One raw sum of a sampler's arena (the lattice's, a cloud's) → host, behind the kernel.  No synchronisation of its own:
+    // gather_sums synchronises once before the outputs are formed, and the slab engines of a multi-device handle — whose `dst` that
+    // handle adds to as soon as this returns — never hold registered memory (MultiEngine::host_register registers nothing), so
+    // there the copy is the bounce buffer's, which is complete on return.
+    void fetch_sum(const DeviceBuf<double>& arena, int f, double* dst, int64_t nodes) { fetch_result(dst, arena.p + (size_t)f * (size_t)nodes, (size_t)nodes * 8); }
+    // the tail of every sampler: the sums the outputs need, slot by slot, then the one synchronisation of the call; `clock` (may be
+    // null) gets a mark between the two
+    void gather_sums(const DeviceBuf<double>& arena, GridSums& G, PassClock* clock = nullptr) {
+        G.for_wanted([&](int f, double* dst) { fetch_sum(arena, f, dst, G.nodes); });
+        if (clock) clock->mark();
         HC(hipStreamSynchronize(stream));
-        G.deliver(count, pressure, density, velocity);
+    }
+    void sample_grid(const double* origin, const double* spacing, const int64_t* counts, const MeanOutputs& out) override {
+        sample("sphmi_sample_grid", fg_ready(), out, [&] { return check_grid_lattice(origin, spacing, counts, D); },
+               [&](int64_t nodes) { fg_launch(origin, spacing, counts, nodes); }, [&](GridSums& G) { gather_sums(fg_arena, G); });
     }
 
     // ---- kernel sums at arbitrary points, on demand (sphmi_point_cloud.h) -------------------------------------------------------------
     // Reads what the lattice reads; writes its own buffers and nothing else.  The positions, the plan (block of every point, counts,
     // offsets, tiles, index) and the arena grow with the call and go back to the device where fg_arena does.  The gradients
     // (sphmi_point_gradients.h) and the moments (sphmi_point_moments.h) share the positions and the plan and keep an arena of their
-    // own each, pg_arena and pm_arena.
-    DeviceBuf<double> pc_arena, pg_arena, pm_arena, pc_pos;
+    // own each: pc_arena[kind], so that a call of one kind never overwrites the sums of another.
+    // What tells the three apart — a new sampler over the same bin is one more PcKind, one more row here and one table of its
+    // outputs in sphmi_series.h: the C function (in messages), the sums per point, the kernel of <T, 2> and of <T, 3>.
+    struct PcSampler { const char* fn; int values; void (*kernel[2])(PointCloudArgs<T>); };
+    static const PcSampler& pc_sampler(PcKind kind) {
+        static const PcSampler rows[PC_KINDS] = {
+            {"sphmi_sample_points", kFgValues, {k_point_cloud<T, 2>, k_point_cloud<T, 3>}},
+            {"sphmi_sample_point_gradients", kPgValues, {k_point_gradients<T, 2>, k_point_gradients<T, 3>}},
+            {"sphmi_sample_point_moments", kPmValues, {k_point_moments<T, 2>, k_point_moments<T, 3>}}};
+        return rows[kind];
+    }
+    DeviceBuf<double> pc_arena[PC_KINDS], pc_pos;
     DeviceBuf<int> pc_block, pc_index, pc_count, pc_tcount;
     DeviceBuf<long long> pc_poff, pc_toff, pc_tsum;
     DeviceBuf<PcTile> pc_tiles;
     long long pc_ntiles = 0;                   // of the last launch
     void pc_free() {
-        pc_arena.free(); pg_arena.free(); pm_arena.free(); pc_pos.free(); pc_block.free(); pc_index.free(); pc_count.free(); pc_tcount.free();
+        for (auto& arena : pc_arena) arena.free();
+        pc_pos.free(); pc_block.free(); pc_index.free(); pc_count.free(); pc_tcount.free();
         pc_poff.free(); pc_toff.free(); pc_tsum.free(); pc_tiles.free();
     }
-    // upload the cloud, bin it and queue the kernel on the engine's stream (a multi-device handle calls it on every slab engine);
-    // n ≥ 1.  `clock` (may be null) gets a mark before the bin, behind it and behind the sampling kernel.  `what`: the same bin,
-    // then k_point_cloud into pc_arena, k_point_gradients into pg_arena or k_point_moments into pm_arena.
-    enum PcWhat { PC_CLOUD, PC_GRADIENTS, PC_MOMENTS };
-    void pc_launch(const double* positions, int64_t n, PassClock* clock = nullptr, PcWhat what = PC_CLOUD) {
-        const char* fn = what == PC_MOMENTS ? "sphmi_sample_point_moments" : what == PC_GRADIENTS ? "sphmi_sample_point_gradients" : "sphmi_sample_points";
+    // upload the cloud, bin it and queue the kernel of `kind` on the engine's stream (a multi-device handle calls it on every slab
+    // engine); n ≥ 1.  `clock` (may be null) gets a mark before the bin, behind it and behind the sampling kernel.
+    void pc_launch(PcKind kind, const double* positions, int64_t n, PassClock* clock = nullptr) {
+        const PcSampler& sampler = pc_sampler(kind);
+        const char* fn = sampler.fn;
         HC(hipSetDevice(cfg.device));
         const PcTiling G = pc_tiling(grid.gmin, grid.np, D, cfg.H_inv);
         const long long nblocks = pc_blocks(G);
@@ -2359,8 +2382,7 @@ struct Engine final : EngineBase {
         auto no_memory = [&](size_t bytes) {
             return text("%s: no device memory for the arena of %lld points (%zu bytes)", fn, (long long)n, bytes);
         };
-        DeviceBuf<double>& arena = what == PC_MOMENTS ? pm_arena : what == PC_GRADIENTS ? pg_arena : pc_arena;
-        arena.need((size_t)(what == PC_MOMENTS ? kPmValues : what == PC_GRADIENTS ? kPgValues : kFgValues) * np, no_memory);
+        pc_arena[kind].need((size_t)sampler.values * np, no_memory);
         pc_pos.need(np * (size_t)D, no_memory); pc_block.need(np, no_memory); pc_index.need(np, no_memory);
         pc_count.need(nb, no_memory); pc_tcount.need(nb, no_memory); pc_poff.need(nb + 1, no_memory); pc_toff.need(nb + 1, no_memory);
         bounce.h2d(pc_pos.p, positions, np * (size_t)D * 8, stream);
@@ -2384,70 +2406,29 @@ struct Engine final : EngineBase {
         PointCloudArgs<T> A{};
         A.pk0 = pk0[iA]; A.pk1 = pk1[iA]; A.half0 = pk0[iH]; A.comp = comp[cur];
         A.type = dd_slab ? type[cur] : nullptr; A.cstart = cstart; A.pos = pc_pos.p; A.tiles = pc_tiles.p; A.index = pc_index.p;
-        A.out = arena.p; A.g = grid; A.n_points = n;
+        A.out = pc_arena[kind].p; A.g = grid; A.n_points = n;
         fill_sample_consts(A);
         A.N = N; A.kernel = cfg.kernel;
-        by_dims([&](auto d) {
-            constexpr int Dd = decltype(d)::value;
-            if (what == PC_MOMENTS) hipLaunchKernelGGL((k_point_moments<T, Dd>), dim3((unsigned)pc_ntiles), dim3(kFgThreads), 0, stream, A);
-            else if (what == PC_GRADIENTS) hipLaunchKernelGGL((k_point_gradients<T, Dd>), dim3((unsigned)pc_ntiles), dim3(kFgThreads), 0, stream, A);
-            else hipLaunchKernelGGL((k_point_cloud<T, decltype(d)::value>), dim3((unsigned)pc_ntiles), dim3(kFgThreads), 0, stream, A);
-        });
+        hipLaunchKernelGGL(sampler.kernel[D == 3], dim3((unsigned)pc_ntiles), dim3(kFgThreads), 0, stream, A);
         HC(hipGetLastError());
         if (clock) clock->mark();
     }
-    // one raw sum of the cloud → host, behind the kernel (as fg_fetch)
-    void pc_fetch(int f, double* dst, int64_t n) { fetch_result(dst, pc_arena.p + (size_t)f * (size_t)n, (size_t)n * 8); }
-    void pg_fetch(int f, double* dst, int64_t n) { fetch_result(dst, pg_arena.p + (size_t)f * (size_t)n, (size_t)n * 8); }
-    void pm_fetch(int f, double* dst, int64_t n) { fetch_result(dst, pm_arena.p + (size_t)f * (size_t)n, (size_t)n * 8); }
-    void sample_points(int64_t n, const double* positions, double* weight, int64_t* count, double* pressure, double* density, double* velocity) override {
-        require_cell_list("sphmi_sample_points", fg_ready(), "(no cell list, no half-step set)");
-        check_sample_points(n, positions, D);
-        if (n == 0) return;
-        PassClock clock("SPHMI_POINTS_CLOCK", stream);                     // the device time of every pass → stderr (tools/sample_points_cost.py)
-        pc_launch(positions, n, &clock);
-        GridSums G(n, weight, count, pressure, density, velocity);
-        for (int f = 0; f < kFgValues; ++f) if (G.want[f]) pc_fetch(f, G.dst(f), n);
-        clock.mark();
-        HC(hipStreamSynchronize(stream));
-        clock.report(text("sphmi_sample_points: %lld points, %lld tiles, %.1f lanes filled of %d:", (long long)n, pc_ntiles, (double)n / (double)pc_ntiles, kPcTile),
-                     {"bin", "sample", "fetch"});
-        G.deliver(count, pressure, density, velocity);
+    // The cloud, its gradients and its moments: the same checks, the same bin, the means (MeanOutputs) or the raw sums as they are
+    // (RawOutputs).  $SPHMI_POINTS_CLOCK: the device time of every pass → stderr (tools/sample_points_cost.py,
+    // point_gradients_cost.py, point_moments_cost.py).
+    template <class Out> void pc_sample(PcKind kind, int64_t n, const double* positions, const Out& out) {
+        const char* fn = pc_sampler(kind).fn;
+        PassClock clock("SPHMI_POINTS_CLOCK", stream);
+        sample(fn, fg_ready(), out, [&] { check_sample_points(n, positions, D, fn); return n; },
+               [&](int64_t) { pc_launch(kind, positions, n, &clock); },
+               [&](GridSums& G) {
+                   gather_sums(pc_arena[kind], G, &clock);
+                   clock.report(text("%s: %lld points, %lld tiles, %.1f lanes filled of %d:", fn, (long long)n, pc_ntiles, (double)n / (double)pc_ntiles, kPcTile),
+                                {"bin", "sample", "fetch"});
+               });
     }
-    // … and their gradients (sphmi_point_gradients.h): the same checks, the same bin, the raw sums as they are
-    void sample_point_gradients(int64_t n, const double* positions, const GradientOutputs& out) override {
-        require_cell_list("sphmi_sample_point_gradients", fg_ready(), "(no cell list, no half-step set)");
-        check_sample_points(n, positions, D, "sphmi_sample_point_gradients");
-        if (n == 0) return;
-        PassClock clock("SPHMI_POINTS_CLOCK", stream);                     // (tools/point_gradients_cost.py)
-        pc_launch(positions, n, &clock, PC_GRADIENTS);
-        bool wanted[kPgValues];
-        out.wanted(wanted);
-        GridSums G(n, out.weight, wanted);
-        for (int f = 0; f < kPgValues; ++f) if (G.want[f]) pg_fetch(f, G.dst(f), n);
-        clock.mark();
-        HC(hipStreamSynchronize(stream));
-        clock.report(text("sphmi_sample_point_gradients: %lld points, %lld tiles, %.1f lanes filled of %d:", (long long)n, pc_ntiles, (double)n / (double)pc_ntiles, kPcTile),
-                     {"bin", "sample", "fetch"});
-        out.deliver(G);
-    }
-    // … and the moments of the weights (sphmi_point_moments.h): the same checks, the same bin, the raw sums as they are
-    void sample_point_moments(int64_t n, const double* positions, const MomentOutputs& out) override {
-        require_cell_list("sphmi_sample_point_moments", fg_ready(), "(no cell list, no half-step set)");
-        check_sample_points(n, positions, D, "sphmi_sample_point_moments");
-        if (n == 0) return;
-        PassClock clock("SPHMI_POINTS_CLOCK", stream);                     // (tools/point_moments_cost.py)
-        pc_launch(positions, n, &clock, PC_MOMENTS);
-        bool wanted[kPmValues];
-        out.wanted(wanted);
-        GridSums G(n, out.weight, wanted);
-        for (int f = 0; f < kPmValues; ++f) if (G.want[f]) pm_fetch(f, G.dst(f), n);
-        clock.mark();
-        HC(hipStreamSynchronize(stream));
-        clock.report(text("sphmi_sample_point_moments: %lld points, %lld tiles, %.1f lanes filled of %d:", (long long)n, pc_ntiles, (double)n / (double)pc_ntiles, kPcTile),
-                     {"bin", "sample", "fetch"});
-        out.deliver(G);
-    }
+    void sample_points(int64_t n, const double* positions, const MeanOutputs& out) override { pc_sample(PC_CLOUD, n, positions, out); }
+    void sample_point_sums(PcKind kind, int64_t n, const double* positions, const RawOutputs& out) override { pc_sample(kind, n, positions, out); }
 
     // ---- the first crossing of S = level along rays, on demand (sphmi_rays.h) ---------------------------------------------------------
     // Reads what the cloud reads; writes its own two buffers and nothing else.  ry_arena holds, in 8-byte words per ray, the inputs
@@ -3452,26 +3433,27 @@ static_assert(SPHMI_MAX_GRID_NODES == sphmi::kMaxGridNodes, "sphmi_series.h and 
 static_assert(7ll * SPHMI_MAX_GRID_NODES < (1ll << 31) && 12ll * SPHMI_MAX_GRID_NODES < (1ll << 31), "sphmi_isosurface_build: the vertices (at most 7 per node) and the elements (at most 12 per cell) fit int32 indices");
 int sphmi_sample_grid(sphmi_handle* h, const double* origin, const double* spacing, const int64_t* counts, double* weight_out, int64_t* count_out,
                       double* pressure_out, double* density_out, double* velocity_out) {
-    SPHMI_GUARD(h, h->e->sample_grid(origin, spacing, counts, weight_out, count_out, pressure_out, density_out, velocity_out));
+    SPHMI_GUARD(h, h->e->sample_grid(origin, spacing, counts, sphmi::MeanOutputs{weight_out, count_out, pressure_out, density_out, velocity_out}));
 }
 static_assert(SPHMI_MAX_SAMPLE_POINTS == sphmi::kMaxSamplePoints, "sphmi_series.h and sphmi.h disagree");
 int sphmi_sample_points(sphmi_handle* h, int64_t n_points, const double* positions, double* weight_out, int64_t* count_out, double* pressure_out,
                         double* density_out, double* velocity_out) {
-    SPHMI_GUARD(h, h->e->sample_points(n_points, positions, weight_out, count_out, pressure_out, density_out, velocity_out));
+    SPHMI_GUARD(h, h->e->sample_points(n_points, positions, sphmi::MeanOutputs{weight_out, count_out, pressure_out, density_out, velocity_out}));
 }
 int sphmi_sample_point_gradients(sphmi_handle* h, int64_t n_points, const double* positions, double* weight_out, int64_t* count_out,
                                  double* sum_pressure_out, double* sum_density_out, double* sum_velocity_out, double* grad_weight_out,
                                  double* grad_pressure_out, double* grad_density_out, double* grad_velocity_out) {
-    const sphmi::GradientOutputs out{weight_out, sum_pressure_out, sum_density_out, sum_velocity_out, grad_weight_out, grad_pressure_out,
-                                     grad_density_out, grad_velocity_out, count_out};
-    SPHMI_GUARD(h, h->e->sample_point_gradients(n_points, positions, out));
+    double* const outputs[] = {sum_pressure_out, sum_density_out, sum_velocity_out, grad_weight_out, grad_pressure_out, grad_density_out, grad_velocity_out};
+    const sphmi::RawOutputs out(sphmi::kPgOutputs, weight_out, count_out, outputs);
+    SPHMI_GUARD(h, h->e->sample_point_sums(sphmi::EngineBase::PC_GRADIENTS, n_points, positions, out));
 }
 int sphmi_sample_point_moments(sphmi_handle* h, int64_t n_points, const double* positions, double* weight_out, int64_t* count_out,
                                double* sum_pressure_out, double* sum_density_out, double* sum_velocity_out, double* moment1_out,
                                double* moment2_out, double* moment_pressure_out, double* moment_density_out, double* moment_velocity_out) {
-    const sphmi::MomentOutputs out{weight_out, sum_pressure_out, sum_density_out, sum_velocity_out, moment1_out, moment2_out,
-                                   moment_pressure_out, moment_density_out, moment_velocity_out, count_out};
-    SPHMI_GUARD(h, h->e->sample_point_moments(n_points, positions, out));
+    double* const outputs[] = {sum_pressure_out, sum_density_out, sum_velocity_out, moment1_out, moment2_out, moment_pressure_out, moment_density_out,
+                               moment_velocity_out};
+    const sphmi::RawOutputs out(sphmi::kPmOutputs, weight_out, count_out, outputs);
+    SPHMI_GUARD(h, h->e->sample_point_sums(sphmi::EngineBase::PC_MOMENTS, n_points, positions, out));
 }
 int sphmi_cast_rays(sphmi_handle* h, int64_t n_rays, const double* origins, const double* directions, const double* t_begin, const double* t_end,
                     double step, double level, int32_t mode, int32_t* status_out, int64_t* interval_out, double* bracket_out, double* point_out,

@@ -1757,107 +1757,65 @@ struct MultiEngine final : EngineBase {
     }
     // Kernel sums on a lattice (sphmi_field_grid.h): every slab samples the WHOLE lattice over the rows it owns — the type byte keeps
     // ghost copies out — the handle adds the raw sums in slab order, then normalises, as for the probes.
-    void sample_grid(const double* origin, const double* spacing, const int64_t* counts, double* weight, int64_t* count, double* pressure,
-                     double* density, double* velocity) override {
-        require_one_process("sphmi_sample_grid");
+    void sample_grid(const double* origin, const double* spacing, const int64_t* counts, const MeanOutputs& out) override {
+        sample("sphmi_sample_grid", any_slab_ready(), out, [&] { return check_grid_lattice(origin, spacing, counts, D); },
+               [&](int64_t nodes) { for (auto& r : R) if (r.e->fg_ready()) r.e->fg_launch(origin, spacing, counts, nodes); },       // all slabs at once, each on its device
+               [&](GridSums& G) { add_slab_sums(G, [](Engine<T>& e) -> const DeviceBuf<double>& { return e.fg_arena; }); });
+    }
+    bool any_slab_ready() const {
         bool any = false;
         for (auto& r : R) any = any || r.e->fg_ready();
-        require_cell_list("sphmi_sample_grid", any, "(no cell list, no half-step set)");
-        const int64_t nodes = check_grid_lattice(origin, spacing, counts, D);
-        for (auto& r : R) if (r.e->fg_ready()) r.e->fg_launch(origin, spacing, counts, nodes);        // all slabs at once, each on its device
-        GridSums G(nodes, weight, count, pressure, density, velocity);
-        add_slab_sums(G, [&](Engine<T>& e, int f, double* dst) { e.fg_fetch(f, dst, nodes); });
-        G.deliver(count, pressure, density, velocity);
+        return any;
     }
-    // the raw sums of a sampler the slabs have queued, added in slab order: fetch(engine, f, dst) brings sum f of one slab
-    template <class Fetch> void add_slab_sums(GridSums& G, Fetch&& fetch) {
+    // the raw sums of a sampler the slabs have queued, added in slab order: arena(engine) is where one slab holds them
+    template <class Arena> void add_slab_sums(GridSums& G, Arena&& arena) {
         std::vector<double> part;
         bool first = true;
         for (auto& r : R) {
             if (!r.e->fg_ready()) continue;                // (a slab that holds no rows has no cell list: it adds nothing)
             HC(hipSetDevice(r.device));
-            for (int f = 0; f < G.values; ++f) {
-                if (!G.want[f]) continue;
-                double* dst = G.dst(f);
-                if (first) { fetch(*r.e, f, dst); continue; }
+            G.for_wanted([&](int f, double* dst) {
+                if (first) { r.e->fetch_sum(arena(*r.e), f, dst, G.nodes); return; }
                 part.resize((size_t)G.nodes);
-                fetch(*r.e, f, part.data());
+                r.e->fetch_sum(arena(*r.e), f, part.data(), G.nodes);
                 for (int64_t k = 0; k < G.nodes; ++k) dst[k] += part[(size_t)k];
-            }
+            });
             HC(hipStreamSynchronize(r.e->stream));
             first = false;
         }
     }
     // Kernel sums at arbitrary points (sphmi_point_cloud.h): every slab bins the WHOLE cloud on its own cell grid and samples it over the
-    // rows it owns; the sums are added like the lattice's, entry p staying the caller's point p.
-    void sample_points(int64_t n, const double* positions, double* weight, int64_t* count, double* pressure, double* density, double* velocity) override {
-        require_one_process("sphmi_sample_points");
-        bool any = false;
-        for (auto& r : R) any = any || r.e->fg_ready();
-        require_cell_list("sphmi_sample_points", any, "(no cell list, no half-step set)");
-        check_sample_points(n, positions, D);
-        if (n == 0) return;
-        for (auto& r : R) if (r.e->fg_ready()) r.e->pc_launch(positions, n);
-        GridSums G(n, weight, count, pressure, density, velocity);
-        add_slab_sums(G, [&](Engine<T>& e, int f, double* dst) { e.pc_fetch(f, dst, n); });
-        G.deliver(count, pressure, density, velocity);
+    // rows it owns; the sums are added like the lattice's, entry p staying the caller's point p.  The gradients
+    // (sphmi_point_gradients.h) and the moments of the weights (sphmi_point_moments.h) are linear in the rows as well: the slabs' raw
+    // sums add up like the cloud's.
+    template <class Out> void pc_sample(PcKind kind, int64_t n, const double* positions, const Out& out) {
+        const char* fn = Engine<T>::pc_sampler(kind).fn;
+        sample(fn, any_slab_ready(), out, [&] { check_sample_points(n, positions, D, fn); return n; },
+               [&](int64_t) { for (auto& r : R) if (r.e->fg_ready()) r.e->pc_launch(kind, positions, n); },
+               [&](GridSums& G) { add_slab_sums(G, [&](Engine<T>& e) -> const DeviceBuf<double>& { return e.pc_arena[kind]; }); });
     }
-    // … and their gradients (sphmi_point_gradients.h): every sum is linear in the rows, so the slabs' raw sums add up like the cloud's
-    void sample_point_gradients(int64_t n, const double* positions, const GradientOutputs& out) override {
-        require_one_process("sphmi_sample_point_gradients");
-        bool any = false;
-        for (auto& r : R) any = any || r.e->fg_ready();
-        require_cell_list("sphmi_sample_point_gradients", any, "(no cell list, no half-step set)");
-        check_sample_points(n, positions, D, "sphmi_sample_point_gradients");
-        if (n == 0) return;
-        for (auto& r : R) if (r.e->fg_ready()) r.e->pc_launch(positions, n, nullptr, Engine<T>::PC_GRADIENTS);
-        bool wanted[kPgValues];
-        out.wanted(wanted);
-        GridSums G(n, out.weight, wanted);
-        add_slab_sums(G, [&](Engine<T>& e, int f, double* dst) { e.pg_fetch(f, dst, n); });
-        out.deliver(G);
+    void sample_points(int64_t n, const double* positions, const MeanOutputs& out) override { pc_sample(PC_CLOUD, n, positions, out); }
+    void sample_point_sums(PcKind kind, int64_t n, const double* positions, const RawOutputs& out) override { pc_sample(kind, n, positions, out); }
+    // What only a handle of one device serves, and why: in rank mode for want of the rows, else for `reason`.
+    [[noreturn]] void single_device_only(const char* fn, const char* reason) const {
+        if (rank_mode) throw EngineError(SPHMI_ERR_STATE, std::string(fn) + ": single-device handles only (a rank-mode process holds one slab of the rows)");
+        throw EngineError(SPHMI_ERR_STATE, std::string(fn) + ": single-device handles only (" + reason + ")");
     }
-    // … and the moments of the weights (sphmi_point_moments.h): linear in the rows as well, added in slab order
-    void sample_point_moments(int64_t n, const double* positions, const MomentOutputs& out) override {
-        require_one_process("sphmi_sample_point_moments");
-        bool any = false;
-        for (auto& r : R) any = any || r.e->fg_ready();
-        require_cell_list("sphmi_sample_point_moments", any, "(no cell list, no half-step set)");
-        check_sample_points(n, positions, D, "sphmi_sample_point_moments");
-        if (n == 0) return;
-        for (auto& r : R) if (r.e->fg_ready()) r.e->pc_launch(positions, n, nullptr, Engine<T>::PC_MOMENTS);
-        bool wanted[kPmValues];
-        out.wanted(wanted);
-        GridSums G(n, out.weight, wanted);
-        add_slab_sums(G, [&](Engine<T>& e, int f, double* dst) { e.pm_fetch(f, dst, n); });
-        out.deliver(G);
-    }
-    // The first crossing along rays (sphmi_rays.h): single-device handles only.  Whether a march point is inside is decided by the slabs'
-    // COMBINED S at that point, at every evaluation of the search — a sum over slabs inside the march, which is not built.
+    // The first crossing along rays (sphmi_rays.h): whether a march point is inside is decided by the slabs' COMBINED S at that point,
+    // at every evaluation of the search — a sum over slabs inside the march, which is not built.
     void cast_rays(int64_t, const RayCall&) override {
-        if (rank_mode) throw EngineError(SPHMI_ERR_STATE, "sphmi_cast_rays: single-device handles only (a rank-mode process holds one slab of the rows)");
-        throw EngineError(SPHMI_ERR_STATE, "sphmi_cast_rays: single-device handles only (a crossing needs the slabs' combined S at every evaluation of the search, which is not built)");
+        single_device_only("sphmi_cast_rays", "a crossing needs the slabs' combined S at every evaluation of the search, which is not built");
     }
-    // Differential fields at the particles (sphmi_particle_fields.h): single-device handles only.  After the corrector a slab's ghost
-    // copies hold the half-step state, so a slab cannot see its neighbours' current rows without a halo exchange of its own.
-    void particle_fields(int64_t*, double*, double*, double*, double*, double*) override {
-        if (rank_mode) throw EngineError(SPHMI_ERR_STATE, "sphmi_particle_fields: single-device handles only (a rank-mode process holds one slab of the rows)");
-        throw EngineError(SPHMI_ERR_STATE, "sphmi_particle_fields: single-device handles only (a slab's ghost copies hold the half-step state; the halo exchange this needs is not built)");
-    }
-    // The neighbour list (sphmi_neighbor_list.h): single-device handles only, for the same reason.
-    void neighbors_build(int32_t, int64_t*, int64_t*) override {
-        if (rank_mode) throw EngineError(SPHMI_ERR_STATE, "sphmi_neighbors_build: single-device handles only (a rank-mode process holds one slab of the rows)");
-        throw EngineError(SPHMI_ERR_STATE, "sphmi_neighbors_build: single-device handles only (a slab's ghost copies hold the half-step state; the halo exchange this needs is not built)");
-    }
-    // The connected bodies (sphmi_components.h): single-device handles only, as for the neighbour list.
-    void components_build(double, uint32_t, int64_t*, int64_t*) override {
-        if (rank_mode) throw EngineError(SPHMI_ERR_STATE, "sphmi_components_build: single-device handles only (a rank-mode process holds one slab of the rows)");
-        throw EngineError(SPHMI_ERR_STATE, "sphmi_components_build: single-device handles only (a slab's ghost copies hold the half-step state; the halo exchange this needs is not built)");
-    }
-    // The free surface as a mesh (sphmi_isosurface.h): single-device handles only — a multi-device handle adds the slabs' sums on the host.
+    // Differential fields at the particles (sphmi_particle_fields.h), the neighbour list (sphmi_neighbor_list.h) and the connected
+    // bodies (sphmi_components.h): after the corrector a slab's ghost copies hold the half-step state, so a slab cannot see its
+    // neighbours' current rows without a halo exchange of its own.
+    static constexpr const char* kNoHalo = "a slab's ghost copies hold the half-step state; the halo exchange this needs is not built";
+    void particle_fields(int64_t*, double*, double*, double*, double*, double*) override { single_device_only("sphmi_particle_fields", kNoHalo); }
+    void neighbors_build(int32_t, int64_t*, int64_t*) override { single_device_only("sphmi_neighbors_build", kNoHalo); }
+    void components_build(double, uint32_t, int64_t*, int64_t*) override { single_device_only("sphmi_components_build", kNoHalo); }
+    // The free surface as a mesh (sphmi_isosurface.h): a multi-device handle adds the slabs' sums on the host.
     void isosurface_build(const double*, const double*, const int64_t*, double, int64_t*, int64_t*) override {
-        if (rank_mode) throw EngineError(SPHMI_ERR_STATE, "sphmi_isosurface_build: single-device handles only (a rank-mode process holds one slab of the rows)");
-        throw EngineError(SPHMI_ERR_STATE, "sphmi_isosurface_build: single-device handles only (a multi-device handle adds the slabs' lattice sums on the host: no device holds S)");
+        single_device_only("sphmi_isosurface_build", "a multi-device handle adds the slabs' lattice sums on the host: no device holds S");
     }
     void download_columns_begin(void* const* columns_out) override {
         require_one_process("sphmi_download_columns");

@@ -23,7 +23,8 @@
 //
 // Results go to the arena at the CALLER's index: kPgValues arrays of n_points doubles — slots 0 … 6 are k_point_cloud's
 // { S, SP, Sρ, Sv[0..2], n }, then G[0..2], GP[0..2], Gρ[0..2] and Gv[a][b] at 16 + 3a + b.  2-D handles write exact zeros to
-// every z slot (Sv[2], G[2], GP[2], Gρ[2], Gv[2][·], Gv[·][2]).
+// every z slot (Sv[2], G[2], GP[2], Gρ[2], Gv[2][·], Gv[·][2]).  The host reads this layout from ONE table, kPgOutputs
+// (sphmi_series.h): which slots an output needs and where they go; the stores at the end of the kernel assert the slots they fill.
 //
 // Budget, read off the code object by tests/test_point_gradients_host.py: the LDS is k_point_cloud's (38 928 B: four workgroups per
 // compute unit); in 3-D a lane carries 24 fp64 sums and the row count, and the kernel takes 128 (fp64 records) / 126 (fp32) of the
@@ -225,6 +226,8 @@ __global__ void __launch_bounds__(kFgThreads, 4) k_point_gradients(const PointCl
         const long long M = A.n_points;
         o[0] = S; o[M] = SP; o[2 * M] = Sr; o[3 * M] = Sx; o[4 * M] = Sy; o[5 * M] = D == 3 ? Sz : 0.0;
         o[6 * M] = (double)n;
+        // the slots below are the entries grad_weight, grad_pressure, grad_density and grad_velocity of kPgOutputs
+        static_assert(kPgOutputs[3].first == 7 && kPgOutputs[4].first == 10 && kPgOutputs[5].first == 13 && kPgOutputs[6].first == 16, "the stores of k_point_gradients fill the slots of kPgOutputs");
 #pragma unroll
         for (int b = 0; b < 3; ++b) {
             const bool z = b >= D;                           // a slot of the third axis on a 2-D handle: an exact zero

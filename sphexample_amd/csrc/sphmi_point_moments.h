@@ -28,7 +28,8 @@
 //
 // Results go to the arena at the CALLER's index: kPmValues arrays of n_points doubles — slots 0 … 6 are k_point_cloud's
 // { S, SP, Sρ, Sv[0..2], n }, then M1 at 7, M2 at 10, P1 at 16, R1 at 19 and V1[a][b] at 22 + 3a + b.  2-D handles write exact zeros
-// to every slot of the third axis.
+// to every slot of the third axis.  The host reads this layout from ONE table, kPmOutputs (sphmi_series.h): which slots an output
+// needs and where they go; the stores at the end of the kernel assert the slots they fill.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -221,6 +222,9 @@ __global__ void __launch_bounds__(kFgThreads, 2) k_point_moments(const PointClou
         const long long M = A.n_points;
         o[0] = S; o[M] = SP; o[2 * M] = Sr; o[3 * M] = Sx; o[4 * M] = Sy; o[5 * M] = D == 3 ? Sz : 0.0;
         o[6 * M] = (double)n;
+        // the slots below are the entries moment1, moment2, moment_pressure, moment_density and moment_velocity of kPmOutputs
+        static_assert(kPmOutputs[3].first == 7 && kPmOutputs[4].first == 10 && kPmOutputs[5].first == 16 && kPmOutputs[6].first == 19 && kPmOutputs[7].first == 22,
+                      "the stores of k_point_moments fill the slots of kPmOutputs");
         // (xx, xy, xz, yy, yz, zz: the entries with a z index are 2, 4 and 5)
         o[10 * M] = M2[0]; o[11 * M] = M2[1]; o[12 * M] = D == 3 ? M2[2] : 0.0;
         o[13 * M] = M2[3]; o[14 * M] = D == 3 ? M2[4] : 0.0; o[15 * M] = D == 3 ? M2[5] : 0.0;

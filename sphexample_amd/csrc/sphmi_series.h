@@ -1,6 +1,8 @@
 // sphmi_series.h — the host side the observers share (group forces, probes, budgets, flow, envelopes, maps, tracers, lattice, columns): the error type, the limits and
 // record-layout constants host and device agree on, the argument checks every kind of handle reports alike, the per-step series
-// and the means of the kernel sums.  Plain C++17, no HIP: tests/host_series/series_main.cpp compiles it alone.
+// and the means of the kernel sums; the slot tables of the samplers that deliver raw sums (kPgOutputs, kPmOutputs: the one statement
+// of their layouts on the host) and the sums of one sampler call (GridSums).  Plain C++17, no HIP: tests/host_series/series_main.cpp
+// compiles it alone.
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -303,11 +305,62 @@ inline void deliver_map_vectors(int64_t bins, const double* c0, const double* c1
     if (out) for (int64_t b = 0; b < bins; ++b) { out[3 * b] = c0[b]; out[3 * b + 1] = c1[b]; out[3 * b + 2] = c2[b]; }
 }
 
+// The samplers that hand their kernel sums out RAW state their layout HERE and nowhere else on the host: one { first slot, width }
+// per caller-visible output, in the order of the C prototype.  Slot 0 (S → weight_out) and slot 6 (n → count_out, as an integer)
+// are not in a table: every sampler has them.  The store statements of k_point_gradients and k_point_moments fill these slots.
+struct OutputSlots { int first, width; };
+constexpr OutputSlots kPgOutputs[] = {{1, 1}, {2, 1}, {3, 3},          // sum_pressure, sum_density, sum_velocity: the cloud's
+                                      {7, 3}, {10, 3}, {13, 3}, {16, 9}}; // grad_weight, grad_pressure, grad_density, grad_velocity
+constexpr OutputSlots kPmOutputs[] = {{1, 1}, {2, 1}, {3, 3},          // sum_pressure, sum_density, sum_velocity: the cloud's
+                                      {7, 3}, {10, 6},                  // moment1, moment2
+                                      {16, 3}, {19, 3}, {22, 9}};       // moment_pressure, moment_density, moment_velocity
+constexpr int kRawOutputsMax = 8;
+// a table tiles [1, values) in order, without gap or overlap, around slot 6
+template <int N> constexpr bool outputs_tile(const OutputSlots (&t)[N], int values) {
+    int at = 1;
+    for (int i = 0; i < N; ++i) {
+        if (at == 6) at = 7;
+        if (t[i].first != at || t[i].width < 1 || (at < 6 && at + t[i].width > 6)) return false;
+        at += t[i].width;
+    }
+    return at == values;
+}
+static_assert(outputs_tile(kPgOutputs, kPgValues), "the outputs of sphmi_sample_point_gradients tile the slots of k_point_gradients");
+static_assert(outputs_tile(kPmOutputs, kPmValues), "the outputs of sphmi_sample_point_moments tile the slots of k_point_moments");
+
+struct GridSums;
+// the caller's pointers of one such call, out[] in table order (any may be null)
+struct RawOutputs {
+    const OutputSlots* table;
+    int entries, values;
+    double* weight;
+    int64_t* count;
+    double* out[kRawOutputsMax];
+    template <int N> RawOutputs(const OutputSlots (&t)[N], double* weight_out, int64_t* count_out, double* const (&outputs)[N])
+        : table(t), entries(N), values(t[N - 1].first + t[N - 1].width), weight(weight_out), count(count_out), out{} {
+        static_assert(N <= kRawOutputsMax, "RawOutputs holds at most kRawOutputsMax pointers");
+        for (int i = 0; i < N; ++i) out[i] = outputs[i];
+    }
+    // the slots of `values` the outputs need → w[values]
+    void wanted(bool* w) const {
+        w[0] = weight != nullptr; w[6] = count != nullptr;
+        for (int i = 0; i < entries; ++i)
+            for (int c = 0; c < table[i].width; ++c) w[table[i].first + c] = out[i] != nullptr;
+    }
+    inline void deliver(const GridSums& G) const;
+};
+// … and the five outputs of the lattice and the cloud, which GridSums turns into means: constructed from and delivered like
+// RawOutputs, so that one call path serves both kinds (EngineBase::sample)
+struct MeanOutputs {
+    double* weight; int64_t* count; double *pressure, *density, *velocity;
+    inline void deliver(const GridSums& G) const;
+};
+
 // The host side of sphmi_sample_grid and sphmi_sample_points: the raw sums { S, SP, Sρ, Sv[3], n } of the lattice
 // (sphmi_field_grid.h) or the cloud (sphmi_point_cloud.h), `nodes` of either, the ones the requested outputs need.  S lands in weight_out itself when that is asked for; the means are formed here, 0 where n == 0.
-// sphmi_sample_point_gradients (sphmi_point_gradients.h) carries `values` = kPgValues sums per point in the same arrays — the
-// first seven are the cloud's — and hands them out RAW (the second constructor, deliver_raw): a multi-device handle adds both kinds
-// with one loop.  sphmi_sample_point_moments (sphmi_point_moments.h) does the same with kPmValues sums.
+// sphmi_sample_point_gradients (sphmi_point_gradients.h) and sphmi_sample_point_moments (sphmi_point_moments.h) carry `values` =
+// kPgValues / kPmValues sums per point in the same arrays — the first seven are the cloud's — and hand them out RAW (the second
+// constructor, RawOutputs::deliver): a multi-device handle adds both kinds with one loop.
 struct GridSums {
     int64_t nodes = 0;
     int values = kFgValues;                    // sums per node
@@ -322,6 +375,7 @@ struct GridSums {
         for (int f = 0; f < kFgValues; ++f) if (want[f] && !(f == 0 && weight)) s[f].assign((size_t)n, 0.0);
         S = weight ? weight : s[0].data();
     }
+    GridSums(int64_t n, const MeanOutputs& o) : GridSums(n, o.weight, o.count, o.pressure, o.density, o.velocity) {}
     void deliver(int64_t* count, double* pressure, double* density, double* velocity) const {
         const double* n = s[6].data();
         for (int64_t k = 0; k < nodes; ++k) {
@@ -333,64 +387,31 @@ struct GridSums {
             if (velocity) for (int d = 0; d < 3; ++d) velocity[3 * k + d] = kernel_mean(s[3 + d][k], S[k], some);
         }
     }
-    // the raw sums of the gradients (V = kPgValues) or the moments (kPmValues): slot f is wanted where wanted[f]; S goes straight into weight_out
-    template <int V> GridSums(int64_t n, double* weight, const bool (&wanted)[V]) : nodes(n), values(V) {
-        static_assert(V <= kSampleValuesMax, "GridSums holds at most kSampleValuesMax sums per node");
-        for (int f = 0; f < V; ++f) {
-            want[f] = wanted[f];
-            if (want[f] && !(f == 0 && weight)) s[f].assign((size_t)n, 0.0);
-        }
-        S = weight ? weight : s[0].data();
+    // the raw sums of the gradients or the moments: the slots the outputs' table asks for; S goes straight into weight_out
+    GridSums(int64_t n, const RawOutputs& out) : nodes(n), values(out.values) {
+        out.wanted(want);
+        for (int f = 0; f < values; ++f) if (want[f] && !(f == 0 && out.weight)) s[f].assign((size_t)n, 0.0);
+        S = out.weight ? out.weight : s[0].data();
     }
-    // slots [first, first + width) → out [nodes × width], as they are; out may be null
-    void deliver_raw(int first, int width, double* out) const {
-        if (!out) return;
+    // the wanted sums in slot order: f(slot, where it goes)
+    template <class F> void for_wanted(F&& f) {
+        for (int k = 0; k < values; ++k) if (want[k]) f(k, dst(k));
+    }
+};
+static_assert(kPgValues <= kSampleValuesMax && kPmValues <= kSampleValuesMax, "GridSums holds at most kSampleValuesMax sums per node");
+
+// n → count_out as an integer; the slots of every other output → [nodes × width], as they are
+inline void RawOutputs::deliver(const GridSums& G) const {
+    if (count) for (int64_t k = 0; k < G.nodes; ++k) count[k] = (int64_t)G.s[6][k];
+    for (int i = 0; i < entries; ++i) {
+        if (!out[i]) continue;
+        const int width = table[i].width;
         for (int c = 0; c < width; ++c) {
-            const double* v = s[first + c].data();
-            for (int64_t k = 0; k < nodes; ++k) out[(size_t)width * k + c] = v[k];
+            const double* v = G.s[table[i].first + c].data();
+            for (int64_t k = 0; k < G.nodes; ++k) out[i][(size_t)width * k + c] = v[k];
         }
     }
-    void deliver_count(int64_t* count) const {
-        if (count) for (int64_t k = 0; k < nodes; ++k) count[k] = (int64_t)s[6][k];
-    }
-};
-
-// sphmi_sample_point_gradients: the slots of kPgValues the caller's outputs need (any may be null)
-struct GradientOutputs {
-    double *weight, *sum_pressure, *sum_density, *sum_velocity, *grad_weight, *grad_pressure, *grad_density, *grad_velocity;
-    int64_t* count;
-    void wanted(bool (&w)[kPgValues]) const {
-        for (int f = 0; f < kPgValues; ++f) w[f] = false;
-        w[0] = weight != nullptr; w[1] = sum_pressure != nullptr; w[2] = sum_density != nullptr;
-        w[3] = w[4] = w[5] = sum_velocity != nullptr; w[6] = count != nullptr;
-        for (int b = 0; b < 3; ++b) { w[7 + b] = grad_weight != nullptr; w[10 + b] = grad_pressure != nullptr; w[13 + b] = grad_density != nullptr; }
-        for (int c = 0; c < 9; ++c) w[16 + c] = grad_velocity != nullptr;
-    }
-    void deliver(const GridSums& G) const {
-        G.deliver_count(count);
-        G.deliver_raw(1, 1, sum_pressure); G.deliver_raw(2, 1, sum_density); G.deliver_raw(3, 3, sum_velocity);
-        G.deliver_raw(7, 3, grad_weight); G.deliver_raw(10, 3, grad_pressure); G.deliver_raw(13, 3, grad_density); G.deliver_raw(16, 9, grad_velocity);
-    }
-};
-
-// sphmi_sample_point_moments: the slots of kPmValues the caller's outputs need (any may be null)
-struct MomentOutputs {
-    double *weight, *sum_pressure, *sum_density, *sum_velocity, *moment1, *moment2, *moment_pressure, *moment_density, *moment_velocity;
-    int64_t* count;
-    void wanted(bool (&w)[kPmValues]) const {
-        for (int f = 0; f < kPmValues; ++f) w[f] = false;
-        w[0] = weight != nullptr; w[1] = sum_pressure != nullptr; w[2] = sum_density != nullptr;
-        w[3] = w[4] = w[5] = sum_velocity != nullptr; w[6] = count != nullptr;
-        for (int b = 0; b < 3; ++b) { w[7 + b] = moment1 != nullptr; w[16 + b] = moment_pressure != nullptr; w[19 + b] = moment_density != nullptr; }
-        for (int c = 0; c < 6; ++c) w[10 + c] = moment2 != nullptr;
-        for (int c = 0; c < 9; ++c) w[22 + c] = moment_velocity != nullptr;
-    }
-    void deliver(const GridSums& G) const {
-        G.deliver_count(count);
-        G.deliver_raw(1, 1, sum_pressure); G.deliver_raw(2, 1, sum_density); G.deliver_raw(3, 3, sum_velocity);
-        G.deliver_raw(7, 3, moment1); G.deliver_raw(10, 6, moment2); G.deliver_raw(16, 3, moment_pressure); G.deliver_raw(19, 3, moment_density);
-        G.deliver_raw(22, 9, moment_velocity);
-    }
-};
+}
+inline void MeanOutputs::deliver(const GridSums& G) const { G.deliver(count, pressure, density, velocity); }
 
 }  // namespace sphmi

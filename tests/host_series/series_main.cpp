@@ -207,7 +207,56 @@ static void test_probe_means() {
     for (int d = 0; d < 3; ++d) CHECK(gv[d] == vel[(size_t)d] && gv[3 + d] == 0.0);
 }
 
+// The raw outputs of the gradients and the moments (RawOutputs over its table, through GridSums): for EVERY subset of the outputs
+// of a 3-point call, exactly the slots of the requested outputs are wanted, slot f filled with 100·f + k arrives as entry (k, c) =
+// 100·(first + c) + k of the output that holds it, count is the integer of slot 6, weight is slot 0 written in place, and a NULL
+// output receives nothing — wanted() and deliver() read one table, and this is the check that they agree.  The arrays have exactly
+// the size a caller gives them (the sanitizer sees a write past them).
+template <int N> static void test_raw_outputs(const OutputSlots (&table)[N], int values) {
+    const int64_t n = 3;
+    CHECK(values <= kSampleValuesMax && N <= kRawOutputsMax);
+    for (unsigned subset = 0; subset < (1u << (N + 2)); ++subset) {           // bit 0: weight, bit 1: count, bit 2 + i: output i
+        std::vector<double> weight((size_t)n, -1.0);
+        std::vector<int64_t> count((size_t)n, -1);
+        std::vector<double> arrays[N];
+        double* ptr[N];
+        bool expect[kSampleValuesMax] = {};
+        expect[0] = subset & 1u; expect[6] = (subset >> 1) & 1u;
+        for (int i = 0; i < N; ++i) {
+            const bool on = (subset >> (2 + i)) & 1u;
+            arrays[i].assign((size_t)n * table[i].width, -1.0);
+            ptr[i] = on ? arrays[i].data() : nullptr;
+            for (int c = 0; c < table[i].width; ++c) expect[table[i].first + c] = on;
+        }
+        const RawOutputs out(table, (subset & 1u) ? weight.data() : nullptr, (subset & 2u) ? count.data() : nullptr, ptr);
+        CHECK(out.values == values && out.entries == N);
+        GridSums G(n, out);
+        CHECK(G.nodes == n && G.values == values);
+        for (int f = 0; f < kSampleValuesMax; ++f) CHECK(G.want[f] == expect[f]);
+        CHECK((subset & 1u) ? G.dst(0) == weight.data() : true);
+        for (int f = 0; f < values; ++f) {
+            if (!G.want[f]) { CHECK(f == 0 || G.s[f].empty()); continue; }   // no host allocation for a slot nobody asked for
+            for (int64_t k = 0; k < n; ++k) G.dst(f)[k] = 100.0 * f + (double)k;
+        }
+        int visited = 0;
+        G.for_wanted([&](int f, double* dst) { CHECK(expect[f] && dst == G.dst(f)); visited += 1; });
+        int expected = 0;
+        for (int f = 0; f < values; ++f) expected += expect[f];
+        CHECK(visited == expected);
+        out.deliver(G);
+        for (int64_t k = 0; k < n; ++k) {
+            CHECK(weight[(size_t)k] == ((subset & 1u) ? (double)k : -1.0));
+            CHECK(count[(size_t)k] == ((subset & 2u) ? 600 + k : -1));
+            for (int i = 0; i < N; ++i)
+                for (int c = 0; c < table[i].width; ++c)
+                    CHECK(arrays[i][(size_t)(table[i].width * k + c)] == (ptr[i] ? 100.0 * (table[i].first + c) + (double)k : -1.0));
+        }
+    }
+}
+
 int main() {
+    test_raw_outputs(kPgOutputs, kPgValues);                   // 2⁹ subsets
+    test_raw_outputs(kPmOutputs, kPmValues);                   // 2¹⁰ subsets
     test_ring();
     test_partial_read_and_dropped();
     test_argument_errors();
