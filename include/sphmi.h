@@ -966,6 +966,46 @@ int sphmi_select_download(sphmi_handle* h, void* position, void* velocity, void*
 int sphmi_select_download_columns(sphmi_handle* h, void* const* columns_out);
 int sphmi_select_release(sphmi_handle* h);
 
+/*
+ * The MOMENT sums at fixed PROBE points at STEP resolution, recorded on the device: the sums of sphmi_sample_point_moments behind every
+ * executed step, as sphmi_probes_enable records its Shepard sums - a pressure sensor on a wall or on the bed whose signal is FITTED at
+ * the sensor (sphexample_amd/fields.py: linear_fit; sphexample_amd/probes.py: fit_series over a whole series), exact for a linear field
+ * however one-sided the support, without stopping sphmi_advance for an on-demand call per step (csrc/sphmi_probe_moments.h).
+ * An observer of its own with its own point set: independent of sphmi_probes_enable, both may be on together, with each other and with
+ * every other observer.  The contract is that of sphmi_probes_enable / sphmi_probes_read wherever it applies:
+ *   enable: after sphmi_upload / sphmi_generate_dam_break_3d, at any later time too.  1 <= n_probes <= SPHMI_MAX_PROBES finite points,
+ *     positions[n_probes x dims]; a probe in empty space or outside the particles' bounding grid is legal and yields zeros.  The handle
+ *     keeps the newest capacity_steps (>= 1) samples that have not been read.  A second call replaces the set and drops the series;
+ *     n_probes = 0 disables.  sphmi_upload and the generator disable.  No step waits for the host: the records of a batch of queued
+ *     steps come back with the control block the host fetches anyway.  sphmi_forces_once records nothing.  Off by default; a handle that
+ *     never enables it launches what it always did.
+ *   Per executed step and probe p at x_p, over the Fluid rows j the handle owns with r^2 = ((dx^2 + dy^2) + dz^2) <= H^2 (inclusive, not
+ *     fused) on the state sphmi_download would deliver directly after that step, w_j = (m0 / rho_j) W(r), e_j = x_j - x_p, all in fp64,
+ *     no self term: n, S, SP, Srho, Sv[3], M1[3], M2[6] (xx, xy, xz, yy, yz, zz), P1[3], R1[3], V1[3][3] as sphmi_sample_point_moments
+ *     defines them.  The sums cover EVERY Fluid row within H on the current positions, however long ago the cell list was rebuilt.
+ *     n, S, SP, Srho and Sv equal the raw sums behind sphmi_probes_read at the same point and step, bit for bit; the order of summation
+ *     depends on the particle order alone, and repeated runs give the same bits.  It differs from that of sphmi_sample_point_moments:
+ *     the two agree to rounding (1e-10 of a sum's largest magnitude on fp64 handles), not to the bit.
+ *   read: delivers and clears the oldest `capacity` samples recorded since the last read, oldest first: iteration_out / time_out / dt_out
+ *     [capacity] as sphmi_probes_read; every other output is [capacity x n_probes x width] with the widths and meanings of
+ *     sphmi_sample_point_moments (weight_out 1, count_out 1, sum_pressure_out 1, sum_density_out 1, sum_velocity_out 3, moment1_out 3,
+ *     moment2_out 6, moment_pressure_out 3, moment_density_out 3, moment_velocity_out 3 x 3), RAW - nothing is divided by S.  2-D handles
+ *     write exact zeros to every slot of the third axis.  Any output pointer may be NULL.  *n_out, *n_dropped, capacity = 0: as
+ *     sphmi_group_forces_read.
+ *   SPHMI_ERR_STATE: before the upload; read while disabled; rank-mode handles (a process holds one slab of the rows); handles with H < h.
+ *   SPHMI_ERR_ARGUMENT: null table, n_probes out of range, a non-finite coordinate, capacity_steps < 1, null n_out.
+ * A record is 3 + 31 n_probes doubles: 254 KB at 1024 probes, and the log of a batch of 32 steps 8 MB on the device and as much in
+ * page-locked host memory.  Multi-device handles of one process: every sum is linear in the rows, so every slab sums the rows it owns
+ * for every probe (ghost copies do not count) and the handle adds the slabs' records in slab order.
+ */
+int sphmi_probe_moments_enable(sphmi_handle* h, int32_t n_probes, const double* positions /* n_probes x dims */, int64_t capacity_steps);
+int sphmi_probe_moments_read(sphmi_handle* h, int64_t capacity, int64_t* iteration_out, double* time_out, double* dt_out,
+                             double* weight_out, int64_t* count_out,
+                             double* sum_pressure_out, double* sum_density_out, double* sum_velocity_out,
+                             double* moment1_out, double* moment2_out,
+                             double* moment_pressure_out, double* moment_density_out, double* moment_velocity_out,
+                             int64_t* n_out, int64_t* n_dropped);
+
 #ifdef __cplusplus
 }
 #endif

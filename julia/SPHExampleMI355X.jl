@@ -28,6 +28,9 @@
 # device — sphmi_group_forces_enable — and collect the series of a run in SPHExampleMI355X.GROUP_FORCES[SimParticles]).
 # SPHMI_PROBES (unset by default; "x,y,z;x,y,z" = sample pressure, density and velocity at these fixed points at every step on the
 # device — sphmi_probes_enable, `dims` coordinates per point — and collect the series in SPHExampleMI355X.PROBES[SimParticles]).
+# SPHMI_PROBE_MOMENTS (unset by default; "x,y,z;x,y,z", the syntax of SPHMI_PROBES = record the raw kernel sums and their first and second
+# moments at these fixed points at every step on the device — sphmi_probe_moments_enable, what a linear fit AT a sensor on a wall needs —
+# and collect the series in SPHExampleMI355X.PROBE_MOMENTS[SimParticles]).
 # SPHMI_BUDGETS (unset by default; "1" = record the energy, momentum and extent budgets of the fluid at every step on the device —
 # sphmi_budgets_enable — and collect the series in SPHExampleMI355X.BUDGETS[SimParticles]).
 # SPHMI_FLOW_BOXES (unset by default; "lo,lo,lo:hi,hi,hi;…" = record the flow through these half-open control boxes, `dims` bounds on
@@ -121,9 +124,9 @@ mutable struct ProbeSeries
     dropped::Int64
 end
 const PROBES = IdDict{Any,ProbeSeries}()
-function probe_positions(D)
-    pts = [parse.(Float64, strip.(split(p, ","))) for p in split(get(ENV, "SPHMI_PROBES", ""), ";") if !isempty(strip(p))]
-    all(p -> length(p) == D, pts) || error("SPHMI_PROBES: every point needs $D coordinates (\"x,y;x,y\" / \"x,y,z;x,y,z\")")
+function probe_positions(D, var = "SPHMI_PROBES")
+    pts = [parse.(Float64, strip.(split(p, ","))) for p in split(get(ENV, var, ""), ";") if !isempty(strip(p))]
+    all(p -> length(p) == D, pts) || error("$var: every point needs $D coordinates (\"x,y;x,y\" / \"x,y,z;x,y,z\")")
     return isempty(pts) ? zeros(Float64, D, 0) : reduce(hcat, pts)
 end
 function read_probes!(h, pr::ProbeSeries)
@@ -139,6 +142,39 @@ function read_probes!(h, pr::ProbeSeries)
     append!(pr.iteration, it); append!(pr.time, t); append!(pr.dt, dt)
     pr.weight = hcat(pr.weight, w); pr.count = hcat(pr.count, c); pr.pressure = hcat(pr.pressure, pp); pr.density = hcat(pr.density, rho)
     pr.velocity = cat(pr.velocity, v; dims = 3); pr.dropped += dropped[]
+    return nothing
+end
+# SPHMI_PROBE_MOMENTS: the step-resolution RAW moment sums at a point set of their own, bound like PROBES — weight[p, s] = Σ w, count[p, s],
+# sum_pressure / sum_density[p, s], sum_velocity[:, p, s], and with e = xⱼ − x_p: moment1[:, p, s] = Σ w e, moment2[:, p, s] = Σ w e ⊗ e as
+# (xx, xy, xz, yy, yz, zz), moment_pressure / moment_density[:, p, s] = Σ w P e / Σ w ρ e, moment_velocity[b, a, p, s] = Σ w v[a] e[b] (the C
+# array's [a][b], column-major).  Nothing is divided by S: the caller solves [[S, M1ᵀ], [M1, M2]] · [a; b] = [Σ w f; Σ w f e] per probe and sample.
+mutable struct ProbeMomentSeries
+    positions::Matrix{Float64}           # dims × probes
+    iteration::Vector{Int64}; time::Vector{Float64}; dt::Vector{Float64}
+    weight::Matrix{Float64}; count::Matrix{Int64}; sum_pressure::Matrix{Float64}; sum_density::Matrix{Float64}      # probes × samples
+    sum_velocity::Array{Float64,3}; moment1::Array{Float64,3}      # 3 × probes × samples
+    moment2::Array{Float64,3}            # 6 × probes × samples
+    moment_pressure::Array{Float64,3}; moment_density::Array{Float64,3}      # 3 × probes × samples
+    moment_velocity::Array{Float64,4}    # 3 × 3 × probes × samples
+    dropped::Int64
+end
+const PROBE_MOMENTS = IdDict{Any,ProbeMomentSeries}()
+function read_probe_moments!(h, pm::ProbeMomentSeries)
+    n = Ref{Int64}(0); dropped = Ref{Int64}(0)
+    check(h, ccall((:sphmi_probe_moments_read, LIB), Cint, (Ptr{Cvoid}, Int64, Ptr{Int64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ref{Int64}, Ref{Int64}), h, 0, C_NULL, C_NULL, C_NULL, C_NULL, C_NULL, C_NULL, C_NULL, C_NULL, C_NULL, C_NULL, C_NULL, C_NULL, C_NULL, n, dropped))
+    k = Int(n[]); k == 0 && return nothing
+    m = size(pm.positions, 2)
+    it = Vector{Int64}(undef, k); t = Vector{Float64}(undef, k); dt = Vector{Float64}(undef, k)
+    w = Matrix{Float64}(undef, m, k); c = Matrix{Int64}(undef, m, k); sp = Matrix{Float64}(undef, m, k); sr = Matrix{Float64}(undef, m, k)
+    sv = Array{Float64,3}(undef, 3, m, k); m1 = Array{Float64,3}(undef, 3, m, k); m2 = Array{Float64,3}(undef, 6, m, k)
+    p1 = Array{Float64,3}(undef, 3, m, k); r1 = Array{Float64,3}(undef, 3, m, k); v1 = Array{Float64,4}(undef, 3, 3, m, k)
+    GC.@preserve it t dt w c sp sr sv m1 m2 p1 r1 v1 check(h, ccall((:sphmi_probe_moments_read, LIB), Cint, (Ptr{Cvoid}, Int64, Ptr{Int64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ref{Int64}, Ref{Int64}),
+                                                                    h, k, pointer(it), pointer(t), pointer(dt), pointer(w), pointer(c), pointer(sp), pointer(sr), pointer(sv), pointer(m1), pointer(m2), pointer(p1), pointer(r1), pointer(v1), n, dropped))
+    append!(pm.iteration, it); append!(pm.time, t); append!(pm.dt, dt)
+    pm.weight = hcat(pm.weight, w); pm.count = hcat(pm.count, c); pm.sum_pressure = hcat(pm.sum_pressure, sp); pm.sum_density = hcat(pm.sum_density, sr)
+    pm.sum_velocity = cat(pm.sum_velocity, sv; dims = 3); pm.moment1 = cat(pm.moment1, m1; dims = 3); pm.moment2 = cat(pm.moment2, m2; dims = 3)
+    pm.moment_pressure = cat(pm.moment_pressure, p1; dims = 3); pm.moment_density = cat(pm.moment_density, r1; dims = 3)
+    pm.moment_velocity = cat(pm.moment_velocity, v1; dims = 4); pm.dropped += dropped[]
     return nothing
 end
 # SPHMI_BUDGETS: the step-resolution budgets of the fluid, bound like GROUP_FORCES — count[s] Fluid rows, energy[:, s] (kinetic, potential,
@@ -575,6 +611,14 @@ function open_session(SimDensityDiffusion, SimViscosity, SimKernel, SimMetaData:
         PROBES[P] = ProbeSeries(points, Int64[], Float64[], Float64[], zeros(Float64, m, 0), zeros(Int64, m, 0), zeros(Float64, m, 0), zeros(Float64, m, 0),
                                 Array{Float64,3}(undef, 3, m, 0), 0)
     end
+    mpoints = probe_positions(D, "SPHMI_PROBE_MOMENTS")      # opt-in as well: SPHMI_PROBE_MOMENTS, a point set of its own
+    if !isempty(mpoints)
+        m = size(mpoints, 2)
+        GC.@preserve mpoints check(h, ccall((:sphmi_probe_moments_enable, LIB), Cint, (Ptr{Cvoid}, Int32, Ptr{Float64}, Int64), h, Int32(m), pointer(mpoints), 1 << 16))
+        e3 = Array{Float64,3}(undef, 3, m, 0)
+        PROBE_MOMENTS[P] = ProbeMomentSeries(mpoints, Int64[], Float64[], Float64[], zeros(Float64, m, 0), zeros(Int64, m, 0), zeros(Float64, m, 0), zeros(Float64, m, 0),
+                                             e3, e3, Array{Float64,3}(undef, 6, m, 0), e3, e3, Array{Float64,4}(undef, 3, 3, m, 0), 0)
+    end
     if budgets_wanted()                            # opt-in as well: SPHMI_BUDGETS
         check(h, ccall((:sphmi_budgets_enable, LIB), Cint, (Ptr{Cvoid}, Int64), h, 1 << 20))
         BUDGETS[P] = BudgetSeries(Int64[], Float64[], Float64[], Int64[], zeros(Float64, 3, 0), zeros(Float64, 3, 0), zeros(Float64, 3, 0), zeros(Float64, 3, 0),
@@ -648,6 +692,7 @@ function SimulationLoop(SimDensityDiffusion::BuiltinDDT, SimViscosity::BuiltinVi
     forward_timers!(SimMetaData.HourGlass, s)
     haskey(GROUP_FORCES, P) && read_group_forces!(h, GROUP_FORCES[P])
     haskey(PROBES, P) && read_probes!(h, PROBES[P])
+    haskey(PROBE_MOMENTS, P) && read_probe_moments!(h, PROBE_MOMENTS[P])
     haskey(BUDGETS, P) && read_budgets!(h, BUDGETS[P])
     haskey(FLOW, P) && read_flow!(h, FLOW[P])
     haskey(ENVELOPES, P) && read_envelopes!(h, ENVELOPES[P], length(P))

@@ -100,6 +100,7 @@ PROTOTYPES = {
     # the step series
     "group_forces_enable": [_P, _I32, _P, _I64], "group_forces_read": [_P, _I64] + [_P] * 4 + _SERIES_TAIL,
     "probes_enable": [_P, _I32, _P, _I64], "probes_read": [_P, _I64] + [_P] * 8 + _SERIES_TAIL,
+    "probe_moments_enable": [_P, _I32, _P, _I64], "probe_moments_read": [_P, _I64] + [_P] * 13 + _SERIES_TAIL,
     "budgets_enable": [_P, _I64], "budgets_read": [_P, _I64] + [_P] * 10 + _SERIES_TAIL,
     "flow_enable": [_P, _I32, _P, _P, _I64], "flow_read": [_P, _I64] + [_P] * 8 + _SERIES_TAIL,
     "tracers_enable": [_P, _I32, _P, _I32, _P, _F, _I64], "tracers_read": [_P, _I64] + [_P] * 6 + _SERIES_TAIL,
@@ -193,7 +194,7 @@ FEATURES = {
     "columns": ("attach_columns", "download_columns", "download_columns_begin"),
     "neighbor_list": ("neighbors_build", "neighbors_read", "neighbors_release"),
     "maps": ("maps_enable", "maps_read", "maps_disable"),
-    **{k: (k + "_enable", k + "_read") for k in ("group_forces", "probes", "budgets", "flow", "envelopes", "tracers")},
+    **{k: (k + "_enable", k + "_read") for k in ("group_forces", "probes", "probe_moments", "budgets", "flow", "envelopes", "tracers")},
     **{k: (k + "_build", k + "_read", k + "_release") for k in ("isosurface", "components")},
     "select": ("select_build", "select_read", "select_download", "select_download_columns", "select_release"),
     **{k: (k,) for k in ("sample_grid", "sample_points", "sample_point_gradients", "sample_point_moments", "cast_rays", "particle_fields")},
@@ -208,7 +209,7 @@ class Backend:
 
     # what this object enabled, attached, pinned and built (class-level: objects made with __new__ start from them too)
     _column_widths = None
-    _force_groups = _probes = _flow_boxes = _map_bins = 0
+    _force_groups = _probes = _moment_probes = _flow_boxes = _map_bins = 0
     _tracers = (0, 0, 0.5)
     _pinned = ()
     _neighbor_shape = _isosurface_shape = _components_shape = _select_shape = None
@@ -355,6 +356,7 @@ class Backend:
         self._column_widths = None         # (sphmi_upload detaches the columns)
         self._force_groups = 0             # (… and disables the group forces)
         self._probes = 0                   # (… and the probes)
+        self._moment_probes = 0            # (… and their moments)
 
     def upload_particles(self, p):
         self.upload(p.Position, p.Velocity, p.Acceleration, p.Density, p.Type, p.ID, p.GroupMarker,
@@ -531,6 +533,29 @@ class Backend:
         weight[n, probes] (S), count[n, probes], pressure[n, probes], density[n, probes], velocity[n, probes, 3];
         `probes_dropped` holds how many older samples the capacity pushed out."""
         return self._read_series("probes", self.PROBE_FIELDS, int(self._probes))
+
+    # -- moment sums at fixed probe points (sphmi_probe_moments_enable / sphmi_probe_moments_read) ---------------------------
+    def probe_moments_enable(self, positions, capacity: int = 4096) -> None:
+        """Record the RAW kernel sums and their moments of `sample_point_moments` at the fixed points `positions` [n, dims] (at most
+        1024) after every executed step, on the device; the newest `capacity` unread samples are kept.  An observer of its own:
+        its point set is independent of `probes_enable`, and both may be on together.  An empty array disables."""
+        x = np.ascontiguousarray(positions, dtype=np.float64).reshape(-1, self.D)
+        self._check(self._fn("probe_moments_enable")(self._h, len(x), _ptr(x) if len(x) else None, int(capacity)))
+        self._moment_probes = len(x)
+
+    def probe_moments_read(self) -> dict:
+        """The steps executed since the last read, oldest first, and clears them: a dict of iteration[n], time[n], dt[n] and the ten
+        arrays of `sample_point_moments` under its key names with a leading steps axis — `weight`, `count`, `sum_pressure`,
+        `sum_density` [n, probes], `sum_velocity`, `moment1`, `moment_pressure`, `moment_density` [n, probes, 3], `moment2`
+        (symmetric) and `moment_velocity` [n, probes, 3, 3] — RAW, plus the handle's `h` and `dims`:
+        ``sphexample_amd.probes.fit_series`` turns the record into fitted values and gradients per step and probe.
+        `probe_moments_dropped` (also in the dict) holds how many older samples the capacity pushed out."""
+        schema = tuple((key, shape, dtype) for key, (dtype, shape) in self.MOMENT_FIELDS.items())
+        out = self._read_series("probe_moments", schema, int(self._moment_probes))
+        out["moment2"] = np.ascontiguousarray(out["moment2"][:, :, self._SYMMETRIC])
+        out["h"], out["dims"] = float(self.cfg.h), int(self.D)
+        out["probe_moments_dropped"] = int(self.probe_moments_dropped)
+        return out
 
     # -- the budgets of the fluid at every step (sphmi_budgets_enable / sphmi_budgets_read) ---------------------------------
     BUDGET_FIELDS = (("count", (), np.int64), ("energy", (3,), np.float64), ("momentum", (3,), np.float64), ("angular", (3,), np.float64),

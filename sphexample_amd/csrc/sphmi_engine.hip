@@ -24,6 +24,7 @@
 #include "sphmi_envelopes.h"
 #include "sphmi_maps.h"
 #include "sphmi_probes.h"
+#include "sphmi_probe_moments.h"
 #include "sphmi_tracers.h"
 #include "sphmi_field_grid.h"
 #include "sphmi_point_cloud.h"
@@ -148,17 +149,18 @@ struct EngineBase {
     // The observers that record once per executed step, in the order their samples are queued and their logs fetched.  `series`
     // (sphmi_series.h) holds the payloads as recorded, RAW: the reads form what they deliver.  A multi-device handle keeps the series
     // itself (those of its slab engines stay empty) and combines the slabs' records slot by slot with `rule` (null: every slot a sum).
-    enum Obs { OBS_GF = 0, OBS_PR, OBS_BG, OBS_FL, OBS_TR, OBS_COUNT };
+    enum Obs { OBS_GF = 0, OBS_PR, OBS_PM, OBS_BG, OBS_FL, OBS_TR, OBS_COUNT };
     struct SeriesObserver {
         const char* what;                      // in error texts
         int (*rule)(int);
         bool on = false;
         StepSeries series;
     };
-    SeriesObserver obs[OBS_COUNT] = {{"group forces", nullptr}, {"probes", nullptr}, {"budgets", bg_rule}, {"flow", nullptr}, {"tracers", nullptr}};
+    SeriesObserver obs[OBS_COUNT] = {{"group forces", nullptr}, {"probes", nullptr}, {"probe moments", nullptr}, {"budgets", bg_rule}, {"flow", nullptr}, {"tracers", nullptr}};
     // the device side of an enable: the handle's own sampling, or that of every slab engine of a multi-device handle
     virtual void gf_enable_device(int32_t n_groups, const uint64_t* markers) = 0;
     virtual void pr_enable_device(int32_t n_probes, const double* positions) = 0;
+    virtual void pm_enable_device(int32_t n_probes, const double* positions) = 0;
     virtual void bg_enable_device(bool on) = 0;
     virtual void fl_enable_device(int32_t n_boxes, const double* lo, const double* hi) = 0;
     void flow_enable(int32_t n_boxes, const double* lo, const double* hi, int64_t capacity_steps) {
@@ -220,6 +222,20 @@ struct EngineBase {
         check_probe_table(n_probes, positions, cfg.dims, capacity_steps);
         pr_enable_device(n_probes, positions);
         obs[OBS_PR].series.reset(kPrValues * n_probes, capacity_steps);
+    }
+    // the moment sums at fixed probes (sphmi_probe_moments.h): an observer of its own, with its own point set, under the contract of the probes
+    void probe_moments_enable(int32_t n_probes, const double* positions, int64_t capacity_steps) {
+        require_one_process("sphmi_probe_moments_enable");
+        check_probe_table(n_probes, positions, cfg.dims, capacity_steps, "sphmi_probe_moments_enable");
+        pm_enable_device(n_probes, positions);
+        obs[OBS_PM].series.reset(kPmValues * n_probes, capacity_steps);
+    }
+    void probe_moments_read(int64_t capacity, int64_t* iteration_out, double* time, double* dt, const RawOutputs& out, int64_t* n_out, int64_t* n_dropped) {
+        require_one_process("sphmi_probe_moments_read");
+        if (!obs[OBS_PM].on) throw EngineError(SPHMI_ERR_STATE, "sphmi_probe_moments_read: sampling is not enabled (sphmi_probe_moments_enable)");
+        obs[OBS_PM].series.read("sphmi_probe_moments_read", capacity, iteration_out, time, dt, n_out, n_dropped, [&](int64_t k, const double* v) {
+            deliver_probe_moments(obs[OBS_PM].series.values / kPmValues, k, v, out);
+        });
     }
     void budgets_enable(int64_t capacity_steps) {
         require_one_process("sphmi_budgets_enable");
@@ -603,7 +619,7 @@ struct Engine final : EngineBase {
         for (auto& e : host_pinned) (void)hipHostUnregister(e.first);
         (void)hipFree(out_arena);
         (void)hipFree(col_arena); (void)hipFree(col_store); (void)hipFree(col_base[0]); (void)hipFree(col_base[1]);
-        gf_release(); pr_release(); bg_release(); fl_release(); en_release(); mp_release(); tr_release(); fg_arena.free(); pc_free(); ry_free(); pf_arena.free(); nl_free(); iso_free(); cc_free(); sel_free();
+        gf_release(); pr_release(); pm_release(); bg_release(); fl_release(); en_release(); mp_release(); tr_release(); fg_arena.free(); pc_free(); ry_free(); pf_arena.free(); nl_free(); iso_free(); cc_free(); sel_free();
         (void)hipFree(slot); (void)hipFree(tmp_idx); (void)hipFree(perm);
         for (int k = 0; k < 2; ++k) { (void)hipFree(tile_cost[k]); (void)hipFree(tile_order[k]); }
         (void)hipFree(kout_d); (void)hipFree(tile_work_d); (void)hipFree(tile_work1_d); (void)hipFree(xcd_clock_d); (void)hipHostFree(xcd_clock_h);
@@ -1806,6 +1822,7 @@ struct Engine final : EngineBase {
     void observe_step(const StepCtrl* ctrl, int set) {
         if (obs[OBS_GF].on) gf_sample(ctrl, set);      // Σ Acceleration of the selected groups → the batch's log
         if (obs[OBS_PR].on) pr_sample(ctrl, set);      // the kernel sums at the probes, on the corrector's output set → the batch's log
+        if (obs[OBS_PM].on) pm_sample(ctrl, set);      // the moment sums at their own probes, on the same set → their own log
         if (obs[OBS_BG].on) bg_sample(ctrl, set);      // the budgets of the fluid, on the same set → the batch's log
         if (obs[OBS_FL].on) fl_sample(ctrl, set);      // the flow through the control boxes: that set against this step's marks
         if (en_mask) en_update(ctrl, set);             // the per-particle envelopes: that set and the half step's density → the rows' records
@@ -1824,7 +1841,7 @@ struct Engine final : EngineBase {
         }
     }
     // a new particle set: every observer described the old one
-    void observers_off() { gf_disable(); pr_disable(); bg_disable(); fl_disable(); en_disable(); mp_disable(); tr_disable(); }
+    void observers_off() { gf_disable(); pr_disable(); pm_disable(); bg_disable(); fl_disable(); en_disable(); mp_disable(); tr_disable(); }
     // Switching a series observer off: nothing is sampled from here on, the series is empty, and once the stream has drained the
     // device side goes back (`release`, which also clears the observer's table).  Not on: only the release, so that an enable that
     // failed half way leaves nothing behind for the next one.
@@ -1928,13 +1945,42 @@ struct Engine final : EngineBase {
         pr_n = n_probes;
         obs[OBS_PR].on = true;
     }
-    void pr_sample(const StepCtrl* ctrl, int set) {
+    // the arguments of a walk over the probes `pos` behind the corrector that read `ctrl` and wrote `set`, recording into the log of observer k
+    ProbeSampleArgs<T> pr_args(Obs k, const StepCtrl* ctrl, int set, const double* pos, int n_probes) const {
         ProbeSampleArgs<T> A{};
-        A.step = step_record(OBS_PR, ctrl); A.pk0 = pk0[set]; A.pk1 = pk1[set]; A.half0 = pk0[iH]; A.comp = comp[cur];
-        A.type = dd_slab ? type[cur] : nullptr; A.cstart = cstart; A.pos = pr_pos_d.p; A.g = grid;
+        A.step = step_record(k, ctrl); A.pk0 = pk0[set]; A.pk1 = pk1[set]; A.half0 = pk0[iH]; A.comp = comp[cur];
+        A.type = dd_slab ? type[cur] : nullptr; A.cstart = cstart; A.pos = pos; A.g = grid;
         fill_sample_consts(A);
-        A.n_probes = pr_n; A.N = N; A.D = D; A.kernel = cfg.kernel;
-        hipLaunchKernelGGL(k_probe_sample<T>, dim3((pr_n + 3) / 4), dim3(256), 0, stream, A);
+        A.n_probes = n_probes; A.N = N; A.D = D; A.kernel = cfg.kernel;
+        return A;
+    }
+    void pr_sample(const StepCtrl* ctrl, int set) {
+        hipLaunchKernelGGL(k_probe_sample<T>, dim3((pr_n + 3) / 4), dim3(256), 0, stream, pr_args(OBS_PR, ctrl, set, pr_pos_d.p, pr_n));
+        HC(hipGetLastError());
+    }
+
+    // ---- moment sums at fixed probe points (sphmi_probe_moments.h) ----------------------------------------------------------------
+    // The probes' machinery with a point set, a log and a kernel of its own: a record is kStepHeader + kPmValues · n_probes doubles,
+    // 254 KB at 1024 probes, and the log of a batch holds kBatch of them on the device and in page-locked host memory.
+    int pm_n = 0;
+    DeviceBuf<double> pm_pos_d;
+    void pm_release() { pm_pos_d.free(); log[OBS_PM].release(); pm_n = 0; }
+    void pm_disable() { observer_off(OBS_PM, &Engine::pm_release); }
+    void pm_enable_device(int32_t n_probes, const double* positions) override {
+        HC(hipSetDevice(cfg.device));
+        pm_disable();
+        if (n_probes == 0) return;
+        if (!(cfg.h <= cfg.H)) throw EngineError(SPHMI_ERR_STATE, "sphmi_probe_moments_enable: handles with H < h are not served (the candidate cells of a probe are laid out for H + h <= 2H)");
+        std::vector<double> xyz((size_t)3 * n_probes, 0.0);
+        for (int p = 0; p < n_probes; ++p) for (int d = 0; d < D; ++d) xyz[3 * (size_t)p + d] = positions[(size_t)p * D + d];
+        pm_pos_d.need(xyz.size());
+        log[OBS_PM].alloc(kStepHeader + kPmValues * n_probes, kStepHeader + kPmValues * n_probes);
+        bounce.h2d(pm_pos_d.p, xyz.data(), xyz.size() * 8, stream);
+        pm_n = n_probes;
+        obs[OBS_PM].on = true;
+    }
+    void pm_sample(const StepCtrl* ctrl, int set) {
+        hipLaunchKernelGGL(k_probe_moments<T>, dim3((pm_n + 3) / 4), dim3(256), 0, stream, pr_args(OBS_PM, ctrl, set, pm_pos_d.p, pm_n));
         HC(hipGetLastError());
     }
 
@@ -3424,6 +3470,18 @@ int sphmi_group_forces_enable(sphmi_handle* h, int32_t n_groups, const uint64_t*
 static_assert(SPHMI_MAX_PROBES == sphmi::kMaxProbes, "sphmi_series.h and sphmi.h disagree");
 int sphmi_probes_enable(sphmi_handle* h, int32_t n_probes, const double* positions, int64_t capacity_steps) {
     SPHMI_GUARD(h, h->e->probes_enable(n_probes, positions, capacity_steps));
+}
+int sphmi_probe_moments_enable(sphmi_handle* h, int32_t n_probes, const double* positions, int64_t capacity_steps) {
+    SPHMI_GUARD(h, h->e->probe_moments_enable(n_probes, positions, capacity_steps));
+}
+int sphmi_probe_moments_read(sphmi_handle* h, int64_t capacity, int64_t* iteration_out, double* time_out, double* dt_out, double* weight_out,
+                             int64_t* count_out, double* sum_pressure_out, double* sum_density_out, double* sum_velocity_out, double* moment1_out,
+                             double* moment2_out, double* moment_pressure_out, double* moment_density_out, double* moment_velocity_out,
+                             int64_t* n_out, int64_t* n_dropped) {
+    double* const outputs[] = {sum_pressure_out, sum_density_out, sum_velocity_out, moment1_out, moment2_out, moment_pressure_out, moment_density_out,
+                               moment_velocity_out};
+    const sphmi::RawOutputs out(sphmi::kPmOutputs, weight_out, count_out, outputs);
+    SPHMI_GUARD(h, h->e->probe_moments_read(capacity, iteration_out, time_out, dt_out, out, n_out, n_dropped));
 }
 int sphmi_probes_read(sphmi_handle* h, int64_t capacity, int64_t* iteration_out, double* time_out, double* dt_out, double* weight_out,
                       int64_t* count_out, double* pressure_out, double* density_out, double* velocity_out, int64_t* n_out, int64_t* n_dropped) {

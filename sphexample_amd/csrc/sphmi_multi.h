@@ -1732,6 +1732,10 @@ struct MultiEngine final : EngineBase {
     void pr_enable_device(int32_t n_probes, const double* positions) override {
         enable_on_slabs(OBS_PR, n_probes > 0, [&](Engine<T>& e) { e.pr_enable_device(n_probes, positions); });
     }
+    // The moment sums at fixed probes (sphmi_probe_moments.h): served as the probes are — every sum is linear in the rows.
+    void pm_enable_device(int32_t n_probes, const double* positions) override {
+        enable_on_slabs(OBS_PM, n_probes > 0, [&](Engine<T>& e) { e.pm_enable_device(n_probes, positions); });
+    }
     // The budgets of the fluid (sphmi_budgets.h): every slab reduces the rows it owns, the handle combines the slabs' raw records of a
     // step in slab order — sums add, extremes take min or max (bg_rule); the read forms the delivered values from the combined record.
     void bg_enable_device(bool on) override {

@@ -82,12 +82,30 @@ __device__ __forceinline__ double pr_kernel_w(int kernel, double alphaD, double 
     return alphaD * (t2 * t2) * (2.0 * q + 1.0);
 }
 
-// The walk of one wave over the candidate rows of the point xp (the header comment): the seven sums, complete in every lane.  `A` supplies
-// the record sets, the cell list and the constants; its point table and its log are not touched.  k_probe_sample and the drifters of
-// sphmi_tracers.h call it: a moving point is sampled with the arithmetic, and in the order, of a fixed one.
-template <class T>
-__device__ __forceinline__ void pr_walk(const ProbeSampleArgs<T>& A, const double (&xp)[3], const int lane, double& n, double& S, double& SP, double& Sr,
-                                        double& Sx, double& Sy, double& Sz) {
+// The seven sums of a probe, as one lane carries them through the walk.  `add` is handed one accepted row — its weight w, Pressure, density,
+// velocity and d = x_p − x_j — and `reduce` closes the walk with one fixed butterfly per sum.  pr_walk is written over such a set:
+// PmSums (sphmi_probe_moments.h) carries these seven, formed by these statements, and the moment sums behind them.
+struct PrSums {
+    static constexpr int kInFlight = kPrInFlight;
+    double n = 0.0, S = 0.0, SP = 0.0, Sr = 0.0, Sx = 0.0, Sy = 0.0, Sz = 0.0;
+    __device__ __forceinline__ void add(double w, double P, double rho, double vx, double vy, double vz, double, double, double) {
+#pragma clang fp contract(off)
+        n += 1.0; S += w; SP += w * P; Sr += w * rho;
+        Sx += w * vx; Sy += w * vy; Sz += w * vz;
+    }
+    __device__ __forceinline__ void reduce() {
+        n = wave_sum(n); S = wave_sum(S); SP = wave_sum(SP); Sr = wave_sum(Sr);
+        Sx = wave_sum(Sx); Sy = wave_sum(Sy); Sz = wave_sum(Sz);
+    }
+};
+
+// The walk of one wave over the candidate rows of the point xp (the header comment): the sums of `s` (zero on entry), complete in every
+// lane.  `A` supplies the record sets, the cell list and the constants; its point table and its log are not touched.  `Sums` names the
+// per-row statements and how many jobs' loads are in flight (kInFlight).  k_probe_sample, the drifters of sphmi_tracers.h and
+// k_probe_moments (sphmi_probe_moments.h) call it: a moving point is sampled with the arithmetic, and in the order, of a fixed one.
+template <class T, class Sums>
+__device__ __forceinline__ void pr_walk(const ProbeSampleArgs<T>& A, const double (&xp)[3], const int lane, Sums& s) {
+    constexpr int kInFlight = Sums::kInFlight;
     using V4 = typename Vec4<T>::type;
     // padded cell range per axis, clamped to the grid (in fp64 before the conversion: a probe may be anywhere)
     int lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0};
@@ -119,7 +137,6 @@ __device__ __forceinline__ void pr_walk(const ProbeSampleArgs<T>& A, const doubl
     for (int o = 1; o < 32; o <<= 1) { const int u = __shfl_up(jincl, o, 64); if (lane >= o) jincl += u; }
     const int jexcl = jincl - ((rc + 63) >> 6);
     const int njobs = nrow > 0 ? __shfl(jincl, nrow - 1, 64) : 0;
-    n = 0.0; S = 0.0; SP = 0.0; Sr = 0.0; Sx = 0.0; Sy = 0.0; Sz = 0.0;
     for (int jbase = 0; jbase < njobs; jbase += 64) {
         // lane l describes job jbase + l: its first row and the rows left in its range
         int job_first = 0, job_left = 0;
@@ -132,13 +149,13 @@ __device__ __forceinline__ void pr_walk(const ProbeSampleArgs<T>& A, const doubl
             }
         }
         const int nj = min(64, njobs - jbase);
-        for (int j0 = 0; j0 < nj; j0 += kPrInFlight) {
-            V4 q0[kPrInFlight], q1[kPrInFlight], lw[kPrInFlight];
-            T hw[kPrInFlight];
-            uint8_t ty[kPrInFlight];
-            bool ok[kPrInFlight];
+        for (int j0 = 0; j0 < nj; j0 += kInFlight) {
+            V4 q0[kInFlight], q1[kInFlight], lw[kInFlight];
+            T hw[kInFlight];
+            uint8_t ty[kInFlight];
+            bool ok[kInFlight];
 #pragma unroll
-            for (int u = 0; u < kPrInFlight; ++u) {
+            for (int u = 0; u < kInFlight; ++u) {
                 const int jl = min(j0 + u, 63);
                 const int first = __shfl(job_first, jl, 64), left = j0 + u < nj ? __shfl(job_left, jl, 64) : 0;
                 ok[u] = lane < left;
@@ -148,7 +165,7 @@ __device__ __forceinline__ void pr_walk(const ProbeSampleArgs<T>& A, const doubl
                 ty[u] = A.type ? A.type[k] : (uint8_t)(q0[u].w > T(0) ? 1 : 2);
             }
 #pragma unroll
-            for (int u = 0; u < kPrInFlight; ++u) {
+            for (int u = 0; u < kInFlight; ++u) {
                 // (no contraction: r² is ((dx² + dy²) + dz²) rounded term by term, the value a host reference forms from the downloaded positions —
                 // a row AT the cut is in or out for both)
 #pragma clang fp contract(off)
@@ -163,14 +180,12 @@ __device__ __forceinline__ void pr_walk(const ProbeSampleArgs<T>& A, const doubl
                     const T rr2 = rr * rr, rr4 = rr2 * rr2;
                     const double P = (double)(A.Cbe * (rr4 * rr2 * rr - T(1)));
                     const double w = (A.m0 / rho) * pr_kernel_w(A.kernel, A.alphaD, sqrt(r2) * A.h_inv);
-                    n += 1.0; S += w; SP += w * P; Sr += w * rho;
-                    Sx += w * (double)q1[u].x; Sy += w * (double)q1[u].y; Sz += w * (double)q1[u].z;
+                    s.add(w, P, rho, (double)q1[u].x, (double)q1[u].y, (double)q1[u].z, dx, dy, dz);
                 }
             }
         }
     }
-    n = wave_sum(n); S = wave_sum(S); SP = wave_sum(SP); Sr = wave_sum(Sr);
-    Sx = wave_sum(Sx); Sy = wave_sum(Sy); Sz = wave_sum(Sz);
+    s.reduce();
 }
 
 template <class T>
@@ -185,11 +200,11 @@ __global__ void __launch_bounds__(256) k_probe_sample(const ProbeSampleArgs<T> A
     double* rec = A.step.at(slot);
     if (p == 0 && lane == 0) A.step.write_header(rec, c);
     const double xp[3] = {A.pos[3 * p], A.pos[3 * p + 1], A.D == 3 ? A.pos[3 * p + 2] : 0.0};
-    double n, S, SP, Sr, Sx, Sy, Sz;
-    pr_walk<T>(A, xp, lane, n, S, SP, Sr, Sx, Sy, Sz);
+    PrSums s;
+    pr_walk<T>(A, xp, lane, s);
     if (lane == 0) {
         double* v = rec + kStepHeader + (size_t)kPrValues * p;
-        v[0] = S; v[1] = SP; v[2] = Sr; v[3] = Sx; v[4] = Sy; v[5] = A.D == 3 ? Sz : 0.0; v[6] = n;
+        v[0] = s.S; v[1] = s.SP; v[2] = s.Sr; v[3] = s.Sx; v[4] = s.Sy; v[5] = A.D == 3 ? s.Sz : 0.0; v[6] = s.n;
     }
 }
 

@@ -72,14 +72,15 @@ inline void check_group_table(int32_t n_groups, const uint64_t* markers, int64_t
             if (markers[a] == markers[b]) throw EngineError(SPHMI_ERR_ARGUMENT, "sphmi_group_forces_enable: duplicate marker");
 }
 
-// sphmi_probes_enable: the argument errors every kind of handle reports alike
-inline void check_probe_table(int32_t n_probes, const double* positions, int dims, int64_t capacity_steps) {
-    if (n_probes < 0 || n_probes > kMaxProbes) throw EngineError(SPHMI_ERR_ARGUMENT, "sphmi_probes_enable: n_probes out of range [0, 1024]");
+// sphmi_probes_enable and sphmi_probe_moments_enable (`fn`): the argument errors every kind of handle reports alike
+inline void check_probe_table(int32_t n_probes, const double* positions, int dims, int64_t capacity_steps, const char* fn = "sphmi_probes_enable") {
+    const std::string name(fn);
+    if (n_probes < 0 || n_probes > kMaxProbes) throw EngineError(SPHMI_ERR_ARGUMENT, name + ": n_probes out of range [0, 1024]");
     if (n_probes == 0) return;
-    if (!positions) throw EngineError(SPHMI_ERR_ARGUMENT, "sphmi_probes_enable: null table");
-    if (capacity_steps < 1) throw EngineError(SPHMI_ERR_ARGUMENT, "sphmi_probes_enable: capacity_steps must be positive");
+    if (!positions) throw EngineError(SPHMI_ERR_ARGUMENT, name + ": null table");
+    if (capacity_steps < 1) throw EngineError(SPHMI_ERR_ARGUMENT, name + ": capacity_steps must be positive");
     for (int64_t k = 0; k < (int64_t)n_probes * dims; ++k)
-        if (!std::isfinite(positions[k])) throw EngineError(SPHMI_ERR_ARGUMENT, "sphmi_probes_enable: non-finite coordinate");
+        if (!std::isfinite(positions[k])) throw EngineError(SPHMI_ERR_ARGUMENT, name + ": non-finite coordinate");
 }
 
 // sphmi_flow_enable: the argument errors every kind of handle reports alike.  A box is half-open, lo <= x < hi per axis; -inf and
@@ -413,5 +414,22 @@ inline void RawOutputs::deliver(const GridSums& G) const {
     }
 }
 inline void MeanOutputs::deliver(const GridSums& G) const { G.deliver(count, pressure, density, velocity); }
+
+// sphmi_probe_moments_read: the raw sums of the k-th delivered step — kPmValues slots per probe, probe-major, as k_probe_moments
+// records them — → the caller's [capacity × n_probes × width] arrays, as they are; n → count_out as an integer.  `out` is built over
+// kPmOutputs: the layout is stated there and nowhere else.
+inline void deliver_probe_moments(int n_probes, int64_t k, const double* sums, const RawOutputs& out) {
+    for (int p = 0; p < n_probes; ++p) {
+        const double* v = sums + (size_t)out.values * p;
+        const size_t at = (size_t)k * n_probes + p;
+        if (out.weight) out.weight[at] = v[0];
+        if (out.count) out.count[at] = (int64_t)v[6];
+        for (int i = 0; i < out.entries; ++i) {
+            if (!out.out[i]) continue;
+            const int width = out.table[i].width;
+            for (int c = 0; c < width; ++c) out.out[i][(size_t)width * at + c] = v[out.table[i].first + c];
+        }
+    }
+}
 
 }  // namespace sphmi

@@ -118,8 +118,9 @@ __global__ void __launch_bounds__(256) k_tr_drift(const TracerDrifterArgs<T> A) 
     const int p = __builtin_amdgcn_readfirstlane((int)((blockIdx.x * blockDim.x + threadIdx.x) >> 6));
     if (p >= A.s.n_probes) return;
     const double xp[3] = {A.X[3 * p], A.X[3 * p + 1], A.s.D == 3 ? A.X[3 * p + 2] : 0.0};
-    double n, S, SP, Sr, Sx, Sy, Sz;
-    pr_walk<T>(A.s, xp, lane, n, S, SP, Sr, Sx, Sy, Sz);
+    PrSums sums;
+    pr_walk<T>(A.s, xp, lane, sums);
+    const double n = sums.n, S = sums.S, SP = sums.SP, Sr = sums.Sr, Sx = sums.Sx, Sy = sums.Sy, Sz = sums.Sz;
     if (lane != 0) return;
     if (S >= A.min_weight) {
 #pragma clang fp contract(off)

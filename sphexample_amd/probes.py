@@ -49,4 +49,41 @@ def water_level(z, S, threshold: float = 0.5):
     return float(z[0])
 
 
-__all__ = ["gauge_column", "water_level"]
+# the sums `linear_fit` reads, by the trailing shape of one probe's entry
+_MOMENT_SHAPES = {"weight": (), "count": (), "sum_pressure": (), "sum_density": (), "sum_velocity": (3,), "moment1": (3,), "moment2": (3, 3),
+                  "moment_pressure": (3,), "moment_density": (3,), "moment_velocity": (3, 3)}
+
+
+def empty_probe_moments(n_probes: int, dims: int, h: float) -> dict:
+    """A record of no steps, shaped like ``Backend.probe_moments_read``'s for `n_probes` probes."""
+    out = {"iteration": np.zeros(0, dtype=np.int64), "time": np.zeros(0), "dt": np.zeros(0)}
+    out.update({key: np.zeros((0, int(n_probes), *shape), dtype=np.int64 if key == "count" else np.float64) for key, shape in _MOMENT_SHAPES.items()})
+    out.update({"h": float(h), "dims": int(dims), "probe_moments_dropped": 0})
+    return out
+
+
+def fit_series(record, **kw) -> dict:
+    """The fitted signal of every probe at every step: `record` is the dict of ``Backend.probe_moments_read`` — the raw moment
+    sums shaped [steps, probes, …], with the handle's `h` and `dims` — and ``sphexample_amd.fields.linear_fit`` is run ONCE over
+    all steps × probes (keywords go to it: `min_count`, `min_rcond`, `h`, `dims`).  Returns its dict reshaped to
+    [steps, probes, …]: `pressure`, `density`, `velocity`, their gradients, `linear` (the entries that were fitted) and `rcond`,
+    with the fallback to the Shepard mean as `linear_fit` defines it, plus the record's `iteration`, `time` and `dt` where it has
+    them.  A probe on a wall or on the bed reads the field AT the sensor, not a fraction of h inside the fluid."""
+    from .fields import linear_fit                        # (fields imports this module)
+    S = np.asarray(record["weight"])
+    if S.ndim != 2:
+        raise ValueError("fit_series: the record of probe_moments_read is needed: weight [steps, probes]")
+    steps, probes = S.shape
+    flat = {k: v for k, v in record.items() if k not in _MOMENT_SHAPES}
+    for key, shape in _MOMENT_SHAPES.items():
+        a = np.asarray(record[key])
+        if a.shape != (steps, probes, *shape):
+            raise ValueError(f"fit_series: {key} is shaped [steps, probes{''.join(', %d' % s for s in shape)}]")
+        flat[key] = a.reshape(steps * probes, *shape)
+    fit = linear_fit(flat, **kw)
+    out = {k: np.asarray(v).reshape(steps, probes, *np.asarray(v).shape[1:]) for k, v in fit.items()}
+    out.update({k: record[k] for k in ("iteration", "time", "dt") if k in record})
+    return out
+
+
+__all__ = ["gauge_column", "water_level", "empty_probe_moments", "fit_series"]

@@ -19,6 +19,7 @@ from .config import (SimulationConstants, SimulationMetaData, SPHDensityDiffusio
                      SPHViscosity, next_output_time)
 from .budgets import empty_budgets
 from .flow import empty_flow
+from .probes import empty_probe_moments
 from .engine import Engine
 from .preprocess import LoadMDBCNormals, SimParticles
 
@@ -47,7 +48,8 @@ def RunSimulation(*, SimGeometry=None, SimMetaData: SimulationMetaData, SimConst
                   async_output: bool = False, group_forces=None, probes=None, field_grid=None,
                   particle_fields=None, budgets: bool = False, neighbor_list: bool = False, isosurface=None, components=None,
                   flow_boxes=None, envelopes=None, maps=None, tracers=None, sample_points=None,
-                  sample_point_gradients=None, rays=None, output_select=None, sample_point_moments=None) -> List[float]:
+                  sample_point_gradients=None, rays=None, output_select=None, sample_point_moments=None,
+                  probe_moments=None) -> List[float]:
     """Same keyword signature as the reference (src/SPHCellList.jl:808-817); returns the list of
     time steps the reference collects in ``TimeSteps`` (:823,:884).  ``SimParticles`` is updated in
     place at every output time, in the engine's cell-sorted order, as the reference's is.
@@ -150,7 +152,13 @@ def RunSimulation(*, SimGeometry=None, SimMetaData: SimulationMetaData, SimConst
     sampled at those points (``Backend.sample_point_moments``; ``sphexample_amd.fields.linear_fit`` turns them into values and
     gradients that are exact for a linear field however one-sided the support — sensors on a wall, on the bed, at the free surface)
     and ``on_output`` receives the dict as its last argument, behind ``output_select`` (``None`` at the first call).  ``None``
-    (default): nothing is sampled and the callback keeps its arguments."""
+    (default): nothing is sampled and the callback keeps its arguments.
+
+    ``probe_moments=positions`` ([n, dims]): the same moment sums are recorded at those fixed points on the device at EVERY step
+    (``Backend.probe_moments_enable``; ``sphexample_amd.probes.fit_series`` turns a record into the fitted signal of every probe at
+    every step) and ``on_output`` receives the samples of the interval, the dict of ``Backend.probe_moments_read``, as its last
+    argument, behind ``sample_point_moments`` — as ``probes=`` hands over its samples (empty arrays at the first call).  ``None``
+    (default): nothing is recorded and the callback keeps its arguments."""
     if SimMetaData.BMode.__name__ == "SimpleMDBC":
         LoadMDBCNormals(SimParticles, ParticleNormalsPath)                       # :827
     host_bytes = SimParticles.Position.dtype.itemsize
@@ -212,6 +220,8 @@ def RunSimulation(*, SimGeometry=None, SimMetaData: SimulationMetaData, SimConst
         (rays, dict, None, None, lambda a: eng.cast_rays(**a)),
         (output_select, lambda v: tuple(v) if isinstance(v, (tuple, list)) else (v,), None, lambda a: eng.select(*a), lambda a: eng.select(*a)),
         (sample_point_moments, cloud, None, None, lambda a: eng.sample_point_moments(a)),
+        (probe_moments, cloud, lambda a: eng.probe_moments_enable(a, capacity=1 << 16),
+         lambda a: empty_probe_moments(len(a), dims, float(SimKernel.h)), lambda a: eng.probe_moments_read()),
     )
     extras = []          # per output: what the callback receives behind the particles — a list of (first value, reader)
     for value, normal, enable, first, read in table:

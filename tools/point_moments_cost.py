@@ -53,12 +53,12 @@ def measure(eng, label, reps):
     os.environ.pop("SPHMI_POINTS_CLOCK", None)
 
 
-def still_wedge(settle):
+def still_wedge_handle(settle):
+    """The settled StillWedge handle, its setup, the boundary rows that touch the water and where each lies (bed, wall, wedge);
+    tools/probe_moments_cost.py puts its per-step probes at the same rows."""
     from sphexample_amd import AllocateDataStructures, Fixed, Fluid, Geometry, LoadMDBCNormals
     from sphexample_amd.cases import setup_still_wedge_mdbc
     from sphexample_amd.engine import make_engine
-    from sphexample_amd.fields import linear_fit
-    from sphexample_amd.rays import water_level
     inp = os.path.join(ROOT, "tests", "golden", "input")
     p = AllocateDataStructures([Geometry(CSVFile=os.path.join(inp, "StillWedge_Dp0.02_Bound.csv"), GroupMarker=1, Type=Fixed, Dimensions=2),
                                 Geometry(CSVFile=os.path.join(inp, "StillWedge_Dp0.02_Fluid.csv"), GroupMarker=2, Type=Fluid, Dimensions=2)])
@@ -78,6 +78,16 @@ def still_wedge(settle):
     bed = np.abs(pts[:, 1] - pts[:, 1].min()) < 1e-9
     wall = (np.abs(pts[:, 0] - pts[:, 0].min()) < 0.5 * dx) | (np.abs(pts[:, 0] - pts[:, 0].max()) < 0.5 * dx)
     where = np.where(bed, "bed", np.where(wall, "wall", "wedge"))
+    return eng, s, pts, where
+
+
+def still_wedge(settle):
+    from sphexample_amd.fields import linear_fit
+    from sphexample_amd.rays import water_level
+    eng, s, pts, where = still_wedge_handle(settle)
+    d = eng.download(("Position", "Type"))
+    F = d["Position"][d["Type"] == 1].astype(np.float64)
+    h, H = eng.cfg.h, eng.cfg.H
     shep = eng.sample_points(pts)
     fit = linear_fit(eng.sample_point_moments(pts))
     level = water_level(eng, pts[:, 0], F[:, 1].max() + 2 * H, pts[:, 1].min())
