@@ -187,27 +187,52 @@ template <class T> struct PointCloudArgs {
     int N, kernel;
 };
 
-template <class T, int D>
-__global__ void __launch_bounds__(kFgThreads, 4) k_point_cloud(const PointCloudArgs<T> A) {
+// The seven sums of a point, as one lane carries them through pc_walk.  `add` is handed one accepted row — the staged row r = { x, y, z,
+// m₀/ρ, P, ρ, v }, its weight w, its distance and d = x_p − x_j — and `store` writes the slots 0 … 6 of every sampler of the family
+// (M = n_points: the stride of a slot).  pc_walk is written over such a set; PcmSums (sphmi_point_moments.h) carries these seven,
+// formed by these statements, and its own sums behind them.  A set also names what its kernel does for registers or speed and
+// another does not (profiles/point_walk.md):
+//     Count      the type the rows are counted in: a double here, an int where 24 more sums fill the registers of a lane
+//     kUniform   the span of the tile and the chunk counts are declared uniform (readfirstlane): they and the loops over them live in
+//                scalar registers.  The larger set needs it — its sums leave the vector file no room; here it is not set
+//     kUnroll2   the row loop is unrolled by two; the larger set leaves its loop to the compiler
+template <int D, class Count = double>
+struct PcSums {
+    static constexpr bool kUniform = false, kUnroll2 = true;
+    Count n = 0;
+    double S = 0.0, SP = 0.0, Sr = 0.0, Sx = 0.0, Sy = 0.0, Sz = 0.0;
+    template <class Args>
+    __device__ __forceinline__ void add(const Args&, const double* r, double w, double, double, double, double) {
+        const double rho = r[5];
+        n += 1; S += w; SP += w * r[4]; Sr += w * rho;
+        Sx += w * r[6]; Sy += w * r[7];
+        if (D == 3) Sz += w * r[8];
+    }
+    __device__ __forceinline__ void store(double* o, long long M) const {
+        o[0] = S; o[M] = SP; o[2 * M] = Sr; o[3 * M] = Sx; o[4 * M] = Sy; o[5 * M] = D == 3 ? Sz : 0.0;
+        o[6 * M] = (double)n;
+    }
+};
+
+// THE WALK of one workgroup over the candidate rows of its tile (SAMPLE in the head comment): from the point xp of this lane
+// (has_point: the lane holds one; a spare lane's xp is set to NaN) to the sums of `s` (zero on entry) over the rows within H of xp, in
+// ascending row order.  `Sums` names the per-row statements and the constants above.  k_point_cloud and k_point_moments call it
+// and differ otherwise in their read of the point and their stores.  k_point_gradients (sphmi_point_gradients.h) keeps a COPY of
+// this function in its body, because under the function it needs scratch (profiles/point_walk.md): a fix here has to be made
+// there too.  The LDS — two staging buffers, the two range tables of a batch, four wave sums: 38 928 B — is k_field_grid's in
+// every instantiation.
+template <class T, int D, class Sums>
+__device__ __forceinline__ void pc_walk(const PointCloudArgs<T>& A, double (&xp)[3], const bool has_point, Sums& s) {
     using V4 = typename Vec4<T>::type;
+    constexpr bool kUniform = Sums::kUniform;
+    auto uniform = [](int v) { return kUniform ? __builtin_amdgcn_readfirstlane(v) : v; };
     __shared__ double s_row[2][kFgThreads * kFgRow];
     __shared__ int s_rs[kFgThreads], s_incl[kFgThreads];
     __shared__ int s_wave[4];
-    static_assert(sizeof(s_row) + sizeof(s_rs) + sizeof(s_incl) + sizeof(s_wave) <= kFgLdsBytes, "LDS of k_point_cloud: no more than k_field_grid");
-    static_assert(4 * kFgLdsBytes <= 160 * 1024, "four workgroups of k_point_cloud per compute unit");
+    static_assert(sizeof(s_row) + sizeof(s_rs) + sizeof(s_incl) + sizeof(s_wave) <= kFgLdsBytes, "LDS of pc_walk: no more than k_field_grid");
+    static_assert(4 * kFgLdsBytes <= 160 * 1024, "the LDS allows four workgroups per compute unit");
     const int t = (int)threadIdx.x, lane = t & 63, wave = t >> 6;
 
-    // the tile of this workgroup, the point of this lane
-    const PcTile tile = A.tiles[blockIdx.x];
-    const bool has_point = t < tile.count;
-    long long p = 0;
-    double xp[3] = {0.0, 0.0, 0.0};
-    if (has_point) {
-        p = (long long)A.index[tile.first + t];
-        if (p < 0 || p >= A.n_points) p = 0;                 // (cannot happen on a consistent index; keeps every access inside the arrays)
-#pragma unroll
-        for (int d = 0; d < D; ++d) xp[d] = A.pos[p * D + d];
-    }
     // the smallest and the largest coordinate of the tile per axis (count ≥ 1: both finite); the first staging buffer is free until the first chunk
     double mn[3] = {0.0, 0.0, 0.0}, mx[3] = {0.0, 0.0, 0.0};
     {
@@ -245,10 +270,12 @@ __global__ void __launch_bounds__(kFgThreads, 4) k_point_cloud(const PointCloudA
         }
     }
     if (!has_point) xp[0] = __longlong_as_double(0x7ff8000000000000ll);      // fails every cut
+    // (every lane holds the same span — it comes from the workgroup's min / max; kUniform says so)
+#pragma unroll
+    for (int d = 0; d < 3; ++d) { lo[d] = uniform(lo[d]); hi[d] = uniform(hi[d]); }
     const int ny = hi[1] - lo[1] + 1, nz = D == 3 ? hi[2] - lo[2] + 1 : 1;
-    const int nrange = empty ? 0 : ny * nz;
+    const int nrange = uniform((int)empty) ? 0 : ny * nz;
 
-    double n = 0.0, S = 0.0, SP = 0.0, Sr = 0.0, Sx = 0.0, Sy = 0.0, Sz = 0.0;
     for (int rbase = 0; rbase < nrange; rbase += kFgThreads) {
         // range rbase + t = (cy, cz): its x-adjacent cells are one range of rows
         int rs = 0, rc = 0;
@@ -271,7 +298,7 @@ __global__ void __launch_bounds__(kFgThreads, 4) k_point_cloud(const PointCloudA
         s_rs[t] = rs - (incl - rc);                          // candidate q of this range is row s_rs + q
         s_incl[t] = incl;
         __syncthreads();
-        const int total = s_incl[kFgThreads - 1];
+        const int total = uniform(s_incl[kFgThreads - 1]);
         const int nchunk = (total + kFgThreads - 1) / kFgThreads;
 
         V4 q0, q1, lw;
@@ -306,6 +333,19 @@ __global__ void __launch_bounds__(kFgThreads, 4) k_point_cloud(const PointCloudA
             r[5] = rho;
             r[6] = (double)q1.x; r[7] = (double)q1.y; r[8] = (double)q1.z;
         };
+        auto row = [&](const double* r) {
+            double dx, dy, dz, r2;
+            {
+                // (no contraction: r² is ((dx² + dy²) + dz²) rounded term by term, as in k_probe_sample and k_field_grid)
+#pragma clang fp contract(off)
+                dx = xp[0] - r[0]; dy = xp[1] - r[1]; dz = D == 3 ? xp[2] - r[2] : 0.0;
+                r2 = dx * dx + dy * dy + dz * dz;
+            }
+            if (r2 <= A.H2) {
+                const double dist = sqrt(r2);
+                s.add(A, r, r[3] * pr_kernel_w(A.kernel, A.alphaD, dist * A.h_inv), dist, dx, dy, dz);
+            }
+        };
         if (nchunk > 0) { load(0); stage(0); }
         __syncthreads();
         for (int c = 0; c < nchunk; ++c) {
@@ -313,33 +353,35 @@ __global__ void __launch_bounds__(kFgThreads, 4) k_point_cloud(const PointCloudA
             if (more) load(c + 1);                           // in flight while chunk c is walked
             const double* R = s_row[c & 1];
             const int cnt = min(kFgThreads, total - c * kFgThreads);
+            if (Sums::kUnroll2) {
 #pragma unroll 2
-            for (int j = 0; j < cnt; ++j) {
-                const double* r = R + j * kFgRow;
-                double r2;
-                {
-                    // (no contraction: r² is ((dx² + dy²) + dz²) rounded term by term, as in k_probe_sample and k_field_grid)
-#pragma clang fp contract(off)
-                    const double dx = xp[0] - r[0], dy = xp[1] - r[1], dz = D == 3 ? xp[2] - r[2] : 0.0;
-                    r2 = dx * dx + dy * dy + dz * dz;
-                }
-                if (r2 <= A.H2) {
-                    const double rho = r[5];
-                    const double w = r[3] * pr_kernel_w(A.kernel, A.alphaD, sqrt(r2) * A.h_inv);
-                    n += 1.0; S += w; SP += w * r[4]; Sr += w * rho;
-                    Sx += w * r[6]; Sy += w * r[7];
-                    if (D == 3) Sz += w * r[8];
-                }
+                for (int j = 0; j < cnt; ++j) row(R + j * kFgRow);
+            } else {
+                for (int j = 0; j < cnt; ++j) row(R + j * kFgRow);
             }
             if (more) stage((c + 1) & 1);                    // the buffer chunk c − 1 was walked from: every lane is past the barrier behind it
             __syncthreads();
         }
     }
+}
+
+template <class T, int D>
+__global__ void __launch_bounds__(kFgThreads, 4) k_point_cloud(const PointCloudArgs<T> A) {
+    const int t = (int)threadIdx.x;
+    // the tile of this workgroup, the point of this lane
+    const PcTile tile = A.tiles[blockIdx.x];
+    const bool has_point = t < tile.count;
+    long long p = 0;
+    double xp[3] = {0.0, 0.0, 0.0};
     if (has_point) {
-        double* o = A.out + p;
-        o[0] = S; o[A.n_points] = SP; o[2 * A.n_points] = Sr; o[3 * A.n_points] = Sx; o[4 * A.n_points] = Sy; o[5 * A.n_points] = D == 3 ? Sz : 0.0;
-        o[6 * A.n_points] = n;
+        p = (long long)A.index[tile.first + t];
+        if (p < 0 || p >= A.n_points) p = 0;                 // (cannot happen on a consistent index; keeps every access inside the arrays)
+#pragma unroll
+        for (int d = 0; d < D; ++d) xp[d] = A.pos[p * D + d];
     }
+    PcSums<D> s;
+    pc_walk<T, D>(A, xp, has_point, s);
+    if (has_point) s.store(A.out + p, A.n_points);
 }
 
 }  // namespace sphmi

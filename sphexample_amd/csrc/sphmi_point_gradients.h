@@ -11,7 +11,10 @@
 // and multiplies x − x_j = 0.  The RAW sums are written and delivered; the caller normalises (sphexample_amd/fields.py: the
 // Shepard-corrected difference form ∇A ≈ (GA − (SA / S) · G) / S).
 //
-// k_point_gradients — k_point_cloud (sphmi_point_cloud.h) with more sums per row.  The cloud is binned by the BIN passes of that
+// k_point_gradients — k_point_cloud (sphmi_point_cloud.h) with more sums per row.  The body below is the one remaining COPY of
+// pc_walk (there: the walk under k_point_cloud and k_point_moments): under the function this kernel's <double, 3> instantiation, which
+// fills its 128 registers, needs 12 bytes of scratch (profiles/point_walk.md).  A fix to the span, the staging or the cut there has to
+// be made here too, and the other way round.  The cloud is binned by the BIN passes of that
 // header, as they are (k_pc_count, k_pc_tiles, scan64 twice, k_pc_scatter, k_pc_describe: tiles of at most 256 points of one block
 // of cells); one workgroup of four waves per tile, one point per lane; the candidate span from the tile's min / max coordinates, the
 // range scan, the chunks of 256 rows converted once to { x, y, z, V, P, ρ, v } in fp64 (kFgRow doubles; rows that are not Fluid,

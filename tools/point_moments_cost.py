@@ -3,13 +3,17 @@
 process: the bench's 1 M-particle case (C3), a few steps in ("at rest") and, with --time, at that simulated time ("developed
 flow").  The cloud is the ~1e6 nodes of the lattice of tools/field_grid_cost.py handed over as points.
 
-    python tools/point_moments_cost.py [--steps 20] [--time 0.4] [--reps 5] [--still-wedge]
+    python tools/point_moments_cost.py [--steps 20] [--time 0.4] [--reps 5] [--clouds N] [--still-wedge]
 
 Per call, medians over --reps calls after one untimed call (which allocates): `kernel` ms of a call with every output NULL (upload,
 bin, kernels), `all` ms of a call that delivers every output; and, on stderr, the library's own line per call with
 SPHMI_POINTS_CLOCK set — the device time of bin / sample / fetch.  The ratio moments : gradients is printed with both; the walk is
 the same, with 30 sums against 24 per accepted row and one kernel evaluation fewer.  The case is bench.py's: the dam-break
 lattice at dp = 0.00425 generated on the device, fp32 kernels.
+
+--clouds N: instead of the above, N clocked calls of sphmi_sample_point_moments on each of the three clouds of
+tools/sample_points_cost.py (lattice, scattered, sphere): the clouds of few points per tile, where a workgroup does little besides
+its prologue.
 
 --still-wedge: a demonstration, not a measurement of time.  The StillWedge fixture (2-D, mDBC, fp64) advanced to --settle seconds;
 at the boundary rows that touch the water — the bed, the wedge's faces — the Shepard pressure of sphmi_sample_points, the fitted
@@ -51,6 +55,20 @@ def measure(eng, label, reps):
             sys.stderr.write(f"[{label}] {name}, all fields: "); sys.stderr.flush()
             call(x)
     os.environ.pop("SPHMI_POINTS_CLOCK", None)
+
+
+def clouds(eng, label, clocked):
+    from field_grid_cost import TANK_HI, TANK_LO
+    from sample_points_cost import sphere
+    rng = np.random.default_rng(5)
+    for name, x in (("lattice", grid_nodes(*lattice(1e6))), ("scattered", rng.uniform(TANK_LO, TANK_HI, (1024, 3))), ("sphere", sphere(100000, rng))):
+        x = np.ascontiguousarray(x)
+        eng.sample_point_moments(x)                                                   # (untimed: allocates)
+        os.environ["SPHMI_POINTS_CLOCK"] = "1"
+        for _ in range(clocked):
+            sys.stderr.write(f"[{label}] cloud {name}, all fields: "); sys.stderr.flush()
+            eng.sample_point_moments(x)
+        os.environ.pop("SPHMI_POINTS_CLOCK", None)
 
 
 def still_wedge_handle(settle):
@@ -112,6 +130,7 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--time", type=float, default=0.0)
     ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--clouds", type=int, default=0)
     ap.add_argument("--still-wedge", action="store_true")
     ap.add_argument("--settle", type=float, default=1.0)
     args = ap.parse_args()
@@ -120,6 +139,10 @@ def main():
         return
     eng = make_generated_dam_break_engine(DP, setup_dam_break_3d(DP), device_float_bytes=4)
     eng.advance(1e9, max_steps=args.steps)
+    if args.clouds > 0:
+        clouds(eng, f"N={eng.N}, fp32, {args.steps} steps in", args.clouds)
+        eng.close()
+        return
     measure(eng, f"N={eng.N}, fp32, {args.steps} steps in", args.reps)
     if args.time > 0:
         t0 = time.perf_counter()

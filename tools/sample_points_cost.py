@@ -7,11 +7,12 @@
   scattered 1 024 points drawn uniformly over the tank, next to what one step costs more with the same points as probes
   sphere    100 000 points on a sphere round the obstacle: the surface-load use
 
-    python tools/sample_points_cost.py [--steps 20] [--time 0.4] [--reps 5]
+    python tools/sample_points_cost.py [--steps 20] [--time 0.4] [--reps 5] [--clocked 1]
 
 Per cloud, medians over --reps calls after one untimed call (which allocates): `kernel` ms of a call with every output NULL, `all` ms
 of a call that delivers all five fields; and, on stderr, the library's own line per call with SPHMI_POINTS_CLOCK set — the device
-time of bin / sample / fetch, the number of tiles and the mean lanes filled.  The case is bench.py's: the dam-break lattice at
+time of bin / sample / fetch, the number of tiles and the mean lanes filled; --clocked N makes N such calls per cloud, for a median
+of the device time.  The case is bench.py's: the dam-break lattice at
 dp = 0.00425 generated on the device, fp32 kernels."""
 import argparse
 import ctypes as C
@@ -36,7 +37,7 @@ def sphere(n, rng):
     return OBSTACLE + RADIUS * v / np.linalg.norm(v, axis=1)[:, None]
 
 
-def measure(eng, label, reps):
+def measure(eng, label, reps, clocked=1):
     f = eng._fn("sample_points")
     g = eng._fn("sample_grid")
     rng = np.random.default_rng(5)
@@ -53,8 +54,9 @@ def measure(eng, label, reps):
         print(f"[{label}] cloud {name}: {len(x)} points, {wet} see water: kernel {k[0]:.2f} ms (min {k[1]:.2f}, max {k[2]:.2f}), "
               f"all fields {a[0]:.2f} ms (min {a[1]:.2f}, max {a[2]:.2f})", flush=True)
         os.environ["SPHMI_POINTS_CLOCK"] = "1"
-        sys.stderr.write(f"[{label}] cloud {name}, all fields: "); sys.stderr.flush()
-        eng.sample_points(x)
+        for _ in range(clocked):
+            sys.stderr.write(f"[{label}] cloud {name}, all fields: "); sys.stderr.flush()
+            eng.sample_points(x)
         os.environ.pop("SPHMI_POINTS_CLOCK", None)
         if name == "lattice":
             po, ps, pc = [v.ctypes.data_as(C.c_void_p) for v in (o, s, c)]
@@ -88,18 +90,19 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--time", type=float, default=0.0)
     ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--clocked", type=int, default=1)
     args = ap.parse_args()
     eng = make_generated_dam_break_engine(DP, setup_dam_break_3d(DP), device_float_bytes=4)
     eng.advance(1e9, max_steps=args.steps)
     label = f"N={eng.N}, fp32, {args.steps} steps in"
-    scattered = measure(eng, label, args.reps)
+    scattered = measure(eng, label, args.reps, args.clocked)
     probe_step(eng, scattered, label)
     if args.time > 0:
         t0 = time.perf_counter()
         pr = eng.advance(args.time)
         print(f"advanced to t = {pr.total_time:.4f} s, iteration {pr.iteration}, in {time.perf_counter() - t0:.1f} s", flush=True)
         label = f"N={eng.N}, fp32, t = {pr.total_time:.3f} s"
-        measure(eng, label, args.reps)
+        measure(eng, label, args.reps, args.clocked)
         probe_step(eng, scattered, label)
     eng.close()
 
