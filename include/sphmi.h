@@ -198,7 +198,7 @@ int sphmi_host_unregister(sphmi_handle* h, void* ptr);
 
 /*
  * StoreKernelOutput (src/SPHCellList.jl:106-116): Kernel[i] = Σⱼ Wᵢⱼ and KernelGradient[i] = Σⱼ ∇ᵢWᵢⱼ of the last
- * neighbour pass, host float type, n and n×dims values, current (cell-sorted) order.  Needs kernel_output = STORE.
+ * neighbour pass (the corrector of the last executed step, or the pass of sphmi_forces_once), host float type, n and n×dims values, current (cell-sorted) order.  Needs kernel_output = STORE.
  */
 int sphmi_download_kernel_output(sphmi_handle* h, void* kernel, void* kernel_gradient);
 

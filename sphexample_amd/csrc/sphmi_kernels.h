@@ -271,7 +271,7 @@ struct ForceParams {
     int visc, ddt, shift;    // model tags for the run-time variant of the kernel
     int exact_cut;           // H < 2h: apply r² ≤ H² per pair (the compiled-in variant requires H = 2h)
     int kernel;              // 0 WendlandC2, 1 CubicSpline (run-time variant only)
-    V4* kout;                // StoreKernelOutput: { Σ∇W, ΣW } of the corrector pass, or null
+    V4* kout;                // StoreKernelOutput: { Σ∇W, ΣW } of the corrector pass or of a forces-only pass, or null
     T dt, dt2;
     T H2, h, h_inv, Cgw, m0, Kddt, linfac, eta2, Kv2, rho0, inv_rho0, g, Cbe;
     T nhinv_half, Cfac, big;   // −1/(2h);  −8·Cgw: ∇W factor = Cfac·u³ with u = clamp(1 − q/2);  2⁴⁰ (step01)
@@ -825,8 +825,8 @@ k_neighbor_force(const ForceParams<T> P) {
                 az += pre * (c1 * gg * wz - c2 * gz);
             }
         }
-        if (MODEL < 0 && P.kout && PASS == PASS_CORRECTOR) {
-            // KernelOutput!, src/SPHCellList.jl:106-116
+        if (MODEL < 0 && P.kout && PASS != PASS_PREDICTOR) {
+            // KernelOutput!, src/SPHCellList.jl:106-116 (the last neighbour pass: the corrector of a step, or sphmi_forces_once)
             const bool in = (r2 <= P.H2) && (jr + (1u << kRecShift) != a_r1);           // the pair loop never meets i == j
             kw += in ? Wq : T(0);
             kgx += fac * dx; kgy += fac * dy; kgz += fac * dz;
@@ -1539,7 +1539,10 @@ k_neighbor_force(const ForceParams<T> P) {
     const T ml = fluid_a ? T(1) : T(0);
     if constexpr (PASS == PASS_FORCES_ONLY) {
         V4 o; o.x = ax; o.y = ay; o.z = az; o.w = drho;
-        if (storer) P.accbuf[a] = o;
+        if (storer) {
+            if (MODEL < 0 && P.kout) { V4 ko; ko.x = kgx; ko.y = kgy; ko.z = kgz; ko.w = kw; P.kout[a] = ko; }
+            P.accbuf[a] = o;
+        }
     } else if constexpr (PASS == PASS_PREDICTOR) {
         // HalfTimeStep (src/SPHCellList.jl:624-638) + LimitDensityAtBoundary! (SimulationEquations.jl:36-42)
         if constexpr (D == 3) az += P.g * gf; else ay += P.g * gf;

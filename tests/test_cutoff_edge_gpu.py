@@ -7,7 +7,8 @@ tests/test_fused_pair_parity_gpu.py) and for fp64 and fp32 handles.
 
 Tolerance per particle and quantity: fp64 handles 1e-10 × the field's maximum; fp32 handles FACTOR·Q·S_i with Q measured numpy.float32 against fp64 on
 these very layouts (the builders keep the corrector's positions x⁺ clear of the cut in fp32 as well).  Laminar viscosity and the kernel output
-(ΣW, Σ∇W) have no restatement in tests/bruteforce.py and therefore no S_i: fp64 handles only.  Figures: profiles/cutoff_edge.md."""
+(ΣW, Σ∇W) have no restatement in tests/bruteforce.py; tests/model_reference.py restates them with an fp64 scale S_i (tests/test_model_reference_gpu.py),
+an fp32 scale does not exist yet: fp64 handles only here.  Figures: profiles/cutoff_edge.md."""
 import functools
 
 import numpy as np
